@@ -5,7 +5,11 @@ One step = one full pass of the hot path (split -> LOD pyramid -> border stitch 
 over the resident 16k x 16k R16 heightmap into 1365 tiles of 512^2 (T=512, b=2, lod_count=6).
 Inputs are already in HBM when the timed region starts; value = tiles / s over all ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, spins up, warms up, times the K steps and prints the line: nothing else.  --full adds every side
+measurement (per-launch durations and the roofline, the closure record, two jobs in flight, end-to-end spans, the other
+workloads, the CPU baseline, the tiling prepass; N > 1: the extra passes below).  --dump-outputs DIR writes what the last
+timed step left in the atlas (tile list, per-tile sums, a seeded sample of whole tiles) as .npy files.
 The headline (`value`, `ms_per_step`) is defined the same way at every N: ONE job at a time on ONE stream per rank.
 N = 1: job after job on the context's stream.  A second pass with two independent jobs in flight (two contexts = two HIP
 streams, an atlas each, the source shared, steps issued round-robin) is reported as `config.ms_per_step_two_in_flight`.
@@ -399,6 +403,52 @@ def verify_against(atlas, oracle, shape, held=None):
     return {"tiles": checked, "identical": identical, "index_contract": True}
 
 
+def held_layers(job, lod_index):
+    """The atlas layers rank 0 holds after a step, from (lod, atlas index) of every tile: None = all (N = 1, replicated
+    result); distributed result: its finest pieces + every lower LOD."""
+    if job is None or job.held is None:
+        return None
+    finest = max(lod for lod, _ in lod_index)
+    held = {i for lod, i in lod_index if lod < finest}
+    for piece in job.held:
+        held.update(range(piece["first_layer"], piece["first_layer"] + piece["layers"]))
+    return held
+
+
+DUMP_SAMPLE_TILES = 48  # whole tiles of 512^2 texels as float32: 48 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(directory, atlas, held=None):
+    """--dump-outputs: what a caller of the timed path receives, the atlas (attachment 0), as .npy files in DIR:
+    tile_coords (float64, one row per tile in allocation order: side, lod, x, y, atlas index), tile_sums (float64: the
+    exact texel sum of every tile) and the texels of a fixed sample of whole tiles chosen by a seeded generator
+    (tile_sample, float32, with their rows of tile_coords in tile_sample_coords)."""
+    import numpy as np
+
+    tiles = [(c, i) for c, i in atlas.tiles() if held is None or i in held]
+    coords = np.array([(c.side, c.lod, c.x, c.y, i) for c, i in tiles], dtype=np.float64).reshape(-1, 5)
+    rows = np.sort(np.random.default_rng(SEED).choice(len(tiles), size=min(DUMP_SAMPLE_TILES, len(tiles)), replace=False))
+    row_of = {i: r for r, (_, i) in enumerate(tiles)}
+    sample_of = {tiles[r][1]: k for k, r in enumerate(rows)}
+    sums = np.zeros(len(tiles), dtype=np.float64)
+    sample = None
+    end = max(row_of, default=-1) + 1
+    for first in range(0, end, 128):
+        data = atlas.download_tiles(0, first, min(128, end - first))
+        if sample is None:
+            sample = np.zeros((len(rows),) + data.shape[1:], dtype=np.float32)
+        for k, tile in enumerate(data):
+            if first + k in row_of:
+                sums[row_of[first + k]] = float(tile.sum(dtype=np.uint64))
+            if first + k in sample_of:
+                sample[sample_of[first + k]] = tile
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "tile_coords.npy"), coords)
+    np.save(os.path.join(directory, "tile_sums.npy"), sums)
+    np.save(os.path.join(directory, "tile_sample.npy"), sample if sample is not None else np.zeros((0,), np.float32))
+    np.save(os.path.join(directory, "tile_sample_coords.npy"), coords[rows])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -430,7 +480,16 @@ def main():
     ap.add_argument("--no-workloads", action="store_true",
                     help="N = 1: skip config.workloads (config 2 height / albedo, the masked 16k job re-run and fresh, config 5 height: each timed by events in this process)")
     ap.add_argument("--verify", action="store_true", help="byte-compare all tiles with the checker's run of the same job (oracle/_ref when built)")
+    ap.add_argument("--full", action="store_true",
+                    help="every side measurement besides the headline (the --no-* options above then select among them); "
+                         "a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the atlas the last step produced as DIR/*.npy (float32 / float64, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_end_to_end = args.no_workloads = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
@@ -623,8 +682,8 @@ def main():
     for i in range(args.steps):
         # one stream: per-launch HIP events (the roofline's launch durations) on every `stride`-th step — each event costs ~2.6 us of
         # stream time, an instrumented step ~10 us more than a plain one; several jobs in flight: none here — a launch that shares the
-        # GPU with another job's says nothing about the kernel, the durations come from the one-stream pass below
-        step(profile=depth == 1 and (i % stride == 0) and not os.environ.get("BT_BENCH_NO_LAUNCH_EVENTS"))
+        # GPU with another job's says nothing about the kernel, the durations come from the one-stream pass below; a plain run: none
+        step(profile=args.full and depth == 1 and (i % stride == 0) and not os.environ.get("BT_BENCH_NO_LAUNCH_EVENTS"))
     stops = []
     for d, _, _ in lanes[:depth]:  # the K steps are over when the last lane's stream has drained
         e = torch.cuda.Event(enable_timing=True)
@@ -638,6 +697,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ms = float(t.item())
     ms_per_step = ms / args.steps
+    if rank == 0 and args.dump_outputs:  # before any side measurement: the atlas exactly as the last timed step left it
+        last = lanes[(issued[0] - 1) % depth][1] if job is None else atlas
+        dump_outputs(args.dump_outputs, last, held_layers(job, [(c.lod, i) for c, i in last.tiles()]))
 
     # N > 1: the N = 1 step of the SAME invocation — rank 0 runs the whole, unsharded job once more on its GPU (its own context, atlas and a
     # complete source) while the other ranks wait at a barrier, so that a SCALE record carries its own baseline: same box, same clocks, same build
@@ -982,12 +1044,7 @@ def main():
         oracle, shape, line["verify_checker"] = oracle_atlas(device, full_src)
         if full_src != src_ptr:
             device.free(full_src)
-        held = None
-        if job is not None and job.held is not None:  # distributed result: rank 0 holds its finest pieces + every lower LOD
-            finest = max(c[1] for c, _ in oracle.tiles())
-            held = {i for c, i in oracle.tiles() if c[1] < finest}
-            for piece in job.held:
-                held.update(range(piece["first_layer"], piece["first_layer"] + piece["layers"]))
+        held = held_layers(job, [(c[1], i) for c, i in oracle.tiles()])
         line["verify_vs_oracle"] = verify_against(atlas, oracle, shape, held)
         for k, (_, a, _) in enumerate(lanes[1:], 1):  # every lane's atlas holds a complete, identical job
             line[f"verify_vs_oracle_lane{k}"] = verify_against(a, oracle, shape)
@@ -995,7 +1052,7 @@ def main():
             line["verify_vs_oracle_overlapped_second_atlas"] = verify_against(a, oracle, shape, held)
     if world > 1:
         dist.barrier()  # the other ranks wait for rank 0's oracle run before tearing the group down
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the other half of the hot path, for the record: the per-frame tiling prepass on scripted camera paths
         # (latency-bound, one launch per frame; not part of `value`)
         try:

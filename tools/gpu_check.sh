@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -q -x "$@" > $O/tests.log 2>&1
 grep -E "passed|failed|error" $O/tests.log | tail -3
-python bench.py --no-cpu-baseline --no-end-to-end 2> $O/bench.err > $O/bench.json
+python bench.py --full --no-cpu-baseline --no-end-to-end 2> $O/bench.err > $O/bench.json
 python - $O <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1] + "/bench.json"))

@@ -12,10 +12,10 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 # the profiled command runs every job on ONE stream (--pipeline 1): a kernel that shares the GPU with another job's has no
 # duration of its own; the roofline of the default (pipelined) bench line is computed from its one-stream pass too
-B="python $R/bench.py --no-cpu-baseline --no-end-to-end --no-extras --no-workloads"  # (only the headline job's kernels in the profiled process)
+B="python $R/bench.py --full --no-cpu-baseline --no-end-to-end --no-extras --no-workloads"  # (only the headline job's kernels in the profiled process)
 C="python $R/tools/config_bench.py"
 
-python $R/bench.py --verify > $O/bench_n1_verified.json 2> $O/bench.log
+python $R/bench.py --full --verify > $O/bench_n1_verified.json 2> $O/bench.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprofv3.json 2> $O/stats.log
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS \
     --kernel-trace --output-format csv -d $O/pmc_sq -o bench -- $B --steps 3 --warmup 1 --spinup-ms 0 > /dev/null 2> $O/pmc_sq.log
