@@ -89,7 +89,7 @@ class SphericalDatasetC(C.Structure):
 
 class RunStatsC(C.Structure):
     _fields_ = [("kernel_launches", C.c_uint32), ("tiles", C.c_uint32), ("algorithmic_bytes", C.c_uint64),
-                ("fused_jobs", C.c_uint32), ("generic_jobs", C.c_uint32), ("prev_zero_launches", C.c_uint32), ("reserved", C.c_uint32)]
+                ("fused_jobs", C.c_uint32), ("generic_jobs", C.c_uint32), ("prev_zero_launches", C.c_uint32), ("variants", C.c_uint32)]
 
 
 class ShardRangeC(C.Structure):

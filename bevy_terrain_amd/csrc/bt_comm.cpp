@@ -267,6 +267,7 @@ extern "C" {
 bt_status bt_preprocessor_run_sharded(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, uint32_t flags) {
     if (!p || !a || !comm) return BT_ERR_INVALID_ARGUMENT;
     if (bt_status s = check_comm(p, comm)) return s;
+    p->stats.variants = 0;
     const uint32_t pass = flags & (BT_RUN_GENERIC | BT_RUN_PROFILE);
     const bool local_only = (flags & BT_RUN_SHARD_LOCAL) && !(flags & BT_RUN_SHARD_FINISH);
     const bool exchange_only = (flags & BT_RUN_SHARD_EXCHANGE) != 0;  // timing: the grouped collective of the compiled plan alone

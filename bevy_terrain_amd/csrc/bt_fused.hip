@@ -2584,6 +2584,7 @@ bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, st
         if (hybrid) {
             Launch ls{};
             ls.kind = kLaunchSplit;
+            ls.variant = BT_VARIANT_HYBRID;
             ls.attachment = ai;
             ls.first_task = uint32_t(tasks.size());
             for (const Task* t : splits) {
@@ -2595,6 +2596,7 @@ bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, st
             plan.push_back(ls);
             Launch lt{};
             lt.kind = kLaunchStitch;
+            lt.variant = BT_VARIANT_HYBRID;
             lt.attachment = ai;
             lt.first_task = uint32_t(tasks.size());
             for (const Task* t : stitches)
@@ -2816,6 +2818,7 @@ bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, st
             }
             Launch ls{};
             ls.kind = kLaunchStitch;
+            ls.variant = BT_VARIANT_STITCH_LAUNCH;
             ls.attachment = ai;
             ls.first_task = first;
             ls.task_count = uint32_t(tasks.size()) - first;
@@ -3001,6 +3004,7 @@ bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, st
                 if (pass == 0) continue;
                 Launch ls{};
                 ls.kind = kLaunchStitch;
+                ls.variant = BT_VARIANT_STITCH_LAUNCH;
                 ls.aux0 = 2u;  // one region per task
                 ls.attachment = ai;
                 ls.first_task = first;
@@ -3172,6 +3176,7 @@ bt_status fused_launch_range(bt_preprocessor* p, bt_atlas* a, const Launch& l, u
     if (l.kind == kLaunchFusedDirect) {
         const uint32_t blocks_per_tile = (job.args.m.center_size + kDirectRows - 1) / kDirectRows;
         const uint32_t wgs_per_tile = (blocks_per_tile + job.args.groups - 1) / job.args.groups;
+        p->stats.variants |= job.direct_rep ? BT_VARIANT_DIRECT_REP : job.direct_skips ? BT_VARIANT_DIRECT_SKIPS : BT_VARIANT_DIRECT;
         if (job.direct_rep)  // a source coarser than the tile grid: rows repeat the pair above, the chained path follows (round 6)
             fused_direct_rgba8_kernel<true><<<job.args.item_count * wgs_per_tile, 256, 0, p->ctx->stream>>>(job.args);
         else if (job.direct_skips && !job.direct_rep)  // a source finer than the tile grid: rows pass over source rows, the chained path follows with two extra (plain) loads per block
@@ -3183,15 +3188,21 @@ bt_status fused_launch_range(bt_preprocessor* p, bt_atlas* a, const Launch& l, u
         if (job.args.lds_rows) {
             size_t lds = sizeof(MainShared) + (job.args.single_buffer ? 1 : 2) * size_t(job.args.lds_rows) * job.args.lds_pitch * 2;
             lds = std::min<size_t>(65536, lds + job.lds_pad);  // (occupancy experiments)
-            if (job.args.m.texture_size == 512 && job.args.lds_pitch == 528 && job.dma)
+            if (job.args.m.texture_size == 512 && job.args.lds_pitch == 528 && job.dma) {
+                p->stats.variants |= BT_VARIANT_MAIN_DMA_528;
                 fused_main_kernel<true, false, 512, 528, true><<<blocks, 256, lds, p->ctx->stream>>>(job.args);
-            else if (job.dma_only)  // a window the register staging cannot batch (a source-to-tile ratio away from 1), or T = 512 at any other pitch: LDS-DMA with a run-time pitch (round 6)
+            } else if (job.dma_only) {  // a window the register staging cannot batch (a source-to-tile ratio away from 1), or T = 512 at any other pitch: LDS-DMA with a run-time pitch (round 6)
+                p->stats.variants |= job.args.single_buffer ? BT_VARIANT_MAIN_SINGLE_BUFFER : job.args.apron_global ? BT_VARIANT_MAIN_APRON_GLOBAL : BT_VARIANT_MAIN_DMA_PITCH;
                 fused_main_kernel<true, false, 0, 0, true><<<blocks, 256, lds, p->ctx->stream>>>(job.args);
-            else if (job.args.m.texture_size == 512 && job.args.lds_pitch == 528)
+            } else if (job.args.m.texture_size == 512 && job.args.lds_pitch == 528) {
+                p->stats.variants |= BT_VARIANT_MAIN_REG_528;
                 fused_main_kernel<true, false, 512, 528><<<blocks, 256, lds, p->ctx->stream>>>(job.args);
-            else
+            } else {
+                p->stats.variants |= BT_VARIANT_MAIN_REG_PITCH;
                 fused_main_kernel<true, false, 0, 0><<<blocks, 256, lds, p->ctx->stream>>>(job.args);
+            }
         } else {
+            p->stats.variants |= BT_VARIANT_MAIN_UNSTAGED;
             fused_corner_kernel<<<job.args.item_count, 64, 0, p->ctx->stream>>>(job.args);
             fused_main_kernel<false, true, 0, 0><<<blocks, 256, sizeof(MainShared), p->ctx->stream>>>(job.args);
         }
@@ -3206,6 +3217,7 @@ bt_status fused_launch_range(bt_preprocessor* p, bt_atlas* a, const Launch& l, u
             for (uint32_t k = 0; k < job.args.apron_lods; k++) extras += (1ull << (2 * (job.args.lod + k))) * blocks_per_tile;
         }
         job.args.tail_extras = uint32_t(extras);
+        p->stats.variants |= job.args.regular ? BT_VARIANT_TAIL_REGULAR : BT_VARIANT_TAIL_IRREGULAR;
         // a 1-D grid: XCD k (blockIdx.x % 8) takes its share of the seam regions, then the k-th eighth of the apron blocks, then the k-th eighth of the mosaic (see the kernel)
         const uint64_t total_m = uint64_t(job.args.sides) * nx * nx, total_a = uint64_t(job.args.sides) * extras;
         const uint32_t blocks = uint32_t(8 * ((total_m + 7) / 8 + (total_a + 7) / 8 + (uint64_t(job.args.seam_count) + 7) / 8));

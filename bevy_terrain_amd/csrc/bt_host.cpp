@@ -1909,7 +1909,10 @@ bt_status run_streamed_impl(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, cons
     };
     // rasters no band covers (a launch that cannot be banded reads them): whole, up front, on the kernels' stream
     if (rc == BT_OK && local) rc = upload_pending_rasters(p, &banded_raster);
-    if (rc == BT_OK && local) p->stats.prev_zero_launches = fused_begin_run(p, a);
+    if (rc == BT_OK && local) {
+        p->stats.variants = 0;
+        p->stats.prev_zero_launches = fused_begin_run(p, a);
+    }
     // per banded raster: the column window that travels (a sharded rank: its strips + halo) and the rows that have
     std::vector<std::array<uint32_t, 4>> window(p->rasters.size());
     std::vector<uint32_t> done_rows(p->rasters.size(), 0);

@@ -229,6 +229,7 @@ struct Launch {
     uint64_t algorithmic_bytes = 0;  // inputs read once + outputs written once
     uint32_t phase = 0;              // sharded runs: 0 = BT_RUN_SHARD_LOCAL part, 2 = BT_RUN_SHARD_FINISH part
     uint32_t kernels = 1;            // kernels this plan entry launches (fused main without an LDS window: fused_corner + itself)
+    uint32_t variant = 0;            // batched launches: the BT_VARIANT_* bit they report (0: BT_VARIANT_GENERIC); fused launches report theirs at launch
 };
 
 // host-side launchers implemented in bt_kernels.hip

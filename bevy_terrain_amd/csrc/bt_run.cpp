@@ -167,6 +167,7 @@ bt_status ensure_compiled(bt_preprocessor* p, bt_atlas* a, uint32_t mode) {
 bt_status run_plan_entry(bt_preprocessor* p, bt_atlas* a, const Launch& l) {
     const Attachment& at = a->attachments[l.attachment];
     AttachmentMeta meta = at.meta;
+    if (l.kind == kLaunchSplit || l.kind == kLaunchDownsample || l.kind == kLaunchStitch) p->stats.variants |= l.variant ? l.variant : uint32_t(BT_VARIANT_GENERIC);
     if (p->compiled_flags & BT_RUN_REFERENCE_DISPATCH) meta.row_limit = meta.texture_size / 8u * 8u;  // (gpu_tile_atlas.rs:105)
     switch (l.kind) {
         case kLaunchSplit:
@@ -228,8 +229,11 @@ extern "C" bt_status bt_preprocessor_run(bt_preprocessor* p, bt_atlas* a, uint32
     };
     if (profile)
         if (bt_status s = record()) return s;
-    // (a sharded step's finishing half alone launches no split: the flags of its local half stand)
-    if (!sharded || (flags & BT_RUN_SHARD_LOCAL)) p->stats.prev_zero_launches = fused_begin_run(p, a);
+    // (a sharded step's finishing half alone launches no split: the flags of its local half stand, and its variants add to that half's)
+    if (!sharded || (flags & BT_RUN_SHARD_LOCAL)) {
+        p->stats.variants = 0;
+        p->stats.prev_zero_launches = fused_begin_run(p, a);
+    }
     for (const Launch& l : p->plan) {
         if (sharded && !(flags & (l.phase == 2 ? BT_RUN_SHARD_FINISH : BT_RUN_SHARD_LOCAL))) {
             if (profile)

@@ -33,7 +33,8 @@ extern "C" {
  * bt_preprocessor_run_streamed_sharded does the same for a BT_RUN_SHARD_DISTRIBUTED rank; bt_stream_stats and bt_run_stats GREW (new
  * trailing fields: callers must be rebuilt against this header); a split onto layers nothing has written since bt_atlas_create takes
  * the "previous value" of a no-data pixel as 0 without fetching it (bt_run_stats.prev_zero_launches) — same bytes;
- * bt_atlas_attachment_storage now counts as a write to every layer of the attachment.  Two BEHAVIOUR CHANGES (not additions): a borrowed
+ * bt_atlas_attachment_storage now counts as a write to every layer of the attachment.  bt_run_stats.reserved is now
+ * bt_run_stats.variants (BT_VARIANT_* bits of the last run; same layout, a field that read 0 before).  Two BEHAVIOUR CHANGES (not additions): a borrowed
  * unaligned device raster (on_device = 1) is copied into the library's padded buffer by EVERY run of a kept queue, not only the first
  * (round 5 froze it at the first run); and the rows of a BT_RASTER_HOST_DEFERRED raster must stay alive until the queue is RELEASED,
  * not merely until its first run (a kept queue that is re-planned for another rank / mode reads what the device does not hold yet).
@@ -348,8 +349,28 @@ typedef struct bt_run_stats {
     uint32_t prev_zero_launches; /* (ABI 6) fused main / direct launches of the LAST run whose finest tiles nothing had written since
                                   * bt_atlas_create: "the previous value" of a no-data pixel (split.wgsl:34-42) was taken as the
                                   * atlas's initial 0 instead of fetched — same bytes, no atlas reads.  0 for re-runs of a kept queue */
-    uint32_t reserved;
+    uint32_t variants; /* (ABI 6) BT_VARIANT_* bits: which plans and kernel variants the LAST bt_preprocessor_run /
+                        * bt_preprocessor_run_sharded launched (cleared at the start of each; streamed runs set them too) */
 } bt_run_stats;
+/* bt_run_stats.variants: one bit per plan and per kernel variant of the preprocessing launches.  The three modes of the run-time-pitch
+ * DMA instance (MAIN_DMA_PITCH, MAIN_APRON_GLOBAL, MAIN_SINGLE_BUFFER) exclude each other: a launch sets exactly one of them. */
+enum {
+    BT_VARIANT_GENERIC = 0x1u,            /* the batched kernels for the whole queue (BT_RUN_GENERIC, or a job that does not qualify) */
+    BT_VARIANT_HYBRID = 0x2u,             /* batched split + stitch of the finest LOD, fused_tail below it (R16 with T > 512 or b > 8) */
+    BT_VARIANT_STITCH_LAUNCH = 0x4u,      /* a batched stitch launch inside a fused plan (apron rows, cube seams) */
+    BT_VARIANT_MAIN_DMA_528 = 0x8u,       /* fused_main, T = 512, LDS pitch 528, LDS-DMA staging */
+    BT_VARIANT_MAIN_DMA_PITCH = 0x10u,    /* fused_main, run-time pitch, LDS-DMA staging, two buffers that hold the apron rows too */
+    BT_VARIANT_MAIN_APRON_GLOBAL = 0x20u, /* the same instance, two buffers, apron rows read from global memory */
+    BT_VARIANT_MAIN_SINGLE_BUFFER = 0x40u, /* the same instance, one buffer, apron rows read from global memory */
+    BT_VARIANT_MAIN_REG_528 = 0x80u,      /* fused_main, T = 512, LDS pitch 528, register staging */
+    BT_VARIANT_MAIN_REG_PITCH = 0x100u,   /* fused_main, run-time pitch, register staging */
+    BT_VARIANT_MAIN_UNSTAGED = 0x200u,    /* fused_corner + fused_main reading the source directly (no LDS window) */
+    BT_VARIANT_DIRECT = 0x400u,           /* fused_direct (Rgba8), source rows step one by one */
+    BT_VARIANT_DIRECT_REP = 0x800u,       /* fused_direct, a source coarser than the tile grid (rows repeat) */
+    BT_VARIANT_DIRECT_SKIPS = 0x1000u,    /* fused_direct, a source finer than the tile grid (rows pass over source rows) */
+    BT_VARIANT_TAIL_REGULAR = 0x2000u,    /* fused_tail, atlas indices in the closed form of the fresh layout */
+    BT_VARIANT_TAIL_IRREGULAR = 0x4000u,  /* fused_tail, atlas indices looked up in the per-LOD grids */
+};
 bt_status bt_preprocessor_last_run_stats(const bt_preprocessor* p, bt_run_stats* out);
 /* Multi-GPU: tiles shard by column strips of the finest LODs (new design, the reference is single-GPU;
  * SURVEY.md §8e).  Every rank builds the SAME queue (same atlas indices), calls set_shard(rank, world),

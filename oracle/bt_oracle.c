@@ -433,6 +433,12 @@ int orc_preprocess_tile(orc_atlas* a, const orc_dataset* d, const void* src, uin
 /* preprocessor.rs:314-343 */
 int orc_preprocess_spherical(orc_atlas* a, uint32_t attachment_index, uint32_t lod_begin, uint32_t lod_end,
                              const void* const src[6], uint32_t w, uint32_t h) {
+    const uint32_t ws[6] = {w, w, w, w, w, w}, hs[6] = {h, h, h, h, h, h};
+    return orc_preprocess_spherical_sized(a, attachment_index, lod_begin, lod_end, src, ws, hs);
+}
+
+int orc_preprocess_spherical_sized(orc_atlas* a, uint32_t attachment_index, uint32_t lod_begin, uint32_t lod_end,
+                                   const void* const src[6], const uint32_t w[6], const uint32_t h[6]) {
     orc_dataset side_datasets[6];
     for (uint32_t side = 0; side < 6; side++) {
         orc_dataset* d = &side_datasets[side];
@@ -444,7 +450,7 @@ int orc_preprocess_spherical(orc_atlas* a, uint32_t attachment_index, uint32_t l
         d->lod_end = lod_end;
     }
     for (uint32_t side = 0; side < 6; side++) {
-        int rc = split_and_downsample(a, &side_datasets[side], src[side], w, h);
+        int rc = split_and_downsample(a, &side_datasets[side], src[side], w[side], h[side]);
         if (rc) return rc;
     }
     push_barrier(a);

@@ -82,6 +82,9 @@ void orc_clear_attachment(orc_atlas* a, uint32_t attachment_index);
 int orc_preprocess_tile(orc_atlas* a, const orc_dataset* d, const void* src, uint32_t w, uint32_t h);
 int orc_preprocess_spherical(orc_atlas* a, uint32_t attachment_index, uint32_t lod_begin,
                              uint32_t lod_end, const void* const src[6], uint32_t w, uint32_t h);
+/* ... with a size per face (face s is w[s] x h[s]) */
+int orc_preprocess_spherical_sized(orc_atlas* a, uint32_t attachment_index, uint32_t lod_begin,
+                                   uint32_t lod_end, const void* const src[6], const uint32_t w[6], const uint32_t h[6]);
 /* executes the queued tasks in order (barriers = sequential phases);
  * threads<=1 -> scalar, else OpenMP over the tasks between two barriers. */
 int orc_run(orc_atlas* a, int threads);

@@ -8,6 +8,21 @@ import bevy_terrain_amd as bt
 FMT = {O.FORMAT_R16: bt.AttachmentFormat.R16, O.FORMAT_RGBA8: bt.AttachmentFormat.Rgba8}
 
 
+def variant_bits():
+    """BT_VARIANT_* of include/bevy_terrain_amd.h, parsed from the text: {name without the prefix: bit} (bt_run_stats.variants)"""
+    import re
+
+    from bevy_terrain_amd import _ffi
+
+    text = open(_ffi.HEADER_PATH).read()
+    return {m.group(1): int(m.group(2), 0) for m in re.finditer(r"\bBT_VARIANT_([A-Z0-9_]+)\s*=\s*(0x[0-9a-fA-F]+|\d+)u?", text)}
+
+
+def variants(stats):
+    """the names of the variants a run launched, from Preprocessor.stats()"""
+    return {name for name, bit in variant_bits().items() if stats["variants"] & bit}
+
+
 def random_raster(fmt, h, w, seed, holes=0.0):
     rng = np.random.default_rng(seed)
     if fmt == O.FORMAT_R16:

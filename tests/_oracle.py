@@ -132,6 +132,7 @@ def lib():
     L.orc_clear_attachment.argtypes = [vp, u32]
     L.orc_preprocess_tile.argtypes = [vp, C.POINTER(Dataset), vp, u32, u32]
     L.orc_preprocess_spherical.argtypes = [vp, u32, u32, u32, C.POINTER(vp), u32, u32]
+    L.orc_preprocess_spherical_sized.argtypes = [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.orc_run.argtypes = [vp, i32]
     L.orc_task_count.argtypes = [vp, C.POINTER(u32)]
     L.orc_task_count.restype = u32
@@ -272,8 +273,12 @@ class OracleAtlas:
         faces = [np.ascontiguousarray(f) for f in faces]
         self._keep.extend(faces)
         ptrs = (C.c_void_p * 6)(*[f.ctypes.data for f in faces])
-        rc = lib().orc_preprocess_spherical(self._h, attachment_index, lod_range[0], lod_range[1], ptrs,
-                                            faces[0].shape[1], faces[0].shape[0])
+        if all(f.shape[:2] == faces[0].shape[:2] for f in faces):
+            rc = lib().orc_preprocess_spherical(self._h, attachment_index, lod_range[0], lod_range[1], ptrs,
+                                                faces[0].shape[1], faces[0].shape[0])
+        else:  # faces of different sizes
+            rc = lib().orc_preprocess_spherical_sized(self._h, attachment_index, lod_range[0], lod_range[1], ptrs,
+                                                      (C.c_uint32 * 6)(*[f.shape[1] for f in faces]), (C.c_uint32 * 6)(*[f.shape[0] for f in faces]))
         if rc:
             raise RuntimeError(f"orc_preprocess_spherical rc={rc}")
         return self

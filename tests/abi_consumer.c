@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
     BEGIN(bt_preprocess_dataset); FIELD(bt_preprocess_dataset, attachment_index); FIELD(bt_preprocess_dataset, side); FIELD(bt_preprocess_dataset, top_left); FIELD(bt_preprocess_dataset, bottom_right); FIELD(bt_preprocess_dataset, lod_begin); FIELD(bt_preprocess_dataset, lod_end); END(bt_preprocess_dataset);
     BEGIN(bt_spherical_dataset); FIELD(bt_spherical_dataset, attachment_index); FIELD(bt_spherical_dataset, lod_begin); FIELD(bt_spherical_dataset, lod_end); END(bt_spherical_dataset);
     BEGIN(bt_tile_tree_entry); FIELD(bt_tile_tree_entry, atlas_index); FIELD(bt_tile_tree_entry, atlas_lod); END(bt_tile_tree_entry);
-    BEGIN(bt_run_stats); FIELD(bt_run_stats, kernel_launches); FIELD(bt_run_stats, tiles); FIELD(bt_run_stats, algorithmic_bytes); FIELD(bt_run_stats, fused_jobs); FIELD(bt_run_stats, generic_jobs); FIELD(bt_run_stats, prev_zero_launches); FIELD(bt_run_stats, reserved); END(bt_run_stats);
+    BEGIN(bt_run_stats); FIELD(bt_run_stats, kernel_launches); FIELD(bt_run_stats, tiles); FIELD(bt_run_stats, algorithmic_bytes); FIELD(bt_run_stats, fused_jobs); FIELD(bt_run_stats, generic_jobs); FIELD(bt_run_stats, prev_zero_launches); FIELD(bt_run_stats, variants); END(bt_run_stats);
     BEGIN(bt_stream_stats); FIELD(bt_stream_stats, streamed); FIELD(bt_stream_stats, bands); FIELD(bt_stream_stats, banded_launches); FIELD(bt_stream_stats, early_tiles); FIELD(bt_stream_stats, uploaded_bytes); FIELD(bt_stream_stats, saved_bytes); END(bt_stream_stats);
     BEGIN(bt_shard_range); FIELD(bt_shard_range, attachment_index); FIELD(bt_shard_range, side); FIELD(bt_shard_range, lod); FIELD(bt_shard_range, first_layer); FIELD(bt_shard_range, layers_per_rank); END(bt_shard_range);
     BEGIN(bt_launch_profile); FIELD(bt_launch_profile, kind); FIELD(bt_launch_profile, tasks); FIELD(bt_launch_profile, algorithmic_bytes); FIELD(bt_launch_profile, avg_ms); FIELD(bt_launch_profile, samples); END(bt_launch_profile);

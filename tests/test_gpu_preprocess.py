@@ -294,6 +294,9 @@ def test_fused_path_resample_ratios(device, W, H):
     src = K.random_raster(O.FORMAT_R16, H, W, seed=W, holes=0.002)
     atlas, pre = K.product_planar(device, src, 3, 128, 2, O.FORMAT_R16)
     assert pre.stats()["fused_jobs"] == 1
+    # (the window of 4100 x 600 is wide and shallow: one staging buffer of its centre rows fits, the unstaged kernel is for 5x both ways)
+    staging = {(200, 170): "MAIN_REG_PITCH", (2500, 2300): "MAIN_UNSTAGED", (4100, 600): "MAIN_SINGLE_BUFFER"}[(W, H)]
+    assert K.variants(pre.stats()) == {staging, "STITCH_LAUNCH"}, K.variants(pre.stats())
     assert K.assert_atlas_equal(atlas, K.oracle_planar(src, 3, 128, 2, O.FORMAT_R16)) == 21
 
 
@@ -1288,6 +1291,11 @@ def test_source_to_tile_ratios_staged_by_dma_alone(device, tmp_path, ratio, cube
     pre = queue(atlas)
     pre.run(atlas, keep_queue=True)
     assert pre.stats()["fused_jobs"] == 1
+    # the variant the docstring names: R16 — the run-time-pitch DMA instance in its plain mode (1.23, 0.8), apron rows from global memory (1.3) or one
+    # buffer (1.41 and up); Rgba8 — kRep below 1, kSkips above 1.02 (a cube with faces of one size: its ratio)
+    variant = {1.23: "MAIN_DMA_PITCH", 0.8: "MAIN_DMA_PITCH", 1.3: "MAIN_APRON_GLOBAL", 1.41: "MAIN_SINGLE_BUFFER", 1.45: "MAIN_SINGLE_BUFFER",
+               1.5: "MAIN_SINGLE_BUFFER", 1.8: "MAIN_SINGLE_BUFFER"}[ratio] if fmt == O.FORMAT_R16 else ("DIRECT_REP" if ratio < 1 else "DIRECT_SKIPS")
+    assert K.variants(pre.stats()) == {variant, "STITCH_LAUNCH"}, (ratio, cube, K.variants(pre.stats()))
     n_tiles = K.assert_atlas_equal(atlas, oracle)
     pre.run(atlas)
     assert K.assert_atlas_equal(atlas, oracle) == n_tiles
