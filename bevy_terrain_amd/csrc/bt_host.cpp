@@ -300,6 +300,10 @@ void bt_ctx_destroy(bt_ctx* ctx) {
 
 bt_status bt_ctx_set_stream(bt_ctx* ctx, void* stream) {
     if (!ctx) return BT_ERR_INVALID_ARGUMENT;
+    // work queued on the outgoing stream (bt_atlas_create's zeroing memset, which a prev_zero launch relies on without reading the layer) is
+    // not ordered before the new stream's: finish it first
+    BT_HIP(hipSetDevice(ctx->device));
+    if (ctx->stream) BT_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     ctx->own_stream = false;
     ctx->stream = hipStream_t(stream);
@@ -1241,6 +1245,7 @@ bt_status bt_atlas_mip_storage(const bt_atlas* a, uint32_t ai, uint32_t level, v
     const Attachment& at = a->attachments[ai];
     const uint32_t s = at.meta.texture_size >> level;
     if (ptr) *ptr = level == 0 ? at.level0 : at.mips[level];
+    if (ptr && level == 0) at.mark_written(0, uint32_t(at.written.size()));  // level 0 is attachment_storage's pointer: the same rule
     if (tile_bytes) *tile_bytes = uint64_t(s) * s * at.meta.pixel_size;
     return BT_OK;
 }

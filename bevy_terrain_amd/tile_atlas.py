@@ -212,8 +212,12 @@ class TileAtlas:
         _ffi.check(_ffi.lib().bt_atlas_generate_mipmaps(self._h, attachment_index, first_layer, count))
 
     def download_mip(self, attachment_index: int, mip: int, atlas_index: int) -> np.ndarray:
+        if mip == 0:  # a read stays a read: bt_atlas_mip_storage(level 0) counts as a write to every layer
+            return self.download_tile(attachment_index, atlas_index)
         p, tb = C.c_void_p(), C.c_uint64()
         _ffi.check(_ffi.lib().bt_atlas_mip_storage(self._h, attachment_index, mip, C.byref(p), C.byref(tb)))
+        if not p.value:
+            raise ValueError(f"mip level {mip} of attachment {attachment_index} has no storage yet (generate_mipmaps or load_tiles allocates it)")
         a = self.config.attachments[attachment_index]
         return self.device.download(p.value + tb.value * atlas_index, self._tile_shape(attachment_index, mip), texel_dtype(a.format))
 

@@ -163,6 +163,7 @@ const char* bt_last_error(void);
 /* `stream` is a hipStream_t owned by the caller (NULL = the library creates its own). */
 bt_status bt_ctx_create(int32_t device, void* stream, bt_ctx** out);
 void bt_ctx_destroy(bt_ctx* ctx);
+/* Waits for the work queued on the current stream (a fresh atlas's zeroing among it) before later work goes to `stream`. */
 bt_status bt_ctx_set_stream(bt_ctx* ctx, void* stream);
 void* bt_ctx_stream(const bt_ctx* ctx);
 bt_status bt_ctx_synchronize(bt_ctx* ctx);
@@ -256,6 +257,9 @@ bt_status bt_atlas_generate_mipmaps(bt_atlas* atlas, uint32_t attachment_index, 
  * that load_tile_config marked as existing.  A missing or wrongly sized file is BT_ERR_IO. */
 bt_status bt_atlas_load_tiles(bt_atlas* atlas, uint32_t attachment_index, const char* directory,
                               const bt_tile_coordinate* coords, uint32_t count);
+/* Device pointer + bytes per tile of mip level `mip_level` of the attachment (layers tightly packed).  Level 0 is the pointer
+ * bt_atlas_attachment_storage returns, and asking for it (device_ptr != NULL) counts as a write to every layer in the same way
+ * (bt_run_stats.prev_zero_launches); read level 0 with bt_atlas_download_tiles to keep the fresh layers' flag. */
 bt_status bt_atlas_mip_storage(const bt_atlas* atlas, uint32_t attachment_index, uint32_t mip_level,
                                void** device_ptr, uint64_t* tile_bytes);
 

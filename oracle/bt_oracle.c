@@ -301,6 +301,12 @@ size_t orc_tile_bytes(const orc_atlas* a, uint32_t ai) {
     return (size_t)at->cfg.texture_size * at->cfg.texture_size * at->pixel_size;
 }
 
+int orc_atlas_set_tile(orc_atlas* a, uint32_t ai, uint32_t atlas_index, const void* texels) {
+    if (ai >= a->n_att || atlas_index >= a->atlas_size || !texels) return -1;
+    memcpy((void*)orc_tile_data(a, ai, atlas_index), texels, orc_tile_bytes(a, ai));
+    return 0;
+}
+
 /* ======================================================================== */
 /* queue construction: preprocess/preprocessor.rs                            */
 /* ======================================================================== */

@@ -101,6 +101,9 @@ uint32_t orc_tiles(const orc_atlas* a, orc_coord* coords, uint32_t* atlas_indice
 uint32_t orc_get_tile(const orc_atlas* a, orc_coord c); /* atlas index or INVALID */
 const void* orc_tile_data(const orc_atlas* a, uint32_t attachment_index, uint32_t atlas_index);
 size_t orc_tile_bytes(const orc_atlas* a, uint32_t attachment_index);
+/* level 0 of layer `atlas_index` := `texels` (orc_tile_bytes bytes): arbitrary previous contents before a job runs (the
+ * atlas's layers start zeroed, like a fresh wgpu texture).  0, or -1 for an attachment / layer out of range. */
+int orc_atlas_set_tile(orc_atlas* a, uint32_t attachment_index, uint32_t atlas_index, const void* texels);
 
 /* tile_atlas.rs:77-116 + 605-612 : "{root}/data/{name}/{coord}.bin", "{root}/config.tc" */
 int orc_save_attachment(const orc_atlas* a, uint32_t attachment_index, const char* dir);

@@ -146,6 +146,8 @@ def lib():
     L.orc_tile_data.restype = vp
     L.orc_tile_bytes.argtypes = [vp, u32]
     L.orc_tile_bytes.restype = sz
+    L.orc_atlas_set_tile.argtypes = [vp, u32, u32, vp]
+    L.orc_atlas_set_tile.restype = i32
     L.orc_save_attachment.argtypes = [vp, u32, C.c_char_p]
     L.orc_save_tile_config.argtypes = [vp, C.c_char_p]
     L.orc_tc_encode.argtypes = [C.POINTER(Coord), u32, vp, sz]
@@ -312,6 +314,16 @@ class OracleAtlas:
         buf = (C.c_uint8 * nbytes).from_address(p)
         a = np.frombuffer(buf, dtype=texel_dtype(fmt)).copy()
         return a.reshape(T, T) if fmt == FORMAT_R16 else a.reshape(T, T, 4)
+
+    def set_tile(self, attachment_index, atlas_index, texels):
+        """level 0 of layer atlas_index := texels (the shape tile() returns): previous contents a later job overlays"""
+        T, _, _, fmt = self.attachments[attachment_index]
+        texels = np.ascontiguousarray(texels, dtype=texel_dtype(fmt))
+        assert texels.shape == ((T, T) if fmt == FORMAT_R16 else (T, T, 4)), texels.shape
+        rc = lib().orc_atlas_set_tile(self._h, attachment_index, atlas_index, _np_ptr(texels))
+        if rc:
+            raise IndexError(f"orc_atlas_set_tile({attachment_index}, {atlas_index})")
+        return self
 
     def save_attachment(self, attachment_index, directory):
         rc = lib().orc_save_attachment(self._h, attachment_index, directory.encode())

@@ -1,6 +1,7 @@
 """Which kernel variant produced the tiles: every plan and kernel variant the launch planner (fused_plan, bt_fused.hip) can choose, pinned by a
 small job that must report EXACTLY its variants (bt_run_stats.variants) and match the oracle tile for tile — on a fresh atlas, re-run onto the
-written atlas (no-data texels fetch their previous value) and through the streamed pipeline.  A planner change (a threshold, the size of
+written atlas (no-data texels fetch their previous value), through the streamed pipeline and onto a fresh atlas primed with non-zero
+previous contents (the fetch must read the right texel of the right layer).  A planner change (a threshold, the size of
 MainShared) that moves a case to another variant fails here and has to be moved on purpose; a variant without a case fails on the CPU
 (test_every_variant_has_a_case)."""
 
@@ -158,18 +159,24 @@ def test_variant_matches_the_oracle(device, tmp_path, cfg):
     first = K.random_raster(fmt, T - 2 * b, T - 2 * b, seed=5) if cfg["first_job"] else None
     second = K.random_raster(R16, 500, 500, seed=6, holes=0.01) if cfg["second"] else None
 
-    oracle = O.OracleAtlas(lods, atlas_size, cube, attachments)
-    for i in range(len(attachments)):
-        oracle.clear_attachment(i)
-    if first is not None:
-        oracle.preprocess_tile(0, first, (0, 1))
-    if cube:
-        oracle.preprocess_spherical(0, srcs, (lod_lo, lods))
-    else:
-        oracle.preprocess_tile(0, srcs[0], (lod_lo, lods), **ds)
-    if second is not None:
-        oracle.preprocess_tile(1, second, (0, lods))
-    oracle.run(16)
+    def run_oracle(prior=None):
+        """prior: {(attachment, layer): texels} the atlas holds before the queue runs (else the atlas's zeros)"""
+        oracle = O.OracleAtlas(lods, atlas_size, cube, attachments)
+        for (i, layer), texels in (prior or {}).items():
+            oracle.set_tile(i, layer, texels)
+        for i in range(len(attachments)):
+            oracle.clear_attachment(i)
+        if first is not None:
+            oracle.preprocess_tile(0, first, (0, 1))
+        if cube:
+            oracle.preprocess_spherical(0, srcs, (lod_lo, lods))
+        else:
+            oracle.preprocess_tile(0, srcs[0], (lod_lo, lods), **ds)
+        if second is not None:
+            oracle.preprocess_tile(1, second, (0, lods))
+        return oracle.run(16)
+
+    oracle = fresh = run_oracle()
 
     server = bt.AssetServer()
     for k, s in enumerate(srcs):
@@ -198,7 +205,7 @@ def test_variant_matches_the_oracle(device, tmp_path, cfg):
             pre.preprocess_tile(bt.PreprocessDataset(attachment_index=1, path="second", lod_range=range(0, lods)), server, atlas, defer_upload=defer)
         return pre
 
-    def check(atlas):
+    def check(atlas, oracle=oracle):
         n = sum(K.assert_atlas_equal(atlas, oracle, attachment=i) for i in range(len(attachments)))
         assert n > 0
         return n
@@ -219,3 +226,25 @@ def test_variant_matches_the_oracle(device, tmp_path, cfg):
     assert check(atlas2) == n
     want = sum(bits[v] for v in cfg["variants"])
     assert masks == [want] * 3, f"launched {[_names(m, bits) for m in masks]}, the table says {sorted(cfg['variants'])}"
+
+    # 4. a fresh atlas whose every layer the queue writes holds non-zero previous contents (tests/_cases.prior_pattern, uploaded by the
+    # host): no launch may take the previous value as 0, and a no-data texel keeps ITS layer's texel — which steps 1 and 2 cannot tell
+    # from 0 (step 2's previous values are the zeros step 1 left at the no-data texels)
+    prior = {(i, idx): K.prior_pattern(attachments[i][3], attachments[i][0], idx + 4096 * i)
+             for i in range(len(attachments)) for _, idx in fresh.tiles()}
+    primed = run_oracle(prior)
+    atlas3 = bt.TileAtlas.new(tc, device)
+    for (i, idx), texels in prior.items():
+        atlas3.upload_tile(i, idx, texels)
+    pre3 = queue(atlas3)
+    pre3.run(atlas3)
+    assert pre3.stats()["variants"] == want, f"launched {_names(pre3.stats()['variants'], bits)} onto the primed atlas"
+    assert check(atlas3, primed) == n
+    assert pre3.stats()["prev_zero_launches"] == 0
+    # not vacuous: the finest tiles of the main job (per face of a cube job) keep the pattern at no-data centre texels the fresh run left 0
+    kept = {}
+    for (side, lod, _, _), idx in fresh.tiles():
+        if lod == lods - 1:
+            k = K.kept_texels(fresh.tile(0, idx), primed.tile(0, idx), prior[(0, idx)], b)
+            kept[side] = kept.get(side, 0) + int(k.sum())
+    assert len(kept) == (6 if cube else 1) and min(kept.values()) >= 16, f"no-data centre texels that keep the previous value, per side: {kept}"

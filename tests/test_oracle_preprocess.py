@@ -220,3 +220,35 @@ def test_block_schedule_and_native_build_give_the_same_bytes(tmp_path):
                 got = np.frombuffer((C.c_uint8 * 2048).from_address(L.orc_tile_data(h, 0, idx)), dtype=np.uint16).reshape(32, 32)
                 assert np.array_equal(got, ref.tile(0, idx)), (path, threads, rows, coord)
             L.orc_atlas_free(h)
+
+
+def test_set_tile_gives_the_previous_value_a_no_data_texel_keeps():
+    """orc_atlas_set_tile: arbitrary previous contents of a layer.  One tile (T = 8, b = 2, c = 4) from a 16 x 16 source whose left
+    half is no-data (0) and whose right half is 1000: centre column px = b reads source columns (0, 0) (u = 0 -> -0.5, clamped), px = b + 2
+    reads (7, 8) — one of them no-data — so both keep the layer's previous texel (split.wgsl:34-42); px = b + 3 reads (11, 12) -> 1000."""
+    T, b = 8, 2
+    src = np.zeros((16, 16), np.uint16)
+    src[:, 8:] = 1000
+    prior = (np.arange(T * T, dtype=np.uint16).reshape(T, T) + 40000)
+    a = O.OracleAtlas(1, 4, False, [(T, b, 1, O.FORMAT_R16)])
+    a.set_tile(0, 0, prior)
+    assert np.array_equal(a.tile(0, 0), prior) and not a.tile(0, 1).any()
+    with pytest.raises(IndexError):
+        a.set_tile(0, 4, prior)
+    a.clear_attachment(0).preprocess_tile(0, src, (0, 1)).run()
+    assert a.tiles() == [((0, 0, 0, 0), 0)]
+    out = a.tile(0, 0)
+    for py in range(b, b + 4):
+        assert out[py, b] == prior[py, b] == 40000 + py * T + b
+        assert out[py, b + 2] == prior[py, b + 2]
+        assert out[py, b + 3] == 1000
+    fresh = run_planar(src, 1, T, b, O.FORMAT_R16, atlas_size=4).tile(0, 0)  # the same job onto the atlas's zeros
+    assert (fresh[b:b + 4, b] == 0).all() and (fresh[b:b + 4, b + 3] == 1000).all()
+    # Rgba8: all four channels of the previous texel are kept; channel 0 decides validity
+    src8 = np.zeros((16, 16, 4), np.uint8)
+    src8[:, 8:] = (100, 20, 30, 40)
+    prior8 = np.stack([prior.astype(np.uint8) | 0x80] * 4, axis=-1) + np.uint8(1) * np.arange(4, dtype=np.uint8)
+    a8 = O.OracleAtlas(1, 4, False, [(T, b, 1, O.FORMAT_RGBA8)]).set_tile(0, 0, prior8)
+    a8.clear_attachment(0).preprocess_tile(0, src8, (0, 1)).run()
+    out8 = a8.tile(0, 0)
+    assert np.array_equal(out8[b:b + 4, b], prior8[b:b + 4, b]) and (out8[b:b + 4, b + 3] == (100, 20, 30, 40)).all()
