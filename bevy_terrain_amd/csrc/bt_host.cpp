@@ -77,9 +77,7 @@ static bt_tile_coordinate neighbour_at(bt_tile_coordinate c, int nx, int ny, boo
 }
 
 void tile_neighbours(bt_tile_coordinate c, bool spherical, bt_tile_coordinate out[8]) {
-    // N, E, S, W, NW, NE, SE, SW (coordinate.rs:209-218) == the region order of stitch.wgsl:57-66
-    static const int kOffsets[8][2] = {{0, -1}, {1, 0}, {0, 1}, {-1, 0}, {-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
-    for (int i = 0; i < 8; i++) out[i] = neighbour_at(c, int(c.x) + kOffsets[i][0], int(c.y) + kOffsets[i][1], spherical);
+    for (int i = 0; i < 8; i++) out[i] = neighbour_at(c, int(c.x) + kNeighbourOffsets[i][0], int(c.y) + kNeighbourOffsets[i][1], spherical);
 }
 
 // ------------------------------------------------------------------ bincode varints (formats/mod.rs)
@@ -1964,7 +1962,7 @@ bt_status run_streamed_impl(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, cons
                 if (rc == BT_OK && hipEventRecord(uploaded, p->ctx->copy_stream) != hipSuccess) rc = BT_ERR_DEVICE;
                 if (rc == BT_OK && hipStreamWaitEvent(p->ctx->stream, uploaded, 0) != hipSuccess) rc = BT_ERR_DEVICE;
             }
-            if (rc == BT_OK) rc = fused_launch_range(p, a, l, sp.item_begin, sp.item_count);
+            if (rc == BT_OK) rc = run_plan_entry(p, a, l, sp.item_begin, sp.item_count);
         } else {
             rc = run_plan_entry(p, a, l);
         }

@@ -229,8 +229,11 @@ struct Launch {
     uint64_t algorithmic_bytes = 0;  // inputs read once + outputs written once
     uint32_t phase = 0;              // sharded runs: 0 = BT_RUN_SHARD_LOCAL part, 2 = BT_RUN_SHARD_FINISH part
     uint32_t kernels = 1;            // kernels this plan entry launches (fused main without an LDS window: fused_corner + itself)
-    uint32_t variant = 0;            // batched launches: the BT_VARIANT_* bit they report (0: BT_VARIANT_GENERIC); fused launches report theirs at launch
+    uint32_t variant = 0;            // the BT_VARIANT_* bit of the kernel instance it runs, chosen at plan time (run_plan_entry reports it)
 };
+
+// the device record of a queued task (the batched kernels, fused_plan's stitch and seam records)
+TaskDev to_device_task(const Task& t);
 
 // host-side launchers implemented in bt_kernels.hip
 bt_status launch_split(bt_ctx* ctx, const AttachmentMeta& m, void* atlas, const TaskDev* tasks, uint32_t n,
@@ -252,7 +255,8 @@ void fused_release(struct ::bt_preprocessor* p);
 
 bt_status release_queue(struct ::bt_preprocessor* p);  // bt_run.cpp
 bt_status ensure_compiled(struct ::bt_preprocessor* p, struct ::bt_atlas* a, uint32_t mode);  // bt_run.cpp: queue -> launch plan
-bt_status run_plan_entry(struct ::bt_preprocessor* p, struct ::bt_atlas* a, const Launch& l);  // bt_run.cpp: one launch of the plan
+// bt_run.cpp: one launch of the plan; a fused main / direct launch runs the items [item_begin, item_begin + item_count) of its list (streamed runs' bands)
+bt_status run_plan_entry(struct ::bt_preprocessor* p, struct ::bt_atlas* a, const Launch& l, uint32_t item_begin = 0, uint32_t item_count = 0xFFFFFFFFu);
 uint32_t fused_begin_run(struct ::bt_preprocessor* p, struct ::bt_atlas* a);  // bt_fused.hip: per run, before its launches (FusedArgs::prev_zero, Attachment::written)
 bt_status upload_pending_rasters(struct ::bt_preprocessor* p, const std::vector<uint8_t>* skip = nullptr);  // bt_host.cpp: deferred host rasters, all at once (skip[i]: not raster i)
 
@@ -274,6 +278,8 @@ struct FusedTile {
 void fused_launch_tiles(const struct ::bt_preprocessor* p, const Launch& l, uint32_t item_begin, uint32_t item_count, std::vector<FusedTile>* out);
 
 // coordinate math (bt_host.cpp)
+// neighbour k of a tile is at (x, y) + kNeighbourOffsets[k]: N, E, S, W, NW, NE, SE, SW (coordinate.rs:209-218) == the region order of stitch.wgsl:57-66
+inline constexpr int kNeighbourOffsets[8][2] = {{0, -1}, {1, 0}, {0, 1}, {-1, 0}, {-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
 void tile_children(bt_tile_coordinate c, bt_tile_coordinate out[4]);
 void tile_neighbours(bt_tile_coordinate c, bool spherical, bt_tile_coordinate out[8]);
 

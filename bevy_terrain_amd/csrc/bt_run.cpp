@@ -15,12 +15,6 @@ using namespace bt;
 
 namespace bt {
 bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan);
-bt_status fused_launch(bt_preprocessor* p, bt_atlas* a, const Launch& l);
-}  // namespace bt
-
-namespace {
-
-constexpr uint32_t kMaxProfiledRuns = 512;  // events kept until bt_preprocessor_profile reads them
 
 TaskDev to_device_task(const Task& t) {
     TaskDev d{};
@@ -42,6 +36,11 @@ TaskDev to_device_task(const Task& t) {
         for (int i = 4; i < 8; i++) d.rel_index[i] = BT_INVALID_ATLAS_INDEX;
     return d;
 }
+}  // namespace bt
+
+namespace {
+
+constexpr uint32_t kMaxProfiledRuns = 512;  // events kept until bt_preprocessor_profile reads them
 
 // reference-shaped plan: every maximal run of same-type, same-attachment tasks inside a phase is a launch
 void generic_plan(const bt_preprocessor* p, const bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan) {
@@ -68,6 +67,7 @@ void generic_plan(const bt_preprocessor* p, const bt_atlas* a, std::vector<TaskD
         }
         Launch l{};
         l.kind = t.type == kSplit ? kLaunchSplit : t.type == kDownsample ? kLaunchDownsample : kLaunchStitch;
+        l.variant = BT_VARIANT_GENERIC;
         l.attachment = t.attachment_index;
         l.first_task = first;
         l.task_count = uint32_t(tasks.size()) - first;
@@ -164,10 +164,10 @@ bt_status ensure_compiled(bt_preprocessor* p, bt_atlas* a, uint32_t mode) {
     return BT_OK;
 }
 
-bt_status run_plan_entry(bt_preprocessor* p, bt_atlas* a, const Launch& l) {
+bt_status run_plan_entry(bt_preprocessor* p, bt_atlas* a, const Launch& l, uint32_t item_begin, uint32_t item_count) {
     const Attachment& at = a->attachments[l.attachment];
     AttachmentMeta meta = at.meta;
-    if (l.kind == kLaunchSplit || l.kind == kLaunchDownsample || l.kind == kLaunchStitch) p->stats.variants |= l.variant ? l.variant : uint32_t(BT_VARIANT_GENERIC);
+    p->stats.variants |= l.variant;
     if (p->compiled_flags & BT_RUN_REFERENCE_DISPATCH) meta.row_limit = meta.texture_size / 8u * 8u;  // (gpu_tile_atlas.rs:105)
     switch (l.kind) {
         case kLaunchSplit:
@@ -177,7 +177,7 @@ bt_status run_plan_entry(bt_preprocessor* p, bt_atlas* a, const Launch& l) {
         case kLaunchStitch:
             return launch_stitch(p->ctx, meta, at.level0, p->tasks_dev + l.first_task, l.task_count, l.aux0 == 1u, l.aux0 == 2u);
         default:
-            return fused_launch(p, a, l);
+            return fused_launch_range(p, a, l, item_begin, item_count);
     }
 }
 }  // namespace bt

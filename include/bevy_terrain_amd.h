@@ -366,7 +366,7 @@ enum {
     BT_VARIANT_MAIN_DMA_PITCH = 0x10u,    /* fused_main, run-time pitch, LDS-DMA staging, two buffers that hold the apron rows too */
     BT_VARIANT_MAIN_APRON_GLOBAL = 0x20u, /* the same instance, two buffers, apron rows read from global memory */
     BT_VARIANT_MAIN_SINGLE_BUFFER = 0x40u, /* the same instance, one buffer, apron rows read from global memory */
-    BT_VARIANT_MAIN_REG_528 = 0x80u,      /* fused_main, T = 512, LDS pitch 528, register staging */
+    BT_VARIANT_MAIN_REG_528 = 0x80u,      /* no longer reported: every R16 raster is 16-byte aligned, so T = 512 at LDS pitch 528 takes MAIN_DMA_528 */
     BT_VARIANT_MAIN_REG_PITCH = 0x100u,   /* fused_main, run-time pitch, register staging */
     BT_VARIANT_MAIN_UNSTAGED = 0x200u,    /* fused_corner + fused_main reading the source directly (no LDS window) */
     BT_VARIANT_DIRECT = 0x400u,           /* fused_direct (Rgba8), source rows step one by one */

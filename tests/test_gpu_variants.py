@@ -20,9 +20,9 @@ MAIN_ROWS = 8  # kMainRows: centre rows of a fused_main chunk
 
 # Variants no job reaches through the API, with the reason
 UNREACHABLE = {
-    "MAIN_REG_528": "fused_main<512, 528> with register staging runs only for a raster whose base or pitch is not 16-byte aligned; every R16 raster is "
-                    "(the library pads what it uploads and copies an unaligned borrowed device raster into a padded buffer: bt_preprocessor_preprocess_tile), "
-                    "so T = 512 at pitch 528 always takes the LDS-DMA instance (MAIN_DMA_528)",
+    "MAIN_REG_528": "no longer reported: the library has no fused_main<512, 528> with register staging.  Every R16 raster is 16-byte aligned in base and "
+                    "pitch (the library pads what it uploads and copies an unaligned borrowed device raster into a padded buffer: bt_preprocessor_preprocess_tile), "
+                    "so T = 512 at pitch 528 takes the LDS-DMA instance (MAIN_DMA_528); an unaligned one would take MAIN_REG_PITCH",
 }
 
 
