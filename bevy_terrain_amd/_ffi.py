@@ -128,6 +128,7 @@ class FrameInfoC(C.Structure):
 
 
 FRAME_PREPASS_UNORDERED, FRAME_PREPASS_PLAIN, FRAME_KEEP_REQUESTS, FRAME_KEEP_HEIGHT = 1, 2, 4, 8
+BOUNDS_SKIP_ZERO, BOUNDS_MAX_GRID = 1, 64
 
 
 class TileTreeEntryC(C.Structure):
@@ -190,6 +191,7 @@ PROTOTYPES = {
     "bt_atlas_load_tile_config": (_i32, [_vp, C.c_char_p]),
     "bt_atlas_load_tiles": (_i32, [_vp, _u32, C.c_char_p, _vp, _u32]),
     "bt_atlas_sample": (_i32, [_vp, _u32, _vp, _u32, _vp]),
+    "bt_atlas_tile_bounds": (_i32, [_vp, _u32, _P(_u32), _u32, _u32, _u32, _P(C.c_uint16), _u64]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),
     "bt_generate_mipmaps": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _u64]),

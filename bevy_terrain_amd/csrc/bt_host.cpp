@@ -291,6 +291,8 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     if (ctx->ev_end) hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     for (auto& kept : ctx->spare_rasters) hipFree(kept.first);
+    if (ctx->bounds_dev) hipFree(ctx->bounds_dev);
+    if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->save_stream) hipStreamDestroy(ctx->save_stream);
     delete ctx;
@@ -336,6 +338,11 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
             freed += ctx->staging_bytes;
         }
     ctx->staging_bytes = 0;
+    if (ctx->bounds_dev) BT_HIP(hipFree(ctx->bounds_dev));
+    if (ctx->bounds_host) BT_HIP(hipHostFree(ctx->bounds_host));
+    if (ctx->bounds_dev || ctx->bounds_host) freed += 2u * ctx->bounds_bytes;
+    ctx->bounds_dev = ctx->bounds_host = nullptr;
+    ctx->bounds_bytes = 0;
     if (freed_bytes) *freed_bytes = freed;
     return BT_OK;
 }
@@ -1236,6 +1243,72 @@ bt_status bt_atlas_sample(bt_atlas* a, uint32_t ai, const bt_tile_lookup* lookup
     hipFree(dev);
     if (e != hipSuccess) return hip_fail(e, "bt_atlas_sample");
     return rc;
+}
+
+bt_status bt_atlas_tile_bounds(bt_atlas* a, uint32_t ai, const uint32_t* layers, uint32_t count, uint32_t grid, uint32_t flags, uint16_t* out,
+                               uint64_t out_bytes) {
+    if (!a || ai >= a->attachments.size()) {
+        set_error("bt_atlas_tile_bounds: %s", a ? "attachment index out of range" : "NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("bt_atlas_tile_bounds: attachment %u is not R16", ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    const uint32_t T = at.meta.texture_size;
+    if (grid == 0 || (grid & (grid - 1u)) || grid > BT_BOUNDS_MAX_GRID || T % grid) {
+        set_error("bt_atlas_tile_bounds: grid %u (a power of two up to %u dividing the texture size %u)", grid, unsigned(BT_BOUNDS_MAX_GRID), T);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (flags & ~uint32_t(BT_BOUNDS_SKIP_ZERO)) {
+        set_error("bt_atlas_tile_bounds: unknown flags 0x%x", flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!count) return BT_OK;
+    const uint64_t cells = (4ull * grid * grid - 1u) / 3u;
+    if (!out || out_bytes < uint64_t(count) * cells * 4u) {
+        set_error("bt_atlas_tile_bounds: %s", out ? "out_bytes below count * (4 g^2 - 1) / 3 * 4" : "NULL out_host");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; layers && i < count; i++)
+        if (layers[i] >= a->config.atlas_size) {
+            set_error("bt_atlas_tile_bounds: layers[%u] = %u, the atlas has %u", i, layers[i], a->config.atlas_size);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (!layers && count > a->config.atlas_size) {
+        set_error("bt_atlas_tile_bounds: %u layers, the atlas has %u", count, a->config.atlas_size);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // chunks of layers whose list + pyramids fit 32 MiB (the 16k job's 1365 layers at grid 64 are one chunk)
+    bt_ctx* ctx = a->ctx;
+    const uint32_t chunk = uint32_t(std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / (cells * 4u + 4u))));
+    const uint64_t list_bytes = (uint64_t(chunk) * 4u + 255u) & ~255ull, need = list_bytes + uint64_t(chunk) * cells * 4u;
+    BT_HIP(hipSetDevice(ctx->device));
+    if (ctx->bounds_bytes < need) {
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->bounds_dev) BT_HIP(hipFree(ctx->bounds_dev));
+        if (ctx->bounds_host) BT_HIP(hipHostFree(ctx->bounds_host));
+        ctx->bounds_dev = ctx->bounds_host = nullptr;
+        ctx->bounds_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->bounds_dev, need));
+        BT_HIP(hipHostMalloc(&ctx->bounds_host, need, hipHostMallocDefault));
+        ctx->bounds_bytes = need;
+    }
+    uint32_t* list = (uint32_t*)ctx->bounds_host;
+    uint8_t* dev = (uint8_t*)ctx->bounds_dev;
+    for (uint32_t first = 0; first < count; first += chunk) {
+        const uint32_t n = std::min(chunk, count - first);
+        for (uint32_t i = 0; i < n; i++) list[i] = layers ? layers[first + i] : first + i;
+        BT_HIP(hipMemcpyAsync(dev, list, n * 4ull, hipMemcpyHostToDevice, ctx->stream));
+        if (bt_status s = launch_tile_bounds(ctx->stream, at.level0, T, (const uint32_t*)dev, n, grid, flags & BT_BOUNDS_SKIP_ZERO,
+                                             (uint32_t*)(dev + list_bytes)))
+            return s;
+        BT_HIP(hipMemcpyAsync((uint8_t*)ctx->bounds_host + list_bytes, dev + list_bytes, n * cells * 4u, hipMemcpyDeviceToHost, ctx->stream));
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+        memcpy(out + uint64_t(first) * cells * 2u, (const uint8_t*)ctx->bounds_host + list_bytes, n * cells * 4u);
+    }
+    return BT_OK;  // a read: Attachment::written stays as it is
 }
 
 bt_status bt_atlas_mip_storage(const bt_atlas* a, uint32_t ai, uint32_t level, void** ptr, uint64_t* tile_bytes) {

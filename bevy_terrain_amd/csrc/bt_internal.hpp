@@ -195,6 +195,11 @@ struct bt_ctx {
         }
     }
     uint32_t io_threads = 0;  // writer / reader threads of the save and load paths; 0 = automatic (bt_ctx_set_io_threads)
+    // bt_atlas_tile_bounds: the layer list and the pyramids of one chunk of layers, on the device and pinned (grown on demand, kept until
+    // bt_ctx_trim: a per-frame caller pays no allocation)
+    void* bounds_dev = nullptr;
+    void* bounds_host = nullptr;
+    uint64_t bounds_bytes = 0;
 };
 
 namespace bt {
@@ -246,6 +251,9 @@ bt_status launch_sample(bt_ctx* ctx, const AttachmentMeta& m, const void* atlas,
 bt_status launch_mip_level(bt_ctx* ctx, uint32_t format, const void* parent, void* child, uint32_t parent_size,
                            uint32_t layers);
 bt_status launch_gather_layers(hipStream_t stream, const void* atlas, const uint32_t* layers, uint32_t count, void* pinned_dst, uint64_t tile_bytes);
+// bt_bounds.hip: the min/max pyramids of `count` R16 layers of size T (layers: device list) -> out (device, (4g^2 - 1) / 3 words per layer)
+bt_status launch_tile_bounds(hipStream_t stream, const void* atlas, uint32_t T, const uint32_t* layers, uint32_t count, uint32_t grid,
+                             bool skip_zero, uint32_t* out);
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 

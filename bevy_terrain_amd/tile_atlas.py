@@ -262,6 +262,25 @@ class TileAtlas:
                                               out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def tile_bounds(self, attachment_index: int, layers=None, grid: int = 1, skip_zero: bool = False) -> List[np.ndarray]:
+        """bt_atlas_tile_bounds: the min/max pyramid of R16 layers (layers=None: the layers of tiles(), in that order) -> one uint16 array
+        per level, finest first, shaped (len(layers), n_k, n_k, 2) with n_k = grid >> k and [..., 0] = min, [..., 1] = max (raw unorm16).
+        A cell covers its block plus the first column to its right and the first row below it; with skip_zero texels equal to 0 are left
+        out and a cell without texels is (0xFFFF, 0)."""
+        if layers is None:
+            layers = [i for _, i in self.tiles()]
+        idx = np.ascontiguousarray(layers, dtype=np.uint32).ravel()
+        levels = [grid >> k for k in range(max(grid, 1).bit_length())]
+        out = np.empty((len(idx), sum(n * n for n in levels), 2), dtype=np.uint16)
+        _ffi.check(_ffi.lib().bt_atlas_tile_bounds(self._h, attachment_index, idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(idx), grid,
+                                                   _ffi.BOUNDS_SKIP_ZERO if skip_zero else 0, out.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                   out.nbytes))
+        result, base = [], 0
+        for n in levels:
+            result.append(out[:, base:base + n * n].reshape(len(idx), n, n, 2))
+            base += n * n
+        return result
+
     def close(self):
         if getattr(self, "_h", None):
             if device_open(getattr(self, "device", None)):

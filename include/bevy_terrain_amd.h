@@ -169,7 +169,7 @@ void* bt_ctx_stream(const bt_ctx* ctx);
 bt_status bt_ctx_synchronize(bt_ctx* ctx);
 /* Gives back what the context keeps between queues: the device rasters finished queues released (kept so that the next queue's
  * sources need not be allocated again: 0.5 GB for a 16k R16 raster, six of 128 MB for a cube job; at most 8 buffers and 4 GiB) and
- * the pinned staging buffers of the save / load paths.
+ * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds.
  * Synchronises the context's stream first.  `freed_bytes` (may be NULL): device + pinned bytes released. */
 bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes);
 /* Host threads that write (bt_preprocessor_save / _run_streamed) and read (bt_atlas_load_tiles) tile files for this context.
@@ -275,6 +275,20 @@ typedef struct bt_tile_lookup {
  * HBM, so the query runs there: `lookups_host` in, `out_vec4_host` (4 floats per lookup) out, synchronous. */
 bt_status bt_atlas_sample(bt_atlas* atlas, uint32_t attachment_index, const bt_tile_lookup* lookups_host, uint32_t count,
                           float* out_vec4_host);
+/* Min/max height pyramid of R16 layers (culling, collision broad phase, picking).  `grid` g (a power of two, 1..BT_BOUNDS_MAX_GRID,
+ * dividing T) cuts a T x T layer into cells of s = T / g texels; level k (0 .. log2 g) has n_k = g >> k cells per side of s << k texels.
+ * Cell (cx, cy) of level k covers x in [cx*s_k, min((cx+1)*s_k, T-1)], y likewise: its own block plus the first column to its right and
+ * the first row below it, so every bilinear sample inside the cell lies within its bounds and a level-(k+1) cell is the min / max of its
+ * four level-k children.  Values are raw unorm16: world height = lerp(min_height, max_height, v / 65535).
+ * BT_BOUNDS_SKIP_ZERO leaves texels equal to 0 (no data) out; a cell left without texels reports min 0xFFFF, max 0 (min > max: empty).
+ * `layers` (NULL: 0 .. count-1; any order, repeats allowed) are read as they are, tile set or not.  Output per entry of `layers`, in list
+ * order: the levels finest first, each n_k x n_k cells row-major (cy major), each cell a {min, max} pair of uint16, so
+ *     out_bytes >= count * (4*g*g - 1) / 3 * 4.
+ * Ordered behind the work queued on the context's stream; synchronous; a read (not a write for bt_run_stats.prev_zero_launches).
+ * Non-R16 attachments: BT_ERR_UNSUPPORTED.  count == 0: BT_OK, nothing touched.  Scratch stays in the context until bt_ctx_trim. */
+enum { BT_BOUNDS_SKIP_ZERO = 1, BT_BOUNDS_MAX_GRID = 64 };
+bt_status bt_atlas_tile_bounds(bt_atlas* atlas, uint32_t attachment_index, const uint32_t* layers /* NULL: 0 .. count-1 */,
+                               uint32_t count, uint32_t grid, uint32_t flags, uint16_t* out_host, uint64_t out_bytes);
 
 /* ------------------------------- Preprocessor (preprocess/preprocessor.rs) */
 bt_status bt_preprocessor_create(bt_ctx* ctx, bt_preprocessor** out); /* Preprocessor::new :224-232 */
