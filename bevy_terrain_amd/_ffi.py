@@ -131,6 +131,19 @@ FRAME_PREPASS_UNORDERED, FRAME_PREPASS_PLAIN, FRAME_KEEP_REQUESTS, FRAME_KEEP_HE
 BOUNDS_SKIP_ZERO, BOUNDS_MAX_GRID = 1, 64
 
 
+RAY_MISS, RAY_HIT, RAY_INSIDE, RAY_INVALID = 0, 1, 2, 3
+RAYCAST_MAX_STEPS, RAYCAST_MAX_REFINE_ROUNDS, RAYCAST_MAX_SAMPLES = 65536, 4, 1 << 24
+
+
+class RayC(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
+class RayHitC(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("step", C.c_uint32), ("t", C.c_double), ("t_above", C.c_double), ("position", C.c_double * 3),
+                ("height", C.c_float), ("_padding", C.c_uint32)]
+
+
 class TileTreeEntryC(C.Structure):
     _fields_ = [("atlas_index", C.c_uint32), ("atlas_lod", C.c_uint32)]
 
@@ -243,6 +256,7 @@ PROTOTYPES = {
     "bt_tile_tree_sample_attachment": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_float), _P(C.c_float)]),
     "bt_tile_tree_approximate_height": (_i32, [_vp, _vp, _P(C.c_float)]),
     "bt_tile_tree_view_state": (_i32, [_vp, _P(ViewStateC)]),
+    "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
     "bt_frame_update": (_i32, [_vp, _vp, _vp, _P(C.c_double), C.c_uint32, _P(FrameInfoC)]),
     "bt_selftest": (_i32, [_vp, _P(_u32)]),
     "bt_synth_fbm_r16": (_i32, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _u32, _u32]),

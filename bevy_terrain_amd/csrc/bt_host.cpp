@@ -293,6 +293,7 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     for (auto& kept : ctx->spare_rasters) hipFree(kept.first);
     if (ctx->bounds_dev) hipFree(ctx->bounds_dev);
     if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
+    if (ctx->raycast_dev) hipFree(ctx->raycast_dev);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->save_stream) hipStreamDestroy(ctx->save_stream);
     delete ctx;
@@ -343,6 +344,12 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
     if (ctx->bounds_dev || ctx->bounds_host) freed += 2u * ctx->bounds_bytes;
     ctx->bounds_dev = ctx->bounds_host = nullptr;
     ctx->bounds_bytes = 0;
+    if (ctx->raycast_dev) {
+        BT_HIP(hipFree(ctx->raycast_dev));
+        freed += ctx->raycast_bytes;
+    }
+    ctx->raycast_dev = nullptr;
+    ctx->raycast_bytes = 0;
     if (freed_bytes) *freed_bytes = freed;
     return BT_OK;
 }

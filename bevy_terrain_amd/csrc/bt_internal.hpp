@@ -200,6 +200,9 @@ struct bt_ctx {
     void* bounds_dev = nullptr;
     void* bounds_host = nullptr;
     uint64_t bounds_bytes = 0;
+    // bt_tile_tree_raycast: the rays and the hits of one call on the device (grown on demand, kept until bt_ctx_trim)
+    void* raycast_dev = nullptr;
+    uint64_t raycast_bytes = 0;
 };
 
 namespace bt {

@@ -18,6 +18,7 @@
 
 #include "bt_internal.hpp"
 #include "bt_model.hpp"
+#include "bt_tile_tree_device.hpp"
 
 using namespace bt;
 using namespace bt::model;
@@ -31,15 +32,6 @@ constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 struct NodeState {  // TileState of the tree (tile_tree.rs:28-43)
     bt_tile_coordinate coordinate;
     uint32_t requested;  // RequestState::Requested
-};
-
-struct TreeParams {
-    Model model;
-    uint32_t lod_count, tree_size, sides;
-    double load_distance, blend_distance;
-    float blend_range, approximate_height;
-    V3 view_world_position;
-    Coordinate view_coordinate[6];  // the view coordinate projected to every side
 };
 
 // One device copy of TileAtlasState::tile_states: open addressing, linear probing; key = coordinate
@@ -178,77 +170,7 @@ __global__ __launch_bounds__(256) void tile_tree_adjust_kernel(const NodeState* 
 
 // ---- sampling ----------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ float unorm16_to_float(uint32_t t) {
-    const float x = float(t), r = 1.0f / 65535.0f;
-    const float q0 = x * r;
-    return __builtin_fmaf(__builtin_fmaf(-q0, 65535.0f, x), r, q0);
-}
-__device__ __forceinline__ float unorm8_to_float(uint32_t t) {
-    const float x = float(t), r = 1.0f / 255.0f;
-    const float q0 = x * r;
-    return __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, x), r, q0);
-}
-
-struct Lookup {  // TileLookup (tile_tree.rs:67-81)
-    uint32_t atlas_index, atlas_lod;
-    float uv[2];
-};
-
-// TileTree::lookup_tile (tile_tree.rs:241-266)
-__device__ __forceinline__ Lookup lookup_tile(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, V3 world_position, uint32_t tree_lod) {
-    const Coordinate c = coordinate_from_world_position(world_position, P.model);
-    const double tile_count = double(1u << tree_lod);
-    const V2 t = compute_tree_xy(c, tile_count);
-    const uint32_t ts = P.tree_size;
-    const uint64_t ix = uint64_t(t.x), iy = uint64_t(t.y);  // `as usize` (non-negative here)
-    const bt_tile_tree_entry e = entries[((c.side * P.lod_count + tree_lod) * ts + uint32_t(ix % ts)) * ts + uint32_t(iy % ts)];
-    if (e.atlas_lod == BT_INVALID_LOD) return {BT_INVALID_ATLAS_INDEX, BT_INVALID_LOD, {0.0f, 0.0f}};
-    const double div = double(1u << (tree_lod - e.atlas_lod));
-    const double qx = t.x / div, qy = t.y / div;
-    return {e.atlas_index, e.atlas_lod, {float(qx - trunc(qx)), float(qy - trunc(qy))}};  // `% 1.0`, as_vec2
-}
-
-// AtlasAttachment::sample + AttachmentData::sample (tile_atlas.rs:249-258, terrain_data/mod.rs:220-263); the same
-// code as bt_kernels.hip sample_kernel
-__device__ __forceinline__ void sample_lookup(const AttachmentMeta& m, const void* __restrict__ atlas, const Lookup& l, float r[4]) {
-    if (l.atlas_index >= m.atlas_size) {
-        r[0] = r[1] = r[2] = r[3] = 0.0f;
-        return;
-    }
-    const uint32_t T = m.texture_size;
-    const float scale = float(m.center_size) / float(T), offset = float(m.border_size) / float(T);
-    float rem[2];
-    int ixy[2];
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        const float u = l.uv[a] * scale + offset;
-        const float uv = u * float(T) - 0.5f;
-        rem[a] = fmodf(uv, 1.0f);
-        ixy[a] = int(uv);
-    }
-    float v[2][2][4];
-#pragma unroll
-    for (int x = 0; x < 2; x++)
-#pragma unroll
-        for (int y = 0; y < 2; y++) {
-            const uint32_t px = uint32_t(min(max(ixy[0] + x, 0), int(T) - 1)), py = uint32_t(min(max(ixy[1] + y, 0), int(T) - 1));
-            const uint64_t index = uint64_t(l.atlas_index) * T * T + uint64_t(py) * T + px;
-            if (m.format == BT_FORMAT_R16) {
-                v[x][y][0] = unorm16_to_float(((const uint16_t*)atlas)[index]);
-                v[x][y][1] = v[x][y][2] = v[x][y][3] = 0.0f;
-            } else {
-                const uint32_t t = ((const uint32_t*)atlas)[index];
-#pragma unroll
-                for (int k = 0; k < 4; k++) v[x][y][k] = unorm8_to_float((t >> (8 * k)) & 0xFFu);
-            }
-        }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float a = v[0][0][k] + (v[0][1][k] - v[0][0][k]) * rem[1];
-        const float b = v[1][0][k] + (v[1][1][k] - v[1][0][k]) * rem[1];
-        r[k] = a + (b - a) * rem[0];
-    }
-}
+// (lookup_tile, sample_lookup and the blend of the two lookups: bt_tile_tree_device.hpp, shared with bt_raycast.hip)
 
 // sample_attachment / sample_height (terrain_data/mod.rs:265-307), one world position per thread
 __global__ __launch_bounds__(128) void tile_tree_sample_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
@@ -259,28 +181,10 @@ __global__ __launch_bounds__(128) void tile_tree_sample_kernel(TreeParams P, con
     const float approximate_height = height ? *height : P.approximate_height;
     const V3 p = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
     const V3 surface = surface_position(P.model, p, double(approximate_height));
-    // compute_blend (tile_tree.rs:223-239)
-    const double view_distance = distance3(P.view_world_position, surface);
-    const double cap = double(P.lod_count) - 0.00001;
-    const double l2 = log2(P.blend_distance / view_distance);
-    const float target_lod = float(l2 < cap ? l2 : cap);
-    const uint32_t lod = !(target_lod > 0.0f) ? 0u : uint32_t(target_lod);  // `as u32` saturates
-    float ratio = 0.0f;
-    if (lod != 0) {  // inverse_mix(lod + blend_range, lod, target_lod) (util.rs:8-10)
-        const float a = float(lod) + P.blend_range, b = float(lod);
-        const float q = (target_lod - a) / (b - a);
-        ratio = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
-    }
     float value[4];
-    sample_lookup(m, atlas, lookup_tile(P, entries, surface, lod), value);
-    if (ratio > 0.0f) {
-        float value2[4];
-        sample_lookup(m, atlas, lookup_tile(P, entries, surface, lod - 1u), value2);
-#pragma unroll
-        for (int k = 0; k < 4; k++) value[k] = value[k] + (value2[k] - value[k]) * ratio;  // Vec4::lerp
-    }
+    sample_surface(P, entries, m, atlas, surface, value);
     out[i] = make_float4(value[0], value[1], value[2], value[3]);
-    if (heights) heights[i] = P.model.min_height + (P.model.max_height - P.model.min_height) * value[0];  // f32::lerp
+    if (heights) heights[i] = height_of_value(P.model, value[0]);
 }
 
 }  // namespace
@@ -609,6 +513,66 @@ bt_status bt_tile_tree_sample_attachment(bt_tile_tree* t, bt_atlas* a, uint32_t 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     hipFree(dev);
     if (e != hipSuccess) return hip_fail(e, "bt_tile_tree_sample_attachment");
+    return BT_OK;
+}
+
+bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds,
+                               bt_ray_hit* hits) {
+    if (!t || !a) {
+        set_error("bt_tile_tree_raycast: NULL %s", t ? "atlas" : "tile tree");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (t->ctx != a->ctx) {
+        set_error("bt_tile_tree_raycast: tile tree and atlas belong to different contexts");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (ai >= a->attachments.size()) {
+        set_error("bt_tile_tree_raycast: attachment index %u out of range", ai);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("bt_tile_tree_raycast: attachment %u is not R16", ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (steps < 1u || steps > uint32_t(BT_RAYCAST_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
+        set_error("bt_tile_tree_raycast: steps %u (1 .. %u) / refine_rounds %u (at most %u)", steps, unsigned(BT_RAYCAST_MAX_STEPS), refine_rounds,
+                  unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a ray costs whole rounds of 64 samples (one wave per ray): that is what the cap counts
+    const uint64_t rounds = (uint64_t(steps) + 1u + 63u) / 64u;
+    if (uint64_t(count) * rounds * 64u > uint64_t(BT_RAYCAST_MAX_SAMPLES)) {
+        set_error("bt_tile_tree_raycast: %u rays x %u rounds of 64 samples exceed BT_RAYCAST_MAX_SAMPLES (%u): split the batch", count, unsigned(rounds),
+                  unsigned(BT_RAYCAST_MAX_SAMPLES));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!count) return BT_OK;
+    if (!rays || !hits) {
+        set_error("bt_tile_tree_raycast: NULL %s", rays ? "hits_out" : "rays");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t in_bytes = sizeof(bt_ray) * uint64_t(count), out_bytes = sizeof(bt_ray_hit) * uint64_t(count);
+    if (ctx->raycast_bytes < in_bytes + out_bytes) {
+        if (ctx->raycast_dev) BT_HIP(hipFree(ctx->raycast_dev));
+        ctx->raycast_dev = nullptr;
+        ctx->raycast_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->raycast_dev, in_bytes + out_bytes));
+        ctx->raycast_bytes = in_bytes + out_bytes;
+    }
+    uint8_t* dev = (uint8_t*)ctx->raycast_dev;
+    BT_HIP(hipMemcpyAsync(dev, rays, in_bytes, hipMemcpyHostToDevice, s));
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    if (bt_status st = launch_raycast(s, make_params(t), t->d_entries, at.meta, at.level0, (const bt_ray*)dev, count, steps, refine_rounds,
+                                      (bt_ray_hit*)(dev + in_bytes), t->d_height))
+        return st;
+    BT_HIP(hipMemcpyAsync(hits, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
+    BT_HIP(hipStreamSynchronize(s));
+    adopt_height(t);
+    t->table_copy_pending = false;
     return BT_OK;
 }
 

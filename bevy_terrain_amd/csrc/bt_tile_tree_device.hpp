@@ -1,0 +1,132 @@
+// Device half of sample_attachment / sample_height (terrain_data/mod.rs:265-307) shared by the kernels that sample the
+// terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip) and raycast_kernel (bt_raycast.hip).  One
+// definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there, bit for bit.
+//
+// Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
+// where the reference defers to glam / libm.  compute_blend's log2 is the platform's (OCML here, libm in the oracle).
+#pragma once
+
+#include "bt_internal.hpp"
+#include "bt_model.hpp"
+
+namespace bt {
+
+struct TreeParams {
+    model::Model model;
+    uint32_t lod_count, tree_size, sides;
+    double load_distance, blend_distance;
+    float blend_range, approximate_height;
+    model::V3 view_world_position;
+    model::Coordinate view_coordinate[6];  // the view coordinate projected to every side
+};
+
+// bt_raycast.hip: `count` rays (device) against the tree's entries and one R16 attachment -> hits (device); height: the tree's device copy
+// of approximate_height (may be NULL: P.approximate_height)
+bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                         const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits, const float* height);
+
+#if defined(__HIPCC__)
+
+__device__ __forceinline__ float unorm16_to_float(uint32_t t) {
+    const float x = float(t), r = 1.0f / 65535.0f;
+    const float q0 = x * r;
+    return __builtin_fmaf(__builtin_fmaf(-q0, 65535.0f, x), r, q0);
+}
+__device__ __forceinline__ float unorm8_to_float(uint32_t t) {
+    const float x = float(t), r = 1.0f / 255.0f;
+    const float q0 = x * r;
+    return __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, x), r, q0);
+}
+
+struct Lookup {  // TileLookup (tile_tree.rs:67-81)
+    uint32_t atlas_index, atlas_lod;
+    float uv[2];
+};
+
+// TileTree::lookup_tile (tile_tree.rs:241-266)
+__device__ __forceinline__ Lookup lookup_tile(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, model::V3 world_position, uint32_t tree_lod) {
+    const model::Coordinate c = model::coordinate_from_world_position(world_position, P.model);
+    const double tile_count = double(1u << tree_lod);
+    const model::V2 t = model::compute_tree_xy(c, tile_count);
+    const uint32_t ts = P.tree_size;
+    const uint64_t ix = uint64_t(t.x), iy = uint64_t(t.y);  // `as usize` (non-negative here)
+    const bt_tile_tree_entry e = entries[((c.side * P.lod_count + tree_lod) * ts + uint32_t(ix % ts)) * ts + uint32_t(iy % ts)];
+    if (e.atlas_lod == BT_INVALID_LOD) return {BT_INVALID_ATLAS_INDEX, BT_INVALID_LOD, {0.0f, 0.0f}};
+    const double div = double(1u << (tree_lod - e.atlas_lod));
+    const double qx = t.x / div, qy = t.y / div;
+    return {e.atlas_index, e.atlas_lod, {float(qx - trunc(qx)), float(qy - trunc(qy))}};  // `% 1.0`, as_vec2
+}
+
+// AtlasAttachment::sample + AttachmentData::sample (tile_atlas.rs:249-258, terrain_data/mod.rs:220-263); the same
+// code as bt_kernels.hip sample_kernel
+__device__ __forceinline__ void sample_lookup(const AttachmentMeta& m, const void* __restrict__ atlas, const Lookup& l, float r[4]) {
+    if (l.atlas_index >= m.atlas_size) {
+        r[0] = r[1] = r[2] = r[3] = 0.0f;
+        return;
+    }
+    const uint32_t T = m.texture_size;
+    const float scale = float(m.center_size) / float(T), offset = float(m.border_size) / float(T);
+    float rem[2];
+    int ixy[2];
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        const float u = l.uv[a] * scale + offset;
+        const float uv = u * float(T) - 0.5f;
+        rem[a] = fmodf(uv, 1.0f);
+        ixy[a] = int(uv);
+    }
+    float v[2][2][4];
+#pragma unroll
+    for (int x = 0; x < 2; x++)
+#pragma unroll
+        for (int y = 0; y < 2; y++) {
+            const uint32_t px = uint32_t(min(max(ixy[0] + x, 0), int(T) - 1)), py = uint32_t(min(max(ixy[1] + y, 0), int(T) - 1));
+            const uint64_t index = uint64_t(l.atlas_index) * T * T + uint64_t(py) * T + px;
+            if (m.format == BT_FORMAT_R16) {
+                v[x][y][0] = unorm16_to_float(((const uint16_t*)atlas)[index]);
+                v[x][y][1] = v[x][y][2] = v[x][y][3] = 0.0f;
+            } else {
+                const uint32_t t = ((const uint32_t*)atlas)[index];
+#pragma unroll
+                for (int k = 0; k < 4; k++) v[x][y][k] = unorm8_to_float((t >> (8 * k)) & 0xFFu);
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float a = v[0][0][k] + (v[0][1][k] - v[0][0][k]) * rem[1];
+        const float b = v[1][0][k] + (v[1][1][k] - v[1][0][k]) * rem[1];
+        r[k] = a + (b - a) * rem[0];
+    }
+}
+
+// sample_attachment (terrain_data/mod.rs:265-295) from the surface position on: compute_blend, the lookups at lod and lod - 1,
+// their samples and the blend.  surface = surface_position(model, sample position, approximate_height).
+__device__ __forceinline__ void sample_surface(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
+                                               const void* __restrict__ atlas, model::V3 surface, float value[4]) {
+    // compute_blend (tile_tree.rs:223-239)
+    const double view_distance = model::distance3(P.view_world_position, surface);
+    const double cap = double(P.lod_count) - 0.00001;
+    const double l2 = log2(P.blend_distance / view_distance);
+    const float target_lod = float(l2 < cap ? l2 : cap);
+    const uint32_t lod = !(target_lod > 0.0f) ? 0u : uint32_t(target_lod);  // `as u32` saturates
+    float ratio = 0.0f;
+    if (lod != 0) {  // inverse_mix(lod + blend_range, lod, target_lod) (util.rs:8-10)
+        const float a = float(lod) + P.blend_range, b = float(lod);
+        const float q = (target_lod - a) / (b - a);
+        ratio = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
+    }
+    sample_lookup(m, atlas, lookup_tile(P, entries, surface, lod), value);
+    if (ratio > 0.0f) {
+        float value2[4];
+        sample_lookup(m, atlas, lookup_tile(P, entries, surface, lod - 1u), value2);
+#pragma unroll
+        for (int k = 0; k < 4; k++) value[k] = value[k] + (value2[k] - value[k]) * ratio;  // Vec4::lerp
+    }
+}
+
+// sample_height's last step (terrain_data/mod.rs:297-307): f32::lerp(min_height, max_height, value.x)
+__device__ __forceinline__ float height_of_value(const model::Model& model, float value) { return model.min_height + (model.max_height - model.min_height) * value; }
+
+#endif  // __HIPCC__
+
+}  // namespace bt

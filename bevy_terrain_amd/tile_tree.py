@@ -48,6 +48,12 @@ def view_state_from_config(model: TerrainModel, view_config: TerrainViewConfig, 
     return v
 
 
+# numpy mirrors of bt_ray / bt_ray_hit (include/bevy_terrain_amd.h)
+RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("direction", np.float64, 3), ("t_min", np.float64), ("t_max", np.float64)])
+RAY_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.float64), ("t_above", np.float64), ("position", np.float64, 3),
+                          ("height", np.float32), ("_padding", np.uint32)])
+
+
 class TileTree:
     def __init__(self, tile_atlas: TileAtlas, model: TerrainModel, lod_count: int, view_config: TerrainViewConfig):
         self.atlas = tile_atlas
@@ -108,6 +114,21 @@ class TileTree:
             out.ctypes.data_as(C.POINTER(C.c_float)), heights.ctypes.data_as(C.POINTER(C.c_float))))
         return out, heights
 
+    def raycast(self, attachment_index: int, origins, directions, t_min, t_max, steps: int = 256, refine_rounds: int = 2) -> np.ndarray:
+        """bt_tile_tree_raycast: one launch for the whole batch.  origins / directions (n, 3), t_min / t_max scalars or (n,); returns a
+        structured array (RAY_HIT_DTYPE): status (_ffi.RAY_*), step, t, t_above, position, height."""
+        origins = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+        n = len(origins)
+        rays = np.zeros(n, RAY_DTYPE)
+        rays["origin"] = origins
+        rays["direction"] = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+        rays["t_min"] = t_min
+        rays["t_max"] = t_max
+        hits = np.zeros(n, RAY_HIT_DTYPE)
+        _ffi.check(_ffi.lib().bt_tile_tree_raycast(self._h, self.atlas._h, attachment_index, rays.ctypes.data_as(C.POINTER(_ffi.RayC)), n, steps,
+                                                   refine_rounds, hits.ctypes.data_as(C.POINTER(_ffi.RayHitC))))
+        return hits
+
     def approximate_height(self) -> float:
         h = C.c_float()
         _ffi.check(_ffi.lib().bt_tile_tree_approximate_height(self._h, self.atlas._h, C.byref(h)))
@@ -149,3 +170,13 @@ def sample_attachment(tile_tree: TileTree, tile_atlas: TileAtlas, attachment_ind
 
 def sample_height(tile_tree: TileTree, tile_atlas: TileAtlas, sample_world_position) -> float:
     return float(tile_tree.sample_attachment(0, np.asarray([sample_world_position]))[1][0])
+
+
+def raycast_terrain(tile_tree: TileTree, tile_atlas: TileAtlas, origin, direction, max_distance: float, steps: int = 256, refine_rounds: int = 2):
+    """One ray from `origin` along `direction` (normalised here) up to `max_distance` against the height attachment: the world position where
+    it meets the ground and the distance to it, or None when it does not (an origin under the ground meets it at distance 0)."""
+    d = np.asarray(direction, dtype=np.float64)
+    hit = tile_tree.raycast(0, [origin], [d / np.linalg.norm(d)], 0.0, max_distance, steps, refine_rounds)[0]
+    if hit["status"] not in (_ffi.RAY_HIT, _ffi.RAY_INSIDE):
+        return None
+    return tuple(float(v) for v in hit["position"]), float(hit["t"])

@@ -169,7 +169,8 @@ void* bt_ctx_stream(const bt_ctx* ctx);
 bt_status bt_ctx_synchronize(bt_ctx* ctx);
 /* Gives back what the context keeps between queues: the device rasters finished queues released (kept so that the next queue's
  * sources need not be allocated again: 0.5 GB for a 16k R16 raster, six of 128 MB for a cube job; at most 8 buffers and 4 GiB) and
- * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds.
+ * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds,
+ * the device scratch of bt_tile_tree_raycast.
  * Synchronises the context's stream first.  `freed_bytes` (may be NULL): device + pinned bytes released. */
 bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes);
 /* Host threads that write (bt_preprocessor_save / _run_streamed) and read (bt_atlas_load_tiles) tile files for this context.
@@ -606,6 +607,57 @@ bt_status bt_tile_tree_sample_attachment(bt_tile_tree* tree, bt_atlas* atlas, ui
 bt_status bt_tile_tree_approximate_height(bt_tile_tree* tree, bt_atlas* atlas, float* height);
 /* the tree's current state as a prepass input (bt_view_state_from_config with the tree's view position / height) */
 bt_status bt_tile_tree_view_state(const bt_tile_tree* tree, bt_view_state* out);
+
+/* Batched ray queries against the terrain ("where does this ray meet the ground": picking, line of sight, collision).  The reference has
+ * no ray query; the ground is wherever its sample_height says it is, LOD blending and best-loaded-tile fallback included, so a hit agrees
+ * with bt_tile_tree_sample_attachment at the hit point bit for bit.
+ *
+ * For a world point p, the tree's current state (view position, approximate height, entries) and the terrain model m, in this order
+ * (IEEE binary64, one rounding per written operation; dot3 / normalize3 = (x*x + y*y) + z*z, v * (1.0 / length)):
+ *     local    = position_world_to_local(m, p)
+ *     n        = normalize3(transform_vector(m, spherical ? local : (0, 1, 0)))
+ *     ground0  = position_local_to_world(m, local, 0.0)
+ *     altitude = dot3(p - ground0, n)
+ *     h        = the `heights` value bt_tile_tree_sample_attachment returns for p (f32; an unloaded tile samples as 0: h = min_height)
+ *     f(p)     = altitude - double(h)
+ * n is the direction along which position_local_to_world displaces the surface by a height, so altitude and h are measured along one
+ * line (on an ellipsoid that is not exactly the geometric normal, by the reference's choice).  A NaN f compares false: not hit.
+ *
+ * A ray is p(t) = origin + t * direction (one multiply, one add per component) for t in [t_min, t_max]; the direction need not be
+ * normalised.  With N = steps and R = refine_rounds:
+ *   coarse march: dt = (t_max - t_min) / double(N), t_i = t_min + double(i) * dt for i = 0 .. N; the hit step is the smallest i with
+ *     f(p(t_i)) <= 0.  None: BT_RAY_MISS.  i == 0: BT_RAY_INSIDE, t = t_above = t_min.  Otherwise BT_RAY_HIT, lo = t_(i-1), hi = t_i;
+ *   R refinement rounds: u_k = lo + (hi - lo) * (double(k) / 64.0) for k = 1 .. 63; k* = the smallest k with f(p(u_k)) <= 0, or 64;
+ *     then hi = (k* == 64 ? hi : u_k*), lo = (k* == 1 ? lo : u_(k*-1)), both from the values before the round;
+ *   t = hi, t_above = lo: f(p(t)) <= 0 and, for a hit, f(p(t_above)) > 0, with t - t_above about dt / 64^R.
+ * A ray with a non-finite component, a zero direction, a non-finite bound or t_max < t_min is BT_RAY_INVALID and is not marched.
+ * BT_RAY_MISS and BT_RAY_INVALID leave every other field of the hit 0.
+ *
+ * Limits, checked before anything is queued (BT_ERR_INVALID_ARGUMENT): 1 <= steps <= BT_RAYCAST_MAX_STEPS, refine_rounds <=
+ * BT_RAYCAST_MAX_REFINE_ROUNDS, and count * 64 * ceil((steps + 1) / 64) <= BT_RAYCAST_MAX_SAMPLES: a ray's samples are counted in whole
+ * rounds of 64, which is what the kernel spends (one wave per ray, 64 samples per round, a round with two active lanes costs what a
+ * full one does); it implies count * (steps + 1) <= BT_RAYCAST_MAX_SAMPLES.  So at most 262144 rays per call (steps <= 63), 255 at
+ * steps 65536; split larger batches.  The longest launch the limits allow is measured in DESIGN.md 3.11.
+ * Non-R16 attachments: BT_ERR_UNSUPPORTED.  count == 0: BT_OK, nothing touched.  One launch, ordered behind the work queued on the context's
+ * stream; synchronous (host arrays in and out); a read (not a write for bt_run_stats.prev_zero_launches).  Scratch (120 bytes of device
+ * memory per ray of the largest batch so far, at most 30 MiB) stays in the context until bt_ctx_trim. */
+enum { BT_RAY_MISS = 0, BT_RAY_HIT = 1, BT_RAY_INSIDE = 2, BT_RAY_INVALID = 3 };
+enum { BT_RAYCAST_MAX_STEPS = 65536, BT_RAYCAST_MAX_REFINE_ROUNDS = 4, BT_RAYCAST_MAX_SAMPLES = 16777216 };
+typedef struct bt_ray {
+    double origin[3];
+    double direction[3];
+    double t_min, t_max;
+} bt_ray;
+typedef struct bt_ray_hit {
+    uint32_t status; /* BT_RAY_* */
+    uint32_t step;   /* the hit step i of the coarse march */
+    double t, t_above;
+    double position[3]; /* p(t) */
+    float height;       /* h sampled at p(t) */
+    uint32_t _padding;
+} bt_ray_hit;
+bt_status bt_tile_tree_raycast(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_ray* rays, uint32_t count,
+                               uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits_out);
 
 /* One frame of one view (src/plugin.rs:46-56: TileTree::compute_requests -> TileAtlas::update's release / request half ->
  * TileTree::adjust_to_tile_atlas -> TileTree::approximate_height -> TilingPrepassNode::run) as ONE call with ONE host

@@ -1,9 +1,9 @@
 #!/bin/bash
-# Register / scratch / LDS use of every kernel of bt_fused.hip as compiled for gfx950 (the metadata the assembler emits):
-#   tools/kernel_resources.sh [pattern]
+# Register / scratch / LDS use of every kernel of a source file (default bt_fused.hip) as compiled for gfx950 (the metadata the assembler emits):
+#   tools/kernel_resources.sh [pattern] [source.hip]          e.g. tools/kernel_resources.sh raycast bt_raycast.hip
 R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/bevy_terrain_amd/csrc
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I../../include -I. -S --cuda-device-only -o /tmp/bt_fused_gfx950.s bt_fused.hip 2>/dev/null
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I../../include -I. -S --cuda-device-only -o /tmp/bt_fused_gfx950.s "${2:-bt_fused.hip}" 2>/dev/null
 python3 - "$1" <<'PY'
 import re, sys
 text = open("/tmp/bt_fused_gfx950.s").read()
