@@ -144,6 +144,14 @@ class RayHitC(C.Structure):
                 ("height", C.c_float), ("_padding", C.c_uint32)]
 
 
+class CullViewC(C.Structure):
+    _fields_ = [("planes", (C.c_float * 4) * 5), ("plane_count", C.c_uint32), ("margin", C.c_float), ("min_height", C.c_float),
+                ("max_height", C.c_float)]
+
+
+HEIGHT_BOUNDS_MAX_LEVELS = 11
+
+
 class TileTreeEntryC(C.Structure):
     _fields_ = [("atlas_index", C.c_uint32), ("atlas_lod", C.c_uint32)]
 
@@ -243,6 +251,14 @@ PROTOTYPES = {
     "bt_tiling_prepass_set_window": (_i32, [_vp, _u32]),
     "bt_tiling_prepass_buffers": (_i32, [_vp, _P(_vp), _P(_vp)]),
     "bt_tiling_prepass_read": (_i32, [_vp, _P(TileCoordinateC), _u32, _P(_u32), _P(IndirectC)]),
+    "bt_height_bounds_create": (_i32, [_vp, _u32, _u32, _P(_vp)]),
+    "bt_height_bounds_destroy": (None, [_vp]),
+    "bt_height_bounds_build": (_i32, [_vp, _vp, _u32]),
+    "bt_height_bounds_read": (_i32, [_vp, _P(C.c_uint16), _u64]),
+    "bt_height_bounds_write": (_i32, [_vp, _P(C.c_uint16), _u64]),
+    "bt_cull_planes": (None, [_P(C.c_float), _P(C.c_float)]),
+    "bt_tiling_prepass_set_culling": (_i32, [_vp, _P(CullViewC), _vp]),
+    "bt_tiling_prepass_cull_stats": (_i32, [_vp, _P(_u32), _P(_u32)]),
     "bt_terrain_view_config_default": (None, [_P(TerrainViewConfigC)]),
     "bt_view_state_from_config": (_i32, [_P(TerrainModelC), _P(TerrainViewConfigC), _P(C.c_double), C.c_float, _P(ViewStateC)]),
     "bt_tile_tree_create": (_i32, [_vp, _P(TerrainModelC), _u32, _P(TerrainViewConfigC), _P(_vp)]),

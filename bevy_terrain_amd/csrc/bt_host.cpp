@@ -1318,6 +1318,128 @@ bt_status bt_atlas_tile_bounds(bt_atlas* a, uint32_t ai, const uint32_t* layers,
     return BT_OK;  // a read: Attachment::written stays as it is
 }
 
+// ---- the height-bounds table of the culling test (bt_height_bounds; read by bt_refine.hip's tile_culled) ----
+
+bt_status bt_height_bounds_create(bt_ctx* ctx, uint32_t sides, uint32_t levels, bt_height_bounds** out) {
+    if (!ctx || !out || (sides != 1u && sides != 6u) || levels < 1u || levels > BT_HEIGHT_BOUNDS_MAX_LEVELS) {
+        set_error("bt_height_bounds_create: %s", !ctx ? "NULL context" : !out ? "NULL out" : "sides is 1 or 6, levels 1..11");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    BT_HIP(hipSetDevice(ctx->device));
+    bt_height_bounds* b = new bt_height_bounds();
+    b->ctx = ctx;
+    b->sides = sides;
+    b->levels = levels;
+    b->entries = height_bounds_offset(sides, levels);
+    hipError_t e = hipMalloc((void**)&b->table, b->entries * 4u);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)b->table, int(0xFFFF0000u), b->entries, ctx->stream);  // (0, 65535)
+    if (e != hipSuccess) {
+        bt_height_bounds_destroy(b);
+        return hip_fail(e, "height bounds table");
+    }
+    *out = b;
+    return BT_OK;
+}
+
+void bt_height_bounds_destroy(bt_height_bounds* b) {
+    if (!b) return;
+    hipSetDevice(b->ctx->device);
+    if (b->table) {
+        hipStreamSynchronize(b->ctx->stream);  // a prepass that borrowed the table may still be running
+        hipFree(b->table);
+    }
+    delete b;
+}
+
+bt_status bt_height_bounds_read(const bt_height_bounds* b, uint16_t* out, uint64_t out_bytes) {
+    if (!b || !out || out_bytes < b->entries * 4u) {
+        set_error("bt_height_bounds_read: %s", !b ? "NULL table" : !out ? "NULL out_host" : "out_bytes below entries * 4");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    BT_HIP(hipSetDevice(b->ctx->device));
+    BT_HIP(hipMemcpyAsync(out, b->table, b->entries * 4u, hipMemcpyDeviceToHost, b->ctx->stream));
+    BT_HIP(hipStreamSynchronize(b->ctx->stream));
+    return BT_OK;
+}
+
+bt_status bt_height_bounds_write(bt_height_bounds* b, const uint16_t* src, uint64_t bytes) {
+    if (!b || !src || bytes != b->entries * 4u) {
+        set_error("bt_height_bounds_write: %s", !b ? "NULL table" : !src ? "NULL src_host" : "bytes is not entries * 4");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    BT_HIP(hipSetDevice(b->ctx->device));
+    BT_HIP(hipMemcpyAsync(b->table, src, bytes, hipMemcpyHostToDevice, b->ctx->stream));
+    BT_HIP(hipStreamSynchronize(b->ctx->stream));  // (src is the caller's, pageable)
+    return BT_OK;
+}
+
+bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* a, uint32_t ai) {
+    if (!b || !a || ai >= a->attachments.size()) {
+        set_error("bt_height_bounds_build: %s", !b ? "NULL table" : !a ? "NULL atlas" : "attachment index out of range");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (a->attachments[ai].meta.format != BT_FORMAT_R16) {
+        set_error("bt_height_bounds_build: attachment %u is not R16", ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (b->ctx != a->ctx || b->sides != (a->config.spherical ? 6u : 1u)) {
+        set_error("bt_height_bounds_build: %s", b->ctx != a->ctx ? "table and atlas belong to different contexts" : "the atlas's side count is not the table's");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // 1. own(tile) of every held tile: the grid-1 bounds of its layer (the existing kernel)
+    constexpr uint32_t kNone = 0x0000FFFFu;  // min > max: not held
+    std::vector<uint32_t> own(b->entries, kNone), layers, slots;
+    auto slot = [&](const bt_tile_coordinate& c) { return height_bounds_offset(b->sides, c.lod) + ((((uint64_t(c.side) << c.lod) + c.y) << c.lod) + c.x); };
+    for (const bt_tile_coordinate& c : a->existing_tiles) {
+        auto it = a->tile_states.find(c);
+        if (it == a->tile_states.end() || it->second.loading != 0 || c.lod >= b->levels || c.side >= b->sides || (c.x >> c.lod) || (c.y >> c.lod)) continue;
+        layers.push_back(it->second.atlas_index);
+        slots.push_back(uint32_t(slot(c)));
+    }
+    std::vector<uint16_t> pairs(2 * layers.size());
+    if (bt_status s = bt_atlas_tile_bounds(a, ai, layers.data(), uint32_t(layers.size()), 1u, 0u, pairs.data(), pairs.size() * 2u)) return s;
+    for (size_t i = 0; i < layers.size(); i++) own[slots[i]] = uint32_t(pairs[2 * i]) | (uint32_t(pairs[2 * i + 1]) << 16);
+    // 2. top down: a tile that is not held takes own of its parent (a root: the whole range); 3. bottom up: the union with the children
+    std::vector<uint32_t> entry(b->entries);
+    for (uint32_t l = 0; l < b->levels; l++) {
+        const uint64_t n = 1ull << l, base = height_bounds_offset(b->sides, l), parent = l ? height_bounds_offset(b->sides, l - 1u) : 0;
+        for (uint64_t side = 0; side < b->sides; side++)
+            for (uint64_t y = 0; y < n; y++)
+                for (uint64_t x = 0; x < n; x++) {
+                    uint32_t& o = own[base + (side * n + y) * n + x];
+                    if (o == kNone) o = l ? own[parent + (side * (n >> 1) + (y >> 1)) * (n >> 1) + (x >> 1)] : 0xFFFF0000u;
+                }
+    }
+    for (uint32_t l = b->levels; l-- > 0;) {
+        const uint64_t n = 1ull << l, base = height_bounds_offset(b->sides, l), child = height_bounds_offset(b->sides, l + 1u);
+        for (uint64_t side = 0; side < b->sides; side++)
+            for (uint64_t y = 0; y < n; y++)
+                for (uint64_t x = 0; x < n; x++) {
+                    uint32_t mn = own[base + (side * n + y) * n + x] & 0xFFFFu, mx = own[base + (side * n + y) * n + x] >> 16;
+                    for (uint64_t k = 0; l + 1u < b->levels && k < 4; k++) {
+                        const uint32_t e = entry[child + (side * 2 * n + 2 * y + (k >> 1)) * 2 * n + 2 * x + (k & 1)];
+                        mn = std::min(mn, e & 0xFFFFu);
+                        mx = std::max(mx, e >> 16);
+                    }
+                    entry[base + (side * n + y) * n + x] = mn | (mx << 16);
+                }
+    }
+    BT_HIP(hipSetDevice(b->ctx->device));
+    BT_HIP(hipMemcpyAsync(b->table, entry.data(), b->entries * 4u, hipMemcpyHostToDevice, b->ctx->stream));
+    BT_HIP(hipStreamSynchronize(b->ctx->stream));
+    return BT_OK;
+}
+
+// culling_bind_group.rs:25-38: row(i) of a column-major matrix is (m[i], m[4 + i], m[8 + i], m[12 + i])
+void bt_cull_planes(const float m[16], float planes[5][4]) {
+    if (!m || !planes) return;
+    for (int i = 0; i < 5; i++)
+        for (int k = 0; k < 4; k++) {
+            const float row3 = m[4 * k + 3], row = m[4 * k + i / 2];
+            planes[i][k] = ((i & 1) == 0 && i != 4) ? row3 + row : row3 - row;
+        }
+}
+
 bt_status bt_atlas_mip_storage(const bt_atlas* a, uint32_t ai, uint32_t level, void** ptr, uint64_t* tile_bytes) {
     if (!a || ai >= a->attachments.size() || level >= a->attachments[ai].mips.size()) return BT_ERR_INVALID_ARGUMENT;
     const Attachment& at = a->attachments[ai];

@@ -347,6 +347,11 @@ inline uint32_t shard_holder(const ::bt_preprocessor* p, uint32_t attachment, ui
 }
 }  // namespace bt
 
+// bt_height_bounds (the min/max height table of the culling test, declared in the header): level l starts at height_bounds_offset(sides, l)
+namespace bt {
+inline uint64_t height_bounds_offset(uint32_t sides, uint32_t level) { return uint64_t(sides) * (((1ull << (2u * level)) - 1u) / 3u); }
+}  // namespace bt
+
 namespace bt {
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

@@ -23,11 +23,15 @@ struct bt_tiling_prepass {
     bt_tile_coordinate* temporary_tiles = nullptr;
     bt_tile_coordinate* final_tiles = nullptr;
     bt_indirect* indirect = nullptr;
-    uint32_t* counters = nullptr;  // [0] final count, [1] overflow flag, [2] tiles visited, [3] passes; unordered form: [8..40) tiles visited per LOD, [40..72) dividing tiles per LOD
-    unsigned long long* bits = nullptr;  // divide bits of every (side, lod) window (allocated on first use)
+    uint32_t* counters = nullptr;  // [0] final count, [1] overflow flag, [2] tiles visited, [3] passes, [4] tiles culled; unordered form: [8..40) tiles visited per LOD, [40..72) dividing tiles per LOD
+    unsigned long long* bits = nullptr;  // divide bits of every (side, lod) window, then their cull bits (allocated on first use)
     int window = 0;                      // window radius of the unordered form (0 = the default, kWinK)
     bool unordered = false;              // the last run was the unordered form: read() derives counters [1..3] from the per-LOD counts
     uint32_t unordered_capacity = 0;
+    bool cull_set = false;                     // bt_tiling_prepass_set_culling
+    bt_cull_view cull{};
+    const bt_height_bounds* bounds = nullptr;  // borrowed
+    bool culled_run = false;                   // the last run culled: counters[4] is its count
 };
 
 namespace bt {
@@ -65,24 +69,14 @@ __device__ __forceinline__ void coordinate_change_lod(Coordinate& c, uint32_t ne
 
 __device__ __forceinline__ float length3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
 
-// refine_tiles.wgsl:17-22 -> compute_subdivision_coordinate (functions.wgsl:133-154) ->
-// approximate_view_distance (:117-131) -> compute_local_position (:73-96)
-// approximate_height: the view's (bt_view_state::approximate_height), or the value bt_frame_update left on the device — passed
-// beside the view: writing it into the by-value kernel argument makes the compiler copy the whole struct to scratch (224 bytes,
-// 14 -> 52 VGPRs in the divide-bits kernel: measured, round 4)
-__device__ bool should_be_divided(const bt_view_state& v, const bt_tile_coordinate& tile, float approximate_height) {
-    Coordinate vc{tile.side, v.origin_lod, uint32_t(v.sides[tile.side].view_xy[0]), uint32_t(v.sides[tile.side].view_xy[1]),
-                  v.sides[tile.side].view_uv[0], v.sides[tile.side].view_uv[1]};
-    coordinate_change_lod(vc, tile.lod);
-    const int off_x = int(vc.x) - int(tile.x), off_y = int(vc.y) - int(tile.y);
-    const float uv_x = off_x < 0 ? 0.0f : (off_x > 0 ? 1.0f : vc.u);
-    const float uv_y = off_y < 0 ? 0.0f : (off_y > 0 ? 1.0f : vc.v);
+// A point of a tile's surface and the normal there: compute_local_position (functions.wgsl:73-96) of the tile coordinate (u, w) =
+// (tile xy + uv) / tile_count, then position_local_to_world / normal_local_to_world (:117-121).  point(tile, uv, h) = world + h * normal:
+// the divide test's and the culling test's (include/bevy_terrain_amd.h).
+struct SurfacePoint {
+    float wx, wy, wz, nx, ny, nz;
+};
 
-    // tile_count(lod) = 2^lod: x / 2^lod == x * 2^-lod bit for bit (no underflow at these magnitudes), and so is / 0.5 == * 2 —
-    // five of the function's eleven IEEE divisions (each ~10 instructions, and this kernel is one CU's VALU)
-    const float inv_tc = __builtin_bit_cast(float, (127u - tile.lod) << 23);
-    float u = (float(tile.x) + uv_x) * inv_tc;
-    float w = (float(tile.y) + uv_y) * inv_tc;
+__device__ __forceinline__ SurfacePoint tile_surface(const bt_view_state& v, uint32_t side, float u, float w) {
     float lx, ly, lz;
     if (v.spherical) {
         const float C_SQR = 0.87f * 0.87f;
@@ -90,7 +84,7 @@ __device__ bool should_be_divided(const bt_view_state& v, const bt_tile_coordina
         w = (w - 0.5f) * 2.0f;
         u = u / sqrtf(1.0f + C_SQR - C_SQR * u * u);
         w = w / sqrtf(1.0f + C_SQR - C_SQR * w * w);
-        switch (tile.side) {
+        switch (side) {
             case 0: lx = -1.0f; ly = -w; lz = u; break;
             case 1: lx = u; ly = -w; lz = 1.0f; break;
             case 2: lx = u; ly = 1.0f; lz = w; break;
@@ -108,24 +102,103 @@ __device__ bool should_be_divided(const bt_view_state& v, const bt_tile_coordina
         ly = 0.0f;
         lz = w - 0.5f;
     }
+    SurfacePoint p;
     const float* m = v.world_from_local;  // 3 columns + translation
-    const float wx = (m[0] * lx + m[3] * ly + m[6] * lz) + m[9];
-    const float wy = (m[1] * lx + m[4] * ly + m[7] * lz) + m[10];
-    const float wz = (m[2] * lx + m[5] * ly + m[8] * lz) + m[11];
+    p.wx = (m[0] * lx + m[3] * ly + m[6] * lz) + m[9];
+    p.wy = (m[1] * lx + m[4] * ly + m[7] * lz) + m[10];
+    p.wz = (m[2] * lx + m[5] * ly + m[8] * lz) + m[11];
     const float nx0 = v.spherical ? lx : 0.0f, ny0 = v.spherical ? ly : 1.0f, nz0 = v.spherical ? lz : 0.0f;
     const float* t = v.local_from_world_transpose;
-    float nx = t[0] * nx0 + t[3] * ny0 + t[6] * nz0;
-    float ny = t[1] * nx0 + t[4] * ny0 + t[7] * nz0;
-    float nz = t[2] * nx0 + t[5] * ny0 + t[8] * nz0;
+    const float nx = t[0] * nx0 + t[3] * ny0 + t[6] * nz0;
+    const float ny = t[1] * nx0 + t[4] * ny0 + t[7] * nz0;
+    const float nz = t[2] * nx0 + t[5] * ny0 + t[8] * nz0;
     const float nl = length3(nx, ny, nz);
-    nx = nx / nl;
-    ny = ny / nl;
-    nz = nz / nl;
-    const float dx = (wx + approximate_height * nx) - v.world_position[0];
-    const float dy = (wy + approximate_height * ny) - v.world_position[1];
-    const float dz = (wz + approximate_height * nz) - v.world_position[2];
+    p.nx = nx / nl;
+    p.ny = ny / nl;
+    p.nz = nz / nl;
+    return p;
+}
+
+// refine_tiles.wgsl:17-22 -> compute_subdivision_coordinate (functions.wgsl:133-154) ->
+// approximate_view_distance (:117-131) -> compute_local_position (:73-96)
+// approximate_height: the view's (bt_view_state::approximate_height), or the value bt_frame_update left on the device — passed
+// beside the view: writing it into the by-value kernel argument makes the compiler copy the whole struct to scratch (224 bytes,
+// 14 -> 52 VGPRs in the divide-bits kernel: measured, round 4)
+__device__ bool should_be_divided(const bt_view_state& v, const bt_tile_coordinate& tile, float approximate_height) {
+    Coordinate vc{tile.side, v.origin_lod, uint32_t(v.sides[tile.side].view_xy[0]), uint32_t(v.sides[tile.side].view_xy[1]),
+                  v.sides[tile.side].view_uv[0], v.sides[tile.side].view_uv[1]};
+    coordinate_change_lod(vc, tile.lod);
+    const int off_x = int(vc.x) - int(tile.x), off_y = int(vc.y) - int(tile.y);
+    const float uv_x = off_x < 0 ? 0.0f : (off_x > 0 ? 1.0f : vc.u);
+    const float uv_y = off_y < 0 ? 0.0f : (off_y > 0 ? 1.0f : vc.v);
+
+    // tile_count(lod) = 2^lod: x / 2^lod == x * 2^-lod bit for bit (no underflow at these magnitudes), and so is / 0.5 == * 2 —
+    // five of the function's eleven IEEE divisions (each ~10 instructions, and this kernel is one CU's VALU)
+    const float inv_tc = __builtin_bit_cast(float, (127u - tile.lod) << 23);
+    const SurfacePoint p = tile_surface(v, tile.side, (float(tile.x) + uv_x) * inv_tc, (float(tile.y) + uv_y) * inv_tc);
+    const float dx = (p.wx + approximate_height * p.nx) - v.world_position[0];
+    const float dy = (p.wy + approximate_height * p.ny) - v.world_position[1];
+    const float dz = (p.wz + approximate_height * p.nz) - v.world_position[2];
     const float view_distance = length3(dx, dy, dz);
     return view_distance < v.subdivision_distance * inv_tc;
+}
+
+// ---- frustum and height-bounds culling (the definition: include/bevy_terrain_amd.h) --------------------------------------
+// The culling kernels are instantiations of their own (template <bool kCull>): with culling off the kernels that run are what they
+// were.  The cull view travels as a kernel argument of its own, never written, so its planes stay in SGPRs (see should_be_divided
+// on what a modified by-value argument costs), the table as a pointer.
+template <bool kCull>
+struct CullArgs {};
+template <>
+struct CullArgs<true> {
+    bt_cull_view cull;
+    const uint32_t* table;  // bt_height_bounds::table, or nullptr: every tile spans (0, 65535)
+    uint32_t levels, sides;
+};
+
+__device__ __forceinline__ float unorm16_height(const bt_cull_view& c, uint32_t v) { return c.min_height + (c.max_height - c.min_height) * (float(v) / 65535.0f); }
+
+// Five surface points (the four corners and the centre) carry all nine points of the test: both heights reuse them.
+__device__ bool tile_culled(const bt_view_state& v, const CullArgs<true>& c, const bt_tile_coordinate& tile) {
+    uint32_t range = 0xFFFF0000u;  // (0, 65535)
+    if (c.table) {
+        const uint32_t lb = min(tile.lod, c.levels - 1u), sh = tile.lod - lb, n = 1u << lb;
+        const uint32_t base = c.sides * (((1u << (2u * lb)) - 1u) / 3u);
+        range = c.table[base + (tile.side * n + (tile.y >> sh)) * n + (tile.x >> sh)];  // one 4-byte load per tile
+    }
+    const float h_lo = unorm16_height(c.cull, range & 0xFFFFu), h_hi = unorm16_height(c.cull, range >> 16);
+    const float inv_tc = __builtin_bit_cast(float, (127u - tile.lod) << 23);
+    const float u0 = (float(tile.x) + 0.0f) * inv_tc, u1 = (float(tile.x) + 1.0f) * inv_tc;
+    const float w0 = (float(tile.y) + 0.0f) * inv_tc, w1 = (float(tile.y) + 1.0f) * inv_tc;
+    const SurfacePoint s[4] = {tile_surface(v, tile.side, u0, w0), tile_surface(v, tile.side, u1, w0), tile_surface(v, tile.side, u0, w1),
+                               tile_surface(v, tile.side, u1, w1)};
+    float px[8], py[8], pz[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+        const float h = k < 4 ? h_lo : h_hi;
+        px[k] = s[k & 3u].wx + h * s[k & 3u].nx;
+        py[k] = s[k & 3u].wy + h * s[k & 3u].ny;
+        pz[k] = s[k & 3u].wz + h * s[k & 3u].nz;
+    }
+    float slack = 0.0f;
+    if (v.spherical) {
+        const SurfacePoint m = tile_surface(v, tile.side, (float(tile.x) + 0.5f) * inv_tc, (float(tile.y) + 0.5f) * inv_tc);
+        const float bx = (m.wx + h_hi * m.nx) - ((px[4] + px[5]) + (px[6] + px[7])) * 0.25f;
+        const float by = (m.wy + h_hi * m.ny) - ((py[4] + py[5]) + (py[6] + py[7])) * 0.25f;
+        const float bz = (m.wz + h_hi * m.nz) - ((pz[4] + pz[5]) + (pz[6] + pz[7])) * 0.25f;
+        slack = length3(bx, by, bz);
+    }
+    slack = slack + c.cull.margin;
+    bool culled = false;
+    for (uint32_t i = 0; i < c.cull.plane_count; i++) {  // (uniform: the planes are scalar loads)
+        const float a = c.cull.planes[i][0], b = c.cull.planes[i][1], cc = c.cull.planes[i][2], d = c.cull.planes[i][3];
+        const float limit = -(slack * length3(a, b, cc));
+        bool outside = true;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) outside = outside && ((a * px[k] + b * py[k]) + cc * pz[k]) + d < limit;
+        culled = culled || outside;
+    }
+    return culled;
 }
 
 // ---- the divide test of every tile that can matter, computed up front ------------------------------------------------
@@ -160,12 +233,16 @@ __device__ __forceinline__ void window_origin(const bt_view_state& v, uint32_t s
 
 // lods: LODs 0 .. lods - 1 get their bits (the host's estimate of how deep this view can refine; anything deeper is
 // evaluated in place by the ordered kernel — an estimate can only cost time, never change the result)
-constexpr uint32_t kCntVisited = 8, kCntDivide = 40, kCounterWords = 72;  // (bt_tiling_prepass::counters)
+constexpr uint32_t kCntCulled = 4, kCntVisited = 8, kCntDivide = 40, kCounterWords = 72;  // (bt_tiling_prepass::counters)
+constexpr size_t kBitsPlane = 6 * size_t(kMaxLods) * kWinWords;  // words of one bit plane (divide bits; the cull bits follow them)
 
 // radius <= kWinK: the window actually used (storage is laid out for kWinK); counters != nullptr: also resets the counters and
-// the indirect arguments the unordered collector (next launch) accumulates into
+// the indirect arguments the unordered collector (next launch) accumulates into.  kCull: the cull test of the same tiles next to the
+// divide test, into the second bit plane
+template <bool kCull>
 __global__ __launch_bounds__(256) void tiling_divide_bits_kernel(bt_view_state view, uint32_t lods, int radius, unsigned long long* __restrict__ bits,
-                                                                 uint32_t* __restrict__ counters, bt_indirect* __restrict__ indirect, const float* __restrict__ height) {
+                                                                 uint32_t* __restrict__ counters, bt_indirect* __restrict__ indirect, const float* __restrict__ height,
+                                                                 CullArgs<kCull> cull) {
     const float approximate_height = height ? *height : view.approximate_height;  // (bt_frame_update: the height sampled earlier on this stream, never seen by the host)
     const uint32_t W = 2u * uint32_t(radius) + 1u, chunks = (W * W + 255u) / 256u;
     const uint32_t chunk = blockIdx.x % chunks, lod = (blockIdx.x / chunks) % lods, side = blockIdx.x / (chunks * lods);
@@ -179,9 +256,24 @@ __global__ __launch_bounds__(256) void tiling_divide_bits_kernel(bt_view_state v
     const uint32_t b = chunk * 256u + threadIdx.x;
     const int tx = ox + int(b % W), ty = oy + int(b / W), last = int((1u << lod) - 1u);
     bool divide = false;
-    if (b < W * W && tx >= 0 && ty >= 0 && tx <= last && ty <= last) divide = should_be_divided(view, bt_tile_coordinate{side, lod, uint32_t(tx), uint32_t(ty)}, approximate_height);
-    const unsigned long long word = __ballot(divide);
-    if ((threadIdx.x & 63u) == 0) bits[(size_t(side) * kMaxLods + lod) * kWinWords + chunk * 4u + (threadIdx.x >> 6)] = word;
+    if constexpr (kCull) {
+        bool culled = false;
+        if (b < W * W && tx >= 0 && ty >= 0 && tx <= last && ty <= last) {
+            const bt_tile_coordinate tile{side, lod, uint32_t(tx), uint32_t(ty)};
+            divide = should_be_divided(view, tile, approximate_height);
+            culled = tile_culled(view, cull, tile);
+        }
+        const unsigned long long word = __ballot(divide), word_c = __ballot(culled);
+        if ((threadIdx.x & 63u) == 0) {
+            const size_t i = (size_t(side) * kMaxLods + lod) * kWinWords + chunk * 4u + (threadIdx.x >> 6);
+            bits[i] = word;
+            bits[kBitsPlane + i] = word_c;
+        }
+    } else {
+        if (b < W * W && tx >= 0 && ty >= 0 && tx <= last && ty <= last) divide = should_be_divided(view, bt_tile_coordinate{side, lod, uint32_t(tx), uint32_t(ty)}, approximate_height);
+        const unsigned long long word = __ballot(divide);
+        if ((threadIdx.x & 63u) == 0) bits[(size_t(side) * kMaxLods + lod) * kWinWords + chunk * 4u + (threadIdx.x >> 6)] = word;
+    }
 }
 
 // ---- the unordered form: the final SET straight from the bits ---------------------------------------------------------
@@ -212,10 +304,16 @@ struct WindowBits {
     __device__ __forceinline__ bool bit(uint32_t lod, uint32_t b) const { return (bits[lod * kWinWords + (b >> 6)] >> (b & 63u)) & 1ull; }
 };
 
+// kCull: a second plane of bits says which window tiles are culled.  reach additionally wants every ancestor's cull bit clear; a
+// reached tile whose own cull bit is set is visited and counted, and neither divides nor is final; the walk over the children no window
+// covers applies the same test in place (so the result still does not depend on the window).
+template <bool kCull>
 __global__ __launch_bounds__(256) void tiling_collect_kernel(bt_view_state view, uint32_t lods, int radius, uint32_t capacity,
                                                              const unsigned long long* __restrict__ bits, bt_tile_coordinate* __restrict__ final_tiles,
-                                                             bt_indirect* __restrict__ indirect, uint32_t* __restrict__ counters, const float* __restrict__ height) {
-    __shared__ unsigned long long s_bits[kMaxLods * kWinWords];
+                                                             bt_indirect* __restrict__ indirect, uint32_t* __restrict__ counters, const float* __restrict__ height,
+                                                             CullArgs<kCull> cull) {
+    constexpr uint32_t kPlane = kMaxLods * kWinWords;  // LDS words of one bit plane of one side
+    __shared__ unsigned long long s_bits[(kCull ? 2u : 1u) * kPlane];
     const float approximate_height = height ? *height : view.approximate_height;
     __shared__ int2 s_origin[kMaxLods];
     const uint32_t W = 2u * uint32_t(radius) + 1u, chunks = (W * W + 255u) / 256u;
@@ -230,20 +328,38 @@ __global__ __launch_bounds__(256) void tiling_collect_kernel(bt_view_state view,
         }
         const uint32_t words = min(lod + 2u, lods) * kWinWords;  // ancestors, the tile itself, its children's window
         for (uint32_t i = tid; i < words; i += 256u) s_bits[i] = bits[size_t(side) * kMaxLods * kWinWords + i];
+        if constexpr (kCull)
+            for (uint32_t i = tid; i < words; i += 256u) s_bits[kPlane + i] = bits[kBitsPlane + size_t(side) * kMaxLods * kWinWords + i];
     }
     __syncthreads();
     {
         const WindowBits wb{s_bits, s_origin, lods, int(W)};
+        const WindowBits wc{s_bits + (kCull ? kPlane : 0u), s_origin, lods, int(W)};  // (kCull only)
         const uint32_t b = chunk * 256u + tid;
         const int tx = s_origin[lod].x + int(b % W), ty = s_origin[lod].y + int(b / W), last = int((1u << lod) - 1u);
         bool reach = b < W * W && tx >= 0 && ty >= 0 && tx <= last && ty <= last;
         for (uint32_t a = lod; reach && a-- > 0;) {  // all ancestors divide (order is irrelevant; an ancestor outside its window is evaluated in place)
             const uint32_t ax = uint32_t(tx) >> (lod - a), ay = uint32_t(ty) >> (lod - a);
             uint32_t ab;
-            reach = wb.inside(a, ax, ay, ab) ? wb.bit(a, ab) : should_be_divided(view, bt_tile_coordinate{side, a, ax, ay}, approximate_height);
+            if constexpr (kCull) {
+                if (wb.inside(a, ax, ay, ab)) {
+                    reach = wb.bit(a, ab) && !wc.bit(a, ab);
+                } else {
+                    const bt_tile_coordinate at{side, a, ax, ay};
+                    reach = !tile_culled(view, cull, at) && should_be_divided(view, at, approximate_height);
+                }
+            } else {
+                reach = wb.inside(a, ax, ay, ab) ? wb.bit(a, ab) : should_be_divided(view, bt_tile_coordinate{side, a, ax, ay}, approximate_height);
+            }
         }
-        const bool divide = reach && wb.bit(lod, b);
-        const bool fin = reach && !divide;
+        bool culled = false;
+        if constexpr (kCull) {
+            culled = reach && wc.bit(lod, b);
+            const unsigned long long ballot_c = __ballot(culled);
+            if (lane == 0 && ballot_c) atomicAdd(&counters[kCntCulled], uint32_t(__popcll(ballot_c)));
+        }
+        const bool divide = reach && !culled && wb.bit(lod, b);
+        const bool fin = reach && !culled && !divide;
         // finals: one reservation per wave
         const unsigned long long ballot_f = __ballot(fin), ballot_r = __ballot(reach), ballot_d = __ballot(divide);
         uint32_t base = 0;
@@ -270,7 +386,11 @@ __global__ __launch_bounds__(256) void tiling_collect_kernel(bt_view_state view,
                     if (!wb.inside(nl, nx, ny, nb)) {
                         atomicAdd(&counters[kCntVisited + nl], 1u);
                         const bt_tile_coordinate node{side, nl, nx, ny};
-                        if (should_be_divided(view, node, approximate_height)) {
+                        bool node_culled = false;
+                        if constexpr (kCull) node_culled = tile_culled(view, cull, node);
+                        if (node_culled) {
+                            atomicAdd(&counters[kCntCulled], 1u);
+                        } else if (should_be_divided(view, node, approximate_height)) {
                             atomicAdd(&counters[kCntDivide + nl], 1u);
                             descend = nl < rc;
                         } else {
@@ -320,17 +440,22 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-template <bool kAssist>
+// kCull (the plain kernel only): refine_tiles drops a culled tile before the divide test — it is neither `divide` nor `fin`, it still
+// counts as visited, and counters[kCntCulled] says how many there were.
+template <bool kAssist, bool kCull>
 __global__ __launch_bounds__(kThreads) void tiling_prepass_kernel(bt_view_state view, uint32_t capacity,
                                                                   bt_tile_coordinate* __restrict__ temporary_tiles,
                                                                   bt_tile_coordinate* __restrict__ final_tiles,
                                                                   bt_indirect* __restrict__ indirect,
                                                                   uint32_t* __restrict__ counters, const unsigned long long* __restrict__ bits, uint32_t assist_lods,
-                                                                  const float* __restrict__ height) {
+                                                                  const float* __restrict__ height, CullArgs<kCull> cull) {
+    static_assert(!(kAssist && kCull), "the two-launch form has no culling variant");
     const float approximate_height = height ? *height : view.approximate_height;
     // The pass state (Parameters, types.wgsl:43-48) is uniform and kept in registers by every thread; only the
     // per-wave counts of a sweep go through LDS (double-buffered by sweep parity: ONE barrier per sweep).
     __shared__ uint32_t s_divide[2][kWaves], s_final[2][kWaves];
+    __shared__ uint32_t s_culled[kCull ? 2 : 1][kWaves];
+    uint32_t culled_total = 0;
 
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const int N = int(capacity);
@@ -366,7 +491,7 @@ __global__ __launch_bounds__(kThreads) void tiling_prepass_kernel(bt_view_state 
             const uint32_t id = base + tid;
             const bool active = id < tile_count;
             bt_tile_coordinate tile{};
-            bool divide = false;
+            bool divide = false, culled = false;
             if (active) {
                 const int parent_index = (N - 1) * (counter > 0 ? 1 : 0) - int(id) * counter;  // :9-11
                 tile = from_lds ? s_tiles[(pass & 1u) * kFrontierCap + id] : temporary_tiles[parent_index];
@@ -379,15 +504,21 @@ __global__ __launch_bounds__(kThreads) void tiling_prepass_kernel(bt_view_state 
                     } else {
                         divide = should_be_divided(view, tile, approximate_height);  // outside its window: the same function, in place
                     }
+                } else if constexpr (kCull) {
+                    culled = tile_culled(view, cull, tile);
+                    divide = !culled && should_be_divided(view, tile, approximate_height);
                 } else {
                     divide = should_be_divided(view, tile, approximate_height);
                 }
             }
-            const bool fin = active && !divide;
+            const bool fin = active && !culled && !divide;
             const unsigned long long ballot_d = __ballot(divide), ballot_f = __ballot(fin);
+            unsigned long long ballot_c = 0;
+            if constexpr (kCull) ballot_c = __ballot(culled);
             if (lane == 0) {
                 s_divide[sweep & 1u][wave] = uint32_t(__popcll(ballot_d));
                 s_final[sweep & 1u][wave] = uint32_t(__popcll(ballot_f));
+                if constexpr (kCull) s_culled[sweep & 1u][wave] = uint32_t(__popcll(ballot_c));
             }
             if constexpr (kAssist) lds_barrier();  // (the counts are LDS; this pass reads no global data it wrote)
             else __syncthreads();
@@ -399,6 +530,7 @@ __global__ __launch_bounds__(kThreads) void tiling_prepass_kernel(bt_view_state 
                 before_f += w < wave ? f : 0u;
                 total_d += d;
                 total_f += f;
+                if constexpr (kCull) culled_total += s_culled[sweep & 1u][w];
             }
             const unsigned long long below = (1ull << lane) - 1ull;
             if (divide) {  // subdivide (:24-31): 4 children at consecutive child_index() values
@@ -450,6 +582,7 @@ __global__ __launch_bounds__(kThreads) void tiling_prepass_kernel(bt_view_state 
         counters[1] = overflow ? 1u : 0u;
         counters[2] = visited;
         counters[3] = view.refinement_count + 1;
+        if constexpr (kCull) counters[kCntCulled] = culled_total;
     }
 }
 
@@ -526,9 +659,9 @@ bt_status prepass_check(bt_tiling_prepass* t, const bt_view_state* view) {
     }
     BT_HIP(hipSetDevice(t->ctx->device));
     if (!t->bits) {
-        BT_HIP(hipMalloc((void**)&t->bits, 6 * size_t(kMaxLods) * kWinWords * sizeof(unsigned long long)));
-        BT_HIP(hipMemsetAsync(t->bits, 0, 6 * size_t(kMaxLods) * kWinWords * sizeof(unsigned long long), t->ctx->stream));
-        BT_HIP(hipFuncSetAttribute((const void*)tiling_prepass_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, int(6 * kMaxLods * (kWinWords * 8 + 8) + 2 * kFrontierCap * 16)));
+        BT_HIP(hipMalloc((void**)&t->bits, 2 * kBitsPlane * sizeof(unsigned long long)));  // divide bits, cull bits
+        BT_HIP(hipMemsetAsync(t->bits, 0, 2 * kBitsPlane * sizeof(unsigned long long), t->ctx->stream));
+        BT_HIP(hipFuncSetAttribute((const void*)tiling_prepass_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, int(6 * kMaxLods * (kWinWords * 8 + 8) + 2 * kFrontierCap * 16)));
     }
     return BT_OK;
 }
@@ -554,31 +687,60 @@ bt_status tiling_prepass_enqueue(bt_tiling_prepass* t, const bt_view_state* view
     const uint32_t sides = view->spherical ? 6u : 1u;
     // (with the height on the device the estimate works from the host's copy, one frame old: it decides how many LODs get their
     // bits up front and can only cost time)
-    const uint32_t lods = form == 2u ? 0u : estimate_lods(view);
-    if (form == 2u || (form == 0u && lods < 12u)) {
-        tiling_prepass_kernel<false><<<1, kThreads, 0, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, nullptr, 0u, device_height);
+    // culling (bt_tiling_prepass_set_culling): no planes cull nothing, and the kernels without the test give exactly that
+    const bool cull = t->cull_set && t->cull.plane_count > 0;
+    CullArgs<true> ca{};
+    if (cull) {
+        if (t->bounds && t->bounds->sides != sides) {
+            set_error("tiling prepass culling: a height-bounds table of %u side(s) for a view of %u", t->bounds->sides, sides);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        ca.cull = t->cull;
+        ca.table = t->bounds ? t->bounds->table : nullptr;
+        ca.levels = t->bounds ? t->bounds->levels : 0u;
+        ca.sides = sides;
+    }
+    if (cull && form != 1u) {  // both ordered forms: the plain kernel (the same list in the same order)
+        tiling_prepass_kernel<false, true><<<1, kThreads, 0, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, nullptr, 0u, device_height, ca);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "tiling_prepass_kernel");
         t->unordered = false;
+        t->culled_run = true;
+        return BT_OK;
+    }
+    const uint32_t lods = form == 2u ? 0u : estimate_lods(view);
+    if (form == 2u || (form == 0u && lods < 12u)) {
+        tiling_prepass_kernel<false, false><<<1, kThreads, 0, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, nullptr, 0u, device_height, CullArgs<false>{});
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "tiling_prepass_kernel");
+        t->unordered = false;
+        t->culled_run = false;
         return BT_OK;
     }
     if (bt_status s = prepass_check(t, view)) return s;
     if (form == 0u) {
         const size_t lds = size_t(sides) * kMaxLods * (kWinWords * sizeof(unsigned long long) + sizeof(int2)) + 2 * size_t(kFrontierCap) * sizeof(bt_tile_coordinate);
-        tiling_divide_bits_kernel<<<sides * lods * kWinChunks, 256, 0, t->ctx->stream>>>(*view, lods, kWinK, t->bits, nullptr, nullptr, device_height);
-        tiling_prepass_kernel<true><<<1, kThreads, lds, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, t->bits, lods, device_height);
+        tiling_divide_bits_kernel<false><<<sides * lods * kWinChunks, 256, 0, t->ctx->stream>>>(*view, lods, kWinK, t->bits, nullptr, nullptr, device_height, CullArgs<false>{});
+        tiling_prepass_kernel<true, false><<<1, kThreads, lds, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, t->bits, lods, device_height, CullArgs<false>{});
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "tiling_prepass_kernel");
         t->unordered = false;
+        t->culled_run = false;
         return BT_OK;
     }
     const int radius = t->window ? t->window : kWinK;
     const uint32_t W = 2u * uint32_t(radius) + 1u, chunks = (W * W + 255u) / 256u;
-    tiling_divide_bits_kernel<<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, t->bits, t->counters, t->indirect, device_height);
-    tiling_collect_kernel<<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, capacity, t->bits, t->final_tiles, t->indirect, t->counters, device_height);
+    if (cull) {
+        tiling_divide_bits_kernel<true><<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, t->bits, t->counters, t->indirect, device_height, ca);
+        tiling_collect_kernel<true><<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, capacity, t->bits, t->final_tiles, t->indirect, t->counters, device_height, ca);
+    } else {
+        tiling_divide_bits_kernel<false><<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, t->bits, t->counters, t->indirect, device_height, CullArgs<false>{});
+        tiling_collect_kernel<false><<<sides * lods * chunks, 256, 0, t->ctx->stream>>>(*view, lods, radius, capacity, t->bits, t->final_tiles, t->indirect, t->counters, device_height, CullArgs<false>{});
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "tiling_collect_kernel");
     t->unordered = true;
+    t->culled_run = cull;
     t->unordered_capacity = capacity;
     return BT_OK;
 }
@@ -593,6 +755,53 @@ bt_status bt_tiling_prepass_run_plain(bt_tiling_prepass* t, const bt_view_state*
 bt_status bt_tiling_prepass_set_window(bt_tiling_prepass* t, uint32_t radius) {
     if (!t || radius > uint32_t(kWinK)) return BT_ERR_INVALID_ARGUMENT;
     t->window = int(radius);
+    return BT_OK;
+}
+
+bt_status bt_tiling_prepass_set_culling(bt_tiling_prepass* t, const bt_cull_view* cull, const bt_height_bounds* bounds) {
+    if (!t) {
+        set_error("bt_tiling_prepass_set_culling: NULL prepass");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!cull) {
+        t->cull_set = false;
+        t->bounds = nullptr;
+        return BT_OK;
+    }
+    if (cull->plane_count > 5u) {
+        set_error("bt_tiling_prepass_set_culling: plane_count %u > 5", cull->plane_count);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(cull->margin >= 0.0f) || !std::isfinite(cull->margin)) {
+        set_error("bt_tiling_prepass_set_culling: margin %g (finite, >= 0)", double(cull->margin));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bounds && (!bounds->table || (bounds->sides != 1u && bounds->sides != 6u) || bounds->levels < 1u || bounds->levels > BT_HEIGHT_BOUNDS_MAX_LEVELS)) {
+        set_error("bt_tiling_prepass_set_culling: not a height-bounds table");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    t->cull = *cull;
+    t->bounds = bounds;
+    t->cull_set = true;
+    return BT_OK;
+}
+
+bt_status bt_tiling_prepass_cull_stats(bt_tiling_prepass* t, uint32_t* visited, uint32_t* culled) {
+    if (!t) {
+        set_error("bt_tiling_prepass_cull_stats: NULL prepass");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    uint32_t counters[kCounterWords] = {0};
+    BT_HIP(hipSetDevice(t->ctx->device));
+    BT_HIP(hipMemcpyAsync(counters, t->counters, sizeof counters, hipMemcpyDeviceToHost, t->ctx->stream));
+    BT_HIP(hipStreamSynchronize(t->ctx->stream));
+    uint32_t v = counters[2];
+    if (t->unordered) {
+        v = 0;
+        for (uint32_t l = 0; l < kMaxLods; l++) v += counters[kCntVisited + l];
+    }
+    if (visited) *visited = v;
+    if (culled) *culled = t->culled_run ? counters[kCntCulled] : 0u;
     return BT_OK;
 }
 

@@ -294,6 +294,50 @@ class TileAtlas:
             pass
 
 
+class HeightBounds:
+    """bt_height_bounds: the min/max height table of the culling test — one raw unorm16 {min, max} pair per quadtree tile of LODs
+    0 .. levels-1, on the device.  Level l follows level l-1; inside a level entry ((side * n + y) * n + x), n = 1 << l."""
+
+    def __init__(self, device: Device, sides: int, levels: int):
+        self.device, self.sides, self.levels = device, sides, levels
+        self._h = None
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().bt_height_bounds_create(device._h, sides, levels, C.byref(h)))
+        self._h = h
+        self.entries = sides * (4 ** levels - 1) // 3
+
+    def level_offset(self, level: int) -> int:
+        return self.sides * (4 ** level - 1) // 3
+
+    def build(self, atlas: "TileAtlas", attachment_index: int = 0) -> "HeightBounds":
+        """from every tile `atlas` holds with lod < levels: the min / max of its whole layer; a missing tile takes its parent's, a
+        missing root the whole range; every entry is then united with its children's"""
+        _ffi.check(_ffi.lib().bt_height_bounds_build(self._h, atlas._h, attachment_index))
+        return self
+
+    def read(self) -> np.ndarray:
+        """(entries, 2) uint16: [:, 0] = min, [:, 1] = max"""
+        out = np.empty((self.entries, 2), dtype=np.uint16)
+        _ffi.check(_ffi.lib().bt_height_bounds_read(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16)), out.nbytes))
+        return out
+
+    def write(self, table: np.ndarray):
+        table = np.ascontiguousarray(table, dtype=np.uint16)
+        _ffi.check(_ffi.lib().bt_height_bounds_write(self._h, table.ctypes.data_as(C.POINTER(C.c_uint16)), table.nbytes))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if device_open(getattr(self, "device", None)):
+                _ffi.lib().bt_height_bounds_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def generate_mipmaps(device: Device, fmt: AttachmentFormat, level0: np.ndarray, mip_level_count: int) -> np.ndarray:
     """AttachmentData::generate_mipmaps (terrain_data/mod.rs:143-219) on the GPU: all levels concatenated."""
     T = level0.shape[0]

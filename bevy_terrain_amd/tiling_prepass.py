@@ -64,6 +64,15 @@ def make_view_state(model: TerrainModel, view_config: TerrainViewConfig, view_wo
     return view_state_from_config(model, view_config, view_world_position, float(np.float32(height)))
 
 
+def cull_planes(clip_from_world) -> np.ndarray:
+    """bt_cull_planes: the five frustum planes (left, right, bottom, top, w - z) of culling_bind_group.rs:25-38 from a 4 x 4
+    clip_from_world matrix given as numpy indexes it (matrix[row, column]); (5, 4) float32, inside is dot(xyz, p) + w >= 0."""
+    m = np.ascontiguousarray(np.asarray(clip_from_world, dtype=np.float32).reshape(4, 4).T)  # column-major, like glam's Mat4
+    out = np.zeros((5, 4), dtype=np.float32)
+    _ffi.lib().bt_cull_planes(m.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
 class TilingPrepass:
     """TerrainViewData buffers + TilingPrepassNode::run as one persistent launch."""
 
@@ -89,6 +98,30 @@ class TilingPrepass:
     def set_window(self, radius: int):
         """window radius of the unordered form (1..28, 0 = default): a tuning / test knob, results do not depend on it"""
         _ffi.check(_ffi.lib().bt_tiling_prepass_set_window(self._h, radius))
+
+    def set_culling(self, planes=None, *, margin: float = 0.0, min_height: float = 0.0, max_height: float = 0.0, bounds=None):
+        """bt_tiling_prepass_set_culling: every later run (all three forms, frame_update included) drops the tiles whose volume lies
+        outside one of `planes` ((n, 4), n <= 5, inside is dot(xyz, p) + w >= 0) together with their subtrees.  A tile's volume spans the
+        heights of `bounds` (a HeightBounds; None: min_height .. max_height) widened by `margin` world units.  planes=None: culling off."""
+        if planes is None:
+            _ffi.check(_ffi.lib().bt_tiling_prepass_set_culling(self._h, None, None))
+            self._bounds = None
+            return
+        planes = np.asarray(planes, dtype=np.float32).reshape(-1, 4)
+        view = _ffi.CullViewC()
+        view.plane_count = len(planes)
+        for i, plane in enumerate(planes[:5]):
+            for k in range(4):
+                view.planes[i][k] = plane[k]
+        view.margin, view.min_height, view.max_height = margin, min_height, max_height
+        _ffi.check(_ffi.lib().bt_tiling_prepass_set_culling(self._h, C.byref(view), bounds._h if bounds is not None else None))
+        self._bounds = bounds  # borrowed by the library: keep it alive
+
+    def cull_stats(self) -> Tuple[int, int]:
+        """(tiles visited, tiles culled) by the last run; synchronises"""
+        visited, culled = C.c_uint32(), C.c_uint32()
+        _ffi.check(_ffi.lib().bt_tiling_prepass_cull_stats(self._h, C.byref(visited), C.byref(culled)))
+        return visited.value, culled.value
 
     def read(self) -> Tuple[np.ndarray, Tuple[int, int, int, int]]:
         """(final tiles as an (n, 4) uint32 array [side, lod, x, y] in append order, indirect draw args)."""

@@ -536,6 +536,83 @@ bt_status bt_tiling_prepass_buffers(const bt_tiling_prepass* t, void** final_til
 bt_status bt_tiling_prepass_read(bt_tiling_prepass* t, bt_tile_coordinate* final_tiles_host, uint32_t cap,
                                  uint32_t* count, bt_indirect* indirect);
 
+/* ---------------- frustum and height-bounds culling in the tiling prepass
+ * The reference declares it and never fills it in: CullingData carries `planes: array<vec4<f32>, 5>` (shaders/types.wgsl:99-103) and
+ * culling_bind_group.rs:25-38 derives them, but CullingUniform::from leaves `planes: default()` and refine_tiles.wgsl reads only
+ * culling_view.world_position; docs/implementation.md:59-71, 76, 82 describes the intent (bounding-box frustum culling of tiles from
+ * min/max height data "stored at a way lower resolution").  The definition, operation by operation (IEEE binary32, one rounding per
+ * written operation, no contraction):
+ *
+ * POINT of a tile.  point(tile, uv, h) is the arithmetic should_be_divided performs (functions.wgsl:73-96, 117-121 with
+ * position_local_to_world / normal_local_to_world): u = (float(x) + uv.x) * 2^-lod, w = (float(y) + uv.y) * 2^-lod, the local position
+ * (cube-sphere warp and normalisation when spherical), world = world_from_local * local + translation, normal = normalize(
+ * local_from_world_transpose * (local, or (0, 1, 0) when planar)), point = world + h * normal.  The divide test is
+ * length3(point(tile, view uv, approximate_height) - world_position) < subdivision_distance * 2^-lod; both run the same device function.
+ *
+ * HEIGHT RANGE of a tile (side, lod, x, y).  With a bt_height_bounds table of L levels: lb = min(lod, L - 1), the entry of cell
+ * (x >> (lod - lb), y >> (lod - lb)) of level lb gives raw (vmin, vmax); without a table (0, 65535).  Then
+ * h = min_height + (max_height - min_height) * (float(v) / 65535.0f): h_lo from vmin, h_hi from vmax.
+ *
+ * VOLUME.  Eight corners P_k = point(tile, uv, h), h in {h_lo, h_hi} (outer loop), uv in (0,0), (1,0), (0,1), (1,1).  A spherical tile
+ * bulges beyond the hull of its corners: bulge = length3(point(tile, (0.5, 0.5), h_hi) - ((T0 + T1) + (T2 + T3)) * 0.25f), T the four
+ * h_hi corners, componentwise, length3(x, y, z) = sqrt((x*x + y*y) + z*z); planar: bulge = 0.  slack = bulge + margin.
+ *
+ * TEST.  For each plane i < plane_count, (a, b, c, d): len_i = sqrt((a*a + b*b) + c*c), s_ik = ((a*P_k.x + b*P_k.y) + c*P_k.z) + d.
+ * The tile is CULLED when for some plane s_ik < -(slack * len_i) holds for all eight k.  Inside is dot(n, p) + d >= 0; planes need not
+ * be normalised; a comparison with a NaN is false, so a NaN plane culls nothing.
+ *
+ * THE CULLED PREPASS.  A tile is visited when all its ancestors divide and none of them is culled.  A visited, culled tile produces
+ * neither children nor a final tile; a visited tile that is not culled behaves as without culling (refine_tiles drops a culled tile
+ * before the divide test).  bt_tiling_prepass_run_plain produces the id-order list with the culled tiles left out,
+ * bt_tiling_prepass_run_unordered the same set, bt_tiling_prepass_run takes the plain kernel while culling is set (same list, same
+ * order; its windows' bits fill the LDS already).  The indirect arguments count the final tiles that remain.  For the overflow verdict
+ * a culled tile counts as visited (it occupied a slot of temporary_tiles) and contributes no children.  No horizon or occlusion
+ * culling: the far side of a planet stays in the list when it is inside the frustum. */
+
+/* The min/max height store of the culling test: one {min, max} pair of raw unorm16 per quadtree tile of LODs 0 .. levels-1, dense, view
+ * independent, on the device.  Level l follows level l-1; inside a level entry ((side * n + y) * n + x), n = 1 << l:
+ * sides * (4^levels - 1) / 3 entries of 4 bytes, 1 <= levels <= BT_HEIGHT_BOUNDS_MAX_LEVELS (33.6 MB for a cube at 11). */
+enum { BT_HEIGHT_BOUNDS_MAX_LEVELS = 11 };
+/* Created and destroyed by the library only; the fields are there to be read (a renderer may bind `table` itself). */
+typedef struct bt_height_bounds {
+    bt_ctx* ctx;
+    uint32_t sides, levels;
+    uint64_t entries; /* sides * (4^levels - 1) / 3 */
+    uint32_t* table;  /* device memory: entries words, min | max << 16 */
+} bt_height_bounds;
+/* sides: 1 (planar) or 6 (cube).  Every entry starts as (0, 65535). */
+bt_status bt_height_bounds_create(bt_ctx* ctx, uint32_t sides, uint32_t levels, bt_height_bounds** out);
+void bt_height_bounds_destroy(bt_height_bounds* b);
+/* Fills the table from every tile the atlas currently holds (bt_atlas_tiles with an atlas index, loaded) with lod < levels, typically
+ * the atlas a preprocessing job has just filled:
+ *   1. own(tile) = the grid-1 result of bt_atlas_tile_bounds for its layer, flags 0: min and max over the whole T x T layer, border
+ *      included, so bilinear samples and stitched texels are inside it;
+ *   2. top down, a tile the atlas does not hold takes own of its parent (what the best-loaded-tile fallback would sample there); a root
+ *      that is not held is (0, 65535);
+ *   3. bottom up, entry(tile) = own(tile) united with entry(child 0..3) for lod + 1 < levels: a parent averages its children, so its own
+ *      range is narrower than theirs, and the union makes an entry hold for every LOD a renderer may blend in.
+ * After it no entry has min > max.  Synchronous; a read of the atlas (not a write for bt_run_stats.prev_zero_launches).  The atlas's side
+ * count must be the table's.  Non-R16 attachment: BT_ERR_UNSUPPORTED. */
+bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* atlas, uint32_t attachment_index);
+/* The whole table, {min, max} pairs in table order: out_bytes / bytes == entries * 4 (bt_height_bounds_write: a table saved earlier). */
+bt_status bt_height_bounds_read(const bt_height_bounds* b, uint16_t* out_host, uint64_t out_bytes);
+bt_status bt_height_bounds_write(bt_height_bounds* b, const uint16_t* src_host, uint64_t bytes);
+
+typedef struct bt_cull_view {
+    float planes[5][4];     /* CullingData.planes; inside: dot(xyz, p) + w >= 0 */
+    uint32_t plane_count;   /* 0..5; 0 culls nothing */
+    float margin;           /* world units added to every tile's slack, finite, >= 0 */
+    float min_height, max_height; /* TerrainConfig's, for the unorm16 -> height map */
+} bt_cull_view;
+/* culling_bind_group.rs:25-38 on a column-major clip_from_world (glam Mat4): left, right, bottom, top, w - z.  Host only. */
+void bt_cull_planes(const float clip_from_world[16], float planes[5][4]);
+/* cull == NULL: culling off (the state after create).  bounds may be NULL (every tile spans min_height .. max_height); it is borrowed
+ * and must outlive its use.  The view's side count is checked against the table's by every run (BT_ERR_INVALID_ARGUMENT before anything
+ * is queued); plane_count > 5 and a negative or non-finite margin are refused here. */
+bt_status bt_tiling_prepass_set_culling(bt_tiling_prepass* t, const bt_cull_view* cull, const bt_height_bounds* bounds);
+/* tiles visited and tiles culled by the last run; synchronises.  After a run without culling: the tiles it visited, 0. */
+bt_status bt_tiling_prepass_cull_stats(bt_tiling_prepass* t, uint32_t* visited, uint32_t* culled);
+
 /* -------------------------- TerrainModel / TerrainViewConfig / TileTree (the per-frame CPU side of the prepass) */
 enum { BT_MODEL_PLANAR = 0, BT_MODEL_SPHERICAL = 1, BT_MODEL_ELLIPSOIDAL = 2 };
 /* TerrainModel (math/terrain_model.rs:41-115): rotation is the identity, as in all three reference constructors.

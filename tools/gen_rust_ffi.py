@@ -66,6 +66,17 @@ def rust_type(ctype, structs, opaque):
     return r
 
 
+def param_type(ctype, inner, structs, opaque):
+    """a parameter's Rust type; inner: the dimensions after the first of an array parameter (`float p[5][4]` -> `*mut [f32; 4]`)"""
+    t = rust_type(ctype, structs, opaque)
+    if inner:
+        qual, elem = t.split(" ", 1)
+        for d in reversed(inner):
+            elem = f"[{elem}; {d}]"
+        t = f"{qual} {elem}"
+    return t
+
+
 def split_declarators(decl):
     """`uint32_t a, b[3], c` -> (type text, [(name, [dims])...])"""
     decl = decl.strip()
@@ -148,7 +159,8 @@ def parse_header(text):
             for a in args.split(","):
                 ctype, decls = split_declarators(a.strip())
                 (pname, dims), = decls
-                params.append((pname, ctype.strip() + ("*" * len(dims))))  # an array parameter is a pointer to its element
+                # an array parameter is a pointer to its element; `float p[5][4]` is a pointer to `[f32; 4]`
+                params.append((pname, ctype.strip() + "*" if dims else ctype.strip(), [parse_int(d, consts) for d in dims[1:]]))
         functions.append((name, ret, params))
     return {"consts": consts, "const_order": const_order, "opaque": opaque, "typedefs": typedefs, "structs": structs, "functions": functions}
 
@@ -208,7 +220,7 @@ def generate(header_text):
     w('#[link(name = "bevy_terrain_amd")]')
     w('extern "C" {')
     for name, ret, params in H["functions"]:
-        ps = ", ".join(f"{ident(p)}: {rust_type(t, structs, opaque)}" for p, t in params)
+        ps = ", ".join(f"{ident(p)}: {param_type(t, inner, structs, opaque)}" for p, t, inner in params)
         r = rust_type(ret, structs, opaque)
         w(f"    pub fn {name}({ps})" + (f" -> {r};" if r else ";"))
     w("}")

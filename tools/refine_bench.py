@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """Times the tiling prepass (one persistent launch per frame) on scripted camera paths; prints one JSON line.
+--cull: the same paths seen through a camera, with frustum culling off and on (time and final tiles).
 Not the headline benchmark (bench.py) — refinement is latency-bound: 10^2..10^4 tiles x 16 B per frame."""
 import json
 import math
@@ -31,14 +32,7 @@ def time_frames(device, prepass, views, **form):
 
 def measure(device, sweep=False):
     out = {}
-    for name, model, positions in (
-        ("planar_side1000", bt.TerrainModel.planar((0.0, 0.0, 0.0), 1000.0, 0.0, 250.0),
-         [(700.0 * (1 - 0.9 * t) * math.cos(19 * t), 900.0 - 770.0 * t, 700.0 * (1 - 0.9 * t) * math.sin(19 * t)) for t in np.linspace(0, 1, 64)]),
-        ("sphere_earth", bt.TerrainModel.sphere((0.0, 0.0, 0.0), 6371000.0, -12000.0, 9000.0),
-         [tuple(np.array([0.3 + math.cos(9 * t) * (1 - t), 0.9, 0.2 + math.sin(9 * t) * (1 - t)]) /
-                np.linalg.norm([0.3 + math.cos(9 * t) * (1 - t), 0.9, 0.2 + math.sin(9 * t) * (1 - t)]) * (6371000.0 + 4.0e6 * (1 - t) + 2.0e3))
-          for t in np.linspace(0, 1, 64)]),
-    ):
+    for name, model, positions, _ in scripted_paths():
         cfg = bt.TerrainViewConfig()
         prepass = bt.TilingPrepass(device, cfg.geometry_tile_count)
         views = [bt.make_view_state(model, cfg, p) for p in positions]
@@ -130,7 +124,81 @@ def measure(device, sweep=False):
     return out
 
 
+def scripted_paths():
+    """the two camera paths of measure(): (name, model, positions, the centre of a spherical model or None)"""
+    return (
+        ("planar_side1000", bt.TerrainModel.planar((0.0, 0.0, 0.0), 1000.0, 0.0, 250.0),
+         [(700.0 * (1 - 0.9 * t) * math.cos(19 * t), 900.0 - 770.0 * t, 700.0 * (1 - 0.9 * t) * math.sin(19 * t)) for t in np.linspace(0, 1, 64)], None),
+        ("sphere_earth", bt.TerrainModel.sphere((0.0, 0.0, 0.0), 6371000.0, -12000.0, 9000.0),
+         [tuple(np.array([0.3 + math.cos(9 * t) * (1 - t), 0.9, 0.2 + math.sin(9 * t) * (1 - t)]) /
+                np.linalg.norm([0.3 + math.cos(9 * t) * (1 - t), 0.9, 0.2 + math.sin(9 * t) * (1 - t)]) * (6371000.0 + 4.0e6 * (1 - t) + 2.0e3))
+          for t in np.linspace(0, 1, 64)], (0.0, 0.0, 0.0)),
+    )
+
+
+def travel_camera(eye, direction, up, fov_y=math.radians(60.0), aspect=16.0 / 9.0, near=0.1):
+    """clip_from_world (m[row, column]) of a perspective_infinite_reverse_rh camera at `eye` looking along `direction`"""
+    eye, f, up = (np.asarray(v, np.float64) for v in (eye, direction, up))
+    f = f / np.linalg.norm(f)
+    s = np.cross(f, up)
+    s /= np.linalg.norm(s)
+    u = np.cross(s, f)
+    view = np.eye(4)
+    view[0, :3], view[1, :3], view[2, :3] = s, u, -f
+    view[:3, 3] = [-np.dot(s, eye), -np.dot(u, eye), np.dot(f, eye)]
+    g = 1.0 / math.tan(0.5 * fov_y)
+    return np.array([[g / aspect, 0, 0, 0], [0, g, 0, 0], [0, 0, 0, near], [0, 0, -1, 0]], np.float64) @ view
+
+
+def measure_cull(device):
+    """--cull: the same paths through a 60 degree x 16:9 camera that looks along the direction of travel — device time per frame and
+    final tiles of the unordered and the plain form with culling off and on (no height-bounds table: every tile spans the model's
+    min_height .. max_height, the widest volumes culling can meet)"""
+    out = {}
+    for name, model, positions, centre in scripted_paths():
+        cfg = bt.TerrainViewConfig()
+        prepass = bt.TilingPrepass(device, cfg.geometry_tile_count)
+        views = [bt.make_view_state(model, cfg, p) for p in positions]
+        planes = []
+        for i, p in enumerate(positions):
+            a, b = (positions[i], positions[i + 1]) if i + 1 < len(positions) else (positions[i - 1], positions[i])
+            up = (0.0, 1.0, 0.0) if centre is None else np.subtract(p, centre)
+            planes.append(bt.cull_planes(travel_camera(p, np.subtract(b, a), up)))
+        result = {"frames": len(views)}
+        for form_name, form in (("unordered", {"unordered": True}), ("plain_single_launch", {"plain": True})):
+            row = {}
+            for culling in (False, True):
+                ms, counts, visited, culled = [], [], [], []
+                for repeat in range(4):  # (the first pass over the path warms the variant up)
+                    ms = []
+                    for v, pl in zip(views, planes):
+                        prepass.set_culling(pl if culling else None, min_height=model.min_height, max_height=model.max_height)
+                        best = None
+                        for _ in range(3):
+                            device.timer_begin()
+                            prepass.run(v, **form)
+                            t = device.timer_end()
+                            best = t if best is None or t < best else best
+                        ms.append(best)
+                        if repeat == 3:
+                            counts.append(len(prepass.read()[0]))
+                            stats = prepass.cull_stats()
+                            visited.append(stats[0])
+                            culled.append(stats[1])
+                row["culling_on" if culling else "culling_off"] = {
+                    "us_per_frame_avg": 1e3 * float(np.mean(ms)), "us_per_frame_max": 1e3 * float(np.max(ms)), "final_tiles_avg": float(np.mean(counts)),
+                    "final_tiles_max": int(np.max(counts)), "tiles_visited_avg": float(np.mean(visited)), "tiles_culled_avg": float(np.mean(culled))}
+            row["time_ratio_on_over_off"] = row["culling_on"]["us_per_frame_avg"] / row["culling_off"]["us_per_frame_avg"]
+            row["final_tiles_kept"] = row["culling_on"]["final_tiles_avg"] / row["culling_off"]["final_tiles_avg"]
+            result[form_name] = row
+        out[name] = result
+    return out
+
+
 def main():
+    if "--cull" in sys.argv:
+        print(json.dumps({"tiling_prepass_culling": measure_cull(bt.Device(0))}))
+        return
     print(json.dumps({"tiling_prepass": measure(bt.Device(0), sweep="--sweep" in sys.argv)}))
 
 
