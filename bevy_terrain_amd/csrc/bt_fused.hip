@@ -2391,11 +2391,6 @@ static Launch job_launch(const JobPlan& j, LaunchKind kind, uint32_t variant) {
     return l;
 }
 
-static bool on_face_edge(const bt_tile_coordinate& c) {
-    const uint32_t n = 1u << c.lod;
-    return c.x == 0 || c.y == 0 || c.x == n - 1 || c.y == n - 1;
-}
-
 // A job qualifies for the fused path when
 //  - the attachment is R16 with T <= 512, even b, c % 4 == 0, c >= 2b;
 //  - at every LOD but the finest, each queued tile has all four children queued (full quadtree below it).

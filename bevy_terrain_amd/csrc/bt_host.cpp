@@ -3,7 +3,6 @@
 // Mirrors the reference's CPU-side behaviour (file:line citations relative to the reference checkout);
 // the arithmetic on texels lives in bt_kernels.hip and bt_fused.hip.
 #include <dirent.h>
-#include <fcntl.h>
 #include <sched.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -15,14 +14,10 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <chrono>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
 #include <thread>
 #include <tuple>
 
-#include "bt_internal.hpp"
+#include "bt_tile_io.hpp"
 
 namespace bt {
 
@@ -143,7 +138,7 @@ static void remove_tree(const std::string& dir) {
     rmdir(dir.c_str());
 }
 
-static bt_status make_dirs(const std::string& dir) {
+bt_status make_dirs(const std::string& dir) {
     std::string cur;
     for (size_t i = 0; i <= dir.size(); i++) {
         if (i == dir.size() || dir[i] == '/') {
@@ -645,286 +640,6 @@ bt_status bt_atlas_upload_tile(bt_atlas* a, uint32_t ai, uint32_t layer, const v
     BT_HIP(hipStreamSynchronize(a->ctx->stream));
     return BT_OK;
 }
-
-}  // extern "C"
-
-namespace {
-
-#ifdef BT_DEBUG_HOOKS
-// tools build: BT_STREAM_TRACE=1 prints host time stamps of the streamed run's launcher, its saver thread and the TileSaver underneath
-std::chrono::steady_clock::time_point g_trace_start;
-bool g_trace = false;
-void trace_stamp(const char* what, size_t k) {
-    if (g_trace) fprintf(stderr, "[stream] %7.3f ms %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g_trace_start).count(), what, k);
-}
-#else
-inline void trace_stamp(const char*, size_t) {}
-#endif
-
-// fs::write for a batch of files on a few threads (the reference spawns one AsyncComputeTaskPool task per tile,
-// tile_atlas.rs:77-116): jobs are (path, bytes) pairs; a chunk's pinned buffer is reused once its jobs are done.
-class FileWriters {
-  public:
-    struct Job {
-        std::string path;
-        const uint8_t* data;
-        size_t bytes;
-        uint32_t buffer;
-        bool read = false;  // fill `data` from the file, which must hold exactly `bytes` (tile load path)
-    };
-    FileWriters(uint32_t threads, uint32_t buffers) : pending_(buffers, 0) {
-        for (uint32_t i = 0; i < threads; i++) workers_.emplace_back([this] { run(); });
-    }
-    ~FileWriters() {
-        {
-            std::lock_guard<std::mutex> lock(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (std::thread& t : workers_) t.join();
-    }
-    void push(std::vector<Job>&& jobs) {
-        {
-            std::lock_guard<std::mutex> lock(m_);
-            for (Job& j : jobs) {
-                pending_[j.buffer]++;
-                queue_.push_back(std::move(j));
-            }
-        }
-        cv_.notify_all();
-    }
-    void wait_buffer(uint32_t buffer) {
-        std::unique_lock<std::mutex> lock(m_);
-        done_.wait(lock, [&] { return pending_[buffer] == 0; });
-    }
-    bt_status status() {
-        std::lock_guard<std::mutex> lock(m_);
-        if (failed_) set_error("%s", error_.c_str());
-        return failed_ ? BT_ERR_IO : BT_OK;
-    }
-
-  private:
-    void run() {
-        for (;;) {
-            Job j;
-            {
-                std::unique_lock<std::mutex> lock(m_);
-                cv_.wait(lock, [&] { return stop_ || !queue_.empty(); });
-                if (queue_.empty()) return;
-                j = std::move(queue_.front());
-                queue_.pop_front();
-            }
-            bool ok = false;
-            std::string why;
-            if (j.read) {
-                const int fd = open(j.path.c_str(), O_RDONLY);
-                if (fd >= 0) {
-                    uint8_t* dst = const_cast<uint8_t*>(j.data);
-                    size_t done = 0;
-                    while (done < j.bytes) {
-                        const ssize_t r = ::read(fd, dst + done, j.bytes - done);
-                        if (r <= 0) break;
-                        done += size_t(r);
-                    }
-                    uint8_t extra;
-                    ok = done == j.bytes && ::read(fd, &extra, 1) == 0;
-                    close(fd);
-                    if (!ok) why = "tile file " + j.path + " does not hold " + std::to_string(j.bytes) + " bytes";
-                } else {
-                    why = "tile file not found: " + j.path;
-                }
-                {
-                    std::lock_guard<std::mutex> lock(m_);
-                    if (!ok && !failed_) {
-                        failed_ = true;
-                        error_ = why;
-                    }
-                    pending_[j.buffer]--;
-                }
-                done_.notify_all();
-                continue;
-            }
-            const int fd = open(j.path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-            if (fd >= 0) {
-                size_t done = 0;
-                while (done < j.bytes) {
-                    const ssize_t w = write(fd, j.data + done, j.bytes - done);
-                    if (w <= 0) break;
-                    done += size_t(w);
-                }
-                ok = done == j.bytes;
-                ok = (close(fd) == 0) && ok;
-                if (!ok) why = "short write to " + j.path;
-            } else {
-                why = "cannot open " + j.path + ": " + strerror(errno);
-            }
-            {
-                std::lock_guard<std::mutex> lock(m_);
-                if (!ok && !failed_) {
-                    failed_ = true;
-                    error_ = why;
-                }
-                pending_[j.buffer]--;
-            }
-            done_.notify_all();
-        }
-    }
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    std::deque<Job> queue_;
-    std::vector<uint32_t> pending_;
-    std::vector<std::thread> workers_;
-    bool stop_ = false, failed_ = false;
-    std::string error_;
-};
-
-// Download + write tiles: D2H through three pinned buffers on `stream` (runs of consecutive layers are one copy), files written by
-// the writer threads while the next chunk downloads.  add() may be called many times (the streamed run hands over band after band,
-// attachment after attachment); the tiles of one add() are written in atlas-index order.
-class TileSaver {
-  public:
-    typedef std::vector<std::pair<uint32_t, bt_tile_coordinate>> Tiles;
-    TileSaver(bt_atlas* a, hipStream_t stream) : a_(a), stream_(stream) {}
-    ~TileSaver() {
-        if (writers_)
-            for (uint32_t k = 0; k < kBuffers; k++) writers_->wait_buffer(k);
-        for (uint32_t k = 0; k < kBuffers; k++)
-            if (copied_[k]) hipEventDestroy(copied_[k]);
-    }
-    bt_status begin() {
-        BT_HIP(hipSetDevice(a_->ctx->device));
-        size_t largest = 32ull << 20;
-        for (const Attachment& at : a_->attachments) largest = std::max<size_t>(largest, at.tile_bytes);
-        if (bt_status s = ctx_staging(a_->ctx, largest)) return s;
-        for (uint32_t k = 0; k < kBuffers; k++) {
-            hipError_t e = hipEventCreateWithFlags(&copied_[k], hipEventDisableTiming);
-            if (e != hipSuccess) return hip_fail(e, "save events");
-        }
-        // 16 writers: measured on tmpfs and the overlay disk, 6 / 8 / 12 / 16 / 24 / 32 / 64 / 128 threads write at 29 / 34 / 42 /
-        // 46-49 / 46 / 35 / 4 / 5 GB/s — beyond ~24 the page-cache allocation lock dominates
-        // (the count follows the CPUs the process may use, not the machine's hardware threads: bt_ctx_set_io_threads)
-        uint32_t threads = ctx_io_threads(a_->ctx);
-#ifdef BT_DEBUG_HOOKS
-        if (const char* e = getenv("BT_SAVE_THREADS")) threads = std::max(1, atoi(e));  // tools build only: writer-count experiments
-#endif
-        writers_.reset(new FileWriters(threads, kBuffers));
-        return BT_OK;
-    }
-    // taper: the call's last tiles travel in shrinking chunks (half of what is left, down to 8 tiles) — full-size chunks keep the
-    // copy engine at its rate, the small ones at the very end shorten the writers' tail behind the last copy
-    bt_status add(uint32_t ai, const std::string& dir, Tiles tiles, bool taper = false) {
-        const Attachment& at = a_->attachments[ai];
-        void** pinned = a_->ctx->staging;
-        if (std::find(dirs_.begin(), dirs_.end(), dir) == dirs_.end()) {
-            if (bt_status s = make_dirs(dir)) return s;
-            dirs_.push_back(dir);
-        }
-        const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (32ull << 20) / at.tile_bytes)));
-        std::sort(tiles.begin(), tiles.end(), [](const auto& l, const auto& r) { return l.first < r.first; });
-        tiles.erase(std::unique(tiles.begin(), tiles.end(), [](const auto& l, const auto& r) { return l.first == r.first && operator_eq(l.second, r.second); }),
-                    tiles.end());
-        const size_t n = tiles.size();
-        for (size_t lo = 0, step = 0; lo < n; lo += step) {
-            step = chunk;
-            if (taper && n - lo <= 2 * size_t(chunk)) step = std::max<size_t>(std::min<size_t>(8, chunk), (n - lo) / 2);
-            const size_t hi = std::min(n, lo + step);
-            const uint32_t k = uint32_t(chunks_++ % kBuffers);
-            trace_stamp("  saver chunk: tiles", hi - lo);
-            writers_->wait_buffer(k);
-            trace_stamp("  saver chunk: buffer free", k);
-            // runs of consecutive layers; equally long runs at a constant layer stride (a band of tile rows in the x-major
-            // atlas order: 4 layers every 32) travel as ONE pitched copy instead of one call per run
-            std::vector<std::pair<size_t, size_t>> runs;  // (first tile of the chunk, length)
-            for (size_t i = lo; i < hi;) {
-                size_t run = 1;
-                while (i + run < hi && tiles[i + run].first == tiles[i].first + run) run++;
-                runs.push_back({i, run});
-                i += run;
-            }
-            bool regular = runs.size() >= 2;
-            const uint64_t stride = regular ? uint64_t(tiles[runs[1].first].first) - tiles[runs[0].first].first : 0;
-            for (size_t q = 1; regular && q < runs.size(); q++)
-                regular = runs[q].second == runs[0].second && uint64_t(tiles[runs[q].first].first) - tiles[runs[q - 1].first].first == stride;
-            if (regular) {
-                hipError_t e = hipMemcpy2DAsync(pinned[k], at.tile_bytes * runs[0].second, (const uint8_t*)at.level0 + at.tile_bytes * tiles[lo].first,
-                                                at.tile_bytes * stride, at.tile_bytes * runs[0].second, runs.size(), hipMemcpyDeviceToHost, stream_);
-                if (e != hipSuccess) return hip_fail(e, "tile download");
-            } else if (runs.size() > 2 && hi - lo <= 64 && at.tile_bytes % 16u == 0) {
-                // an irregular chunk (the lower LODs behind a band's tiles, a cube's face-edge tiles, merged hand-overs): ONE gather kernel that
-                // writes the pinned buffer over PCIe instead of one copy-engine call per run — a burst of small copy calls stalled the issuing
-                // thread for 15 - 20 ms now and then (config 2's 37-tile chunk: 2.2 -> 21.0 ms between two stamps, round 6 traces), the kernel never
-                uint32_t layers[64];
-                for (size_t i = lo; i < hi; i++) layers[i - lo] = tiles[i].first;
-                if (bt_status s = launch_gather_layers(stream_, at.level0, layers, uint32_t(hi - lo), pinned[k], at.tile_bytes)) return s;
-            } else {
-                for (const auto& [i, run] : runs) {
-                    hipError_t e = hipMemcpyAsync((uint8_t*)pinned[k] + at.tile_bytes * (i - lo), (const uint8_t*)at.level0 + at.tile_bytes * tiles[i].first,
-                                                  at.tile_bytes * run, hipMemcpyDeviceToHost, stream_);
-                    if (e != hipSuccess) return hip_fail(e, "tile download");
-                }
-            }
-            hipError_t e = hipEventRecord(copied_[k], stream_);
-            if (e != hipSuccess) return hip_fail(e, "tile download");
-            trace_stamp("  saver chunk: copy issued", k);
-            if (bt_status s = hand_over()) return s;  // the chunk enqueued BEFORE this one: wait for its copies, queue its files
-            trace_stamp("  saver chunk: previous chunk handed over", k);
-            in_flight_.assign(tiles.begin() + lo, tiles.begin() + hi);
-            in_flight_buffer_ = k;
-            in_flight_ai_ = ai;
-            in_flight_dir_ = dir;
-            have_in_flight_ = true;
-            saved_bytes_ += uint64_t(hi - lo) * at.tile_bytes;
-        }
-        return BT_OK;
-    }
-    bt_status finish() {
-        if (bt_status s = hand_over()) return s;
-        for (uint32_t k = 0; k < kBuffers; k++) writers_->wait_buffer(k);
-        return writers_->status();
-    }
-    uint64_t saved_bytes() const { return saved_bytes_; }
-
-  private:
-    static constexpr uint32_t kBuffers = bt_ctx::kStagingBuffers;
-    bt_status hand_over() {
-        if (!have_in_flight_) return BT_OK;
-        have_in_flight_ = false;
-        const Attachment& at = a_->attachments[in_flight_ai_];
-        hipError_t e = hipEventSynchronize(copied_[in_flight_buffer_]);
-        if (e != hipSuccess) return hip_fail(e, "tile download");
-        std::vector<FileWriters::Job> jobs;
-        for (size_t i = 0; i < in_flight_.size(); i++) {
-            char name[64];
-            bt_tile_name(in_flight_[i].second, name, sizeof name);
-            jobs.push_back({in_flight_dir_ + "/" + name + ".bin", (const uint8_t*)a_->ctx->staging[in_flight_buffer_] + at.tile_bytes * i, size_t(at.tile_bytes), in_flight_buffer_});
-        }
-        writers_->push(std::move(jobs));
-        return BT_OK;
-    }
-    bt_atlas* a_;
-    hipStream_t stream_;
-    size_t chunks_ = 0;
-    hipEvent_t copied_[kBuffers] = {};
-    std::unique_ptr<FileWriters> writers_;
-    std::vector<std::string> dirs_;  // directories that exist by now
-    Tiles in_flight_;
-    uint32_t in_flight_buffer_ = 0, in_flight_ai_ = 0;
-    std::string in_flight_dir_;
-    bool have_in_flight_ = false;
-    uint64_t saved_bytes_ = 0;
-};
-
-bt_status save_tiles(bt_atlas* a, uint32_t ai, const char* directory, std::vector<std::pair<uint32_t, bt_tile_coordinate>> tiles) {
-    if (tiles.empty()) return make_dirs(directory);
-    TileSaver saver(a, a->ctx->stream);
-    if (bt_status s = saver.begin()) return s;
-    if (bt_status s = saver.add(ai, directory, std::move(tiles))) return s;
-    return saver.finish();
-}
-
-}  // namespace
-
-extern "C" {
 
 // every existing tile that holds a slot (a tile known only from load_tile_config has no data to write)
 bt_status bt_atlas_save_attachment(bt_atlas* a, uint32_t ai, const char* directory) {
@@ -1791,459 +1506,6 @@ bt_status bt_preprocessor_save(bt_preprocessor* p, bt_atlas* a, const char* asse
     if (p->shard_world > 1 && p->shard_distributed && p->shard_rank != 0) return BT_OK;  // config.tc: rank 0
     if (bt_status s = make_dirs(terrain)) return s;
     return bt_atlas_save_tile_config(a, (terrain + "/config.tc").c_str());
-}
-
-// ------------------------------------------------------------------------------------------------ streamed run
-}  // extern "C"
-
-namespace bt {
-bool fused_source_window(const bt_preprocessor* p, uint32_t raster, uint32_t out[4]);
-bt_status shard_exchange(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, hipStream_t stream, bool distributed);  // bt_comm.cpp: the grouped collective of a sharded step
-bt_status shard_check_comm(const bt_preprocessor* p, const bt_comm* comm);
-
-// Deferred host rasters travel when the queue runs.  A SHARDED preprocessor (compiled plan known) uploads only the texels its
-// own launches read — its column strips + halo (a rank never touches the rest of the source).  What has travelled is
-// remembered per raster (Raster::windows, every rectangle the device holds): when a kept queue is compiled again — another rank / world
-// (bt_preprocessor_set_shard), BT_RUN_GENERIC or BT_RUN_REFERENCE_DISPATCH, whose launches read the whole raster — and its launches read
-// texels outside every such rectangle, the missing window travels before the run (the caller keeps the rows of a deferred raster alive
-// until the queue is RELEASED: the ABI-6 lifetime rule of bt_raster).  A borrowed device raster that is not 16-byte aligned is copied into
-// its padded buffer by EVERY run ("borrowed" means "read at run time", whatever the width).  skip[i] != 0: raster i is handled by the
-// caller (the streamed run uploads it band by band).
-bt_status upload_pending_rasters(bt_preprocessor* p, const std::vector<uint8_t>* skip) {
-    for (size_t i = 0; i < p->rasters.size(); i++) {
-        Raster& r = p->rasters[i];
-        if (skip && i < skip->size() && (*skip)[i]) continue;
-        if (r.dev_src) {
-            const uint64_t px2 = r.format == BT_FORMAT_R16 ? 2 : 4;
-            BT_HIP(hipMemcpy2DAsync((void*)r.dev.data, r.dev.pitch, r.dev_src, r.dev_src_pitch, uint64_t(r.dev.width) * px2, r.dev.height, hipMemcpyDeviceToDevice, p->ctx->stream));
-            r.pending = false;
-            continue;
-        }
-        if (!r.host) continue;  // not a deferred raster
-        uint32_t w[4] = {0u, 0u, r.dev.width, r.dev.height};
-        const uint64_t px = r.format == BT_FORMAT_R16 ? 2 : 4;
-        const bool window = p->shard_world > 1 && p->compiled && fused_source_window(p, uint32_t(i), w);
-        if (!window) {
-            w[0] = w[1] = 0;
-            w[2] = r.dev.width;
-            w[3] = r.dev.height;
-        }
-        const bool empty = !(w[2] > w[0] && w[3] > w[1]);
-        const bool covered = empty || r.holds(w);
-        if (!r.pending && covered) continue;
-        p->uploaded_source_bytes = 0;  // (the last deferred raster that was looked at: an empty window travels as 0 bytes)
-        if (covered) {
-            r.pending = false;
-            continue;
-        }
-        if (w[0] == 0 && w[1] == 0 && w[2] == r.dev.width && w[3] == r.dev.height && r.host_pitch == r.dev.pitch) {
-            BT_HIP(hipMemcpyAsync((void*)r.dev.data, r.host, r.host_bytes, hipMemcpyHostToDevice, p->ctx->stream));
-            p->uploaded_source_bytes = r.host_bytes;
-        } else {  // a window, or a padded device copy: pitched
-            const uint64_t off_dev = uint64_t(w[1]) * r.dev.pitch + uint64_t(w[0]) * px, off_host = uint64_t(w[1]) * r.host_pitch + uint64_t(w[0]) * px;
-            BT_HIP(hipMemcpy2DAsync((uint8_t*)r.dev.data + off_dev, r.dev.pitch, (const uint8_t*)r.host + off_host, r.host_pitch, (w[2] - w[0]) * px, w[3] - w[1],
-                                    hipMemcpyHostToDevice, p->ctx->stream));
-            p->uploaded_source_bytes = uint64_t(w[2] - w[0]) * px * (w[3] - w[1]);
-        }
-        BT_HIP(hipStreamSynchronize(p->ctx->stream));
-        r.add_window(w);
-        r.pending = false;
-    }
-    return BT_OK;
-}
-}  // namespace bt
-
-namespace {
-// The upload and download queues of the streamed run.  They get NON-DEFAULT PRIORITIES — not for the priority's sake: the runtime maps HIP
-// streams onto a handful of hardware queues round-robin PER PRIORITY CLASS, and a process that owns a few other default-priority streams
-// (a host application does; bench.py's second lane does) can land the download stream on the kernels' own hardware queue, where every copy
-// then waits behind the next bands' kernels: config 2 end to end 6.6 -> 8.9 ms with exactly one extra stream in the process (round 6
-// probe).  A class of their own keeps the three queues apart whatever else the process has created.
-bt_status ctx_side_streams(bt_ctx* ctx) {
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
-    if (!ctx->copy_stream) BT_HIP(hipStreamCreateWithPriority(&ctx->copy_stream, hipStreamNonBlocking, greatest));
-    if (!ctx->save_stream) BT_HIP(hipStreamCreateWithPriority(&ctx->save_stream, hipStreamNonBlocking, least));
-    return BT_OK;
-}
-
-// One step of a streamed run: an upload (optional), a launch — a whole plan entry or a band of a fused main / direct launch — and the
-// tiles that are complete, and may leave, once that launch has run.
-struct StreamStep {
-    size_t plan_index = 0;
-    bool band = false;
-    uint32_t item_begin = 0, item_count = 0;
-    int32_t raster = -1;        // band: rows below `row_end` of this deferred raster travel first (those that have not yet)
-    uint32_t row_end = 0;
-    uint32_t attachment = 0;
-    TileSaver::Tiles early;     // the band's finished finest tiles
-    TileSaver::Tiles rest;      // behind the attachment's last launch: every tile of it that has not left yet
-    bool exchange_before = false;  // a sharded run with a communicator: the grouped collective precedes this step's launch
-};
-
-bt_status run_streamed_impl(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, const char* assets_root, uint32_t flags, bt_stream_stats* out) {
-    if (!p || !a || !assets_root) return BT_ERR_INVALID_ARGUMENT;
-    if (p->ctx != a->ctx) {
-        set_error("preprocessor and atlas belong to different contexts");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const bool sharded = p->shard_world > 1;
-    uint32_t halves = flags & (BT_RUN_SHARD_LOCAL | BT_RUN_SHARD_FINISH);
-    if (!sharded || !halves) halves = BT_RUN_SHARD_LOCAL | BT_RUN_SHARD_FINISH;
-    const bool local = (halves & BT_RUN_SHARD_LOCAL) != 0, finish = (halves & BT_RUN_SHARD_FINISH) != 0;
-    if (sharded && local && finish && !comm) {
-        set_error("bt_preprocessor_run_streamed_sharded: both halves in one call need a communicator (or call BT_RUN_SHARD_LOCAL, exchange, BT_RUN_SHARD_FINISH)");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    BT_HIP(hipSetDevice(p->ctx->device));
-    bt_stream_stats st{};
-    const uint32_t mode = flags & (BT_RUN_GENERIC | BT_RUN_REFERENCE_DISPATCH);
-    if (bt_status s = ensure_compiled(p, a, mode)) return s;
-    if (sharded) {
-        // only the distributed result makes sense here (a replicated atlas has no "share" to write): the finest LOD stays where it was computed
-        if (p->shard_pieces.empty()) {
-            set_error("bt_preprocessor_run_streamed_sharded: the queue does not shard (world %u must divide its units; fused plans only)", p->shard_world);
-            return BT_ERR_UNSUPPORTED;
-        }
-        for (const bt_shard_piece& piece : p->shard_pieces)
-            if (piece.side != p->shard_pieces[0].side) {
-                set_error("BT_RUN_SHARD_DISTRIBUTED needs a one-sided (planar) job: cube seams read finest tiles of other ranks");
-                return BT_ERR_UNSUPPORTED;
-            }
-        p->shard_distributed = true;
-    }
-    if (!p->saves_recorded) {
-        for (const Task& t : p->queue)
-            if (t.type == kSave) a->to_save.push_back({t.coord, t.atlas_index, t.attachment_index});
-        p->saves_recorded = true;
-    }
-
-    // ---- the steps: the plan's entries in launch order (a sharded step: the local half, the exchange, the finishing half), bandable
-    // launches cut into bands
-    uint32_t rows_per_band = 0;  // automatic
-#ifdef BT_DEBUG_HOOKS
-    if (const char* e = getenv("BT_STREAM_BAND_ROWS")) rows_per_band = uint32_t(std::max(1, atoi(e)));
-#endif
-    std::vector<StreamStep> steps;
-    std::vector<uint8_t> banded_raster(p->rasters.size(), 0);
-    std::vector<std::vector<StreamBand>> bands_of(p->plan.size());
-    for (int half = 0; half < 2; half++) {
-        if (half == 0 ? !local : !finish) continue;
-        bool first_of_half = true;
-        for (size_t i = 0; i < p->plan.size(); i++) {
-            const Launch& l = p->plan[i];
-            if (sharded ? (l.phase == 2) != (half == 1) : half == 1) continue;
-            std::vector<StreamBand>& bands = bands_of[i];
-            bool bandable = fused_stream_bands(p, l, rows_per_band, &bands) && !bands.empty();
-            for (const StreamBand& b : bands) {
-                const Raster& r = p->rasters[b.raster];
-                bandable = bandable && r.host != nullptr && r.pending && !r.dev_src;  // a deferred host raster that has not travelled
-            }
-            StreamStep proto;
-            proto.plan_index = i;
-            proto.attachment = l.attachment;
-            proto.exchange_before = sharded && comm && half == 1 && first_of_half && local;
-            first_of_half = false;
-            if (!bandable) {
-                bands.clear();
-                steps.push_back(proto);
-                continue;
-            }
-            for (size_t k = 0; k < bands.size(); k++) {
-                StreamStep sb = proto;
-                sb.exchange_before = proto.exchange_before && k == 0;
-                sb.band = true;
-                sb.item_begin = bands[k].item_begin;
-                sb.item_count = bands[k].item_count;
-                sb.raster = int32_t(bands[k].raster);
-                // (the last band of a raster takes the rest of it: rows below the last tile row's apron that no kernel reads still count as uploaded)
-                const bool last_of_raster = k + 1 == bands.size() || bands[k + 1].raster != bands[k].raster;
-                sb.row_end = last_of_raster ? p->rasters[bands[k].raster].dev.height : bands[k].source_row_end;
-                banded_raster[bands[k].raster] = 1;
-                steps.push_back(sb);
-            }
-            st.banded_launches++;
-            st.bands += uint32_t(bands.size());
-        }
-    }
-    // (a sharded one-call run whose plan has no finishing launch — a single-LOD job — still owes the step its collective)
-    bool exchange_scheduled = false;
-    for (const StreamStep& sp : steps) exchange_scheduled = exchange_scheduled || sp.exchange_before;
-    const bool exchange_at_end = sharded && comm && local && finish && !exchange_scheduled;
-    const bool streamable = st.bands > 1;
-    if (!streamable) {  // the same result, one leg after the other
-        const uint32_t keep = mode | BT_RUN_KEEP_QUEUE;
-        if (!sharded) {
-            if (bt_status s = bt_preprocessor_run(p, a, keep)) return s;
-        } else {
-            if (local)
-                if (bt_status s = bt_preprocessor_run(p, a, keep | BT_RUN_SHARD_LOCAL | BT_RUN_SHARD_DISTRIBUTED)) return s;
-            if (local && finish)
-                if (bt_status s = shard_exchange(p, a, comm, p->ctx->stream, true)) return s;
-            if (finish)
-                if (bt_status s = bt_preprocessor_run(p, a, keep | BT_RUN_SHARD_FINISH | BT_RUN_SHARD_DISTRIBUTED)) return s;
-        }
-        bt_stream_stats none{};
-        if (finish) {
-            for (const AtlasTileAttachment& t : a->to_save)  // what bt_preprocessor_save is about to write (a sharded rank: its share)
-                if (t.atlas_index != BT_INVALID_ATLAS_INDEX && (!sharded || shard_holder(p, t.attachment_index, t.coordinate.lod, t.atlas_index) == p->shard_rank))
-                    none.saved_bytes += a->attachments[t.attachment_index].tile_bytes;
-            if (bt_status s = bt_preprocessor_save(p, a, assets_root)) return s;
-        }
-        if (out) *out = none;
-        return ((flags & BT_RUN_KEEP_QUEUE) || !finish) ? BT_OK : release_queue(p);
-    }
-    if (bt_status s = ctx_side_streams(p->ctx)) return s;
-
-    // ---- which tiles leave after which step.  A finest tile of a banded launch leaves with its band when nothing later writes it: the
-    // attachment has ONE job in the queue (an overlay or an adjacent dataset would write or stitch it again), and on a cube it does not
-    // touch a face edge (its cross-face aprons are stitched after the last face).  Everything else of an attachment leaves behind the
-    // attachment's last launch.  A sharded rank writes its share only (shard_holder).
-    const std::string terrain = std::string(assets_root) + "/" + a->config.path;
-    auto dir_of = [&](uint32_t ai) { return terrain + "/data/" + a->attachments[ai].cfg.name; };
-    std::vector<uint32_t> jobs_of(a->attachments.size(), 0);
-    {
-        std::vector<std::vector<uint32_t>> seen(a->attachments.size());
-        for (const Task& t : p->queue)
-            if (t.type == kSplit && std::find(seen[t.attachment_index].begin(), seen[t.attachment_index].end(), t.job) == seen[t.attachment_index].end()) {
-                seen[t.attachment_index].push_back(t.job);
-                jobs_of[t.attachment_index]++;
-            }
-    }
-    std::vector<uint8_t> in_plan(a->attachments.size(), 0);
-    for (const StreamStep& sp : steps) in_plan[sp.attachment] = 1;
-    // to_save entries of the attachments this run handles, by (attachment, atlas index)
-    std::vector<std::unordered_map<uint32_t, bt_tile_coordinate>> waiting(a->attachments.size());
-    for (const AtlasTileAttachment& t : a->to_save) {
-        if (t.atlas_index == BT_INVALID_ATLAS_INDEX || !in_plan[t.attachment_index]) continue;
-        if (sharded && shard_holder(p, t.attachment_index, t.coordinate.lod, t.atlas_index) != p->shard_rank) continue;
-        waiting[t.attachment_index][t.atlas_index] = t.coordinate;
-    }
-    const bool spherical = a->config.spherical != 0;
-    for (StreamStep& sp : steps) {
-        if (!sp.band || jobs_of[sp.attachment] != 1) continue;
-        std::vector<FusedTile> tiles;
-        fused_launch_tiles(p, p->plan[sp.plan_index], sp.item_begin, sp.item_count, &tiles);
-        for (const FusedTile& t : tiles) {
-            const bt_tile_coordinate& c = t.coordinate;
-            const uint32_t n = 1u << c.lod;
-            if (spherical && (c.x == 0 || c.y == 0 || c.x == n - 1 || c.y == n - 1)) continue;
-            auto w = waiting[sp.attachment].find(t.atlas_index);
-            if (w == waiting[sp.attachment].end() || !operator_eq(w->second, c)) continue;
-            sp.early.push_back({t.atlas_index, c});
-            waiting[sp.attachment].erase(w);
-        }
-        st.early_tiles += uint32_t(sp.early.size());
-    }
-    if (finish)
-        for (uint32_t ai = 0; ai < a->attachments.size(); ai++) {
-            if (!in_plan[ai] || waiting[ai].empty()) continue;
-            size_t last = steps.size();
-            for (size_t k = 0; k < steps.size(); k++)
-                if (steps[k].attachment == ai) last = k;
-            for (const auto& [index, coord] : waiting[ai]) steps[last].rest.push_back({index, coord});
-        }
-    size_t last_saving = 0;
-    for (size_t k = 0; k < steps.size(); k++)
-        if (!steps[k].early.empty() || !steps[k].rest.empty()) last_saving = k;
-
-    const size_t ns = steps.size();
-    std::vector<hipEvent_t> computed(ns, nullptr);
-    hipEvent_t uploaded = nullptr;
-    bt_status rc = BT_OK;
-    for (hipEvent_t& e : computed)
-        if (rc == BT_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = BT_ERR_DEVICE;
-    if (rc == BT_OK && hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess) rc = BT_ERR_DEVICE;
-
-#ifdef BT_DEBUG_HOOKS
-    g_trace = getenv("BT_STREAM_TRACE") != nullptr;
-    g_trace_start = std::chrono::steady_clock::now();
-#endif
-    auto stamp = [](const char* what, size_t k) { trace_stamp(what, k); };
-    // the saver: step after step as their kernels are enqueued (host handshake), ordered on the GPU by events
-    std::mutex m;
-    std::condition_variable cv;
-    size_t launched = 0;  // steps whose `computed` event has been recorded
-    bool abort_run = false;
-    bt_status save_rc = BT_OK;
-    char save_error[512] = "";
-    uint64_t saved_bytes = 0;
-    std::thread saver([&] {
-        hipSetDevice(p->ctx->device);
-        TileSaver ts(a, p->ctx->save_stream);
-        bt_status s = ts.begin();
-        for (size_t k = 0; k < ns && s == BT_OK;) {
-            if (steps[k].early.empty() && steps[k].rest.empty()) {
-                k++;
-                continue;
-            }
-            // The saver takes what is ready: step k and every following step of the same attachment that the launcher has enqueued by
-            // now travel as ONE hand-over (sorted by layer, cut into 32 MB chunks).  When the download + write side is the slower one — it
-            // is, on PCIe — the bands it falls behind on merge into full-size chunks instead of paying the per-chunk latencies band by band
-            // (config 2's 8 MB and 16 MB bands: 0.6 / 0.9 ms each, i.e. 13 - 17 GB/s; merged 32 MB chunks move at 45).
-            size_t last = k;
-            {
-                std::unique_lock<std::mutex> lock(m);
-                cv.wait(lock, [&] { return launched > k || abort_run; });
-                if (abort_run) break;
-                while (last + 1 < ns && launched > last + 1 && steps[last + 1].attachment == steps[k].attachment) last++;
-            }
-            if (hipStreamWaitEvent(p->ctx->save_stream, computed[last], 0) != hipSuccess) s = BT_ERR_DEVICE;
-            stamp("saver: steps taken up to", last);
-            TileSaver::Tiles tiles;
-            for (size_t q = k; q <= last; q++) {
-                tiles.insert(tiles.end(), steps[q].early.begin(), steps[q].early.end());
-                tiles.insert(tiles.end(), steps[q].rest.begin(), steps[q].rest.end());
-            }
-            if (s == BT_OK && !tiles.empty()) s = ts.add(steps[k].attachment, dir_of(steps[k].attachment), std::move(tiles), last >= last_saving);
-            stamp("saver: copies issued, previous chunks handed to the writers", last);
-            k = last + 1;
-        }
-        if (s == BT_OK) s = ts.finish();
-        saved_bytes = ts.saved_bytes();
-        if (s != BT_OK) {
-            snprintf(save_error, sizeof save_error, "%s", bt_last_error());
-            save_rc = s;
-        }
-    });
-
-    // this thread: upload what a step needs (a pageable copy holds the host until it is done; the GPU meanwhile runs the step before), launch it
-    auto publish = [&](size_t n) {
-        { std::lock_guard<std::mutex> lock(m); launched = n; }
-        cv.notify_all();
-    };
-    // rasters no band covers (a launch that cannot be banded reads them): whole, up front, on the kernels' stream
-    if (rc == BT_OK && local) rc = upload_pending_rasters(p, &banded_raster);
-    if (rc == BT_OK && local) {
-        p->stats.variants = 0;
-        p->stats.prev_zero_launches = fused_begin_run(p, a);
-    }
-    // per banded raster: the column window that travels (a sharded rank: its strips + halo) and the rows that have
-    std::vector<std::array<uint32_t, 4>> window(p->rasters.size());
-    std::vector<uint32_t> done_rows(p->rasters.size(), 0);
-    for (size_t i = 0; i < p->rasters.size() && rc == BT_OK; i++) {
-        if (!banded_raster[i]) continue;
-        const Raster& r = p->rasters[i];
-        uint32_t w[4] = {0u, 0u, r.dev.width, r.dev.height};
-        if (!(sharded && fused_source_window(p, uint32_t(i), w))) {
-            w[0] = w[1] = 0;
-            w[2] = r.dev.width;
-            w[3] = r.dev.height;
-        }
-        window[i] = {w[0], w[1], w[2], w[3]};
-        done_rows[i] = w[1];
-    }
-    for (size_t k = 0; k < ns && rc == BT_OK; k++) {
-        const StreamStep& sp = steps[k];
-        const Launch& l = p->plan[sp.plan_index];
-        if (sp.exchange_before) rc = shard_exchange(p, a, comm, p->ctx->stream, true);
-        if (rc != BT_OK) break;
-        if (sp.band) {
-            Raster& r = p->rasters[size_t(sp.raster)];
-            const std::array<uint32_t, 4>& w = window[size_t(sp.raster)];
-            const uint32_t end_row = std::min(sp.row_end, w[3]);
-            uint32_t& done = done_rows[size_t(sp.raster)];
-            if (end_row > done && w[2] > w[0]) {
-                stamp("upload begin", k);
-                const uint64_t px = r.format == BT_FORMAT_R16 ? 2 : 4;
-                const uint8_t* host = (const uint8_t*)r.host;
-                uint8_t* dev = (uint8_t*)r.dev.data;
-                hipError_t ce;
-                if (r.host_pitch == r.dev.pitch && w[0] == 0 && w[2] == r.dev.width) {
-                    const uint64_t off = uint64_t(done) * r.dev.pitch, end = std::min<uint64_t>(r.host_bytes, uint64_t(end_row) * r.dev.pitch);
-                    ce = hipMemcpyAsync(dev + off, host + off, end - off, hipMemcpyHostToDevice, p->ctx->copy_stream);
-                    st.uploaded_bytes += end - off;
-                } else {  // a column window (a sharded rank's strips) or a padded device copy (the caller's rows are not 16-byte aligned): pitched
-                    ce = hipMemcpy2DAsync(dev + uint64_t(done) * r.dev.pitch + w[0] * px, r.dev.pitch, host + uint64_t(done) * r.host_pitch + w[0] * px, r.host_pitch,
-                                          uint64_t(w[2] - w[0]) * px, end_row - done, hipMemcpyHostToDevice, p->ctx->copy_stream);
-                    st.uploaded_bytes += uint64_t(w[2] - w[0]) * px * (end_row - done);
-                }
-                if (ce != hipSuccess) rc = BT_ERR_DEVICE;
-                stamp("upload call returned", k);
-                done = end_row;
-                if (rc == BT_OK && hipEventRecord(uploaded, p->ctx->copy_stream) != hipSuccess) rc = BT_ERR_DEVICE;
-                if (rc == BT_OK && hipStreamWaitEvent(p->ctx->stream, uploaded, 0) != hipSuccess) rc = BT_ERR_DEVICE;
-            }
-            if (rc == BT_OK) rc = run_plan_entry(p, a, l, sp.item_begin, sp.item_count);
-        } else {
-            rc = run_plan_entry(p, a, l);
-        }
-        if (rc == BT_OK && hipEventRecord(computed[k], p->ctx->stream) != hipSuccess) rc = BT_ERR_DEVICE;
-        if (rc == BT_OK) publish(k + 1);
-    }
-    if (rc == BT_OK && exchange_at_end) rc = shard_exchange(p, a, comm, p->ctx->stream, true);
-    // a raster counts as uploaded only when every band of it went out; after a failure a later run of the kept queue uploads it whole
-    if (rc == BT_OK)
-        for (size_t i = 0; i < p->rasters.size(); i++)
-            if (banded_raster[i]) {
-                Raster& r = p->rasters[i];
-                const uint32_t w[4] = {window[i][0], window[i][1], window[i][2], window[i][3]};
-                r.pending = false;
-                if (w[2] > w[0] && w[3] > w[1]) r.add_window(w);
-            }
-    p->uploaded_source_bytes = st.uploaded_bytes;
-    if (rc != BT_OK) {
-        { std::lock_guard<std::mutex> lock(m); abort_run = true; }
-        cv.notify_all();
-    }
-    stamp("all launched", ns);
-    saver.join();
-    stamp("saver done", ns);
-    hipStreamSynchronize(p->ctx->stream);
-    if (rc != BT_OK || save_rc != BT_OK) {  // nothing of this call may still read the caller's raster or write the pinned buffers
-        hipStreamSynchronize(p->ctx->copy_stream);
-        hipStreamSynchronize(p->ctx->save_stream);
-    }
-    for (hipEvent_t e : computed) if (e) hipEventDestroy(e);
-    if (uploaded) hipEventDestroy(uploaded);
-    if (rc == BT_ERR_DEVICE) set_error("bt_preprocessor_run_streamed: HIP call failed (%s)", hipGetErrorString(hipGetLastError()));
-    if (rc != BT_OK) return rc;
-    if (save_rc != BT_OK) {
-        set_error("%s", save_error);
-        return save_rc;
-    }
-    st.saved_bytes = saved_bytes;
-    // What the saver wrote leaves the atlas's list.  A finishing call wrote every entry of the plan's attachments (a sharded rank: its
-    // share — the others' entries go too, their holders write them); a local-only call only the early tiles.  Whatever else waits (Save
-    // tasks of another attachment from an earlier run that was not saved yet) goes through bt_preprocessor_save, which also writes config.tc.
-    a->to_save.erase(std::remove_if(a->to_save.begin(), a->to_save.end(),
-                                    [&](const AtlasTileAttachment& t) {
-                                        if (!in_plan[t.attachment_index]) return false;
-                                        if (finish) return true;
-                                        const auto& w = waiting[t.attachment_index];
-                                        const bool mine = !sharded || shard_holder(p, t.attachment_index, t.coordinate.lod, t.atlas_index) == p->shard_rank;
-                                        return mine && w.find(t.atlas_index) == w.end();  // (held by this rank and no longer waiting: it left with a band)
-                                    }),
-                     a->to_save.end());
-    if (finish)
-        if (bt_status s = bt_preprocessor_save(p, a, assets_root)) return s;
-    st.streamed = 1;
-    if (out) *out = st;
-    return ((flags & BT_RUN_KEEP_QUEUE) || !finish) ? BT_OK : release_queue(p);
-}
-}  // namespace
-
-extern "C" {
-
-// The reference's own span (preprocessor.rs:363,419: sources loaded -> all saves done) as ONE overlapped pipeline: the source
-// rasters travel to the GPU in bands of tile rows on a copy queue, each band's kernels start when its rows (and the few
-// apron rows below it) have landed, and a second thread downloads and writes a band's finished tiles on a third queue while
-// the next bands upload and run: H2D, kernels, D2H and the file system work at the same time (PCIe is full duplex).  Round 6: every
-// fused main / direct launch of the plan is banded — several attachments (examples/preprocess_planar.rs:16-60), the six faces of a
-// cube job (examples/preprocess_spherical.rs:20-48) — and a sharded rank streams its own window and share.
-bt_status bt_preprocessor_run_streamed(bt_preprocessor* p, bt_atlas* a, const char* assets_root, uint32_t flags, bt_stream_stats* out) {
-    if (p && p->shard_world > 1) {
-        set_error("bt_preprocessor_run_streamed: a sharded preprocessor runs through bt_preprocessor_run_streamed_sharded");
-        return BT_ERR_UNSUPPORTED;
-    }
-    return run_streamed_impl(p, a, nullptr, assets_root, flags, out);
-}
-
-bt_status bt_preprocessor_run_streamed_sharded(bt_preprocessor* p, bt_atlas* a, bt_comm* comm, const char* assets_root, uint32_t flags, bt_stream_stats* out) {
-    if (!p) return BT_ERR_INVALID_ARGUMENT;
-    if (comm && p->shard_world > 1)
-        if (bt_status s = shard_check_comm(p, comm)) return s;
-    return run_streamed_impl(p, a, comm, assets_root, flags, out);
 }
 
 bt_status bt_preprocessor_last_run_stats(const bt_preprocessor* p, bt_run_stats* out) {

@@ -209,6 +209,7 @@ namespace bt {
 bt_status ctx_staging(bt_ctx* ctx, size_t bytes_per_buffer);  // ensures ctx->staging[*] hold at least that much
 uint32_t usable_cpus();                  // CPUs this process may use: affinity mask capped by the cgroup CPU quota
 uint32_t ctx_io_threads(const bt_ctx* ctx);  // the resolved thread count of the save / load paths
+bt_status make_dirs(const std::string& dir);  // mkdir -p
 }
 
 struct bt_atlas {
@@ -269,9 +270,18 @@ bt_status ensure_compiled(struct ::bt_preprocessor* p, struct ::bt_atlas* a, uin
 // bt_run.cpp: one launch of the plan; a fused main / direct launch runs the items [item_begin, item_begin + item_count) of its list (streamed runs' bands)
 bt_status run_plan_entry(struct ::bt_preprocessor* p, struct ::bt_atlas* a, const Launch& l, uint32_t item_begin = 0, uint32_t item_count = 0xFFFFFFFFu);
 uint32_t fused_begin_run(struct ::bt_preprocessor* p, struct ::bt_atlas* a);  // bt_fused.hip: per run, before its launches (FusedArgs::prev_zero, Attachment::written)
-bt_status upload_pending_rasters(struct ::bt_preprocessor* p, const std::vector<uint8_t>* skip = nullptr);  // bt_host.cpp: deferred host rasters, all at once (skip[i]: not raster i)
+bt_status check_distributed_one_sided(const struct ::bt_preprocessor* p);  // bt_run.cpp: BT_RUN_SHARD_DISTRIBUTED is refused for a cube job
+void record_saves(struct ::bt_preprocessor* p, struct ::bt_atlas* a);      // bt_run.cpp: the queue's Save tasks -> bt_atlas::to_save, once per queue and save
+bool fused_plan(struct ::bt_preprocessor* p, struct ::bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan);  // bt_fused.hip: queue -> fused launch plan; false: the generic plan
+bool fused_source_window(const struct ::bt_preprocessor* p, uint32_t raster, uint32_t out[4]);  // bt_fused.hip: the texels of a raster the plan's launches read; false: no window is known
+// bt_stream.cpp: w = the fused source window of raster i when the caller asks for it and the plan has one, else the whole raster
+void raster_window(const struct ::bt_preprocessor* p, uint32_t i, bool use_fused_window, uint32_t w[4]);
+bt_status upload_pending_rasters(struct ::bt_preprocessor* p, const std::vector<uint8_t>* skip = nullptr);  // bt_stream.cpp: deferred host rasters, all at once (skip[i]: not raster i)
+// bt_comm.cpp: the grouped collective of a sharded step, and whether a communicator fits the preprocessor's rank and world
+bt_status shard_exchange(struct ::bt_preprocessor* p, struct ::bt_atlas* a, bt_comm* comm, hipStream_t stream, bool distributed);
+bt_status shard_check_comm(const struct ::bt_preprocessor* p, const bt_comm* comm);
 
-// streamed run (bt_host.cpp drives it): a fused main / direct launch cut into bands of whole tile rows
+// streamed run (bt_stream.cpp drives it): a fused main / direct launch cut into bands of whole tile rows
 struct StreamBand {
     uint32_t item_begin, item_count;  // into the job's item list ((side, tile row, x) order)
     uint32_t tile_y_begin, tile_y_end;
@@ -293,6 +303,10 @@ void fused_launch_tiles(const struct ::bt_preprocessor* p, const Launch& l, uint
 inline constexpr int kNeighbourOffsets[8][2] = {{0, -1}, {1, 0}, {0, 1}, {-1, 0}, {-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
 void tile_children(bt_tile_coordinate c, bt_tile_coordinate out[4]);
 void tile_neighbours(bt_tile_coordinate c, bool spherical, bt_tile_coordinate out[8]);
+inline bool on_face_edge(const bt_tile_coordinate& c) {  // the tile touches an edge of its cube face
+    const uint32_t n = 1u << c.lod;
+    return c.x == 0 || c.y == 0 || c.x == n - 1 || c.y == n - 1;
+}
 
 }  // namespace bt
 

@@ -14,8 +14,6 @@
 using namespace bt;
 
 namespace bt {
-bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan);
-
 TaskDev to_device_task(const Task& t) {
     TaskDev d{};
     d.atlas_index = t.atlas_index;
@@ -35,6 +33,25 @@ TaskDev to_device_task(const Task& t) {
     if (t.type == kDownsample)
         for (int i = 4; i < 8; i++) d.rel_index[i] = BT_INVALID_ATLAS_INDEX;
     return d;
+}
+
+// the finest LOD stays on its owners: possible when nothing after the exchange reads finest tiles of other
+// ranks, i.e. not for cube jobs (their face seams are stitched from the neighbour face's finest tiles)
+bt_status check_distributed_one_sided(const bt_preprocessor* p) {
+    for (const bt_shard_piece& piece : p->shard_pieces)
+        if (piece.side != p->shard_pieces[0].side) {
+            set_error("BT_RUN_SHARD_DISTRIBUTED needs a one-sided (planar) job: cube seams read finest tiles of other ranks");
+            return BT_ERR_UNSUPPORTED;
+        }
+    return BT_OK;
+}
+
+// Save tasks: remembered until bt_preprocessor_save (the reference starts them as tasks drain)
+void record_saves(bt_preprocessor* p, bt_atlas* a) {
+    if (p->saves_recorded) return;  // (re-runs of a kept queue produce the same tiles: recorded once per queue and save)
+    for (const Task& t : p->queue)
+        if (t.type == kSave) a->to_save.push_back({t.coord, t.atlas_index, t.attachment_index});
+    p->saves_recorded = true;
 }
 }  // namespace bt
 
@@ -198,15 +215,8 @@ extern "C" bt_status bt_preprocessor_run(bt_preprocessor* p, bt_atlas* a, uint32
     // every argument check comes before the first profile event and before the atlas bookkeeping: an early error return leaves neither an
     // orphan event (the rows of p->events would no longer line up with profiled_phases) nor layers marked written by launches that never ran
     const bool sharded = p->shard_world > 1;
-    if (sharded && (flags & BT_RUN_SHARD_DISTRIBUTED)) {
-        // the finest LOD stays on its owners: possible when nothing after the exchange reads finest tiles of other
-        // ranks, i.e. not for cube jobs (their face seams are stitched from the neighbour face's finest tiles)
-        for (const bt_shard_piece& piece : p->shard_pieces)
-            if (piece.side != p->shard_pieces[0].side) {
-                set_error("BT_RUN_SHARD_DISTRIBUTED needs a one-sided (planar) job: cube seams read finest tiles of other ranks");
-                return BT_ERR_UNSUPPORTED;
-            }
-    }
+    if (sharded && (flags & BT_RUN_SHARD_DISTRIBUTED))
+        if (bt_status s = check_distributed_one_sided(p)) return s;
     if (sharded && !(flags & (BT_RUN_SHARD_LOCAL | BT_RUN_SHARD_FINISH))) {
         set_error("a sharded preprocessor runs with BT_RUN_SHARD_LOCAL and / or BT_RUN_SHARD_FINISH");
         return BT_ERR_INVALID_ARGUMENT;
@@ -251,12 +261,7 @@ extern "C" bt_status bt_preprocessor_run(bt_preprocessor* p, bt_atlas* a, uint32
         p->profiled_runs++;
     }
 
-    // Save tasks: remembered until bt_preprocessor_save (the reference starts them as tasks drain)
-    if (!p->saves_recorded) {  // (re-runs of a kept queue produce the same tiles: recorded once per queue and save)
-        for (const Task& t : p->queue)
-            if (t.type == kSave) a->to_save.push_back({t.coord, t.atlas_index, t.attachment_index});
-        p->saves_recorded = true;
-    }
+    record_saves(p, a);
     if (!(flags & BT_RUN_KEEP_QUEUE)) return release_queue(p);
     return BT_OK;
 }
@@ -307,10 +312,6 @@ extern "C" bt_status bt_preprocessor_profile(bt_preprocessor* p, bt_launch_profi
     return BT_OK;
 }
 
-namespace bt {
-bool fused_source_window(const bt_preprocessor* p, uint32_t raster, uint32_t out[4]);
-}
-
 // Which texels of source raster `raster_index` (the order of the preprocess_* calls; a cube job adds six) does this preprocessor
 // read?  Compiles the plan if necessary.  A sharded fused plan: this rank's column strips + halo; anything else: the whole raster.
 extern "C" bt_status bt_preprocessor_source_window(bt_preprocessor* p, bt_atlas* a, uint32_t raster_index, uint32_t flags, uint32_t window[4], uint64_t* uploaded_bytes) {
@@ -320,11 +321,7 @@ extern "C" bt_status bt_preprocessor_source_window(bt_preprocessor* p, bt_atlas*
         return BT_ERR_INVALID_ARGUMENT;
     }
     if (bt_status s = ensure_compiled(p, a, flags & (BT_RUN_GENERIC | BT_RUN_REFERENCE_DISPATCH))) return s;
-    if (!fused_source_window(p, raster_index, window)) {
-        window[0] = window[1] = 0;
-        window[2] = p->rasters[raster_index].dev.width;
-        window[3] = p->rasters[raster_index].dev.height;
-    }
+    raster_window(p, raster_index, true, window);
     if (uploaded_bytes) *uploaded_bytes = p->uploaded_source_bytes;
     return BT_OK;
 }
