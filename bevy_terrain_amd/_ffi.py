@@ -151,6 +151,21 @@ class CullViewC(C.Structure):
 
 HEIGHT_BOUNDS_MAX_LEVELS = 11
 
+EDIT_ADD, EDIT_FLATTEN = 0, 1
+EDIT_FALLOFF_SMOOTH, EDIT_FALLOFF_HARD = 0, 1
+EDIT_MAX_STAMPS = 256
+
+
+class EditStampC(C.Structure):
+    _fields_ = [("side", C.c_uint32), ("mode", C.c_uint32), ("falloff", C.c_uint32), ("_pad", C.c_uint32), ("center", C.c_float * 2),
+                ("radius", C.c_float), ("amount", C.c_float)]
+
+
+class EditStatsC(C.Structure):
+    _fields_ = [("tiles_edited", C.c_uint32), ("tiles_missing", C.c_uint32), ("tiles_with_children", C.c_uint32),
+                ("tiles_downsampled", C.c_uint32), ("tiles_stitched", C.c_uint32), ("layers_mipped", C.c_uint32), ("launches", C.c_uint32),
+                ("changed_count", C.c_uint32)]
+
 
 class TileTreeEntryC(C.Structure):
     _fields_ = [("atlas_index", C.c_uint32), ("atlas_lod", C.c_uint32)]
@@ -213,6 +228,9 @@ PROTOTYPES = {
     "bt_atlas_load_tiles": (_i32, [_vp, _u32, C.c_char_p, _vp, _u32]),
     "bt_atlas_sample": (_i32, [_vp, _u32, _vp, _u32, _vp]),
     "bt_atlas_tile_bounds": (_i32, [_vp, _u32, _P(_u32), _u32, _u32, _u32, _P(C.c_uint16), _u64]),
+    "bt_atlas_edit_height": (_i32, [_vp, _u32, _u32, _P(EditStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_write_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),
     "bt_generate_mipmaps": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _u64]),

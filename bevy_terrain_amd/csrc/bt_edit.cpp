@@ -1,0 +1,502 @@
+// bt_atlas_edit_height / bt_atlas_write_region / bt_atlas_save_tiles: the host half of in-place editing.
+//
+// An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
+// include/bevy_terrain_amd.h): the ancestors' centres, the aprons of every written tile and of its existing neighbours, the mips.  The plan
+// is index arithmetic on the host: per LOD from `lod` down to 0 the dirty rectangle of every tile (the parent's mosaic rectangle is
+// [x0 >> 1, x1 >> 1], cut at tile boundaries; the centre size need not be a power of two), the items of each launch, the stitch tasks.  It
+// travels through pinned memory into scratch of the context in ONE copy; the kernels (bt_edit.hip, launch_stitch, the mip kernels) follow
+// on the context's stream and the call returns.
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <tuple>
+
+#include "bt_tile_io.hpp"
+
+using namespace bt;
+
+namespace {
+
+struct Rect {
+    uint32_t x0, y0, x1, y1;  // inclusive
+};
+struct Box {  // a rectangle of mosaic texels of one side
+    uint32_t side;
+    Rect r;
+};
+struct CoordLess {
+    bool operator()(const bt_tile_coordinate& l, const bt_tile_coordinate& r) const {
+        return std::tie(l.side, l.lod, l.x, l.y) < std::tie(r.side, r.lod, r.x, r.y);
+    }
+};
+struct Dirty {
+    uint32_t layer;
+    Rect r;  // in centre texels of the tile
+};
+typedef std::map<bt_tile_coordinate, Dirty, CoordLess> DirtyTiles;
+
+// the layer of a tile the atlas holds, or BT_INVALID_ATLAS_INDEX (bt_atlas_get_tile)
+uint32_t layer_of(const bt_atlas* a, const bt_tile_coordinate& c) {
+    if (is_invalid(c) || !a->existing_tiles.count(c)) return BT_INVALID_ATLAS_INDEX;
+    const auto it = a->tile_states.find(c);
+    return it != a->tile_states.end() && it->second.atlas_index < a->config.atlas_size ? it->second.atlas_index : BT_INVALID_ATLAS_INDEX;
+}
+
+void unite(DirtyTiles& tiles, const bt_tile_coordinate& c, uint32_t layer, const Rect& r) {
+    auto [it, fresh] = tiles.emplace(c, Dirty{layer, r});
+    if (fresh) return;
+    Rect& u = it->second.r;
+    u = {std::min(u.x0, r.x0), std::min(u.y0, r.y0), std::max(u.x1, r.x1), std::max(u.y1, r.y1)};
+}
+
+// tiles covered by at least one of the (inclusive) tile rectangles: strips between the distinct x bounds, merged y intervals in each
+uint64_t union_area(const std::vector<Rect>& rects) {
+    std::vector<uint64_t> xs;
+    for (const Rect& r : rects) {
+        xs.push_back(r.x0);
+        xs.push_back(uint64_t(r.x1) + 1u);
+    }
+    std::sort(xs.begin(), xs.end());
+    xs.erase(std::unique(xs.begin(), xs.end()), xs.end());
+    uint64_t area = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> spans;
+    for (size_t i = 0; i + 1 < xs.size(); i++) {
+        spans.clear();
+        for (const Rect& r : rects)
+            if (r.x0 <= xs[i] && xs[i] <= r.x1) spans.push_back({r.y0, uint64_t(r.y1) + 1u});
+        std::sort(spans.begin(), spans.end());
+        uint64_t covered = 0, end = 0;
+        for (const auto& [lo, hi] : spans) {
+            if (hi <= end) continue;
+            covered += hi - std::max(lo, end);
+            end = hi;
+        }
+        area += covered * (xs[i + 1] - xs[i]);
+    }
+    return area;
+}
+
+struct Plan {
+    std::vector<std::vector<EditItem>> levels;  // [0]: the edited tiles of `lod`; [k]: the downsample items of lod - k
+    std::vector<uint32_t> max_rows;             // the tallest rectangle of each level
+    std::vector<TaskDev> stitches;
+    std::vector<std::pair<bt_tile_coordinate, uint32_t>> changed;  // (tile, layer): LOD descending, then layer
+    bt_edit_stats stats{};
+};
+
+EditItem make_item(const bt_tile_coordinate& c, const Dirty& d, uint32_t centre) {
+    EditItem it{};
+    it.layer = d.layer;
+    it.x0 = d.r.x0, it.y0 = d.r.y0, it.x1 = d.r.x1, it.y1 = d.r.y1;
+    it.gx0 = c.x * centre, it.gy0 = c.y * centre;
+    it.side = c.side;
+    for (uint32_t& ch : it.child) ch = BT_INVALID_ATLAS_INDEX;
+    return it;
+}
+
+// boxes of mosaic texels of `lod` -> the whole plan.  Host index arithmetic only.
+void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std::vector<Box>& boxes, Plan& plan) {
+    const uint32_t c = at.meta.center_size;
+    const bool spherical = a->config.spherical != 0;
+    DirtyTiles cur;
+    // the tiles of `lod` each box meets: existing ones get the box's part of their centre, the others are counted
+    uint64_t met = 0;
+    for (uint32_t side = 0; side < 6; side++) {
+        std::vector<Rect> tile_rects;
+        for (const Box& bx : boxes)
+            if (bx.side == side) tile_rects.push_back({bx.r.x0 / c, bx.r.y0 / c, bx.r.x1 / c, bx.r.y1 / c});
+        if (!tile_rects.empty()) met += union_area(tile_rects);
+    }
+    for (const Box& bx : boxes) {
+        const Rect t = {bx.r.x0 / c, bx.r.y0 / c, bx.r.x1 / c, bx.r.y1 / c};
+        auto visit = [&](const bt_tile_coordinate& tile, uint32_t layer) {
+            const uint64_t ox = uint64_t(tile.x) * c, oy = uint64_t(tile.y) * c;
+            const Rect r = {uint32_t(std::max<uint64_t>(bx.r.x0, ox) - ox), uint32_t(std::max<uint64_t>(bx.r.y0, oy) - oy),
+                            uint32_t(std::min<uint64_t>(bx.r.x1, ox + c - 1u) - ox), uint32_t(std::min<uint64_t>(bx.r.y1, oy + c - 1u) - oy)};
+            unite(cur, tile, layer, r);
+        };
+        const uint64_t count = (uint64_t(t.x1) - t.x0 + 1u) * (uint64_t(t.y1) - t.y0 + 1u);
+        if (count <= a->existing_tiles.size()) {
+            for (uint32_t y = t.y0; y <= t.y1; y++)
+                for (uint32_t x = t.x0; x <= t.x1; x++) {
+                    const bt_tile_coordinate tile = {bx.side, lod, x, y};
+                    const uint32_t layer = layer_of(a, tile);
+                    if (layer != BT_INVALID_ATLAS_INDEX) visit(tile, layer);
+                }
+        } else {  // a box over more tiles than the atlas holds: walk the atlas's instead
+            for (const bt_tile_coordinate& tile : a->existing_tiles) {
+                if (tile.side != bx.side || tile.lod != lod || tile.x < t.x0 || tile.x > t.x1 || tile.y < t.y0 || tile.y > t.y1) continue;
+                const uint32_t layer = layer_of(a, tile);
+                if (layer != BT_INVALID_ATLAS_INDEX) visit(tile, layer);
+            }
+        }
+    }
+    plan.stats.tiles_edited = uint32_t(cur.size());
+    plan.stats.tiles_missing = uint32_t(std::min<uint64_t>(met - std::min<uint64_t>(met, cur.size()), 0xFFFFFFFFull));
+    if (cur.empty()) return;
+
+    DirtyTiles written = cur;  // every tile of every LOD whose centre the call writes
+    auto level_items = [&](const DirtyTiles& tiles, bool with_children) {
+        std::vector<EditItem> items;
+        uint32_t rows = 0;
+        for (const auto& [coord, d] : tiles) {
+            EditItem it = make_item(coord, d, c);
+            if (with_children) {
+                bt_tile_coordinate ch[4];
+                tile_children(coord, ch);
+                for (int k = 0; k < 4; k++) it.child[k] = layer_of(a, ch[k]);
+            }
+            rows = std::max(rows, d.r.y1 - d.r.y0 + 1u);
+            items.push_back(it);
+        }
+        plan.levels.push_back(std::move(items));
+        plan.max_rows.push_back(rows);
+    };
+    level_items(cur, false);
+    for (const auto& [coord, d] : cur) {
+        bt_tile_coordinate ch[4];
+        tile_children(coord, ch);
+        for (int k = 0; k < 4; k++)
+            if (layer_of(a, ch[k]) != BT_INVALID_ATLAS_INDEX) {
+                plan.stats.tiles_with_children++;
+                break;
+            }
+    }
+    for (uint32_t l = lod; l > 0 && !cur.empty(); l--) {
+        DirtyTiles next;
+        for (const auto& [coord, d] : cur) {
+            const bt_tile_coordinate parent = {coord.side, l - 1u, coord.x >> 1, coord.y >> 1};
+            const uint32_t layer = layer_of(a, parent);
+            if (layer == BT_INVALID_ATLAS_INDEX) continue;  // the chain of ancestors ends where a parent does not exist
+            const uint32_t ox = (coord.x & 1u) * (c / 2u), oy = (coord.y & 1u) * (c / 2u);
+            unite(next, parent, layer, {ox + (d.r.x0 >> 1), oy + (d.r.y0 >> 1), ox + (d.r.x1 >> 1), oy + (d.r.y1 >> 1)});
+        }
+        if (next.empty()) break;
+        level_items(next, true);
+        plan.stats.tiles_downsampled += uint32_t(next.size());
+        written.insert(next.begin(), next.end());
+        cur.swap(next);
+    }
+
+    // aprons: every written tile and every existing neighbour of one, all eight regions
+    std::map<bt_tile_coordinate, uint32_t, CoordLess> touched;
+    for (const auto& [coord, d] : written) touched.emplace(coord, d.layer);
+    if (at.meta.border_size > 0) {
+        for (const auto& [coord, d] : written) {
+            bt_tile_coordinate nb[8];
+            tile_neighbours(coord, spherical, nb);
+            for (const bt_tile_coordinate& n : nb) {
+                const uint32_t layer = layer_of(a, n);
+                if (layer != BT_INVALID_ATLAS_INDEX) touched.emplace(n, layer);
+            }
+        }
+    }
+    for (const auto& [coord, layer] : touched) plan.changed.push_back({coord, layer});
+    std::sort(plan.changed.begin(), plan.changed.end(), [](const auto& l, const auto& r) {
+        if (l.first.lod != r.first.lod) return l.first.lod > r.first.lod;
+        return l.second < r.second;
+    });
+    if (at.meta.border_size > 0) {
+        for (const auto& [coord, layer] : plan.changed) {
+            TaskDev t{};
+            t.atlas_index = layer;
+            t.side = coord.side, t.lod = coord.lod, t.x = coord.x, t.y = coord.y;
+            bt_tile_coordinate nb[8];
+            tile_neighbours(coord, spherical, nb);
+            for (int k = 0; k < 8; k++) {
+                t.rel_index[k] = layer_of(a, nb[k]);
+                t.rel_side[k] = nb[k].side;
+            }
+            plan.stitches.push_back(t);
+        }
+        plan.stats.tiles_stitched = uint32_t(plan.stitches.size());
+    }
+    plan.stats.changed_count = uint32_t(plan.changed.size());
+}
+
+uint64_t align16(uint64_t v) { return (v + 15u) & ~uint64_t(15); }
+
+// `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read
+bt_status edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev) {
+    need = (need + 255u) & ~uint64_t(255);
+    if (!ctx->edit_copied) BT_HIP(hipEventCreateWithFlags(&ctx->edit_copied, hipEventDisableTiming));
+    if (need > ctx->edit_bytes) {
+        if (ctx->edit_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers that go away
+        if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
+        if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
+        ctx->edit_dev = ctx->edit_host = nullptr;
+        ctx->edit_bytes = ctx->edit_used = 0;
+        const uint64_t bytes = std::max<uint64_t>(1ull << 20, 2u * need);
+        BT_HIP(hipMalloc(&ctx->edit_dev, bytes));
+        BT_HIP(hipHostMalloc(&ctx->edit_host, bytes, hipHostMallocDefault));
+        ctx->edit_bytes = bytes;
+    }
+    if (ctx->edit_used + need > ctx->edit_bytes) {
+        // the ring wraps: the pinned records of earlier calls must have been copied (their device halves are safe: this call's copy and
+        // kernels are ordered behind theirs on the stream)
+        BT_HIP(hipEventSynchronize(ctx->edit_copied));
+        ctx->edit_used = 0;
+    }
+    *host = (uint8_t*)ctx->edit_host + ctx->edit_used;
+    *dev = (uint8_t*)ctx->edit_dev + ctx->edit_used;
+    ctx->edit_used += need;
+    return BT_OK;
+}
+
+struct RegionSource {
+    const void* dev;
+    uint32_t rx0, ry0, width;
+};
+
+// uploads the plan and enqueues its launches; the first launch is the brush (stamps) or the region copy (region)
+bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* stamps, uint32_t stamp_count, const RegionSource* region) {
+    Attachment& at = a->attachments[ai];
+    bt_ctx* ctx = a->ctx;
+    if (plan.levels.empty()) return BT_OK;
+    uint64_t bytes = align16(uint64_t(stamp_count) * sizeof(bt_edit_stamp)) + align16(plan.stitches.size() * sizeof(TaskDev));
+    for (const auto& items : plan.levels) bytes += align16(items.size() * sizeof(EditItem));
+    uint8_t *host = nullptr, *dev = nullptr;
+    if (bt_status s = edit_scratch(ctx, bytes, &host, &dev)) return s;
+    uint64_t off = 0;
+    auto put = [&](const void* src, uint64_t n) {
+        if (n) memcpy(host + off, src, n);
+        const uint8_t* where = dev + off;
+        off += align16(n);
+        return where;
+    };
+    const bt_edit_stamp* stamps_dev = (const bt_edit_stamp*)put(stamps, uint64_t(stamp_count) * sizeof(bt_edit_stamp));
+    std::vector<const EditItem*> items_dev;
+    for (const auto& items : plan.levels) items_dev.push_back((const EditItem*)put(items.data(), items.size() * sizeof(EditItem)));
+    const TaskDev* stitches_dev = (const TaskDev*)put(plan.stitches.data(), plan.stitches.size() * sizeof(TaskDev));
+    BT_HIP(hipMemcpyAsync(dev, host, off, hipMemcpyHostToDevice, ctx->stream));
+    BT_HIP(hipEventRecord(ctx->edit_copied, ctx->stream));
+
+    for (const auto& [coord, layer] : plan.changed) at.mark_written(layer, 1);
+    const uint32_t n0 = uint32_t(plan.levels[0].size());
+    if (region) {
+        if (bt_status s = launch_edit_region(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], region->dev, region->rx0, region->ry0, region->width)) return s;
+    } else {
+        if (bt_status s = launch_edit_brush(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], stamps_dev, stamp_count)) return s;
+    }
+    plan.stats.launches = 1;
+    for (size_t k = 1; k < plan.levels.size(); k++) {
+        if (bt_status s = launch_edit_downsample(ctx->stream, at.meta, at.level0, items_dev[k], uint32_t(plan.levels[k].size()), plan.max_rows[k])) return s;
+        plan.stats.launches++;
+    }
+    if (!plan.stitches.empty()) {
+        if (bt_status s = launch_stitch(ctx, at.meta, at.level0, stitches_dev, uint32_t(plan.stitches.size()))) return s;
+        plan.stats.launches++;
+    }
+    if (at.mips.size() > 1) {  // the existing mip kernels, one pass per run of consecutive layers
+        std::vector<uint32_t> layers;
+        for (const auto& [coord, layer] : plan.changed) layers.push_back(layer);
+        std::sort(layers.begin(), layers.end());
+        layers.erase(std::unique(layers.begin(), layers.end()), layers.end());
+        for (size_t i = 0; i < layers.size();) {
+            size_t run = 1;
+            while (i + run < layers.size() && layers[i + run] == layers[i] + run) run++;
+            if (bt_status s = bt_atlas_generate_mipmaps(a, ai, layers[i], uint32_t(run))) return s;
+            plan.stats.launches += uint32_t(at.mips.size() - 1);
+            i += run;
+        }
+        plan.stats.layers_mipped = uint32_t(layers.size());
+    }
+    return BT_OK;
+}
+
+void report(const Plan& plan, bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
+    for (uint32_t i = 0; i < plan.changed.size() && i < changed_cap; i++) changed[i] = plan.changed[i].first;
+    if (stats) *stats = plan.stats;
+}
+
+// what both edit calls check of the atlas: attachment, LOD, format and centre size
+bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, bool brush, const char* what) {
+    if (ai >= a->attachments.size()) {
+        set_error("%s: attachment %u of %zu", what, ai, a->attachments.size());
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (lod >= a->config.lod_count || lod > 30u) {
+        set_error("%s: lod %u of lod_count %u", what, lod, a->config.lod_count);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const AttachmentMeta& m = a->attachments[ai].meta;
+    if (m.format != BT_FORMAT_R16 && (brush || m.format != BT_FORMAT_RGBA8)) {
+        set_error("%s: attachment format %u (%s)", what, m.format, brush ? "the brush edits R16 heights" : "R16 and Rgba8 only");
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (m.center_size % 2u) {
+        set_error("%s: odd centre size %u (texture_size %u, border_size %u): a parent texel would straddle two children", what, m.center_size, m.texture_size, m.border_size);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if ((uint64_t(m.center_size) << lod) > 0xFFFFFFFFull) {
+        set_error("%s: a mosaic of %u x 2^%u texels", what, m.center_size, lod);
+        return BT_ERR_UNSUPPORTED;
+    }
+    return BT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bt_status bt_atlas_edit_height(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_edit_stamp* stamps, uint32_t count, bt_tile_coordinate* changed,
+                               uint32_t changed_cap, bt_edit_stats* stats) {
+    if (stats) *stats = bt_edit_stats{};
+    // the stamps first: what can be refused without the atlas is refused without it
+    if (count > BT_EDIT_MAX_STAMPS) {
+        set_error("bt_atlas_edit_height: %u stamps, at most %u per call", count, BT_EDIT_MAX_STAMPS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if ((count && !stamps) || (changed_cap && !changed)) {
+        set_error("bt_atlas_edit_height: NULL %s", count && !stamps ? "stamps" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_edit_stamp& s = stamps[i];
+        const char* bad = nullptr;
+        if (s.side >= 6u) bad = "side";
+        else if (s.mode != BT_EDIT_ADD && s.mode != BT_EDIT_FLATTEN) bad = "mode";
+        else if (s.falloff != BT_EDIT_FALLOFF_SMOOTH && s.falloff != BT_EDIT_FALLOFF_HARD) bad = "falloff";
+        else if (!std::isfinite(s.center[0]) || !std::isfinite(s.center[1])) bad = "center (not finite)";
+        else if (!std::isfinite(s.radius) || !(s.radius > 0.0f)) bad = "radius (finite and > 0)";
+        else if (!std::isfinite(s.amount)) bad = "amount (not finite)";
+        if (bad) {
+            set_error("bt_atlas_edit_height: stamp %u: %s", i, bad);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (!a) {
+        set_error("bt_atlas_edit_height: NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_target(a, ai, lod, true, "bt_atlas_edit_height")) return s;
+    const uint32_t sides = a->config.spherical ? 6u : 1u;
+    for (uint32_t i = 0; i < count; i++)
+        if (stamps[i].side >= sides) {
+            set_error("bt_atlas_edit_height: stamp %u: side %u of %u", i, stamps[i].side, sides);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (!count) return BT_OK;
+    const Attachment& at = a->attachments[ai];
+    // a stamp's box [floor(center - radius), ceil(center + radius)], clipped to the face: a texel outside it is at least radius + 1 away on
+    // one axis, and rounding is monotonic, so its d2 is not below r2 in binary32 either
+    const double size = double(uint64_t(at.meta.center_size) << lod);
+    std::vector<Box> boxes;
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_edit_stamp& s = stamps[i];
+        double lo[2], hi[2];
+        bool empty = false;
+        for (int k = 0; k < 2; k++) {
+            lo[k] = std::max(0.0, std::floor(double(s.center[k]) - double(s.radius)));
+            hi[k] = std::min(size - 1.0, std::ceil(double(s.center[k]) + double(s.radius)));
+            empty = empty || lo[k] > hi[k];
+        }
+        if (!empty) boxes.push_back({s.side, {uint32_t(lo[0]), uint32_t(lo[1]), uint32_t(hi[0]), uint32_t(hi[1])}});
+    }
+    hipError_t e = hipSetDevice(a->ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    Plan plan;
+    build_plan(a, at, lod, boxes, plan);
+    const bt_status rc = run_plan(a, ai, plan, stamps, count, nullptr);
+    report(plan, changed, changed_cap, stats);
+    return rc;
+}
+
+bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                const void* texels, uint64_t row_pitch, bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
+    if (stats) *stats = bt_edit_stats{};
+    if (!a) {
+        set_error("bt_atlas_write_region: NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (changed_cap && !changed) {
+        set_error("bt_atlas_write_region: NULL changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_target(a, ai, lod, false, "bt_atlas_write_region")) return s;
+    if (side >= (a->config.spherical ? 6u : 1u)) {
+        set_error("bt_atlas_write_region: side %u", side);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    Attachment& at = a->attachments[ai];
+    const uint64_t size = uint64_t(at.meta.center_size) << lod;
+    if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
+        set_error("bt_atlas_write_region: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", x0, x0 + width, y0, y0 + height, (unsigned long long)size);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!width || !height) return BT_OK;
+    const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
+    if (!row_pitch) row_pitch = row_bytes;
+    if (!texels || row_pitch < row_bytes) {
+        set_error("bt_atlas_write_region: %s", !texels ? "NULL texels_host" : "row_pitch smaller than a row");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    Plan plan;
+    build_plan(a, at, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, plan);
+    if (plan.levels.empty()) {  // the rectangle meets no tile the atlas holds
+        report(plan, changed, changed_cap, stats);
+        return BT_OK;
+    }
+    // the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
+    const uint64_t total = row_bytes * height;
+    if (total > ctx->edit_region_bytes) {
+        if (ctx->edit_region_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // a region launch in flight reads the buffer that goes away
+        if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
+        ctx->edit_region_dev = nullptr;
+        ctx->edit_region_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->edit_region_dev, total));
+        ctx->edit_region_bytes = total;
+    }
+    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
+        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
+    hipEvent_t copied[bt_ctx::kStagingBuffers] = {};
+    bt_status rc = BT_OK;
+    uint32_t chunk = 0;
+    for (uint32_t row = 0; row < height && rc == BT_OK; row += chunk_rows, chunk++) {
+        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
+        hipError_t e = copied[k] ? hipEventSynchronize(copied[k]) : hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
+        for (uint32_t r = 0; r < rows && e == hipSuccess; r++)
+            memcpy((uint8_t*)ctx->staging[k] + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region_dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(copied[k], ctx->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "bt_atlas_write_region staging");
+    }
+    if (rc == BT_OK) {
+        const RegionSource src = {ctx->edit_region_dev, x0, y0, width};
+        rc = run_plan(a, ai, plan, nullptr, 0, &src);
+    }
+    for (hipEvent_t ev : copied)  // the staging buffers are free again once the copies have run: the one wait of this call
+        if (ev) {
+            const hipError_t e = hipEventSynchronize(ev);
+            if (e != hipSuccess && rc == BT_OK) rc = hip_fail(e, "bt_atlas_write_region staging");
+            hipEventDestroy(ev);
+        }
+    report(plan, changed, changed_cap, stats);
+    return rc;
+}
+
+bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {
+    if (!a || !directory || (count && !coords)) {
+        set_error("bt_atlas_save_tiles: NULL %s", !a ? "atlas" : !directory ? "directory" : "coords");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (ai >= a->attachments.size()) {
+        set_error("bt_atlas_save_tiles: attachment %u of %zu", ai, a->attachments.size());
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    TileSaver::Tiles tiles;
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t layer = layer_of(a, coords[i]);
+        if (layer == BT_INVALID_ATLAS_INDEX) {
+            set_error("bt_atlas_save_tiles: tile %u_%u_%u_%u is not in the atlas", coords[i].side, coords[i].lod, coords[i].x, coords[i].y);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        tiles.push_back({layer, coords[i]});
+    }
+    return save_tiles(a, ai, directory, std::move(tiles));
+}
+
+}  // extern "C"

@@ -1,0 +1,188 @@
+// In-place editing of atlas layers (bt_atlas_edit_height / bt_atlas_write_region): the kernels.  The planning is in bt_edit.cpp.
+//
+// An item is ONE tile's dirty rectangle of one launch: (layer, inclusive rectangle in centre texels, mosaic origin of the tile's centre).
+// grid = (items, row blocks of the tallest rectangle); a workgroup of four waves takes kEditRows rows of its item, a wave one row at a
+// time, lanes along x: a row is one coalesced run of dwords.
+//   R16: a lane owns one ALIGNED 32-bit pair of texels (T is even: an odd centre size is refused, so rows start on a dword).  At an odd
+//   rectangle edge half of the pair lies outside the rectangle (another centre texel, or an apron texel): the lane writes that half back
+//   from its own read.  Items of a launch are different layers and rows are different dwords, so no two lanes touch the same dword.
+//   Rgba8: a lane owns one texel.
+//
+// edit_brush_kernel   the stamps of bt_atlas_edit_height on the texels of the rectangle; the stamp array is indexed by the loop counter
+//                     only (wave-uniform: scalar loads), and a stamp whose side is not the item's is skipped by the whole wave.
+// edit_region_kernel  the same layout, copying from the staged rectangle of bt_atlas_write_region.
+// edit_downsample_kernel  the rectangle of a parent's centre from its four children: downsample_texel of bt_downsample.hpp, the device
+//                     function downsample_kernel runs.  One launch per LOD (a level reads what the level below wrote).
+//
+// Arithmetic contract of the brush (include/bevy_terrain_amd.h): IEEE binary32, one rounding per written operation; this file is compiled
+// with -ffp-contract=off, `/` is the correctly rounded division.
+#include "bt_internal.hpp"
+
+namespace bt {
+
+namespace {
+
+#include "bt_downsample.hpp"  // unorm16_to_float, float_to_unorm, Texel, downsample_texel
+
+constexpr uint32_t kEditThreads = 256;
+constexpr uint32_t kEditRows = 16;  // rows of a rectangle per workgroup: four per wave
+
+// t -> t' of one stamp that has passed the side test (the header's BRUSH section, line by line)
+__device__ __forceinline__ uint32_t stamp_texel(const bt_edit_stamp& s, float r2, float fx, float fy, uint32_t t) {
+    const float dx = fx - s.center[0];
+    const float dy = fy - s.center[1];
+    const float d2 = (dx * dx) + (dy * dy);
+    if (!(d2 < r2) || t == 0u) return t;
+    float w = 1.0f;
+    if (s.falloff == BT_EDIT_FALLOFF_SMOOTH) {
+        const float q = d2 / r2;
+        const float sm = 1.0f - q;
+        w = sm * sm;
+    }
+    const float h = unorm16_to_float(t);  // == f32(t) / 65535 for every t (bt_selftest)
+    const float hn = s.mode == BT_EDIT_FLATTEN ? h + (s.amount - h) * w : h + s.amount * w;
+    return max(1u, float_to_unorm(hn, 65535.0f));
+}
+
+// the rows and the dword range a workgroup's waves walk: calls body(row y, dword p) for every (row of this workgroup, dword of the row)
+// first / last: the first and last dword index (inside the tile row) that holds a texel of the rectangle
+template <typename Body>
+__device__ __forceinline__ void for_each_dword(const EditItem& it, uint32_t first, uint32_t last, Body body) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t y_begin = it.y0 + blockIdx.y * kEditRows;
+    if (y_begin > it.y1) return;
+    const uint32_t y_end = min(y_begin + kEditRows - 1u, it.y1);
+    for (uint32_t y = y_begin + wave; y <= y_end; y += kEditThreads / 64u)
+        for (uint32_t p = first + lane; p <= last; p += 64u) body(y, p);
+}
+
+__global__ __launch_bounds__(kEditThreads) void edit_brush_kernel(AttachmentMeta m, uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
+                                                                  const bt_edit_stamp* __restrict__ stamps, uint32_t stamp_count) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    uint32_t* tile = reinterpret_cast<uint32_t*>(atlas + uint64_t(it.layer) * Tsz * Tsz);
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
+    for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
+        uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
+        const uint32_t old = *dst;
+        const uint32_t px = 2u * p;
+        const bool in0 = px >= px0, in1 = px + 1u <= px1;  // (px <= px1 and px + 1 >= px0 hold for every dword of the range)
+        uint32_t t0 = old & 0xFFFFu, t1 = old >> 16;
+        const float fy = float(it.gy0 + y);
+        const float fx0 = float(it.gx0 + px - b), fx1 = float(it.gx0 + px + 1u - b);  // (the half outside the rectangle is not used)
+        for (uint32_t k = 0; k < stamp_count; k++) {
+            const bt_edit_stamp s = stamps[k];
+            if (s.side != it.side) continue;
+            const float r2 = s.radius * s.radius;
+            if (in0) t0 = stamp_texel(s, r2, fx0, fy, t0);
+            if (in1) t1 = stamp_texel(s, r2, fx1, fy, t1);
+        }
+        *dst = t0 | (t1 << 16);
+    });
+}
+
+template <uint32_t FORMAT>
+__global__ __launch_bounds__(kEditThreads) void edit_region_kernel(AttachmentMeta m, void* __restrict__ atlas_, const EditItem* __restrict__ items,
+                                                                   const void* __restrict__ src_, uint32_t rx0, uint32_t ry0, uint32_t src_width) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
+    if constexpr (FORMAT == BT_FORMAT_R16) {
+        uint32_t* tile = reinterpret_cast<uint32_t*>((uint16_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz);
+        const uint16_t* src = (const uint16_t*)src_;
+        for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
+            uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
+            const uint32_t old = *dst;
+            const uint32_t px = 2u * p;
+            const bool in0 = px >= px0, in1 = px + 1u <= px1;
+            const uint16_t* row = src + uint64_t(it.gy0 + y - ry0) * src_width;
+            // (the column of the half outside the rectangle may lie outside the staged rows: it is not read)
+            const uint32_t t0 = in0 ? uint32_t(row[it.gx0 + px - b - rx0]) : (old & 0xFFFFu);
+            const uint32_t t1 = in1 ? uint32_t(row[it.gx0 + px + 1u - b - rx0]) : (old >> 16);
+            *dst = t0 | (t1 << 16);
+        });
+    } else {
+        uint32_t* tile = (uint32_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz;
+        const uint32_t* src = (const uint32_t*)src_;
+        for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) {
+            tile[uint64_t(b + y) * Tsz + px] = src[uint64_t(it.gy0 + y - ry0) * src_width + (it.gx0 + px - b - rx0)];
+        });
+    }
+}
+
+// centre texel (tx, ty) of a parent: the child it lies in and the 2x2 block of that child's centre (downsample_kernel's mapping).  The child
+// layers come as four scalars selected by comparisons: a dynamically indexed copy of the item would be promoted to LDS.
+struct EditChildren {
+    uint32_t c0, c1, c2, c3;
+};
+template <uint32_t FORMAT>
+__device__ __forceinline__ uint32_t parent_texel(const AttachmentMeta& m, const typename Texel<FORMAT>::type* __restrict__ base, EditChildren ch, uint32_t tx, uint32_t ty) {
+    const uint32_t Tsz = m.texture_size, b = m.border_size, child_size = m.center_size / 2u;
+    const bool right = tx >= child_size, low = ty >= child_size;
+    const uint32_t layer = low ? (right ? ch.c3 : ch.c2) : (right ? ch.c1 : ch.c0);
+    const typename Texel<FORMAT>::type* child = layer < m.atlas_size ? base + uint64_t(layer) * Tsz * Tsz : nullptr;
+    return downsample_texel<FORMAT>(child, Tsz, 2u * (right ? tx - child_size : tx) + b, 2u * (low ? ty - child_size : ty) + b);
+}
+
+template <uint32_t FORMAT>
+__global__ __launch_bounds__(kEditThreads) void edit_downsample_kernel(AttachmentMeta m, void* __restrict__ atlas_, const EditItem* __restrict__ items) {
+    using T = typename Texel<FORMAT>::type;
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    T* base = (T*)atlas_;
+    const EditChildren ch = {it.child[0], it.child[1], it.child[2], it.child[3]};
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
+    if constexpr (FORMAT == BT_FORMAT_R16) {
+        uint32_t* tile = reinterpret_cast<uint32_t*>(base + uint64_t(it.layer) * Tsz * Tsz);
+        for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
+            uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
+            const uint32_t px = 2u * p;
+            const bool in0 = px >= px0, in1 = px + 1u <= px1;
+            // (the half of a dword outside the rectangle: its texel is computed from a clamped column and dropped, the parent's value kept)
+            const uint32_t t0 = parent_texel<FORMAT>(m, base, ch, in0 ? px - b : it.x0, y);
+            const uint32_t t1 = parent_texel<FORMAT>(m, base, ch, in1 ? px + 1u - b : it.x1, y);
+            const uint32_t old = (in0 && in1) ? 0u : *dst;
+            *dst = (in0 ? t0 : (old & 0xFFFFu)) | ((in1 ? t1 : (old >> 16)) << 16);
+        });
+    } else {
+        T* tile = base + uint64_t(it.layer) * Tsz * Tsz;
+        for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) { tile[uint64_t(b + y) * Tsz + px] = parent_texel<FORMAT>(m, base, ch, px - b, y); });
+    }
+}
+
+bt_status edit_launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BT_OK : hip_fail(e, what);
+}
+
+dim3 edit_grid(uint32_t n, uint32_t max_rows) { return dim3(n, (max_rows + kEditRows - 1u) / kEditRows); }
+
+}  // namespace
+
+bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                            const bt_edit_stamp* stamps, uint32_t stamp_count) {
+    if (!n || !max_rows) return BT_OK;
+    edit_brush_kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, (uint16_t*)atlas, items, stamps, stamp_count);
+    return edit_launched("edit_brush_kernel");
+}
+
+bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                             const void* src, uint32_t rx0, uint32_t ry0, uint32_t src_width) {
+    if (!n || !max_rows) return BT_OK;
+    if (m.format == BT_FORMAT_R16)
+        edit_region_kernel<BT_FORMAT_R16><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
+    else
+        edit_region_kernel<BT_FORMAT_RGBA8><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
+    return edit_launched("edit_region_kernel");
+}
+
+bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows) {
+    if (!n || !max_rows) return BT_OK;
+    if (m.format == BT_FORMAT_R16)
+        edit_downsample_kernel<BT_FORMAT_R16><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
+    else
+        edit_downsample_kernel<BT_FORMAT_RGBA8><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
+    return edit_launched("edit_downsample_kernel");
+}
+
+}  // namespace bt

@@ -289,6 +289,10 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     if (ctx->bounds_dev) hipFree(ctx->bounds_dev);
     if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
     if (ctx->raycast_dev) hipFree(ctx->raycast_dev);
+    if (ctx->edit_dev) hipFree(ctx->edit_dev);
+    if (ctx->edit_host) hipHostFree(ctx->edit_host);
+    if (ctx->edit_region_dev) hipFree(ctx->edit_region_dev);
+    if (ctx->edit_copied) hipEventDestroy(ctx->edit_copied);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->save_stream) hipStreamDestroy(ctx->save_stream);
     delete ctx;
@@ -345,6 +349,12 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
     }
     ctx->raycast_dev = nullptr;
     ctx->raycast_bytes = 0;
+    if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
+    if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
+    if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
+    freed += 2u * ctx->edit_bytes + ctx->edit_region_bytes;
+    ctx->edit_dev = ctx->edit_host = ctx->edit_region_dev = nullptr;
+    ctx->edit_bytes = ctx->edit_used = ctx->edit_region_bytes = 0;
     if (freed_bytes) *freed_bytes = freed;
     return BT_OK;
 }

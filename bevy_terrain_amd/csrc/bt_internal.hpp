@@ -203,6 +203,16 @@ struct bt_ctx {
     // bt_tile_tree_raycast: the rays and the hits of one call on the device (grown on demand, kept until bt_ctx_trim)
     void* raycast_dev = nullptr;
     uint64_t raycast_bytes = 0;
+    // bt_atlas_edit_height / bt_atlas_write_region: the plans (items, stamps, stitch tasks) of the calls in flight, pinned and on the device,
+    // handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is recorded behind each
+    // call's copy and waited for when the ring wraps), and the staged rectangle of write_region on the device (grown on demand, kept
+    // until bt_ctx_trim)
+    void* edit_dev = nullptr;
+    void* edit_host = nullptr;
+    uint64_t edit_bytes = 0, edit_used = 0;
+    hipEvent_t edit_copied = nullptr;
+    void* edit_region_dev = nullptr;
+    uint64_t edit_region_bytes = 0;
 };
 
 namespace bt {
@@ -258,6 +268,20 @@ bt_status launch_gather_layers(hipStream_t stream, const void* atlas, const uint
 // bt_bounds.hip: the min/max pyramids of `count` R16 layers of size T (layers: device list) -> out (device, (4g^2 - 1) / 3 words per layer)
 bt_status launch_tile_bounds(hipStream_t stream, const void* atlas, uint32_t T, const uint32_t* layers, uint32_t count, uint32_t grid,
                              bool skip_zero, uint32_t* out);
+// bt_edit.hip: the in-place edit kernels.  An item is one tile's dirty rectangle (inclusive, in centre texels) of one launch
+struct EditItem {
+    uint32_t layer;           // the atlas layer written
+    uint32_t x0, y0, x1, y1;  // the rectangle inside the tile's centre
+    uint32_t gx0, gy0;        // mosaic position of the tile's centre texel (0, 0)
+    uint32_t side;
+    uint32_t child[4];        // downsample: the four child layers, BT_INVALID_ATLAS_INDEX where absent
+};
+bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                            const bt_edit_stamp* stamps, uint32_t stamp_count);
+// src: the staged rectangle (device, `src_width` texels per row, tightly packed) whose texel (0, 0) is mosaic texel (rx0, ry0)
+bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                             const void* src, uint32_t rx0, uint32_t ry0, uint32_t src_width);
+bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows);
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 

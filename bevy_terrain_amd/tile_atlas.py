@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -106,6 +107,30 @@ class Device:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class EditStamp:
+    """bt_edit_stamp: one brush stamp of TileAtlas.edit_height.  center / radius are in mosaic texels of the edited LOD on `side`
+    (mosaic_position); amount is a normalised height (1 = max_height - min_height): the signed delta of "add", the target of "flatten"."""
+    center: Tuple[float, float]
+    radius: float
+    amount: float
+    mode: str = "add"        # "add" | "flatten"
+    falloff: str = "smooth"  # "smooth": w = (1 - d^2 / r^2)^2 | "hard": w = 1
+    side: int = 0
+
+    def _c(self):
+        return _ffi.EditStampC(self.side, {"add": _ffi.EDIT_ADD, "flatten": _ffi.EDIT_FLATTEN}[self.mode],
+                               {"smooth": _ffi.EDIT_FALLOFF_SMOOTH, "hard": _ffi.EDIT_FALLOFF_HARD}[self.falloff], 0,
+                               (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.amount))
+
+
+def mosaic_position(uv, lod: int, center_size: int) -> Tuple[float, float]:
+    """The mosaic position (EditStamp.center units) of face coordinate uv in [0, 1]^2 at `lod`: the face is 2^lod * center_size texels
+    wide and texel g covers [g / n, (g + 1) / n) with its position at the integer g, so the middle of texel g maps to g."""
+    n = (1 << lod) * center_size
+    return (float(uv[0]) * n - 0.5, float(uv[1]) * n - 0.5)
 
 
 def texel_dtype(fmt: AttachmentFormat):
@@ -280,6 +305,43 @@ class TileAtlas:
             result.append(out[:, base:base + n * n].reshape(len(idx), n, n, 2))
             base += n * n
         return result
+
+    def _edit_result(self, call) -> Tuple[List[TileCoordinate], dict]:
+        """runs call(changed, cap, stats) and, if the list did not fit, is NOT run again: the first call sizes the list for any edit"""
+        cap = max(self.atlas_size, 1)  # a call cannot write more tiles than the atlas has layers
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.EditStatsC()
+        _ffi.check(call(changed, cap, C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.EditStatsC._fields_}
+        return [TileCoordinate._from_c(changed[i]) for i in range(min(stats.changed_count, cap))], out
+
+    def edit_height(self, attachment_index: int, stamps, lod: Optional[int] = None) -> Tuple[List[TileCoordinate], dict]:
+        """bt_atlas_edit_height: apply the EditStamps, in list order, to the centre texels of the existing tiles of `lod` (default: the
+        finest, lod_count - 1) of an R16 attachment, then restore the ancestors, the aprons and the mips that depend on them, on the
+        device and without synchronising.  Returns (changed tiles: LOD descending then atlas index, bt_edit_stats as a dict).  Tiles finer
+        than `lod` are not touched (stats["tiles_with_children"]); height-bounds tables and tile-tree state are the caller's to refresh."""
+        lod = self.lod_count - 1 if lod is None else lod
+        stamps = list(stamps)
+        arr = (_ffi.EditStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
+        return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_edit_height(self._h, attachment_index, lod, arr, len(stamps), changed, cap, stats))
+
+    def write_region(self, attachment_index: int, texels: np.ndarray, x0: int, y0: int, lod: Optional[int] = None, side: int = 0):
+        """bt_atlas_write_region: copy `texels` ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros allowed) verbatim over the centre
+        texels at mosaic position (x0, y0) of `lod` on `side`, then propagate like edit_height.  Returns (changed, stats)."""
+        lod = self.lod_count - 1 if lod is None else lod
+        a = self.config.attachments[attachment_index]
+        texels = np.ascontiguousarray(texels, dtype=texel_dtype(a.format))
+        if texels.ndim != (2 if a.format == AttachmentFormat.R16 else 3):
+            raise ValueError(f"write_region: texels of shape {texels.shape} for a {a.format.name} attachment")
+        h, w = texels.shape[:2]
+        return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_write_region(
+            self._h, attachment_index, side, lod, x0, y0, w, h, texels.ctypes.data_as(C.c_void_p), 0, changed, cap, stats))
+
+    def save_tiles(self, attachment_index: int, directory: str, coords):
+        """bt_atlas_save_tiles: "{directory}/{coord}.bin" of the listed tiles only (the `changed` list of an edit)."""
+        coords = list(coords)
+        arr = (_ffi.TileCoordinateC * max(len(coords), 1))(*[c._c() for c in coords])
+        _ffi.check(_ffi.lib().bt_atlas_save_tiles(self._h, attachment_index, directory.encode(), arr, len(coords)))
 
     def close(self):
         if getattr(self, "_h", None):

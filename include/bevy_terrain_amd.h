@@ -291,6 +291,78 @@ enum { BT_BOUNDS_SKIP_ZERO = 1, BT_BOUNDS_MAX_GRID = 64 };
 bt_status bt_atlas_tile_bounds(bt_atlas* atlas, uint32_t attachment_index, const uint32_t* layers /* NULL: 0 .. count-1 */,
                                uint32_t count, uint32_t grid, uint32_t flags, uint16_t* out_host, uint64_t out_bytes);
 
+/* ---------------- in-place editing: change centre texels of tiles in HBM and restore everything that depends on them
+ * (docs/development.md "Real-Time Editing" of the reference names it as missing; it has no such operation).
+ *
+ * THE INVARIANT.  After any job of this library an attachment's atlas state is a function F of its "primary" centre texels:
+ *   1. a tile none of whose four children exists is primary: its centre texels are data;
+ *   2. any other existing tile is derived: its centre is downsample (downsample.wgsl:12-40) of its children's centres, an absent child
+ *      reads as 0, a texel without data (count 0) is 0, taps in the order (0,0), (0,1), (1,0), (1,1);
+ *   3. every existing tile's apron is stitch (stitch.wgsl:53-118) of its neighbours' centres: a missing neighbour clamps into the tile's
+ *      own centre, cube faces go through project_to_side;
+ *   4. mip levels 1.. of a layer are generate_mipmaps of its level 0 (attachments with mip_level_count > 1).
+ * "Exists" = the atlas holds a layer for the tile (bt_atlas_tiles with an atlas index).  An edit at LOD `lod` changes centre texels of
+ * existing tiles of that LOD and then restores 2 - 4 for what depends on them: the ancestors up to LOD 0 (stopping where a parent does
+ * not exist), the aprons of the written tiles and of their existing neighbours at every written LOD, the mips of every written layer.
+ * Tiles finer than `lod` are NOT touched (bt_edit_stats.tiles_with_children counts the edited tiles that have one): edit at the finest
+ * LOD the atlas holds there.  The result is byte-identical to F of the edited texels.
+ *
+ * MOSAIC COORDINATES.  With c = texture_size - 2 * border_size, centre texel (i, j) of tile (side, lod, X, Y) is texel
+ * (gx, gy) = (X * c + i, Y * c + j) of the face's mosaic of 2^lod * c texels per side; its position is the integer pair itself.
+ *
+ * THE BRUSH (bt_atlas_edit_height; R16 only).  IEEE binary32, one rounding per written operation, no contraction; f32(n) is exact for the
+ * mosaic sizes that occur.  A centre texel (gx, gy) with raw value t takes the stamps IN LIST ORDER, those whose `side` is the tile's:
+ *     dx = f32(gx) - center[0];  dy = f32(gy) - center[1];  d2 = (dx * dx) + (dy * dy);  r2 = radius * radius
+ *     the stamp is skipped unless d2 < r2
+ *     w = 1 (BT_EDIT_FALLOFF_HARD);  q = d2 / r2, s = 1 - q, w = s * s (BT_EDIT_FALLOFF_SMOOTH)
+ *     h = f32(t) / 65535
+ *     h' = h + amount * w (BT_EDIT_ADD);  h' = h + (amount - h) * w (BT_EDIT_FLATTEN)
+ *     t' = max(1, floor(0.5 + 65535 * clamp(h', 0, 1)))          and t' is the t of the next stamp
+ * A texel equal to 0 (no data) is never changed and a stamp never produces 0: the hole mask of a terrain is not the brush's to alter.  A
+ * stamp is clipped to its face (it does not continue across a cube edge).  The tiles a stamp can reach are those that meet its box
+ * [floor(center - radius), ceil(center + radius)] on both axes (no texel outside it passes d2 < r2); tiles_edited / tiles_missing count
+ * the tiles of `lod` that meet a stamp's box and exist / do not exist, and every existing one is written, changed or not.
+ *
+ * bt_atlas_write_region (R16 and Rgba8) copies a width x height rectangle of centre texels, mosaic coordinates of `lod` on `side`, texels
+ * in the attachment's format, zeros allowed, verbatim from host memory (row_pitch bytes per row, 0 = tightly packed), then propagates
+ * in the same way.  The rectangle must lie inside [0, 2^lod * c)^2.  The texels travel through the context's pinned staging buffers;
+ * the call waits for that copy and for nothing else.
+ *
+ * BOTH.  Texels that fall into tiles the atlas does not hold are skipped (tiles_missing); nothing outside the existing tiles' layers is
+ * written.  `changed` (may be NULL with changed_cap 0) receives every tile, of all LODs, whose layer the call wrote — edited tiles, their
+ * ancestors, and the existing neighbours of those (their aprons) — LOD descending, then atlas index, up to changed_cap entries;
+ * stats->changed_count is the full number.  The list is host index arithmetic: the calls enqueue on the context's stream behind earlier
+ * work and return without synchronising (apart from the staging copy above); every written layer counts as written for
+ * bt_run_stats.prev_zero_launches.  Launches: one brush / region launch, one downsample launch per LOD above (the levels depend on each
+ * other), one stitch launch, and the mip launches of the written layers (mip_level_count - 1 per run of consecutive layers).
+ * Height-bounds tables (bt_height_bounds, bt_atlas_tile_bounds results) and a tile tree's approximate height are the caller's to refresh
+ * from `changed`.  Plan scratch (device + pinned) stays in the context until bt_ctx_trim.
+ * BT_OK with nothing touched: count == 0, width == 0 or height == 0.  BT_ERR_INVALID_ARGUMENT: NULL atlas or a NULL required pointer
+ * (stamps, texels_host, changed with changed_cap > 0), attachment_index or lod >= lod_count out of range, side out of range (planar: 0;
+ * cube: 0..5), a non-finite center or amount, a radius that is not finite or <= 0, an unknown mode or falloff, count > BT_EDIT_MAX_STAMPS,
+ * a rectangle outside the mosaic, a row_pitch smaller than a row.  BT_ERR_UNSUPPORTED: an odd centre size c, Rg16 / Rgb8 attachments, a
+ * brush on an Rgba8 attachment.  Neither call aborts. */
+enum { BT_EDIT_ADD = 0, BT_EDIT_FLATTEN = 1 };          /* bt_edit_stamp.mode */
+enum { BT_EDIT_FALLOFF_SMOOTH = 0, BT_EDIT_FALLOFF_HARD = 1 };
+#define BT_EDIT_MAX_STAMPS 256u
+typedef struct bt_edit_stamp {
+    uint32_t side, mode, falloff, _pad;
+    float center[2];   /* mosaic texel units of `lod` on `side`: texel gx of tile X column i is X*c + i, position = the integer itself */
+    float radius;      /* texels, finite, > 0 */
+    float amount;      /* normalised height (1 = max_height - min_height): ADD delta (signed), FLATTEN target */
+} bt_edit_stamp;
+typedef struct bt_edit_stats {
+    uint32_t tiles_edited, tiles_missing, tiles_with_children, tiles_downsampled, tiles_stitched, layers_mipped, launches, changed_count;
+} bt_edit_stats;
+bt_status bt_atlas_edit_height(bt_atlas* atlas, uint32_t attachment_index, uint32_t lod, const bt_edit_stamp* stamps, uint32_t count,
+                               bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+bt_status bt_atlas_write_region(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                uint32_t width, uint32_t height, const void* texels_host, uint64_t row_pitch,
+                                bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+/* bt_atlas_save_attachment for a list of tiles (the `changed` list of an edit): writes "{directory}/{coord}.bin" of the listed tiles only.
+ * A coordinate the atlas holds no layer for: BT_ERR_INVALID_ARGUMENT before anything is written.  count == 0: the directory is created. */
+bt_status bt_atlas_save_tiles(bt_atlas* atlas, uint32_t attachment_index, const char* directory, const bt_tile_coordinate* coords, uint32_t count);
+
 /* ------------------------------- Preprocessor (preprocess/preprocessor.rs) */
 bt_status bt_preprocessor_create(bt_ctx* ctx, bt_preprocessor** out); /* Preprocessor::new :224-232 */
 void bt_preprocessor_destroy(bt_preprocessor* p);

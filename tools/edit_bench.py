@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Times bt_atlas_edit_height on bench.py's 16k job (synth_fbm_r16 16384^2, T = 512, lod_count 6, 1365 tiles); prints one JSON line.  Not the
+headline benchmark (bench.py).
+
+Per case (one SMOOTH ADD stamp of radius 4 / 32 / 256 / 2048 texels across a four-tile corner of the finest LOD, and 64 stamps of radius
+32): device time per call from a device-event pair around `--calls` back-to-back calls (no synchronise in between; the plan ring of the
+context serves the calls in flight) after a spin-up of the same calls, the median of `--repeats` such windows; `launches` and
+`changed_count` of the call; host time per call (the planning + enqueue, a host clock around the same window ended by a synchronise).
+Successive calls of a window use the same stamps: the texels saturate after some calls, the work does not change.
+
+Next to them what a host can do without the call: (a) re-running the kept preprocess queue (bench.py's headline step) and (b) a
+download_tiles / upload_tile round trip of the same changed tile set, the host patching left out (wall time, it is synchronous).
+
+    python tools/edit_bench.py [--calls N] [--repeats N]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bevy_terrain_amd as bt
+
+SIZE, TEXTURE_SIZE, BORDER, LOD_COUNT, ATLAS_SIZE, SEED = 16384, 512, 2, 6, 2048, 42  # bench.py's 16k job
+CENTER = TEXTURE_SIZE - 2 * BORDER
+
+
+def cases():
+    corner = (16 * CENTER + 0.25, 16 * CENTER - 0.5)  # where four finest tiles meet, mid-terrain
+    out = {f"r{r}": [bt.EditStamp(corner, float(r), 0.01)] for r in (4, 32, 256, 2048)}
+    out["64_stamps_r32"] = [bt.EditStamp((corner[0] + 97.0 * (k % 8) - 340.0, corner[1] + 97.0 * (k // 8) - 340.0), 32.0, 0.01) for k in range(64)]
+    return out
+
+
+def median(values):
+    values = sorted(values)
+    return values[len(values) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=5)
+    args = ap.parse_args()
+    device = bt.Device(0)
+    cfg = bt.TerrainConfig(lod_count=LOD_COUNT, atlas_size=ATLAS_SIZE, path="terrains/bench16k",
+                           model=bt.TerrainModel.planar((0.0, 0.0, 0.0), 1000.0, 0.0, 1.0))
+    cfg.add_attachment(bt.AttachmentConfig(name="height", texture_size=TEXTURE_SIZE, border_size=BORDER, format=bt.AttachmentFormat.R16))
+    atlas = bt.TileAtlas.new(cfg, device)
+    src = device.synth_fbm_r16(SIZE, SIZE, SEED)
+    pre = bt.Preprocessor.new().clear_attachment(0, atlas).preprocess_tile(
+        bt.PreprocessDataset(attachment_index=0, path="synthetic/fbm16k", lod_range=range(0, LOD_COUNT)),
+        bt.AssetServer().insert("synthetic/fbm16k", (src, SIZE, SIZE)), atlas)
+    pre.run(atlas, keep_queue=True)
+    index = {c: i for c, i in atlas.tiles()}
+    assert len(index) == 1365, len(index)
+    result = {"tool": "edit_bench", "tiles": len(index), "texture_size": TEXTURE_SIZE, "lod_count": LOD_COUNT, "calls_per_window": args.calls,
+              "windows": args.repeats, "note": "device ms per call: event pair around back-to-back calls, median of the windows"}
+
+    # (a) the kept queue again: the whole terrain, whatever the footprint
+    for _ in range(3):
+        pre.run(atlas, keep_queue=True)
+    windows = []
+    for _ in range(args.repeats):
+        device.synchronize()
+        device.timer_begin()
+        for _ in range(20):
+            pre.run(atlas, keep_queue=True, sync=False)
+        windows.append(device.timer_end() / 20)
+    result["rerun_kept_queue_device_ms"] = round(median(windows), 4)
+
+    for name, stamps in cases().items():
+        changed, stats = atlas.edit_height(0, stamps)
+        for _ in range(args.calls // 4):  # spin-up: code objects, scratch growth, clocks
+            atlas.edit_height(0, stamps)
+        device_ms, host_ms = [], []
+        for _ in range(args.repeats):
+            device.synchronize()
+            t0 = time.perf_counter()
+            device.timer_begin()
+            for _ in range(args.calls):
+                atlas.edit_height(0, stamps)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / args.calls)  # planning + enqueue: nothing has been waited for yet
+            device_ms.append(device.timer_end() / args.calls)
+        # (b) the same tile set by hand: download, (patch on the host), upload — synchronous calls
+        layers = [index[c] for c in changed]
+        tiles = [atlas.download_tile(0, i) for i in layers]
+        round_trip = []
+        for _ in range(args.repeats):
+            device.synchronize()
+            t0 = time.perf_counter()
+            tiles = [atlas.download_tile(0, i) for i in layers]
+            for i, t in zip(layers, tiles):
+                atlas.upload_tile(0, i, t)
+            round_trip.append((time.perf_counter() - t0) * 1e3)
+        result[name] = {"stamps": len(stamps), "device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
+                        "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"],
+                        "download_upload_round_trip_wall_ms": round(median(round_trip), 3)}
+    print(json.dumps(result), flush=True)
+    pre.close()
+    device.free(src)
+
+
+if __name__ == "__main__":
+    main()
