@@ -167,6 +167,11 @@ class EditStatsC(C.Structure):
                 ("changed_count", C.c_uint32)]
 
 
+class BoundsUpdateStatsC(C.Structure):
+    _fields_ = [("tiles_listed", C.c_uint32), ("layers_reduced", C.c_uint32), ("launches", C.c_uint32), ("_pad", C.c_uint32),
+                ("entries_written", C.c_uint64)]
+
+
 class TileTreeEntryC(C.Structure):
     _fields_ = [("atlas_index", C.c_uint32), ("atlas_lod", C.c_uint32)]
 
@@ -272,6 +277,7 @@ PROTOTYPES = {
     "bt_height_bounds_create": (_i32, [_vp, _u32, _u32, _P(_vp)]),
     "bt_height_bounds_destroy": (None, [_vp]),
     "bt_height_bounds_build": (_i32, [_vp, _vp, _u32]),
+    "bt_height_bounds_update": (_i32, [_vp, _vp, _u32, _P(TileCoordinateC), _u32, _P(BoundsUpdateStatsC)]),
     "bt_height_bounds_read": (_i32, [_vp, _P(C.c_uint16), _u64]),
     "bt_height_bounds_write": (_i32, [_vp, _P(C.c_uint16), _u64]),
     "bt_cull_planes": (None, [_P(C.c_float), _P(C.c_float)]),

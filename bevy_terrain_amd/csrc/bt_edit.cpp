@@ -216,8 +216,10 @@ void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std
 
 uint64_t align16(uint64_t v) { return (v + 15u) & ~uint64_t(15); }
 
-// `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read
-bt_status edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev) {
+}  // namespace
+
+// `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read (bt_height_bounds_update shares it)
+bt_status bt::edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev) {
     need = (need + 255u) & ~uint64_t(255);
     if (!ctx->edit_copied) BT_HIP(hipEventCreateWithFlags(&ctx->edit_copied, hipEventDisableTiming));
     if (need > ctx->edit_bytes) {
@@ -242,6 +244,8 @@ bt_status edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev
     ctx->edit_used += need;
     return BT_OK;
 }
+
+namespace {
 
 struct RegionSource {
     const void* dev;

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cerrno>
 #include <cmath>
 #include <cstdarg>
@@ -458,6 +459,8 @@ bt_status bt_atlas_create(bt_ctx* ctx, const bt_terrain_config* config, bt_atlas
         }
     }
     bt_atlas* a = new bt_atlas();
+    static std::atomic<uint64_t> next_uid{1};
+    a->uid = next_uid++;
     a->ctx = ctx;
     a->config = *config;
     for (uint32_t i = 0; i < config->attachment_count; i++) {
@@ -1051,13 +1054,17 @@ bt_status bt_height_bounds_create(bt_ctx* ctx, uint32_t sides, uint32_t levels, 
         return BT_ERR_INVALID_ARGUMENT;
     }
     BT_HIP(hipSetDevice(ctx->device));
-    bt_height_bounds* b = new bt_height_bounds();
+    HeightBoundsImpl* impl = new HeightBoundsImpl();  // (the public struct is its first member)
+    bt_height_bounds* b = &impl->pub;
     b->ctx = ctx;
     b->sides = sides;
     b->levels = levels;
     b->entries = height_bounds_offset(sides, levels);
     hipError_t e = hipMalloc((void**)&b->table, b->entries * 4u);
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)b->table, int(0xFFFF0000u), b->entries, ctx->stream);  // (0, 65535)
+    // the shadow of an empty atlas: nothing held (the table above is what a build of one gives)
+    if (e == hipSuccess) e = hipMalloc((void**)&impl->shadow, b->entries * 4u);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)impl->shadow, int(kBoundsNotHeld), b->entries, ctx->stream);
     if (e != hipSuccess) {
         bt_height_bounds_destroy(b);
         return hip_fail(e, "height bounds table");
@@ -1073,7 +1080,8 @@ void bt_height_bounds_destroy(bt_height_bounds* b) {
         hipStreamSynchronize(b->ctx->stream);  // a prepass that borrowed the table may still be running
         hipFree(b->table);
     }
-    delete b;
+    if (bounds_impl(b)->shadow) hipFree(bounds_impl(b)->shadow);
+    delete bounds_impl(b);
 }
 
 bt_status bt_height_bounds_read(const bt_height_bounds* b, uint16_t* out, uint64_t out_bytes) {
@@ -1093,6 +1101,7 @@ bt_status bt_height_bounds_write(bt_height_bounds* b, const uint16_t* src, uint6
         return BT_ERR_INVALID_ARGUMENT;
     }
     BT_HIP(hipSetDevice(b->ctx->device));
+    bounds_impl(b)->current = false;  // own(tile) of these entries is unknown: bt_height_bounds_update asks for a build first
     BT_HIP(hipMemcpyAsync(b->table, src, bytes, hipMemcpyHostToDevice, b->ctx->stream));
     BT_HIP(hipStreamSynchronize(b->ctx->stream));  // (src is the caller's, pageable)
     return BT_OK;
@@ -1112,7 +1121,7 @@ bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* a, uint32_t ai) 
         return BT_ERR_INVALID_ARGUMENT;
     }
     // 1. own(tile) of every held tile: the grid-1 bounds of its layer (the existing kernel)
-    constexpr uint32_t kNone = 0x0000FFFFu;  // min > max: not held
+    constexpr uint32_t kNone = kBoundsNotHeld;  // min > max: not held
     std::vector<uint32_t> own(b->entries, kNone), layers, slots;
     auto slot = [&](const bt_tile_coordinate& c) { return height_bounds_offset(b->sides, c.lod) + ((((uint64_t(c.side) << c.lod) + c.y) << c.lod) + c.x); };
     for (const bt_tile_coordinate& c : a->existing_tiles) {
@@ -1124,6 +1133,7 @@ bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* a, uint32_t ai) 
     std::vector<uint16_t> pairs(2 * layers.size());
     if (bt_status s = bt_atlas_tile_bounds(a, ai, layers.data(), uint32_t(layers.size()), 1u, 0u, pairs.data(), pairs.size() * 2u)) return s;
     for (size_t i = 0; i < layers.size(); i++) own[slots[i]] = uint32_t(pairs[2 * i]) | (uint32_t(pairs[2 * i + 1]) << 16);
+    const std::vector<uint32_t> shadow = own;  // before the fill: what bt_height_bounds_update starts from
     // 2. top down: a tile that is not held takes own of its parent (a root: the whole range); 3. bottom up: the union with the children
     std::vector<uint32_t> entry(b->entries);
     for (uint32_t l = 0; l < b->levels; l++) {
@@ -1150,8 +1160,14 @@ bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* a, uint32_t ai) 
                 }
     }
     BT_HIP(hipSetDevice(b->ctx->device));
+    HeightBoundsImpl* impl = bounds_impl(b);
+    impl->current = false;
     BT_HIP(hipMemcpyAsync(b->table, entry.data(), b->entries * 4u, hipMemcpyHostToDevice, b->ctx->stream));
+    BT_HIP(hipMemcpyAsync(impl->shadow, shadow.data(), b->entries * 4u, hipMemcpyHostToDevice, b->ctx->stream));
     BT_HIP(hipStreamSynchronize(b->ctx->stream));
+    impl->atlas_uid = a->uid;
+    impl->attachment = ai;
+    impl->current = true;
     return BT_OK;
 }
 

@@ -231,6 +231,7 @@ struct bt_atlas {
     std::unordered_map<bt_tile_coordinate, bt::TileState, bt::CoordHash, bt::CoordEq> tile_states;
     std::deque<bt_atlas_tile> unused_tiles;        // LRU of free / released slots (:307-309, 459-476)
     std::deque<bt::AtlasTileAttachment> to_load;   // queued by request_tile (:445-451), drained by bt_atlas_update
+    uint64_t uid = 0;                              // unique per bt_atlas_create of the process (an address can come back)
     uint64_t state_version = 1;                    // bumped whenever tile_states changes (device copies are rebuilt lazily)
     // the Save tasks of the preprocessor runs since the last bt_preprocessor_save (preprocessor.rs:378-380)
     std::vector<bt::AtlasTileAttachment> to_save;
@@ -388,6 +389,21 @@ inline uint32_t shard_holder(const ::bt_preprocessor* p, uint32_t attachment, ui
 // bt_height_bounds (the min/max height table of the culling test, declared in the header): level l starts at height_bounds_offset(sides, l)
 namespace bt {
 inline uint64_t height_bounds_offset(uint32_t sides, uint32_t level) { return uint64_t(sides) * (((1ull << (2u * level)) - 1u) / 3u); }
+constexpr uint32_t kBoundsNotHeld = 0x0000FFFFu;  // min > max: the shadow's (and bt_height_bounds_build's) word of a tile the atlas does not hold
+// What bt_height_bounds_create really allocates: the public struct first (the handle points at it), then what bt_height_bounds_update
+// needs.  shadow has the table's shape and holds own(tile) of every held tile, kBoundsNotHeld elsewhere: an entry is own united with the
+// children, so the table alone does not say what own was.  current: table and shadow describe `atlas` / `attachment` as of the last build
+// or update (bt_height_bounds_write clears it).
+struct HeightBoundsImpl {
+    bt_height_bounds pub{};
+    uint32_t* shadow = nullptr;
+    uint64_t atlas_uid = 0;  // bt_atlas::uid
+    uint32_t attachment = 0;
+    bool current = false;
+};
+inline HeightBoundsImpl* bounds_impl(bt_height_bounds* b) { return reinterpret_cast<HeightBoundsImpl*>(b); }
+// bt_edit.cpp: `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read
+bt_status edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev);
 }  // namespace bt
 
 namespace bt {

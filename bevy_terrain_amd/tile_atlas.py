@@ -319,7 +319,7 @@ class TileAtlas:
         """bt_atlas_edit_height: apply the EditStamps, in list order, to the centre texels of the existing tiles of `lod` (default: the
         finest, lod_count - 1) of an R16 attachment, then restore the ancestors, the aprons and the mips that depend on them, on the
         device and without synchronising.  Returns (changed tiles: LOD descending then atlas index, bt_edit_stats as a dict).  Tiles finer
-        than `lod` are not touched (stats["tiles_with_children"]); height-bounds tables and tile-tree state are the caller's to refresh."""
+        than `lod` are not touched (stats["tiles_with_children"]); a HeightBounds table follows with update(atlas, changed), tile-tree state is the caller's to refresh."""
         lod = self.lod_count - 1 if lod is None else lod
         stamps = list(stamps)
         arr = (_ffi.EditStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
@@ -376,6 +376,17 @@ class HeightBounds:
         missing root the whole range; every entry is then united with its children's"""
         _ffi.check(_ffi.lib().bt_height_bounds_build(self._h, atlas._h, attachment_index))
         return self
+
+    def update(self, atlas: "TileAtlas", tiles, attachment_index: int = 0) -> dict:
+        """bt_height_bounds_update: bring the table, last built or updated against `atlas`, up to date after `tiles` changed (in content
+        or in being held) — the `changed` list of TileAtlas.edit_height / write_region as it is, or tiles just loaded or dropped.  The
+        result is what build() would give; queued on the device's stream behind the edit, without synchronising.  Returns
+        bt_bounds_update_stats as a dict."""
+        tiles = list(tiles)
+        arr = (_ffi.TileCoordinateC * max(len(tiles), 1))(*[c._c() for c in tiles])
+        stats = _ffi.BoundsUpdateStatsC()
+        _ffi.check(_ffi.lib().bt_height_bounds_update(self._h, atlas._h, attachment_index, arr, len(tiles), C.byref(stats)))
+        return {name: getattr(stats, name) for name, _ in _ffi.BoundsUpdateStatsC._fields_ if name != "_pad"}
 
     def read(self) -> np.ndarray:
         """(entries, 2) uint16: [:, 0] = min, [:, 1] = max"""

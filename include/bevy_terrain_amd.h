@@ -335,8 +335,9 @@ bt_status bt_atlas_tile_bounds(bt_atlas* atlas, uint32_t attachment_index, const
  * work and return without synchronising (apart from the staging copy above); every written layer counts as written for
  * bt_run_stats.prev_zero_launches.  Launches: one brush / region launch, one downsample launch per LOD above (the levels depend on each
  * other), one stitch launch, and the mip launches of the written layers (mip_level_count - 1 per run of consecutive layers).
- * Height-bounds tables (bt_height_bounds, bt_atlas_tile_bounds results) and a tile tree's approximate height are the caller's to refresh
- * from `changed`.  Plan scratch (device + pinned) stays in the context until bt_ctx_trim.
+ * A bt_height_bounds table follows an edit by bt_height_bounds_update(table, atlas, attachment_index, changed, changed_count), queued behind
+ * the edit on the same stream; bt_atlas_tile_bounds results and a tile tree's approximate height are the caller's to refresh from
+ * `changed`.  Plan scratch (device + pinned) stays in the context until bt_ctx_trim.
  * BT_OK with nothing touched: count == 0, width == 0 or height == 0.  BT_ERR_INVALID_ARGUMENT: NULL atlas or a NULL required pointer
  * (stamps, texels_host, changed with changed_cap > 0), attachment_index or lod >= lod_count out of range, side out of range (planar: 0;
  * cube: 0..5), a non-finite center or amount, a radius that is not finite or <= 0, an unknown mode or falloff, count > BT_EDIT_MAX_STAMPS,
@@ -643,7 +644,9 @@ bt_status bt_tiling_prepass_read(bt_tiling_prepass* t, bt_tile_coordinate* final
 
 /* The min/max height store of the culling test: one {min, max} pair of raw unorm16 per quadtree tile of LODs 0 .. levels-1, dense, view
  * independent, on the device.  Level l follows level l-1; inside a level entry ((side * n + y) * n + x), n = 1 << l:
- * sides * (4^levels - 1) / 3 entries of 4 bytes, 1 <= levels <= BT_HEIGHT_BOUNDS_MAX_LEVELS (33.6 MB for a cube at 11). */
+ * sides * (4^levels - 1) / 3 entries of 4 bytes, 1 <= levels <= BT_HEIGHT_BOUNDS_MAX_LEVELS (33.6 MB for a cube at 11).  Beside the
+ * table the library keeps a private shadow of the same shape for bt_height_bounds_update (own(tile) of every held tile): the object
+ * behind a bt_height_bounds* is larger than the struct below, and its device footprint is twice the table's (67 MB for a cube at 11). */
 enum { BT_HEIGHT_BOUNDS_MAX_LEVELS = 11 };
 /* Created and destroyed by the library only; the fields are there to be read (a renderer may bind `table` itself). */
 typedef struct bt_height_bounds {
@@ -666,7 +669,41 @@ void bt_height_bounds_destroy(bt_height_bounds* b);
  * After it no entry has min > max.  Synchronous; a read of the atlas (not a write for bt_run_stats.prev_zero_launches).  The atlas's side
  * count must be the table's.  Non-R16 attachment: BT_ERR_UNSUPPORTED. */
 bt_status bt_height_bounds_build(bt_height_bounds* b, bt_atlas* atlas, uint32_t attachment_index);
-/* The whole table, {min, max} pairs in table order: out_bytes / bytes == entries * 4 (bt_height_bounds_write: a table saved earlier). */
+/* Brings the table up to date after some tiles have changed, without reducing the others again and without synchronising.
+ * PRECONDITIONS.  `b` was last brought up to date against this `atlas` and `attachment_index`, by bt_height_bounds_build or by earlier
+ * updates; `tiles` lists every tile that has changed since then, in layer content or in whether the atlas holds it ("held" is what
+ * bt_height_bounds_build tests: listed by bt_atlas_tiles with an atlas index, not loading).  Typically the `changed` list of
+ * bt_atlas_edit_height / bt_atlas_write_region, or the tiles just loaded or dropped.  Listing more tiles than changed is harmless.
+ * RESULT.  The table is byte-identical to what bt_height_bounds_build(b, atlas, attachment_index) would produce at that point: a
+ * recomputation, not a union with the old entries, so ranges shrink as well as grow.
+ * INPUT.  Duplicates are allowed.  Tiles with lod >= levels are ignored (they have no entry; deeper tiles read their ancestor at
+ * levels - 1).  A listed tile the atlas does not hold is legal: that is how a dropped tile is reported.
+ * HOW.  With U the distinct listed tiles of lod < levels: own(tile) of U's held tiles is reduced again (one grid-1 workgroup per layer, as
+ * in step 1 of the build, into device scratch); then a table kernel rewrites U, the ancestors of U up to LOD 0, and the whole subtree,
+ * down to levels - 1, below every child of a tile of U that the atlas does not hold (those tiles take own of their nearest held
+ * ancestor, which may be the changed one).  Up to 4096 rewritten entries that is one launch of one workgroup (two launches per call);
+ * above, one launch per step and level, at most 2 + levels per call.  Cost follows the list and those subtrees, not the terrain.
+ * ASYNCHRONOUS.  The call enqueues on the context's stream behind earlier work (the edit whose `changed` list it is given) and returns
+ * without synchronising; a prepass queued behind it reads the new table.  The plan travels through the pinned ring of the edit calls;
+ * scratch stays in the context until bt_ctx_trim.  A read of the atlas (not a write for bt_run_stats.prev_zero_launches).
+ * STATUS.  BT_OK with nothing touched: count == 0.  BT_ERR_INVALID_ARGUMENT, before anything is queued: NULL b or atlas, NULL tiles with
+ * count > 0, attachment index out of range, table and atlas of different contexts or side counts, a coordinate with side >= sides or
+ * x >> lod or y >> lod non-zero, and a table that is not current — never built, overwritten by bt_height_bounds_write since its last
+ * build, or last built against another atlas or attachment: build first.  BT_ERR_UNSUPPORTED: a non-R16 attachment.  Never aborts.
+ * NOT COVERED.  Evictions are not reported: bt_atlas_request_tile reuses an LRU slot without saying which tile left, and a caller who
+ * tracks that lists the tile itself.  A tile tree's approximate height and bt_atlas_tile_bounds pyramids are not refreshed.  The edit's
+ * `changed` list is conservative (every neighbour of a written tile): each listed layer is reduced whether its range moved or not. */
+typedef struct bt_bounds_update_stats {
+    uint32_t tiles_listed;    /* distinct listed tiles with lod < levels */
+    uint32_t layers_reduced;  /* those of them the atlas holds: one grid-1 reduction each */
+    uint32_t launches;
+    uint32_t _pad;
+    uint64_t entries_written; /* table entries the call recomputed */
+} bt_bounds_update_stats;
+bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* atlas, uint32_t attachment_index, const bt_tile_coordinate* tiles,
+                                  uint32_t count, bt_bounds_update_stats* stats /* may be NULL */);
+/* The whole table, {min, max} pairs in table order: out_bytes / bytes == entries * 4 (bt_height_bounds_write: a table saved earlier; the
+ * library does not know own(tile) of a written table, so bt_height_bounds_update refuses it until the next build). */
 bt_status bt_height_bounds_read(const bt_height_bounds* b, uint16_t* out_host, uint64_t out_bytes);
 bt_status bt_height_bounds_write(bt_height_bounds* b, const uint16_t* src_host, uint64_t bytes);
 

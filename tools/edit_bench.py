@@ -12,6 +12,11 @@ Next to them what a host can do without the call: (a) re-running the kept prepro
 download_tiles / upload_tile round trip of the same changed tile set, the host patching left out (wall time, it is synchronous).
 
     python tools/edit_bench.py [--calls N] [--repeats N]
+
+--bounds: instead of the above, what keeping a 6-level bt_height_bounds table current costs after a stamp of radius 32 and of radius 2048:
+per call the stamp alone, stamp + bt_height_bounds_update(changed) and stamp + bt_height_bounds_build, each as device time (the event pair
+around the window; the build synchronises inside, so its window holds its host work too) and as wall time of the window ended by a
+synchronise; the update's stats.
 """
 import argparse
 import json
@@ -40,10 +45,60 @@ def median(values):
     return values[len(values) // 2]
 
 
+def bounds_mode(device, atlas, args, result):
+    """stamp, stamp + update, stamp + build: the same windows as the edit cases, the build's with a tenth of the calls (it is synchronous).
+    The calls go to the C entry points with arrays made once, as a renderer's would: `changed` passes from the edit to the update as it is."""
+    import ctypes as C
+
+    from bevy_terrain_amd import _ffi
+
+    L = _ffi.lib()
+    hb = bt.HeightBounds(device, 1, LOD_COUNT).build(atlas, 0)
+    cap = atlas.atlas_size
+    changed = (_ffi.TileCoordinateC * cap)()
+    edit_stats, update_stats = _ffi.EditStatsC(), _ffi.BoundsUpdateStatsC()
+    all_cases = cases()
+    for name in ("r32", "r2048"):
+        stamps = (_ffi.EditStampC * len(all_cases[name]))(*[s._c() for s in all_cases[name]])
+
+        def stamp():
+            _ffi.check(L.bt_atlas_edit_height(atlas._h, 0, LOD_COUNT - 1, stamps, len(stamps), changed, cap, C.byref(edit_stats)))
+
+        def stamp_update():
+            stamp()
+            _ffi.check(L.bt_height_bounds_update(hb._h, atlas._h, 0, changed, edit_stats.changed_count, C.byref(update_stats)))
+
+        def stamp_build():
+            stamp()
+            _ffi.check(L.bt_height_bounds_build(hb._h, atlas._h, 0))
+
+        stamp_update()
+        row = {"changed_count": edit_stats.changed_count,
+               "update_stats": {field: getattr(update_stats, field) for field, _ in _ffi.BoundsUpdateStatsC._fields_ if field != "_pad"}}
+        for label, call, calls in (("stamp", stamp, args.calls), ("stamp_update", stamp_update, args.calls), ("stamp_build", stamp_build, max(args.calls // 10, 1))):
+            for _ in range(max(calls // 4, 1)):
+                call()
+            device_ms, host_ms, wall_ms = [], [], []
+            for _ in range(args.repeats):
+                device.synchronize()
+                t0 = time.perf_counter()
+                device.timer_begin()
+                for _ in range(calls):
+                    call()
+                host_ms.append((time.perf_counter() - t0) * 1e3 / calls)  # planning + enqueue (the build: everything, it synchronises)
+                device_ms.append(device.timer_end() / calls)
+                wall_ms.append((time.perf_counter() - t0) * 1e3 / calls)  # timer_end has waited for the window
+            row[label] = {"device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
+                          "wall_ms_per_call": round(median(wall_ms), 4), "calls_per_window": calls}
+        result[name] = row
+    hb.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--bounds", action="store_true", help="time stamp + bt_height_bounds_update and stamp + bt_height_bounds_build")
     args = ap.parse_args()
     device = bt.Device(0)
     cfg = bt.TerrainConfig(lod_count=LOD_COUNT, atlas_size=ATLAS_SIZE, path="terrains/bench16k",
@@ -59,6 +114,13 @@ def main():
     assert len(index) == 1365, len(index)
     result = {"tool": "edit_bench", "tiles": len(index), "texture_size": TEXTURE_SIZE, "lod_count": LOD_COUNT, "calls_per_window": args.calls,
               "windows": args.repeats, "note": "device ms per call: event pair around back-to-back calls, median of the windows"}
+
+    if args.bounds:
+        bounds_mode(device, atlas, args, result)
+        print(json.dumps(result), flush=True)
+        pre.close()
+        device.free(src)
+        return
 
     # (a) the kept queue again: the whole terrain, whatever the footprint
     for _ in range(3):
