@@ -3,7 +3,9 @@ definition (tests/_edit_model.py, pinned to the goldens by test_edit_model.py).
 
 Every comparison downloads ALL layers of the attachment and compares every existing tile of every LOD byte for byte with
 propagate(apply_stamps(before)); layers that are not in `changed` must hold their bytes from before (layers without a tile included), every
-differing layer must be in `changed`, and `changed` must be a subset of {edited tiles, their ancestors, existing neighbours of those}."""
+differing layer must be in `changed`, and `changed` must be a subset of {edited tiles, their ancestors, existing neighbours of those}.
+The shapes these cases leave out (a row beyond one lane trip, Rgba8 beyond one block, the plan's rarer branches, the cube at lod_count 3,
+256 stamps, the plan ring's wrap) are in tests/test_gpu_edit_shapes.py."""
 import os
 
 import numpy as np
@@ -34,22 +36,43 @@ def source_r16(n=64, seed=5):
     return src
 
 
-def planar(device, T, b, lods=3, fmt=R16, src=None, mips=1, **ds):
+def planar(device, T, b, lods=3, fmt=R16, src=None, mips=1, lod_range=None, then=(), **ds):
+    """lod_range: the LODs the job fills (default: all of them); then: further jobs as (lod_range, extent keywords), each queued WITHOUT
+    the clear and run on its own behind the first"""
     if src is None:
         src = source_r16() if fmt == R16 else K.random_raster(RGBA8, 64, 64, seed=8, holes=0.03)
-    atlas, pre = K.product_planar(device, src, lods, T, b, fmt, atlas_size=ATLAS, mips=mips, **ds)
+    if lod_range is None and not then:
+        atlas, pre = K.product_planar(device, src, lods, T, b, fmt, atlas_size=ATLAS, mips=mips, **ds)
+        return atlas
+    cfg = bt.TerrainConfig(lod_count=lods, atlas_size=ATLAS, path="terrains/edit", model=bt.TerrainModel.planar((0, 0, 0), 1000.0, 0.0, 1.0))
+    cfg.add_attachment(bt.AttachmentConfig(name="att", texture_size=T, border_size=b, format=K.FMT[fmt], mip_level_count=mips))
+    atlas = bt.TileAtlas.new(cfg, device)
+    server = bt.AssetServer().insert("src", src)
+    for k, (levels, extent) in enumerate([(lod_range or range(0, lods), ds)] + list(then)):
+        pre = bt.Preprocessor.new()
+        if k == 0:
+            pre.clear_attachment(0, atlas)
+        pre.preprocess_tile(bt.PreprocessDataset(attachment_index=0, path="src", lod_range=levels, **extent), server, atlas).run(atlas)
     return atlas
 
 
-def cube(device, T=16, b=2, lods=2, n=40):
-    cfg = bt.TerrainConfig(lod_count=lods, atlas_size=ATLAS, path="terrains/edit")
-    cfg.add_attachment(bt.AttachmentConfig(name="att", texture_size=T, border_size=b, format=bt.AttachmentFormat.R16))
+def cube_faces(n=40):
+    """the six source rasters of cube(): fBm with a zero block each"""
+    faces = []
+    for s in range(6):
+        face = K.smooth_raster(n, n, 100 + s).copy()
+        face[3 + s:6 + s, 30:33] = 0
+        faces.append(face)
+    return faces
+
+
+def cube(device, T=16, b=2, lods=2, n=40, mips=1, atlas_size=ATLAS):
+    cfg = bt.TerrainConfig(lod_count=lods, atlas_size=atlas_size, path="terrains/edit")
+    cfg.add_attachment(bt.AttachmentConfig(name="att", texture_size=T, border_size=b, format=bt.AttachmentFormat.R16, mip_level_count=mips))
     atlas = bt.TileAtlas.new(cfg, device)
     server = bt.AssetServer()
     paths = [f"face{s}" for s in range(6)]
-    for s, p in enumerate(paths):
-        face = K.smooth_raster(n, n, 100 + s).copy()
-        face[3 + s:6 + s, 30:33] = 0
+    for p, face in zip(paths, cube_faces(n)):
         server.insert(p, face)
     pre = bt.Preprocessor.new().clear_attachment(0, atlas)
     pre.preprocess_spherical(bt.SphericalDataset(attachment_index=0, paths=paths, lod_range=range(0, lods)), server, atlas)
