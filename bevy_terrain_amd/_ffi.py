@@ -149,6 +149,10 @@ class CullViewC(C.Structure):
                 ("max_height", C.c_float)]
 
 
+class HorizonViewC(C.Structure):
+    _fields_ = [("eye", C.c_float * 3), ("vh", C.c_float), ("occluder_radius", C.c_float), ("margin", C.c_float)]
+
+
 HEIGHT_BOUNDS_MAX_LEVELS = 11
 
 EDIT_ADD, EDIT_FLATTEN = 0, 1
@@ -283,6 +287,8 @@ PROTOTYPES = {
     "bt_cull_planes": (None, [_P(C.c_float), _P(C.c_float)]),
     "bt_tiling_prepass_set_culling": (_i32, [_vp, _P(CullViewC), _vp]),
     "bt_tiling_prepass_cull_stats": (_i32, [_vp, _P(_u32), _P(_u32)]),
+    "bt_tiling_prepass_set_horizon": (_i32, [_vp, _P(HorizonViewC)]),
+    "bt_cull_horizon": (_i32, [_P(TerrainModelC), _P(C.c_double), C.c_float, _P(HorizonViewC)]),
     "bt_terrain_view_config_default": (None, [_P(TerrainViewConfigC)]),
     "bt_view_state_from_config": (_i32, [_P(TerrainModelC), _P(TerrainViewConfigC), _P(C.c_double), C.c_float, _P(ViewStateC)]),
     "bt_tile_tree_create": (_i32, [_vp, _P(TerrainModelC), _u32, _P(TerrainViewConfigC), _P(_vp)]),

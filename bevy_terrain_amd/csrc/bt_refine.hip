@@ -32,6 +32,8 @@ struct bt_tiling_prepass {
     bt_cull_view cull{};
     const bt_height_bounds* bounds = nullptr;  // borrowed
     bool culled_run = false;                   // the last run culled: counters[4] is its count
+    bool horizon_set = false;                  // bt_tiling_prepass_set_horizon
+    bt_horizon_view horizon{};
 };
 
 namespace bt {
@@ -71,9 +73,10 @@ __device__ __forceinline__ float length3(float x, float y, float z) { return sqr
 
 // A point of a tile's surface and the normal there: compute_local_position (functions.wgsl:73-96) of the tile coordinate (u, w) =
 // (tile xy + uv) / tile_count, then position_local_to_world / normal_local_to_world (:117-121).  point(tile, uv, h) = world + h * normal:
-// the divide test's and the culling test's (include/bevy_terrain_amd.h).
+// the divide test's and the culling test's (include/bevy_terrain_amd.h).  l is the local position itself (the unit sphere's when spherical):
+// the horizon test works from it.
 struct SurfacePoint {
-    float wx, wy, wz, nx, ny, nz;
+    float wx, wy, wz, nx, ny, nz, lx, ly, lz;
 };
 
 __device__ __forceinline__ SurfacePoint tile_surface(const bt_view_state& v, uint32_t side, float u, float w) {
@@ -116,6 +119,9 @@ __device__ __forceinline__ SurfacePoint tile_surface(const bt_view_state& v, uin
     p.nx = nx / nl;
     p.ny = ny / nl;
     p.nz = nz / nl;
+    p.lx = lx;
+    p.ly = ly;
+    p.lz = lz;
     return p;
 }
 
@@ -154,11 +160,27 @@ struct CullArgs<true> {
     bt_cull_view cull;
     const uint32_t* table;  // bt_height_bounds::table, or nullptr: every tile spans (0, 65535)
     uint32_t levels, sides;
+    uint32_t horizon_on;    // bt_tiling_prepass_set_horizon: the horizon test runs after the planes (a scalar branch)
+    bt_horizon_view horizon;
 };
 
 __device__ __forceinline__ float unorm16_height(const bt_cull_view& c, uint32_t v) { return c.min_height + (c.max_height - c.min_height) * (float(v) / 65535.0f); }
 
-// Five surface points (the four corners and the centre) carry all nine points of the test: both heights reuse them.
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// q(tile, uv, h) = l + h * (local_from_world * n): the point in scaled space (the unit sphere's frame), from l and never from the world point
+struct ScaledPoint {
+    float x, y, z;
+};
+__device__ __forceinline__ ScaledPoint scaled_point(const bt_view_state& v, const SurfacePoint& s, float h) {
+    const float* t = v.local_from_world_transpose;
+    const float gx = (t[0] * s.nx + t[1] * s.ny) + t[2] * s.nz;
+    const float gy = (t[3] * s.nx + t[4] * s.ny) + t[5] * s.nz;
+    const float gz = (t[6] * s.nx + t[7] * s.ny) + t[8] * s.nz;
+    return {s.lx + h * gx, s.ly + h * gy, s.lz + h * gz};
+}
+
+// Five surface points (the four corners and the centre) carry all nine points of either test: both heights reuse them.
 __device__ bool tile_culled(const bt_view_state& v, const CullArgs<true>& c, const bt_tile_coordinate& tile) {
     uint32_t range = 0xFFFF0000u;  // (0, 65535)
     if (c.table) {
@@ -181,8 +203,9 @@ __device__ bool tile_culled(const bt_view_state& v, const CullArgs<true>& c, con
         pz[k] = s[k & 3u].wz + h * s[k & 3u].nz;
     }
     float slack = 0.0f;
+    SurfacePoint m{};
     if (v.spherical) {
-        const SurfacePoint m = tile_surface(v, tile.side, (float(tile.x) + 0.5f) * inv_tc, (float(tile.y) + 0.5f) * inv_tc);
+        m = tile_surface(v, tile.side, (float(tile.x) + 0.5f) * inv_tc, (float(tile.y) + 0.5f) * inv_tc);
         const float bx = (m.wx + h_hi * m.nx) - ((px[4] + px[5]) + (px[6] + px[7])) * 0.25f;
         const float by = (m.wy + h_hi * m.ny) - ((py[4] + py[5]) + (py[6] + py[7])) * 0.25f;
         const float bz = (m.wz + h_hi * m.nz) - ((pz[4] + pz[5]) + (pz[6] + pz[7])) * 0.25f;
@@ -197,6 +220,36 @@ __device__ bool tile_culled(const bt_view_state& v, const CullArgs<true>& c, con
 #pragma unroll
         for (uint32_t k = 0; k < 8; k++) outside = outside && ((a * px[k] + b * py[k]) + cc * pz[k]) + d < limit;
         culled = culled || outside;
+    }
+    // the horizon test (uniform: the word and the view are kernel arguments; a spherical view, checked by the host)
+    if (c.horizon_on && c.horizon.vh > 0.0f) {
+        const bt_horizon_view& hv = c.horizon;
+        float qx[8], qy[8], qz[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) {
+            const ScaledPoint q = scaled_point(v, s[k & 3u], k < 4 ? h_lo : h_hi);
+            qx[k] = q.x;
+            qy[k] = q.y;
+            qz[k] = q.z;
+        }
+        const ScaledPoint qc = scaled_point(v, m, h_hi);
+        const float dx = qc.x - ((qx[4] + qx[5]) + (qx[6] + qx[7])) * 0.25f;
+        const float dy = qc.y - ((qy[4] + qy[5]) + (qy[6] + qy[7])) * 0.25f;
+        const float dz = qc.z - ((qz[4] + qz[5]) + (qz[6] + qz[7])) * 0.25f;
+        const float bulge = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+        const float widen = (bulge + hv.margin) + BT_HORIZON_GUARD;  // (m of the definition)
+        const float E = sqrtf(dot3(hv.eye[0], hv.eye[1], hv.eye[2], hv.eye[0], hv.eye[1], hv.eye[2])), sv = sqrtf(hv.vh), lim = widen * E;
+        bool hidden = true;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) {
+            const float vx = qx[k] - hv.eye[0], vy = qy[k] - hv.eye[1], vz = qz[k] - hv.eye[2];
+            const float ap = -dot3(vx, vy, vz, hv.eye[0], hv.eye[1], hv.eye[2]);
+            const float along = ap / E;
+            const float sq = dot3(vx, vy, vz, vx, vy, vz) - along * along;
+            const float perp = sqrtf(sq > 0.0f ? sq : 0.0f);
+            hidden = hidden && (ap - hv.vh) > lim && ((along * hv.occluder_radius) - (perp * sv)) > lim;
+        }
+        culled = culled || hidden;
     }
     return culled;
 }
@@ -687,8 +740,13 @@ bt_status tiling_prepass_enqueue(bt_tiling_prepass* t, const bt_view_state* view
     const uint32_t sides = view->spherical ? 6u : 1u;
     // (with the height on the device the estimate works from the host's copy, one frame old: it decides how many LODs get their
     // bits up front and can only cost time)
-    // culling (bt_tiling_prepass_set_culling): no planes cull nothing, and the kernels without the test give exactly that
-    const bool cull = t->cull_set && t->cull.plane_count > 0;
+    // culling (bt_tiling_prepass_set_culling): no planes cull nothing, and the kernels without the test give exactly that — unless a
+    // horizon view is set (bt_tiling_prepass_set_horizon), whose test reads the culling state's heights and table
+    if (t->horizon_set && (!t->cull_set || !view->spherical)) {
+        set_error("tiling prepass horizon culling: %s", !t->cull_set ? "culling is not set (the horizon test reads its heights and table)" : "a planar view has no horizon");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool cull = t->cull_set && (t->cull.plane_count > 0 || t->horizon_set);
     CullArgs<true> ca{};
     if (cull) {
         if (t->bounds && t->bounds->sides != sides) {
@@ -699,6 +757,8 @@ bt_status tiling_prepass_enqueue(bt_tiling_prepass* t, const bt_view_state* view
         ca.table = t->bounds ? t->bounds->table : nullptr;
         ca.levels = t->bounds ? t->bounds->levels : 0u;
         ca.sides = sides;
+        ca.horizon_on = t->horizon_set ? 1u : 0u;
+        if (t->horizon_set) ca.horizon = t->horizon;
     }
     if (cull && form != 1u) {  // both ordered forms: the plain kernel (the same list in the same order)
         tiling_prepass_kernel<false, true><<<1, kThreads, 0, t->ctx->stream>>>(*view, capacity, t->temporary_tiles, t->final_tiles, t->indirect, t->counters, nullptr, 0u, device_height, ca);
@@ -783,6 +843,30 @@ bt_status bt_tiling_prepass_set_culling(bt_tiling_prepass* t, const bt_cull_view
     t->cull = *cull;
     t->bounds = bounds;
     t->cull_set = true;
+    return BT_OK;
+}
+
+bt_status bt_tiling_prepass_set_horizon(bt_tiling_prepass* t, const bt_horizon_view* horizon) {
+    if (!t) {
+        set_error("bt_tiling_prepass_set_horizon: NULL prepass");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!horizon) {
+        t->horizon_set = false;
+        return BT_OK;
+    }
+    const bt_horizon_view& h = *horizon;
+    if (!std::isfinite(h.eye[0]) || !std::isfinite(h.eye[1]) || !std::isfinite(h.eye[2]) || !std::isfinite(h.vh) || !std::isfinite(h.occluder_radius) ||
+        !std::isfinite(h.margin)) {
+        set_error("bt_tiling_prepass_set_horizon: a non-finite field");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(h.occluder_radius > 0.0f && h.occluder_radius <= 1.0f) || !(h.margin >= 0.0f)) {
+        set_error("bt_tiling_prepass_set_horizon: occluder_radius %g (in (0, 1]), margin %g (>= 0)", double(h.occluder_radius), double(h.margin));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    t->horizon = h;
+    t->horizon_set = true;
     return BT_OK;
 }
 

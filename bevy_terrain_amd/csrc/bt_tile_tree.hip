@@ -295,6 +295,50 @@ bt_status bt_view_state_from_config(const bt_terrain_model* model, const bt_terr
     return BT_OK;
 }
 
+// f64 -> f32 with a directed rounding (the nearest value, stepped back when it lies on the wrong side)
+static float f32_toward_zero(double d) {
+    const float f = float(d);
+    return fabs(double(f)) > fabs(d) ? nextafterf(f, 0.0f) : f;
+}
+static float f32_up(double d) {
+    const float f = float(d);
+    return double(f) < d ? nextafterf(f, INFINITY) : f;
+}
+
+bt_status bt_cull_horizon(const bt_terrain_model* model, const double view_world_position[3], float margin_world, bt_horizon_view* out) {
+    if (!view_world_position || !out) {
+        set_error("bt_cull_horizon: NULL %s", !out ? "out" : "view_world_position");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_model(model)) return s;
+    if (model->kind == BT_MODEL_PLANAR) {
+        set_error("bt_cull_horizon: a planar model has no horizon");
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!std::isfinite(view_world_position[0]) || !std::isfinite(view_world_position[1]) || !std::isfinite(view_world_position[2]) ||
+        !(margin_world >= 0.0f) || !std::isfinite(margin_world)) {
+        set_error("bt_cull_horizon: a non-finite position, or margin %g (finite, >= 0)", double(margin_world));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Model m = make_model(*model);
+    const double shortest = std::min(m.scale.x, std::min(m.scale.y, m.scale.z));
+    const V3 local = inverse_transform_point(m, {view_world_position[0], view_world_position[1], view_world_position[2]});
+    bt_horizon_view h;
+    h.eye[0] = float(local.x);
+    h.eye[1] = float(local.y);
+    h.eye[2] = float(local.z);
+    h.occluder_radius = f32_toward_zero(1.0 + std::min(double(m.min_height), 0.0) / shortest);
+    if (!(h.occluder_radius > 0.0f)) {
+        set_error("bt_cull_horizon: min_height %g reaches the centre of a model whose shortest axis is %g", double(m.min_height), shortest);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const V3 e = {double(h.eye[0]), double(h.eye[1]), double(h.eye[2])};
+    h.vh = float(dot3(e, e) - double(h.occluder_radius) * double(h.occluder_radius));
+    h.margin = f32_up(double(margin_world) / shortest);
+    *out = h;
+    return BT_OK;
+}
+
 bt_status bt_tile_tree_create(bt_ctx* ctx, const bt_terrain_model* model, uint32_t lod_count, const bt_terrain_view_config* vc, bt_tile_tree** out) {
     if (!ctx || !vc || !out) return BT_ERR_INVALID_ARGUMENT;
     *out = nullptr;

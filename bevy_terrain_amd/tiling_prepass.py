@@ -73,6 +73,17 @@ def cull_planes(clip_from_world) -> np.ndarray:
     return out
 
 
+def cull_horizon(model: TerrainModel, eye: Sequence[float], margin: float = 0.0) -> _ffi.HorizonViewC:
+    """bt_cull_horizon: the horizon view of a frame for TilingPrepass.set_horizon — the eye (a world position) in the scaled space of a
+    spherical or ellipsoidal model, the occluding sphere that lies inside its terrain, `margin` world units around every tile."""
+    from .tile_tree import model_c
+
+    out = _ffi.HorizonViewC()
+    pos = (C.c_double * 3)(*eye)
+    _ffi.check(_ffi.lib().bt_cull_horizon(C.byref(model_c(model)), pos, C.c_float(margin), C.byref(out)))
+    return out
+
+
 class TilingPrepass:
     """TerrainViewData buffers + TilingPrepassNode::run as one persistent launch."""
 
@@ -116,6 +127,12 @@ class TilingPrepass:
         view.margin, view.min_height, view.max_height = margin, min_height, max_height
         _ffi.check(_ffi.lib().bt_tiling_prepass_set_culling(self._h, C.byref(view), bounds._h if bounds is not None else None))
         self._bounds = bounds  # borrowed by the library: keep it alive
+
+    def set_horizon(self, horizon: Optional[_ffi.HorizonViewC] = None):
+        """bt_tiling_prepass_set_horizon: every later run (all three forms, frame_update included) also drops the tiles that lie behind
+        the horizon of `horizon` (cull_horizon's result) with their subtrees.  Needs culling set (set_culling; zero planes give horizon
+        culling alone: the test reads its heights and bounds) and a spherical view.  None: off."""
+        _ffi.check(_ffi.lib().bt_tiling_prepass_set_horizon(self._h, C.byref(horizon) if horizon is not None else None))
 
     def cull_stats(self) -> Tuple[int, int]:
         """(tiles visited, tiles culled) by the last run; synchronises"""

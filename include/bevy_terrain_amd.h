@@ -639,8 +639,34 @@ bt_status bt_tiling_prepass_read(bt_tiling_prepass* t, bt_tile_coordinate* final
  * before the divide test).  bt_tiling_prepass_run_plain produces the id-order list with the culled tiles left out,
  * bt_tiling_prepass_run_unordered the same set, bt_tiling_prepass_run takes the plain kernel while culling is set (same list, same
  * order; its windows' bits fill the LDS already).  The indirect arguments count the final tiles that remain.  For the overflow verdict
- * a culled tile counts as visited (it occupied a slot of temporary_tiles) and contributes no children.  No horizon or occlusion
- * culling: the far side of a planet stays in the list when it is inside the frustum. */
+ * a culled tile counts as visited (it occupied a slot of temporary_tiles) and contributes no children.  With a horizon view set
+ * (bt_tiling_prepass_set_horizon, below) a tile is culled when the frustum test OR the horizon test culls it, and everything in this
+ * paragraph holds for either: the far side of a planet, behind the horizon of a sphere that lies inside the terrain, is dropped.
+ * Occlusion by terrain in front of that horizon (a ridge hiding a valley) is not tested: such tiles stay in the list.
+ *
+ * HORIZON CULLING (spherical and ellipsoidal views).  The test works in SCALED SPACE, the local frame of bt_view_state, in which the
+ * ellipsoid is the unit sphere; there the horizon of an ellipsoid is the horizon of a sphere, exactly.  Same arithmetic contract, with
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, and max(x, 0) = x when x > 0, else 0.
+ *
+ * SCALED POINT of a tile, q(tile, uv, h).  l is the unit local position POINT computes (the cube-sphere warp and normalisation, before
+ * world_from_local), n its world normal, t = local_from_world_transpose: g_r = (t[3r]*n.x + t[3r+1]*n.y) + t[3r+2]*n.z for r = 0, 1, 2
+ * (local_from_world * n), q = l + h * g componentwise, one multiply and one add each.  q is computed from l, never from the world
+ * point: a planet far from the world origin does not lose the test to cancellation.
+ *
+ * PER TILE.  h_lo, h_hi as in HEIGHT RANGE (the culling state's table and min_height / max_height).  Eight points Q_k = q(tile, uv, h),
+ * h in {h_lo, h_hi} (outer loop), uv in (0,0), (1,0), (0,1), (1,1).  d = q(tile, (0.5, 0.5), h_hi) - ((Q_4 + Q_5) + (Q_6 + Q_7)) * 0.25f,
+ * bulge = sqrt(dot3(d, d)), m = (bulge + margin) + BT_HORIZON_GUARD.  E = sqrt(dot3(eye, eye)), sv = sqrt(vh), lim = m * E.
+ *
+ * PER POINT k.  vt = Q_k - eye, ap = -dot3(vt, eye), along = ap / E, perp = sqrt(max(dot3(vt, vt) - along * along, 0)).  The point is
+ * HIDDEN when both (ap - vh) > lim and ((along * occluder_radius) - (perp * sv)) > lim.
+ *
+ * The tile is HORIZON-CULLED when vh > 0 and all eight points are hidden.  A comparison with a NaN is false, so NaNs cull nothing.
+ * Why it is conservative: what a sphere hides from the eye is its tangent cone intersected with the half-space beyond the tangent
+ * circle, a convex set; the two inequalities say that the ball of radius m around the point lies inside it (along - vh / E is the
+ * distance beyond the plane, (along * r - perp * sv) / E the distance inside the cone); so the hull of the eight points widened by m is
+ * hidden — the volume argument of the frustum test.  BT_HORIZON_GUARD covers the binary32 rounding of the test itself when the eye is
+ * close to the occluder (vh tiny, sv short of digits). */
+#define BT_HORIZON_GUARD 9.5367431640625e-07f /* 2^-20, scaled units */
 
 /* The min/max height store of the culling test: one {min, max} pair of raw unorm16 per quadtree tile of LODs 0 .. levels-1, dense, view
  * independent, on the device.  Level l follows level l-1; inside a level entry ((side * n + y) * n + x), n = 1 << l:
@@ -722,6 +748,20 @@ bt_status bt_tiling_prepass_set_culling(bt_tiling_prepass* t, const bt_cull_view
 /* tiles visited and tiles culled by the last run; synchronises.  After a run without culling: the tiles it visited, 0. */
 bt_status bt_tiling_prepass_cull_stats(bt_tiling_prepass* t, uint32_t* visited, uint32_t* culled);
 
+/* The horizon test's view (HORIZON CULLING above); bt_cull_horizon fills it per frame, like bt_cull_planes the planes. */
+typedef struct bt_horizon_view {
+    float eye[3];           /* the eye in scaled space */
+    float vh;               /* |eye|^2 - occluder_radius^2; <= 0 (eye inside the occluder): culls nothing */
+    float occluder_radius;  /* (0, 1]: scaled radius of a sphere that lies inside the terrain everywhere */
+    float margin;           /* scaled units, finite, >= 0 */
+} bt_horizon_view;
+/* horizon == NULL: off (the state after create).  Refused here: a non-finite field, occluder_radius outside (0, 1], a negative margin.
+ * The state holds for every later run of all three forms and for bt_frame_update until it is set again; callers set it per frame,
+ * like the planes.  The test reads the culling state's heights and table: a run with a horizon view set but culling not set
+ * (bt_tiling_prepass_set_culling(NULL)), or with a planar view, is BT_ERR_INVALID_ARGUMENT before anything is queued.  A cull view with
+ * plane_count == 0 is legal and gives horizon culling alone.  bt_tiling_prepass_cull_stats counts the tiles culled by either test. */
+bt_status bt_tiling_prepass_set_horizon(bt_tiling_prepass* t, const bt_horizon_view* horizon /* NULL: off */);
+
 /* -------------------------- TerrainModel / TerrainViewConfig / TileTree (the per-frame CPU side of the prepass) */
 enum { BT_MODEL_PLANAR = 0, BT_MODEL_SPHERICAL = 1, BT_MODEL_ELLIPSOIDAL = 2 };
 /* TerrainModel (math/terrain_model.rs:41-115): rotation is the identity, as in all three reference constructors.
@@ -758,6 +798,13 @@ void bt_terrain_view_config_default(bt_terrain_view_config* out);
  * TerrainModel::transform() (terrain_model.rs:195-201).  f64 on the host, `as f32` where the reference casts. */
 bt_status bt_view_state_from_config(const bt_terrain_model* model, const bt_terrain_view_config* view_config,
                                     const double view_world_position[3], float approximate_height, bt_view_state* out);
+/* The horizon view of a frame (HORIZON CULLING, bt_tiling_prepass_set_horizon).  Host only, float64 throughout.
+ * eye = f32(local_from_world * (view - model.position)); occluder_radius = 1 + min(min_height, 0) / min(axes) rounded toward zero to
+ * binary32 (a height h displaces a scaled point by at most |h| / the shortest axis, so that sphere lies inside the terrain);
+ * vh = f32(dot64(eye32, eye32) - radius32^2), from the ROUNDED eye and radius, so the three fields agree with each other;
+ * margin = margin_world / min(axes), rounded up.  BT_ERR_UNSUPPORTED: a planar model.  BT_ERR_INVALID_ARGUMENT: NULL pointers, a
+ * non-finite position, a negative or non-finite margin, a min_height that reaches the centre (radius <= 0). */
+bt_status bt_cull_horizon(const bt_terrain_model* model, const double view_world_position[3], float margin_world, bt_horizon_view* out);
 
 typedef struct bt_tile_tree bt_tile_tree; /* TileTree + GpuTileTree of one (terrain, view) pair */
 /* TileTree::new (tile_tree.rs:135-173).  The node tables (tile states, TileTreeEntry data, origins) live in HBM. */

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Times the tiling prepass (one persistent launch per frame) on scripted camera paths; prints one JSON line.
 --cull: the same paths seen through a camera, with frustum culling off and on (time and final tiles).
+--horizon: the sphere's path, one orbit view and one near-ground level view, culled, with the horizon view off and on.
+--root DIR: measure the library of another checkout of this repository (a parent commit built in DIR) with this tool.
 Not the headline benchmark (bench.py) — refinement is latency-bound: 10^2..10^4 tiles x 16 B per frame."""
 import json
 import math
@@ -9,6 +11,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
@@ -165,7 +169,7 @@ def measure_cull(device):
             up = (0.0, 1.0, 0.0) if centre is None else np.subtract(p, centre)
             planes.append(bt.cull_planes(travel_camera(p, np.subtract(b, a), up)))
         result = {"frames": len(views)}
-        for form_name, form in (("unordered", {"unordered": True}), ("plain_single_launch", {"plain": True})):
+        for form_name, form in (("unordered", {"unordered": True}), ("plain_single_launch", {"plain": True}), ("default_entry", {})):
             row = {}
             for culling in (False, True):
                 ms, counts, visited, culled = [], [], [], []
@@ -195,7 +199,66 @@ def measure_cull(device):
     return out
 
 
+def measure_horizon(device):
+    """--horizon: the sphere through the camera of --cull (five planes, no table), with the horizon view off and on — the 64 views of the
+    scripted path, one view from low orbit at the limb and one level view 2 m above max_height: device time per frame, final tiles,
+    tiles visited and culled, for all three forms"""
+    name, model, positions, centre = scripted_paths()[1]
+    cfg = bt.TerrainViewConfig()
+    prepass = bt.TilingPrepass(device, cfg.geometry_tile_count)
+    groups = {"path": []}
+    for i, p in enumerate(positions):
+        a, b = (positions[i], positions[i + 1]) if i + 1 < len(positions) else (positions[i - 1], positions[i])
+        groups["path"].append((p, travel_camera(p, np.subtract(b, a), np.subtract(p, centre))))
+    d = np.array([0.3, 0.9, 0.2]) / np.linalg.norm([0.3, 0.9, 0.2])
+    side = np.cross(d, [0.0, 0.0, 1.0])
+    side /= np.linalg.norm(side)
+    radius = model.radius
+    orbit = d * (radius + 4.0e5)
+    dip = math.acos(radius / (radius + 4.0e5))  # the limb lies this far below level
+    groups["orbit_400km_at_the_limb"] = [(tuple(orbit), travel_camera(orbit, math.cos(dip) * side - math.sin(dip) * d, d))]
+    ground = d * (radius + model.max_height + 2.0)
+    groups["near_ground_level_2m"] = [(tuple(ground), travel_camera(ground, side, d))]
+    out = {}
+    for group, cameras in groups.items():
+        views = [bt.make_view_state(model, cfg, p) for p, _ in cameras]
+        planes = [bt.cull_planes(clip) for _, clip in cameras]
+        horizons = [bt.cull_horizon(model, p) for p, _ in cameras]
+        result = {"frames": len(views)}
+        for form_name, form in (("unordered", {"unordered": True}), ("plain_single_launch", {"plain": True}), ("default_entry", {})):
+            row = {}
+            for on in (False, True):
+                counts, visited, culled = [], [], []
+                for repeat in range(4):  # (the first pass warms the variant up)
+                    ms = []
+                    for v, pl, hz in zip(views, planes, horizons):
+                        prepass.set_culling(pl, min_height=model.min_height, max_height=model.max_height)
+                        prepass.set_horizon(hz if on else None)
+                        samples = []
+                        for _ in range(3 if len(views) > 1 else 48):
+                            device.timer_begin()
+                            prepass.run(v, **form)
+                            samples.append(device.timer_end())
+                        ms.append(min(samples) if len(views) > 1 else float(np.median(samples)))
+                        if repeat == 3:
+                            counts.append(len(prepass.read()[0]))
+                            stats = prepass.cull_stats()
+                            visited.append(stats[0])
+                            culled.append(stats[1])
+                row["horizon_on" if on else "horizon_off"] = {
+                    "us_per_frame_avg": 1e3 * float(np.mean(ms)), "us_per_frame_max": 1e3 * float(np.max(ms)), "final_tiles_avg": float(np.mean(counts)),
+                    "tiles_visited_avg": float(np.mean(visited)), "tiles_culled_avg": float(np.mean(culled))}
+            row["time_ratio_on_over_off"] = row["horizon_on"]["us_per_frame_avg"] / row["horizon_off"]["us_per_frame_avg"]
+            row["final_tiles_kept"] = row["horizon_on"]["final_tiles_avg"] / row["horizon_off"]["final_tiles_avg"]
+            result[form_name] = row
+        out[group] = result
+    return out
+
+
 def main():
+    if "--horizon" in sys.argv:
+        print(json.dumps({"tiling_prepass_horizon": measure_horizon(bt.Device(0))}))
+        return
     if "--cull" in sys.argv:
         print(json.dumps({"tiling_prepass_culling": measure_cull(bt.Device(0))}))
         return
