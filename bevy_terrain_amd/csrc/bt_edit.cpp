@@ -1,4 +1,4 @@
-// bt_atlas_edit_height / bt_atlas_write_region / bt_atlas_save_tiles: the host half of in-place editing.
+// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_write_region / bt_atlas_save_tiles: the host half of in-place editing.
 //
 // An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
 // include/bevy_terrain_amd.h): the ancestors' centres, the aprons of every written tile and of its existing neighbours, the mips.  The plan
@@ -251,13 +251,41 @@ struct RegionSource {
     const void* dev;
     uint32_t rx0, ry0, width;
 };
+struct SmoothSource {
+    const bt_smooth_stamp* stamps;
+    uint32_t kernel_radius;
+};
 
-// uploads the plan and enqueues its launches; the first launch is the brush (stamps) or the region copy (region)
-bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* stamps, uint32_t stamp_count, const RegionSource* region) {
+// the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height
+bt_status region_scratch(bt_ctx* ctx, uint64_t bytes) {
+    if (bytes <= ctx->edit_region_bytes) return BT_OK;
+    if (ctx->edit_region_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // a launch in flight uses the buffer that goes away
+    if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
+    ctx->edit_region_dev = nullptr;
+    ctx->edit_region_bytes = 0;
+    BT_HIP(hipMalloc(&ctx->edit_region_dev, bytes));
+    ctx->edit_region_bytes = bytes;
+    return BT_OK;
+}
+
+// uploads the plan and enqueues its launches; the first step is the brush (stamps), the region copy (region) or the smoothing pair (smooth:
+// its stamps; `stamps` is NULL then)
+bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* stamps, uint32_t stamp_count, const RegionSource* region,
+                   const SmoothSource* smooth = nullptr) {
     Attachment& at = a->attachments[ai];
     bt_ctx* ctx = a->ctx;
     if (plan.levels.empty()) return BT_OK;
-    uint64_t bytes = align16(uint64_t(stamp_count) * sizeof(bt_edit_stamp)) + align16(plan.stitches.size() * sizeof(TaskDev));
+    const uint64_t stamp_bytes = uint64_t(stamp_count) * (smooth ? sizeof(bt_smooth_stamp) : sizeof(bt_edit_stamp));
+    std::vector<uint64_t> offsets;  // smooth: where each item's rectangle starts in the scratch, in dwords
+    uint64_t scratch_dwords = 0;
+    if (smooth) {
+        for (const EditItem& it : plan.levels[0]) {
+            offsets.push_back(scratch_dwords);
+            scratch_dwords += smooth_item_dwords(it, at.meta.border_size);
+        }
+        if (bt_status s = region_scratch(ctx, scratch_dwords * sizeof(uint32_t))) return s;
+    }
+    uint64_t bytes = align16(stamp_bytes) + align16(offsets.size() * sizeof(uint64_t)) + align16(plan.stitches.size() * sizeof(TaskDev));
     for (const auto& items : plan.levels) bytes += align16(items.size() * sizeof(EditItem));
     uint8_t *host = nullptr, *dev = nullptr;
     if (bt_status s = edit_scratch(ctx, bytes, &host, &dev)) return s;
@@ -268,7 +296,8 @@ bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* st
         off += align16(n);
         return where;
     };
-    const bt_edit_stamp* stamps_dev = (const bt_edit_stamp*)put(stamps, uint64_t(stamp_count) * sizeof(bt_edit_stamp));
+    const uint8_t* stamps_dev = put(smooth ? (const void*)smooth->stamps : (const void*)stamps, stamp_bytes);
+    const uint64_t* offsets_dev = (const uint64_t*)put(offsets.data(), offsets.size() * sizeof(uint64_t));
     std::vector<const EditItem*> items_dev;
     for (const auto& items : plan.levels) items_dev.push_back((const EditItem*)put(items.data(), items.size() * sizeof(EditItem)));
     const TaskDev* stitches_dev = (const TaskDev*)put(plan.stitches.data(), plan.stitches.size() * sizeof(TaskDev));
@@ -279,10 +308,14 @@ bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* st
     const uint32_t n0 = uint32_t(plan.levels[0].size());
     if (region) {
         if (bt_status s = launch_edit_region(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], region->dev, region->rx0, region->ry0, region->width)) return s;
+    } else if (smooth) {
+        if (bt_status s = launch_edit_smooth(ctx->stream, at.meta, at.level0, items_dev[0], offsets_dev, n0, plan.max_rows[0], (const bt_smooth_stamp*)stamps_dev,
+                                             stamp_count, smooth->kernel_radius, ctx->edit_region_dev))
+            return s;
     } else {
-        if (bt_status s = launch_edit_brush(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], stamps_dev, stamp_count)) return s;
+        if (bt_status s = launch_edit_brush(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], (const bt_edit_stamp*)stamps_dev, stamp_count)) return s;
     }
-    plan.stats.launches = 1;
+    plan.stats.launches = smooth ? 2 : 1;
     for (size_t k = 1; k < plan.levels.size(); k++) {
         if (bt_status s = launch_edit_downsample(ctx->stream, at.meta, at.level0, items_dev[k], uint32_t(plan.levels[k].size()), plan.max_rows[k])) return s;
         plan.stats.launches++;
@@ -339,6 +372,18 @@ bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, bool brush,
     return BT_OK;
 }
 
+// a stamp's box (the header's BRUSH section), clipped to the face; nothing is added where it misses the face
+void add_stamp_box(std::vector<Box>& boxes, const Attachment& at, uint32_t lod, uint32_t side, const float center[2], float radius) {
+    const double size = double(uint64_t(at.meta.center_size) << lod);
+    double lo[2], hi[2];
+    for (int k = 0; k < 2; k++) {
+        lo[k] = std::max(0.0, std::floor(double(center[k]) - double(radius)));
+        hi[k] = std::min(size - 1.0, std::ceil(double(center[k]) + double(radius)));
+        if (lo[k] > hi[k]) return;
+    }
+    boxes.push_back({side, {uint32_t(lo[0]), uint32_t(lo[1]), uint32_t(hi[0]), uint32_t(hi[1])}});
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,24 +429,71 @@ bt_status bt_atlas_edit_height(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_
     const Attachment& at = a->attachments[ai];
     // a stamp's box [floor(center - radius), ceil(center + radius)], clipped to the face: a texel outside it is at least radius + 1 away on
     // one axis, and rounding is monotonic, so its d2 is not below r2 in binary32 either
-    const double size = double(uint64_t(at.meta.center_size) << lod);
     std::vector<Box> boxes;
-    for (uint32_t i = 0; i < count; i++) {
-        const bt_edit_stamp& s = stamps[i];
-        double lo[2], hi[2];
-        bool empty = false;
-        for (int k = 0; k < 2; k++) {
-            lo[k] = std::max(0.0, std::floor(double(s.center[k]) - double(s.radius)));
-            hi[k] = std::min(size - 1.0, std::ceil(double(s.center[k]) + double(s.radius)));
-            empty = empty || lo[k] > hi[k];
-        }
-        if (!empty) boxes.push_back({s.side, {uint32_t(lo[0]), uint32_t(lo[1]), uint32_t(hi[0]), uint32_t(hi[1])}});
-    }
+    for (uint32_t i = 0; i < count; i++) add_stamp_box(boxes, at, lod, stamps[i].side, stamps[i].center, stamps[i].radius);
     hipError_t e = hipSetDevice(a->ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     Plan plan;
     build_plan(a, at, lod, boxes, plan);
     const bt_status rc = run_plan(a, ai, plan, stamps, count, nullptr);
+    report(plan, changed, changed_cap, stats);
+    return rc;
+}
+
+bt_status bt_atlas_smooth_height(bt_atlas* a, uint32_t ai, uint32_t lod, uint32_t kernel_radius, const bt_smooth_stamp* stamps, uint32_t count,
+                                 bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
+    if (stats) *stats = bt_edit_stats{};
+    // as bt_atlas_edit_height: what can be refused without the atlas is refused without it
+    if (count > BT_EDIT_MAX_STAMPS) {
+        set_error("bt_atlas_smooth_height: %u stamps, at most %u per call", count, BT_EDIT_MAX_STAMPS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (kernel_radius == 0u || kernel_radius > BT_SMOOTH_MAX_KERNEL) {
+        set_error("bt_atlas_smooth_height: kernel_radius %u (1 .. %u)", kernel_radius, BT_SMOOTH_MAX_KERNEL);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if ((count && !stamps) || (changed_cap && !changed)) {
+        set_error("bt_atlas_smooth_height: NULL %s", count && !stamps ? "stamps" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_smooth_stamp& s = stamps[i];
+        const char* bad = nullptr;
+        if (s.side >= 6u) bad = "side";
+        else if (s.falloff != BT_EDIT_FALLOFF_SMOOTH && s.falloff != BT_EDIT_FALLOFF_HARD) bad = "falloff";
+        else if (!std::isfinite(s.center[0]) || !std::isfinite(s.center[1])) bad = "center (not finite)";
+        else if (!std::isfinite(s.radius) || !(s.radius > 0.0f)) bad = "radius (finite and > 0)";
+        else if (!std::isfinite(s.strength) || !(s.strength > 0.0f) || !(s.strength <= 1.0f)) bad = "strength (finite, in (0, 1])";
+        if (bad) {
+            set_error("bt_atlas_smooth_height: stamp %u: %s", i, bad);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (!a) {
+        set_error("bt_atlas_smooth_height: NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_target(a, ai, lod, true, "bt_atlas_smooth_height")) return s;
+    const Attachment& at = a->attachments[ai];
+    if (kernel_radius > at.meta.border_size) {
+        set_error("bt_atlas_smooth_height: kernel_radius %u beyond border_size %u: the box would leave the tile's layer", kernel_radius, at.meta.border_size);
+        return BT_ERR_UNSUPPORTED;
+    }
+    const uint32_t sides = a->config.spherical ? 6u : 1u;
+    for (uint32_t i = 0; i < count; i++)
+        if (stamps[i].side >= sides) {
+            set_error("bt_atlas_smooth_height: stamp %u: side %u of %u", i, stamps[i].side, sides);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (!count) return BT_OK;
+    std::vector<Box> boxes;
+    for (uint32_t i = 0; i < count; i++) add_stamp_box(boxes, at, lod, stamps[i].side, stamps[i].center, stamps[i].radius);
+    hipError_t e = hipSetDevice(a->ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    Plan plan;
+    build_plan(a, at, lod, boxes, plan);
+    const SmoothSource smooth = {stamps, kernel_radius};
+    const bt_status rc = run_plan(a, ai, plan, nullptr, count, nullptr, &smooth);
     report(plan, changed, changed_cap, stats);
     return rc;
 }
@@ -445,14 +537,7 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
     }
     // the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
     const uint64_t total = row_bytes * height;
-    if (total > ctx->edit_region_bytes) {
-        if (ctx->edit_region_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // a region launch in flight reads the buffer that goes away
-        if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
-        ctx->edit_region_dev = nullptr;
-        ctx->edit_region_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->edit_region_dev, total));
-        ctx->edit_region_bytes = total;
-    }
+    if (bt_status s = region_scratch(ctx, total)) return s;
     if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
         if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
     const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));

@@ -11,6 +11,10 @@
 // edit_brush_kernel   the stamps of bt_atlas_edit_height on the texels of the rectangle; the stamp array is indexed by the loop counter
 //                     only (wave-uniform: scalar loads), and a stamp whose side is not the item's is skipped by the whole wave.
 // edit_region_kernel  the same layout, copying from the staged rectangle of bt_atlas_write_region.
+// edit_smooth_kernel<K>  the box mean of bt_atlas_smooth_height (kernel_radius K) and its stamps.  It READS the layers and writes the new dwords
+//                     of every item's rectangle into device scratch: other workgroups read the rows it would write (as halo), so nothing of
+//                     the call may land in a layer before every workgroup has read.  edit_smooth_copy_kernel, the next launch, moves them in.
+//                     A workgroup stages its row block in LDS; see the kernel.
 // edit_downsample_kernel  the rectangle of a parent's centre from its four children: downsample_texel of bt_downsample.hpp, the device
 //                     function downsample_kernel runs.  One launch per LOD (a level reads what the level below wrote).
 //
@@ -110,6 +114,141 @@ __global__ __launch_bounds__(kEditThreads) void edit_region_kernel(AttachmentMet
     }
 }
 
+// ---- smoothing.  A texel in LDS is one dword, already in the form the sums add: (1 << 24) | u for u != 0, 0 for a hole, so a tap is ONE
+// integer add and the total carries the count in bits 24.. (<= 81) and the sum below (<= 81 * 65535 < 2^23).  A lane owns the aligned pair
+// (2p, 2p + 1) as everywhere in this file and reads whole pairs (8 bytes): the 32 lanes of a half wave read 256 consecutive bytes of one
+// staged row, which is one pass of the 64 banks whatever the row pitch, so the pitch is just the window's width.  The staging stores are
+// 8-byte stores of consecutive lanes as well.
+//
+// The window of a workgroup: its kEditRows rows plus K above and below, by one trip of the lanes (64 pairs) plus kHalo = ceil(K / 2) pairs
+// left and right; a wider rectangle is walked in such column chunks, each staged with its own halo.  K <= border_size keeps every row
+// and every texel a data texel taps inside the layer; a PAIR of the halo may lie outside the row (odd K at the layer's edge): it is
+// staged as holes and only the discarded half of an edge pair ever taps it.
+// Separable: a wave takes four consecutive rows; per pair it forms the row sums of the 4 + 2K staged rows those need, once each, and adds
+// 2K + 1 of them per output row.  Integer sums: every order gives the same bits.
+template <uint32_t K>
+struct SmoothWindow {
+    static constexpr uint32_t kHalo = (K + 1u) / 2u;          // pairs
+    static constexpr uint32_t kPairs = 64u + 2u * kHalo;      // pitch, in pairs
+    static constexpr uint32_t kRows = kEditRows + 2u * K;
+    static constexpr uint32_t kWaveRows = kEditRows / (kEditThreads / 64u);  // output rows of a wave
+};
+
+__device__ __forceinline__ uint32_t smooth_pack(uint32_t u) { return u ? (1u << 24) | u : 0u; }
+
+// steps 1 - 3 of the header's SMOOTHING section for one texel: t0 its value before the call, acc the packed box total
+__device__ __forceinline__ uint32_t smooth_texel(const bt_smooth_stamp* __restrict__ stamps, uint32_t stamp_count, uint32_t side, float fx, float fy, uint32_t t0,
+                                                 uint32_t acc) {
+    if (t0 == 0u) return 0u;
+    const float mean = float(acc & 0xFFFFFFu) / (65535.0f * float(acc >> 24));
+    uint32_t t = t0;
+    for (uint32_t k = 0; k < stamp_count; k++) {
+        const bt_smooth_stamp s = stamps[k];
+        if (s.side != side) continue;
+        const float r2 = s.radius * s.radius;
+        const float dx = fx - s.center[0];
+        const float dy = fy - s.center[1];
+        const float d2 = (dx * dx) + (dy * dy);
+        if (!(d2 < r2)) continue;
+        float w = 1.0f;
+        if (s.falloff == BT_EDIT_FALLOFF_SMOOTH) {
+            const float q = d2 / r2;
+            const float sm = 1.0f - q;
+            w = sm * sm;
+        }
+        const float a = s.strength * w;
+        const float h = unorm16_to_float(t);
+        const float hn = h + (mean - h) * a;
+        t = max(1u, float_to_unorm(hn, 65535.0f));
+    }
+    return t;
+}
+
+template <uint32_t K>
+__global__ __launch_bounds__(kEditThreads) void edit_smooth_kernel(AttachmentMeta m, const uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
+                                                                   const uint64_t* __restrict__ offsets, const bt_smooth_stamp* __restrict__ stamps,
+                                                                   uint32_t stamp_count, uint32_t* __restrict__ scratch) {
+    using W = SmoothWindow<K>;
+    __shared__ uint2 window[W::kRows][W::kPairs];
+    const EditItem it = items[blockIdx.x];
+    const uint32_t y_begin = it.y0 + blockIdx.y * kEditRows;
+    if (y_begin > it.y1) return;  // (the whole workgroup: no barrier is skipped by a part of it)
+    const uint32_t y_end = min(y_begin + kEditRows - 1u, it.y1);
+    const uint32_t Tsz = m.texture_size, b = m.border_size, row_pairs = Tsz / 2u;
+    const uint32_t* tile = reinterpret_cast<const uint32_t*>(atlas + uint64_t(it.layer) * Tsz * Tsz);
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1, first = px0 >> 1, last = px1 >> 1, width = last - first + 1u;
+    uint32_t* out = scratch + offsets[blockIdx.x];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t staged_rows = y_end - y_begin + 1u + 2u * K;  // staged row r is layer row b + y_begin - K + r
+    for (uint32_t chunk = first; chunk <= last; chunk += 64u) {
+        if (chunk != first) __syncthreads();  // the window of the previous chunk has been read
+        const uint32_t staged_pairs = min(64u, last - chunk + 1u) + 2u * W::kHalo;  // staged pair i is pair chunk - kHalo + i of the row
+        for (uint32_t r = wave; r < staged_rows; r += kEditThreads / 64u) {
+            const uint32_t* row = tile + uint64_t(b + y_begin - K + r) * row_pairs;
+            for (uint32_t i = lane; i < staged_pairs; i += 64u) {
+                const uint32_t p = chunk + i - W::kHalo;  // (wraps below 0: then it is not < row_pairs either)
+                const uint32_t pair = p < row_pairs ? row[p] : 0u;
+                window[r][i] = make_uint2(smooth_pack(pair & 0xFFFFu), smooth_pack(pair >> 16));
+            }
+        }
+        __syncthreads();
+        const uint32_t p = chunk + lane, j0 = wave * W::kWaveRows;  // the wave's output rows are y_begin + j0 ..
+        if (p > last || y_begin + j0 > y_end) continue;
+        uint32_t row0[W::kWaveRows + 2u * K], row1[W::kWaveRows + 2u * K], centre[W::kWaveRows];
+#pragma unroll
+        for (uint32_t r = 0; r < W::kWaveRows + 2u * K; r++) {  // (rows past the staged ones hold stale words: their sums feed rows past y_end only)
+            uint32_t e[2u * (2u * W::kHalo + 1u)];
+#pragma unroll
+            for (uint32_t i = 0; i <= 2u * W::kHalo; i++) {
+                const uint2 v = window[j0 + r][lane + i];
+                e[2u * i] = v.x, e[2u * i + 1u] = v.y;
+            }
+            uint32_t s0 = 0, s1 = 0;
+#pragma unroll
+            for (uint32_t d = 0; d <= 2u * K; d++) {
+                s0 += e[2u * W::kHalo - K + d];
+                s1 += e[2u * W::kHalo + 1u - K + d];
+            }
+            row0[r] = s0, row1[r] = s1;
+            if (r >= K && r < K + W::kWaveRows) centre[r - K] = (e[2u * W::kHalo] & 0xFFFFu) | (e[2u * W::kHalo + 1u] << 16);
+        }
+        const uint32_t px = 2u * p;
+        const bool in0 = px >= px0, in1 = px + 1u <= px1;
+        const float fx0 = float(it.gx0 + px - b), fx1 = float(it.gx0 + px + 1u - b);  // (the half outside the rectangle is not used)
+#pragma unroll
+        for (uint32_t j = 0; j < W::kWaveRows; j++) {
+            const uint32_t y = y_begin + j0 + j;
+            if (y > y_end) break;
+            uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+            for (uint32_t d = 0; d <= 2u * K; d++) a0 += row0[j + d], a1 += row1[j + d];
+            uint32_t t0 = centre[j] & 0xFFFFu, t1 = centre[j] >> 16;
+            const float fy = float(it.gy0 + y);
+            if (in0) t0 = smooth_texel(stamps, stamp_count, it.side, fx0, fy, t0, a0);
+            if (in1) t1 = smooth_texel(stamps, stamp_count, it.side, fx1, fy, t1, a1);
+            out[uint64_t(y - it.y0) * width + (p - first)] = t0 | (t1 << 16);
+        }
+    }
+}
+
+// scratch -> layers: edit_region_kernel<R16>'s ownership of dwords, the source being item-relative
+__global__ __launch_bounds__(kEditThreads) void edit_smooth_copy_kernel(AttachmentMeta m, uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
+                                                                        const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ scratch) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    uint32_t* tile = reinterpret_cast<uint32_t*>(atlas + uint64_t(it.layer) * Tsz * Tsz);
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1, first = px0 >> 1, width = (px1 >> 1) - first + 1u;
+    const uint32_t* src = scratch + offsets[blockIdx.x];
+    for_each_dword(it, first, px1 >> 1, [&](uint32_t y, uint32_t p) {
+        uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
+        const uint32_t px = 2u * p;
+        const bool in0 = px >= px0, in1 = px + 1u <= px1;
+        const uint32_t fresh = src[uint64_t(y - it.y0) * width + (p - first)];
+        const uint32_t old = (in0 && in1) ? 0u : *dst;
+        *dst = (in0 ? (fresh & 0xFFFFu) : (old & 0xFFFFu)) | ((in1 ? (fresh >> 16) : (old >> 16)) << 16);
+    });
+}
+
 // centre texel (tx, ty) of a parent: the child it lies in and the 2x2 block of that child's centre (downsample_kernel's mapping).  The child
 // layers come as four scalars selected by comparisons: a dynamically indexed copy of the item would be promoted to LDS.
 struct EditChildren {
@@ -174,6 +313,22 @@ bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* 
     else
         edit_region_kernel<BT_FORMAT_RGBA8><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
     return edit_launched("edit_region_kernel");
+}
+
+bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, const uint64_t* offsets, uint32_t n, uint32_t max_rows,
+                             const bt_smooth_stamp* stamps, uint32_t stamp_count, uint32_t kernel_radius, void* scratch) {
+    if (!n || !max_rows) return BT_OK;
+    const dim3 grid = edit_grid(n, max_rows);
+    switch (kernel_radius) {
+        case 1: edit_smooth_kernel<1><<<grid, kEditThreads, 0, stream>>>(m, (const uint16_t*)atlas, items, offsets, stamps, stamp_count, (uint32_t*)scratch); break;
+        case 2: edit_smooth_kernel<2><<<grid, kEditThreads, 0, stream>>>(m, (const uint16_t*)atlas, items, offsets, stamps, stamp_count, (uint32_t*)scratch); break;
+        case 3: edit_smooth_kernel<3><<<grid, kEditThreads, 0, stream>>>(m, (const uint16_t*)atlas, items, offsets, stamps, stamp_count, (uint32_t*)scratch); break;
+        case 4: edit_smooth_kernel<4><<<grid, kEditThreads, 0, stream>>>(m, (const uint16_t*)atlas, items, offsets, stamps, stamp_count, (uint32_t*)scratch); break;
+        default: set_error("edit_smooth_kernel: kernel_radius %u", kernel_radius); return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = edit_launched("edit_smooth_kernel")) return s;
+    edit_smooth_copy_kernel<<<grid, kEditThreads, 0, stream>>>(m, (uint16_t*)atlas, items, offsets, (const uint32_t*)scratch);
+    return edit_launched("edit_smooth_copy_kernel");
 }
 
 bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows) {

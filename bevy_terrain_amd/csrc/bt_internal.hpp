@@ -205,8 +205,8 @@ struct bt_ctx {
     uint64_t raycast_bytes = 0;
     // bt_atlas_edit_height / bt_atlas_write_region: the plans (items, stamps, stitch tasks) of the calls in flight, pinned and on the device,
     // handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is recorded behind each
-    // call's copy and waited for when the ring wraps), and the staged rectangle of write_region on the device (grown on demand, kept
-    // until bt_ctx_trim)
+    // call's copy and waited for when the ring wraps), and the staged rectangle of write_region / the new texels of smooth_height on the
+    // device (grown on demand, kept until bt_ctx_trim)
     void* edit_dev = nullptr;
     void* edit_host = nullptr;
     uint64_t edit_bytes = 0, edit_used = 0;
@@ -283,6 +283,15 @@ bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* a
 bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
                              const void* src, uint32_t rx0, uint32_t ry0, uint32_t src_width);
 bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows);
+// bt_atlas_smooth_height, two launches: edit_smooth_kernel<kernel_radius> reads the layers and writes the new dwords of every item's rectangle
+// to `scratch` (device), the copy launch moves them into the layers.  offsets[i] (device): where item i's rectangle starts in `scratch`, in
+// dwords; it holds (y1 - y0 + 1) rows of ((b + x1) >> 1) - ((b + x0) >> 1) + 1 dwords, the aligned pairs of texels the rectangle touches
+// (smooth_item_dwords)
+inline uint64_t smooth_item_dwords(const EditItem& it, uint32_t border_size) {
+    return uint64_t(it.y1 - it.y0 + 1u) * (((border_size + it.x1) >> 1) - ((border_size + it.x0) >> 1) + 1u);
+}
+bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, const uint64_t* offsets, uint32_t n, uint32_t max_rows,
+                             const bt_smooth_stamp* stamps, uint32_t stamp_count, uint32_t kernel_radius, void* scratch);
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 

@@ -126,6 +126,21 @@ class EditStamp:
                                (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.amount))
 
 
+@dataclass
+class SmoothStamp:
+    """bt_smooth_stamp: one stamp of TileAtlas.smooth_height.  center / radius as EditStamp's; strength in (0, 1] is how far a texel under
+    the stamp's full weight moves towards the box mean of its neighbourhood (1: onto it)."""
+    center: Tuple[float, float]
+    radius: float
+    strength: float = 1.0
+    falloff: str = "smooth"  # "smooth": w = (1 - d^2 / r^2)^2 | "hard": w = 1
+    side: int = 0
+
+    def _c(self):
+        return _ffi.SmoothStampC(self.side, {"smooth": _ffi.EDIT_FALLOFF_SMOOTH, "hard": _ffi.EDIT_FALLOFF_HARD}[self.falloff],
+                                 (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.strength))
+
+
 def mosaic_position(uv, lod: int, center_size: int) -> Tuple[float, float]:
     """The mosaic position (EditStamp.center units) of face coordinate uv in [0, 1]^2 at `lod`: the face is 2^lod * center_size texels
     wide and texel g covers [g / n, (g + 1) / n) with its position at the integer g, so the middle of texel g maps to g."""
@@ -324,6 +339,16 @@ class TileAtlas:
         stamps = list(stamps)
         arr = (_ffi.EditStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
         return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_edit_height(self._h, attachment_index, lod, arr, len(stamps), changed, cap, stats))
+
+    def smooth_height(self, attachment_index: int, stamps, kernel_radius: int = 1, lod: Optional[int] = None) -> Tuple[List[TileCoordinate], dict]:
+        """bt_atlas_smooth_height: move the centre texels under the SmoothStamps towards the mean of their (2 * kernel_radius + 1)^2 box
+        (no-data texels excluded and left alone; kernel_radius 1 .. 4 and <= border_size), every mean taken from the state BEFORE the call:
+        one call is one Jacobi pass under all its stamps.  Then everything is restored as by edit_height.  Returns (changed, stats);
+        stats["launches"] counts two launches for the brush."""
+        lod = self.lod_count - 1 if lod is None else lod
+        stamps = list(stamps)
+        arr = (_ffi.SmoothStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
+        return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_smooth_height(self._h, attachment_index, lod, kernel_radius, arr, len(stamps), changed, cap, stats))
 
     def write_region(self, attachment_index: int, texels: np.ndarray, x0: int, y0: int, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_write_region: copy `texels` ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros allowed) verbatim over the centre

@@ -360,6 +360,47 @@ bt_status bt_atlas_edit_height(bt_atlas* atlas, uint32_t attachment_index, uint3
 bt_status bt_atlas_write_region(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
                                 uint32_t width, uint32_t height, const void* texels_host, uint64_t row_pitch,
                                 bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+/* SMOOTHING (bt_atlas_smooth_height; R16 only): the third brush.  Let S be a tile's level-0 layer, centre AND apron, AS IT STOOD BEFORE THE
+ * CALL, k = kernel_radius (1 .. BT_SMOOTH_MAX_KERNEL, and k <= border_size: the box of a centre texel then lies inside the tile's own
+ * layer, whose apron holds the neighbours' centre texels by item 3 of F), b = border_size.  Centre texel (i, j) of an existing tile of
+ * `lod`, at layer pixel (px, py) = (b + i, b + j) and mosaic position (gx, gy):
+ *   1. t0 = S[py][px].  A texel equal to 0 (no data) is never changed.
+ *   2. the box mean, in integers and therefore independent of the order of summation:
+ *        sum = the sum of S[py + dy][px + dx] over dx, dy in [-k, k];  n = the number of those texels that are != 0  (n >= 1: the texel itself)
+ *        m = f32(sum) / (65535 * f32(n))       binary32; both operands are exact (sum <= 81 * 65535 < 2^24), one correctly rounded division
+ *   3. the stamps IN LIST ORDER, those whose `side` is the tile's, with the running value t starting at t0:
+ *        dx, dy, d2, r2, the test d2 < r2 and w exactly as in THE BRUSH
+ *        a = strength * w;  h = f32(t) / 65535;  h' = h + (m - h) * a;  t' = max(1, floor(0.5 + 65535 * clamp(h', 0, 1)))
+ *      one rounding per written operation, no contraction.
+ * Then F is restored exactly as by bt_atlas_edit_height: the same plan, the same `changed` order, the same stats fields; the stamp's box,
+ * the clipping to the face, tiles_edited / tiles_missing / tiles_with_children, "tiles finer than `lod` are not touched" and "enqueues and
+ * returns without synchronising" carry over unchanged.  Consequences:
+ *   - m comes from the state before the call for EVERY stamp of the call: one call is one Jacobi pass under all its stamps.  N calls of one
+ *     stamp are NOT one call of N stamps (unlike ADD / FLATTEN, whose stamps only see their own texel).
+ *   - Edges.  Where a neighbour tile does not exist the box sees the tile's own centre clamped (that is what the apron holds); across a
+ *     cube edge it sees the re-projected neighbour; at a cube corner the diagonal is clamped.
+ *   - Precondition.  The call assumes F holds beforehand; every operation of this library leaves it so (an overlay dataset whose
+ *     neighbours' aprons are stale, DESIGN.md 3.13, is the caller's concern).
+ *   - Fixed points.  A constant field and a linear ramp are fixed points (for a ramp sum = n * t, so m == h bit for bit and t' == t), and
+ *     so is an isolated data texel (n = 1).  Holes are neither filled nor created.
+ * Launches: TWO for the brush (no lane may read a texel the call has already written, and other workgroups write the rows next to a
+ * workgroup's own: the first launch reads the layers and writes the new texels to scratch of the context, the second copies them in),
+ * then as above: stats->launches = 2 + downsample levels + stitch + mips.  The scratch is the staged-rectangle buffer of
+ * bt_atlas_write_region (stream-ordered with it; kept until bt_ctx_trim).
+ * BT_ERR_INVALID_ARGUMENT (all checked before any device work): NULL atlas, NULL stamps with count > 0, NULL changed with changed_cap > 0,
+ * count > BT_EDIT_MAX_STAMPS, kernel_radius 0 or > BT_SMOOTH_MAX_KERNEL, a bad side or falloff, a non-finite center, a radius that is not
+ * finite or <= 0, a strength that is not finite or outside (0, 1], attachment_index or lod out of range.  BT_ERR_UNSUPPORTED:
+ * kernel_radius > border_size, an odd centre size, a non-R16 attachment.  count == 0: BT_OK with nothing touched. */
+#define BT_SMOOTH_MAX_KERNEL 4u
+typedef struct bt_smooth_stamp {
+    uint32_t side, falloff;      /* BT_EDIT_FALLOFF_* */
+    float center[2];             /* mosaic texels of `lod` on `side`, as bt_edit_stamp */
+    float radius;                /* texels, finite, > 0 */
+    float strength;              /* finite, 0 < strength <= 1 */
+} bt_smooth_stamp;
+bt_status bt_atlas_smooth_height(bt_atlas* atlas, uint32_t attachment_index, uint32_t lod, uint32_t kernel_radius,
+                                 const bt_smooth_stamp* stamps, uint32_t count,
+                                 bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
 /* bt_atlas_save_attachment for a list of tiles (the `changed` list of an edit): writes "{directory}/{coord}.bin" of the listed tiles only.
  * A coordinate the atlas holds no layer for: BT_ERR_INVALID_ARGUMENT before anything is written.  count == 0: the directory is created. */
 bt_status bt_atlas_save_tiles(bt_atlas* atlas, uint32_t attachment_index, const char* directory, const bt_tile_coordinate* coords, uint32_t count);

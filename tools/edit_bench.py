@@ -8,6 +8,11 @@ context serves the calls in flight) after a spin-up of the same calls, the media
 `changed_count` of the call; host time per call (the planning + enqueue, a host clock around the same window ended by a synchronise).
 Successive calls of a window use the same stamps: the texels saturate after some calls, the work does not change.
 
+Then the smoothing brush (bt_atlas_smooth_height): one SMOOTH stamp of strength 0.5 at the same corner and radii, kernel_radius 1 and 2, the
+same windows (rows `smooth_r{radius}_k{kernel_radius}`; the ADD rows above are their yardstick, taken in the same run), and what a host
+would do for the same tile set without the call: download the changed tiles, (filter on the host: left out), bt_atlas_write_region of the
+stamp's box (wall time, `download_write_region_wall_ms`, with its two legs).
+
 Next to them what a host can do without the call: (a) re-running the kept preprocess queue (bench.py's headline step) and (b) a
 download_tiles / upload_tile round trip of the same changed tile set, the host patching left out (wall time, it is synchronous).
 
@@ -161,9 +166,59 @@ def main():
         result[name] = {"stamps": len(stamps), "device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
                         "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"],
                         "download_upload_round_trip_wall_ms": round(median(round_trip), 3)}
+    smooth_cases(device, atlas, index, args, result)
     print(json.dumps(result), flush=True)
     pre.close()
     device.free(src)
+
+
+def smooth_cases(device, atlas, index, args, result):
+    import numpy as np
+
+    corner = (16 * CENTER + 0.25, 16 * CENTER - 0.5)
+    size = CENTER << (LOD_COUNT - 1)
+    for r in (4, 32, 256, 2048):
+        stamps = [bt.SmoothStamp(corner, float(r), 0.5)]
+        for k in (1, 2):
+            changed, stats = atlas.smooth_height(0, stamps, k)
+            for _ in range(args.calls // 4):
+                atlas.smooth_height(0, stamps, k)
+            device_ms, host_ms = [], []
+            for _ in range(args.repeats):
+                device.synchronize()
+                t0 = time.perf_counter()
+                device.timer_begin()
+                for _ in range(args.calls):
+                    atlas.smooth_height(0, stamps, k)
+                host_ms.append((time.perf_counter() - t0) * 1e3 / args.calls)
+                device_ms.append(device.timer_end() / args.calls)
+            result[f"smooth_r{r}_k{k}"] = {"device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
+                                           "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"]}
+        # the same tile set by hand: download the changed tiles, (filter), write the stamp's box back through write_region
+        lo = [max(0, int(np.floor(corner[i] - r))) for i in range(2)]
+        hi = [min(size - 1, int(np.ceil(corner[i] + r))) for i in range(2)]
+        layers = [index[c] for c in changed]
+        region = np.zeros((hi[1] - lo[1] + 1, hi[0] - lo[0] + 1), np.uint16)
+        for c in changed:  # the box's texels as they stand, from the finest tiles' centres: the round trip leaves the terrain as it is
+            if c.lod != LOD_COUNT - 1:
+                continue
+            ox, oy = c.x * CENTER, c.y * CENTER
+            xa, xb, ya, yb = max(lo[0], ox), min(hi[0] + 1, ox + CENTER), max(lo[1], oy), min(hi[1] + 1, oy + CENTER)
+            if xa < xb and ya < yb:
+                tile = atlas.download_tile(0, index[c])
+                region[ya - lo[1]:yb - lo[1], xa - lo[0]:xb - lo[0]] = tile[BORDER + ya - oy:BORDER + yb - oy, BORDER + xa - ox:BORDER + xb - ox]
+        legs = []
+        for _ in range(args.repeats):
+            device.synchronize()
+            t0 = time.perf_counter()
+            for i in layers:
+                atlas.download_tile(0, i)
+            t1 = time.perf_counter()
+            atlas.write_region(0, region, lo[0], lo[1])
+            device.synchronize()
+            legs.append(((time.perf_counter() - t0) * 1e3, (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+        total, down, up = (round(median([leg[i] for leg in legs]), 3) for i in range(3))
+        result[f"smooth_r{r}_by_hand"] = {"download_write_region_wall_ms": total, "download_ms": down, "write_region_ms": up, "tiles": len(layers)}
 
 
 if __name__ == "__main__":
