@@ -139,8 +139,6 @@ __global__ __launch_bounds__(kWideThreads) void bounds_update_unite(UpdateArgs a
     if (w < a.level_work[level + 1u] - a.level_work[level]) unite_one(a, a.windows, level, w);
 }
 
-uint64_t align16(uint64_t v) { return (v + 15u) & ~uint64_t(15); }
-
 bool held_layer(const bt_atlas* a, const bt_tile_coordinate& c, uint32_t* layer) {  // what bt_height_bounds_build tests
     if (!a->existing_tiles.count(c)) return false;
     const auto it = a->tile_states.find(c);
@@ -149,21 +147,12 @@ bool held_layer(const bt_atlas* a, const bt_tile_coordinate& c, uint32_t* layer)
     return true;
 }
 
-}  // namespace
-
-}  // namespace bt
-
-using namespace bt;
-
-extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, uint32_t ai, const bt_tile_coordinate* tiles, uint32_t count,
-                                             bt_bounds_update_stats* stats) {
-    if (stats) *stats = bt_bounds_update_stats{};
+bt_status check_update(bt_height_bounds* b, const bt_atlas* a, uint32_t ai, const bt_tile_coordinate* tiles, uint32_t count) {
     if (!b || !a || ai >= a->attachments.size()) {
         set_error("bt_height_bounds_update: %s", !b ? "NULL table" : !a ? "NULL atlas" : "attachment index out of range");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    const Attachment& at = a->attachments[ai];
-    if (at.meta.format != BT_FORMAT_R16) {
+    if (a->attachments[ai].meta.format != BT_FORMAT_R16) {
         set_error("bt_height_bounds_update: attachment %u is not R16", ai);
         return BT_ERR_UNSUPPORTED;
     }
@@ -188,16 +177,24 @@ extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, u
             return BT_ERR_INVALID_ARGUMENT;
         }
     }
-    if (!count) return BT_OK;
+    return BT_OK;
+}
 
-    // ---- the plan
+// the host plan: index arithmetic, no HIP call
+struct UpdatePlan {
+    std::vector<uint32_t> layers;  // the held tiles of U: the layers whose own range is reduced
+    std::vector<Scatter> scatter;  // U
+    std::vector<Window> windows;   // level by level
+    uint32_t level_window[kMaxLevels + 1] = {}, level_work[kMaxLevels + 1] = {};  // UpdateArgs'
+    uint64_t total = 0;            // affected entries
+};
+
+bt_status plan_update(const bt_height_bounds* b, const bt_atlas* a, const bt_tile_coordinate* tiles, uint32_t count, UpdatePlan& plan) {
     const uint32_t levels = b->levels, sides = b->sides;
     typedef std::unordered_set<bt_tile_coordinate, CoordHash, CoordEq> TileSet;
     auto slot = [&](const bt_tile_coordinate& c) { return uint32_t(height_bounds_offset(sides, c.lod) + ((((uint64_t(c.side) << c.lod) + c.y) << c.lod) + c.x)); };
     TileSet listed, roots;
     std::vector<bt_tile_coordinate> singles;  // U and its ancestors, each once
-    std::vector<uint32_t> layers;
-    std::vector<Scatter> scatter;
     for (uint32_t i = 0; i < count; i++) {
         const bt_tile_coordinate& c = tiles[i];
         if (c.lod >= levels || !listed.insert(c).second) continue;
@@ -207,13 +204,13 @@ extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, u
                 set_error("bt_height_bounds_update: tile %u_%u_%u_%u has atlas index %u, the atlas has %u layers", c.side, c.lod, c.x, c.y, layer, a->config.atlas_size);
                 return BT_ERR_INVALID_ARGUMENT;
             }
-            scatter.push_back({slot(c), uint32_t(layers.size())});
-            layers.push_back(layer);
+            plan.scatter.push_back({slot(c), uint32_t(plan.layers.size())});
+            plan.layers.push_back(layer);
         } else {
-            scatter.push_back({slot(c), kNoSource});
+            plan.scatter.push_back({slot(c), kNoSource});
         }
     }
-    if (scatter.empty()) return BT_OK;  // every listed tile lies below the table
+    if (plan.scatter.empty()) return BT_OK;
     TileSet seen = listed;
     for (const bt_tile_coordinate& u : listed) {
         singles.push_back(u);
@@ -245,59 +242,61 @@ extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, u
         if (covered(c, false)) continue;
         for (uint32_t l = c.lod; l < levels; l++) level_windows[l].push_back({c.side | ((l - c.lod) << 8), c.x << (l - c.lod), c.y << (l - c.lod), 0u});
     }
-    UpdateArgs args{};
-    std::vector<Window> windows;
-    uint64_t total = 0;
     for (uint32_t l = 0; l < levels; l++) {
-        args.level_window[l] = uint32_t(windows.size());
-        args.level_work[l] = uint32_t(total);
+        plan.level_window[l] = uint32_t(plan.windows.size());
+        plan.level_work[l] = uint32_t(plan.total);
         uint64_t first = 0;
         for (Window w : level_windows[l]) {
             w.first = uint32_t(first);
             first += 1ull << (2u * (w.side_shift >> 8));
-            windows.push_back(w);
+            plan.windows.push_back(w);
         }
-        total += first;
+        plan.total += first;
     }
-    args.level_window[levels] = uint32_t(windows.size());
-    args.level_work[levels] = uint32_t(total);  // (distinct entries: at most b->entries < 2^24)
+    plan.level_window[levels] = uint32_t(plan.windows.size());
+    plan.level_work[levels] = uint32_t(plan.total);  // (distinct entries: at most b->entries < 2^24)
+    return BT_OK;
+}
 
-    // ---- the plan's records -> the context's ring, the reduced ranges behind them (device only)
+// the plan's records -> the context's ring, the reduced ranges behind them (device only); then the launches
+bt_status run_update(bt_height_bounds* b, const bt_atlas* a, const Attachment& at, const UpdatePlan& plan, bt_bounds_update_stats* stats) {
     bt_ctx* ctx = a->ctx;
+    HeightBoundsImpl* impl = bounds_impl(b);
     BT_HIP(hipSetDevice(ctx->device));
-    const uint64_t layers_bytes = align16(layers.size() * 4u), scatter_bytes = align16(scatter.size() * sizeof(Scatter)),
-                   windows_bytes = align16(windows.size() * sizeof(Window)), upload = layers_bytes + scatter_bytes + windows_bytes;
-    uint8_t *host = nullptr, *dev = nullptr;
-    if (bt_status s = edit_scratch(ctx, upload + layers_bytes, &host, &dev)) return s;
-    if (!layers.empty()) memcpy(host, layers.data(), layers.size() * 4u);
-    memcpy(host + layers_bytes, scatter.data(), scatter.size() * sizeof(Scatter));
-    memcpy(host + layers_bytes + scatter_bytes, windows.data(), windows.size() * sizeof(Window));
+    PlanRing ring;
+    const uint64_t layers_at = ring.add(plan.layers), scatter_at = ring.add(plan.scatter), windows_at = ring.add(plan.windows);
+    const uint64_t own_at = ring.device_only(plan.layers.size() * 4u);
+    uint8_t* dev = nullptr;
     impl->current = false;  // until everything below is queued
-    BT_HIP(hipMemcpyAsync(dev, host, upload, hipMemcpyHostToDevice, ctx->stream));
-    BT_HIP(hipEventRecord(ctx->edit_copied, ctx->stream));
+    if (bt_status s = ring.commit(ctx, &dev)) return s;
+    UpdateArgs args{};
     args.table = b->table;
     args.shadow = impl->shadow;
-    args.own = (const uint32_t*)(dev + upload);
-    args.scatter = (const Scatter*)(dev + layers_bytes);
-    args.windows = (const Window*)(dev + layers_bytes + scatter_bytes);
-    args.scatter_count = uint32_t(scatter.size());
-    args.sides = sides;
-    args.levels = levels;
+    args.own = (const uint32_t*)(dev + own_at);
+    args.scatter = (const Scatter*)(dev + scatter_at);
+    args.windows = (const Window*)(dev + windows_at);
+    args.scatter_count = uint32_t(plan.scatter.size());
+    args.sides = b->sides;
+    args.levels = b->levels;
+    memcpy(args.level_window, plan.level_window, sizeof args.level_window);
+    memcpy(args.level_work, plan.level_work, sizeof args.level_work);
 
     uint32_t launches = 0;
-    if (!layers.empty()) {  // a read of the atlas: Attachment::written stays as it is
-        if (bt_status s = launch_tile_bounds(ctx->stream, at.level0, at.meta.texture_size, (const uint32_t*)dev, uint32_t(layers.size()), 1u, false, (uint32_t*)(dev + upload))) return s;
+    if (!plan.layers.empty()) {  // a read of the atlas: Attachment::written stays as it is
+        if (bt_status s = launch_tile_bounds(ctx->stream, at.level0, at.meta.texture_size, (const uint32_t*)(dev + layers_at), uint32_t(plan.layers.size()), 1u, false,
+                                             (uint32_t*)(dev + own_at)))
+            return s;
         launches++;
     }
     auto blocks = [](uint32_t n) { return (n + kWideThreads - 1u) / kWideThreads; };
-    if (total <= kBoundsUpdateSmall) {
-        bounds_update_small<<<1, kSmallThreads, windows.size() * sizeof(Window), ctx->stream>>>(args);
+    if (plan.total <= kBoundsUpdateSmall) {
+        bounds_update_small<<<1, kSmallThreads, plan.windows.size() * sizeof(Window), ctx->stream>>>(args);
         launches++;
     } else {
         bounds_update_scatter<<<blocks(args.scatter_count), kWideThreads, 0, ctx->stream>>>(args);
-        bounds_update_fill<<<blocks(uint32_t(total)), kWideThreads, 0, ctx->stream>>>(args);
+        bounds_update_fill<<<blocks(uint32_t(plan.total)), kWideThreads, 0, ctx->stream>>>(args);
         launches += 2;
-        for (uint32_t l = levels - 1u; l-- > 0u;) {
+        for (uint32_t l = b->levels - 1u; l-- > 0u;) {
             const uint32_t work = args.level_work[l + 1u] - args.level_work[l];
             if (!work) continue;
             bounds_update_unite<<<blocks(work), kWideThreads, 0, ctx->stream>>>(args, l);
@@ -308,10 +307,27 @@ extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, u
     if (e != hipSuccess) return hip_fail(e, "bounds_update kernels");
     impl->current = true;
     if (stats) {
-        stats->tiles_listed = uint32_t(scatter.size());
-        stats->layers_reduced = uint32_t(layers.size());
+        stats->tiles_listed = uint32_t(plan.scatter.size());
+        stats->layers_reduced = uint32_t(plan.layers.size());
         stats->launches = launches;
-        stats->entries_written = total;
+        stats->entries_written = plan.total;
     }
     return BT_OK;
+}
+
+}  // namespace
+
+}  // namespace bt
+
+using namespace bt;
+
+extern "C" bt_status bt_height_bounds_update(bt_height_bounds* b, bt_atlas* a, uint32_t ai, const bt_tile_coordinate* tiles, uint32_t count,
+                                             bt_bounds_update_stats* stats) {
+    if (stats) *stats = bt_bounds_update_stats{};
+    if (bt_status s = check_update(b, a, ai, tiles, count)) return s;
+    if (!count) return BT_OK;
+    UpdatePlan plan;
+    if (bt_status s = plan_update(b, a, tiles, count, plan)) return s;
+    if (plan.scatter.empty()) return BT_OK;  // every listed tile lies below the table
+    return run_update(b, a, a->attachments[ai], plan, stats);
 }

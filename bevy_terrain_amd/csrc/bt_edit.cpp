@@ -214,13 +214,17 @@ void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std
     plan.stats.changed_count = uint32_t(plan.changed.size());
 }
 
-uint64_t align16(uint64_t v) { return (v + 15u) & ~uint64_t(15); }
-
 }  // namespace
 
-// `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read (bt_height_bounds_update shares it)
-bt_status bt::edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev) {
-    need = (need + 255u) & ~uint64_t(255);
+uint64_t bt::PlanRing::add(const void* src, uint64_t bytes) {
+    records.push_back({src, bytes, size});
+    size += (bytes + 15u) & ~uint64_t(15);
+    if (src) upload = size;
+    return records.back().at;
+}
+
+bt_status bt::PlanRing::commit(bt_ctx* ctx, uint8_t** dev) {
+    const uint64_t need = (size + 255u) & ~uint64_t(255);
     if (!ctx->edit_copied) BT_HIP(hipEventCreateWithFlags(&ctx->edit_copied, hipEventDisableTiming));
     if (need > ctx->edit_bytes) {
         if (ctx->edit_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers that go away
@@ -239,22 +243,17 @@ bt_status bt::edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t**
         BT_HIP(hipEventSynchronize(ctx->edit_copied));
         ctx->edit_used = 0;
     }
-    *host = (uint8_t*)ctx->edit_host + ctx->edit_used;
+    uint8_t* host = (uint8_t*)ctx->edit_host + ctx->edit_used;
     *dev = (uint8_t*)ctx->edit_dev + ctx->edit_used;
     ctx->edit_used += need;
+    for (const Record& r : records)
+        if (r.src && r.bytes) memcpy(host + r.at, r.src, r.bytes);
+    BT_HIP(hipMemcpyAsync(*dev, host, upload, hipMemcpyHostToDevice, ctx->stream));
+    BT_HIP(hipEventRecord(ctx->edit_copied, ctx->stream));  // what the wrap of a later call waits for
     return BT_OK;
 }
 
 namespace {
-
-struct RegionSource {
-    const void* dev;
-    uint32_t rx0, ry0, width;
-};
-struct SmoothSource {
-    const bt_smooth_stamp* stamps;
-    uint32_t kernel_radius;
-};
 
 // the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height
 bt_status region_scratch(bt_ctx* ctx, uint64_t bytes) {
@@ -268,60 +267,102 @@ bt_status region_scratch(bt_ctx* ctx, uint64_t bytes) {
     return BT_OK;
 }
 
-// uploads the plan and enqueues its launches; the first step is the brush (stamps), the region copy (region) or the smoothing pair (smooth:
-// its stamps; `stamps` is NULL then)
-bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* stamps, uint32_t stamp_count, const RegionSource* region,
-                   const SmoothSource* smooth = nullptr) {
+// The first step of a plan, the one that writes the rectangles of the edited tiles (the steps after it are the same for every call): the
+// brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps.  prepare() runs once the plan is known
+// to write something: it adds what the step wants in the ring and readies its device buffer; launch() follows the ring's commit.
+struct FirstStep {
+    enum Kind { kBrush, kRegion, kSmooth } kind;
+    // brush: bt_edit_stamp[count]; smooth: bt_smooth_stamp[count] and the box's kernel_radius
+    const void* stamps = nullptr;
+    uint32_t count = 0, kernel_radius = 0;
+    // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart; copied: the events of the staging
+    // buffers, for bt_atlas_write_region to wait on
+    const void* texels = nullptr;
+    uint64_t row_pitch = 0;
+    uint32_t x0 = 0, y0 = 0, width = 0, height = 0;
+    hipEvent_t copied[bt_ctx::kStagingBuffers] = {};
+    // prepare() -> launch()
+    std::vector<uint64_t> offsets;  // smooth: where each item's rectangle starts in the scratch, in dwords
+    uint64_t stamps_at = 0, offsets_at = 0;
+
+    uint32_t launches() const { return kind == kSmooth ? 2u : 1u; }
+    bt_status prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::vector<EditItem>& items, PlanRing& ring);
+    bt_status stage_region(bt_ctx* ctx, uint64_t row_bytes);
+    bt_status launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ring, const EditItem* items, uint32_t n, uint32_t max_rows) const;
+};
+
+bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::vector<EditItem>& items, PlanRing& ring) {
+    switch (kind) {
+        case kBrush: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_edit_stamp)); return BT_OK;
+        case kRegion: return stage_region(ctx, uint64_t(width) * m.pixel_size);
+        case kSmooth: {
+            uint64_t scratch_dwords = 0;
+            for (const EditItem& it : items) {
+                offsets.push_back(scratch_dwords);
+                scratch_dwords += smooth_item_dwords(it, m.border_size);
+            }
+            if (bt_status s = region_scratch(ctx, scratch_dwords * sizeof(uint32_t))) return s;
+            stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_smooth_stamp));
+            offsets_at = ring.add(offsets);
+            return BT_OK;
+        }
+    }
+    return BT_OK;
+}
+
+// the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
+bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
+    const uint64_t total = row_bytes * height;
+    if (bt_status s = region_scratch(ctx, total)) return s;
+    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
+        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
+    uint32_t chunk = 0;
+    for (uint32_t row = 0; row < height; row += chunk_rows, chunk++) {
+        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
+        hipError_t e = copied[k] ? hipEventSynchronize(copied[k]) : hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
+        for (uint32_t r = 0; r < rows && e == hipSuccess; r++)
+            memcpy((uint8_t*)ctx->staging[k] + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region_dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(copied[k], ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "bt_atlas_write_region staging");
+    }
+    return BT_OK;
+}
+
+bt_status FirstStep::launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ring, const EditItem* items, uint32_t n, uint32_t max_rows) const {
+    switch (kind) {
+        case kBrush: return launch_edit_brush(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_edit_stamp*)(ring + stamps_at), count);
+        case kRegion: return launch_edit_region(ctx->stream, at.meta, at.level0, items, n, max_rows, ctx->edit_region_dev, x0, y0, width);
+        case kSmooth:
+            return launch_edit_smooth(ctx->stream, at.meta, at.level0, items, (const uint64_t*)(ring + offsets_at), n, max_rows, (const bt_smooth_stamp*)(ring + stamps_at), count,
+                                      kernel_radius, ctx->edit_region_dev);
+    }
+    return BT_OK;
+}
+
+// uploads the plan and enqueues its launches
+bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, FirstStep& first) {
     Attachment& at = a->attachments[ai];
     bt_ctx* ctx = a->ctx;
     if (plan.levels.empty()) return BT_OK;
-    const uint64_t stamp_bytes = uint64_t(stamp_count) * (smooth ? sizeof(bt_smooth_stamp) : sizeof(bt_edit_stamp));
-    std::vector<uint64_t> offsets;  // smooth: where each item's rectangle starts in the scratch, in dwords
-    uint64_t scratch_dwords = 0;
-    if (smooth) {
-        for (const EditItem& it : plan.levels[0]) {
-            offsets.push_back(scratch_dwords);
-            scratch_dwords += smooth_item_dwords(it, at.meta.border_size);
-        }
-        if (bt_status s = region_scratch(ctx, scratch_dwords * sizeof(uint32_t))) return s;
-    }
-    uint64_t bytes = align16(stamp_bytes) + align16(offsets.size() * sizeof(uint64_t)) + align16(plan.stitches.size() * sizeof(TaskDev));
-    for (const auto& items : plan.levels) bytes += align16(items.size() * sizeof(EditItem));
-    uint8_t *host = nullptr, *dev = nullptr;
-    if (bt_status s = edit_scratch(ctx, bytes, &host, &dev)) return s;
-    uint64_t off = 0;
-    auto put = [&](const void* src, uint64_t n) {
-        if (n) memcpy(host + off, src, n);
-        const uint8_t* where = dev + off;
-        off += align16(n);
-        return where;
-    };
-    const uint8_t* stamps_dev = put(smooth ? (const void*)smooth->stamps : (const void*)stamps, stamp_bytes);
-    const uint64_t* offsets_dev = (const uint64_t*)put(offsets.data(), offsets.size() * sizeof(uint64_t));
-    std::vector<const EditItem*> items_dev;
-    for (const auto& items : plan.levels) items_dev.push_back((const EditItem*)put(items.data(), items.size() * sizeof(EditItem)));
-    const TaskDev* stitches_dev = (const TaskDev*)put(plan.stitches.data(), plan.stitches.size() * sizeof(TaskDev));
-    BT_HIP(hipMemcpyAsync(dev, host, off, hipMemcpyHostToDevice, ctx->stream));
-    BT_HIP(hipEventRecord(ctx->edit_copied, ctx->stream));
+    PlanRing ring;
+    if (bt_status s = first.prepare(ctx, at.meta, plan.levels[0], ring)) return s;
+    std::vector<uint64_t> items_at;
+    for (const auto& items : plan.levels) items_at.push_back(ring.add(items));
+    const uint64_t stitches_at = ring.add(plan.stitches);
+    uint8_t* dev = nullptr;
+    if (bt_status s = ring.commit(ctx, &dev)) return s;
 
     for (const auto& [coord, layer] : plan.changed) at.mark_written(layer, 1);
-    const uint32_t n0 = uint32_t(plan.levels[0].size());
-    if (region) {
-        if (bt_status s = launch_edit_region(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], region->dev, region->rx0, region->ry0, region->width)) return s;
-    } else if (smooth) {
-        if (bt_status s = launch_edit_smooth(ctx->stream, at.meta, at.level0, items_dev[0], offsets_dev, n0, plan.max_rows[0], (const bt_smooth_stamp*)stamps_dev,
-                                             stamp_count, smooth->kernel_radius, ctx->edit_region_dev))
-            return s;
-    } else {
-        if (bt_status s = launch_edit_brush(ctx->stream, at.meta, at.level0, items_dev[0], n0, plan.max_rows[0], (const bt_edit_stamp*)stamps_dev, stamp_count)) return s;
-    }
-    plan.stats.launches = smooth ? 2 : 1;
+    if (bt_status s = first.launch(ctx, at, dev, (const EditItem*)(dev + items_at[0]), uint32_t(plan.levels[0].size()), plan.max_rows[0])) return s;
+    plan.stats.launches = first.launches();
     for (size_t k = 1; k < plan.levels.size(); k++) {
-        if (bt_status s = launch_edit_downsample(ctx->stream, at.meta, at.level0, items_dev[k], uint32_t(plan.levels[k].size()), plan.max_rows[k])) return s;
+        if (bt_status s = launch_edit_downsample(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at[k]), uint32_t(plan.levels[k].size()), plan.max_rows[k])) return s;
         plan.stats.launches++;
     }
     if (!plan.stitches.empty()) {
-        if (bt_status s = launch_stitch(ctx, at.meta, at.level0, stitches_dev, uint32_t(plan.stitches.size()))) return s;
+        if (bt_status s = launch_stitch(ctx, at.meta, at.level0, (const TaskDev*)(dev + stitches_at), uint32_t(plan.stitches.size()))) return s;
         plan.stats.launches++;
     }
     if (at.mips.size() > 1) {  // the existing mip kernels, one pass per run of consecutive layers
@@ -341,9 +382,17 @@ bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, const bt_edit_stamp* st
     return BT_OK;
 }
 
-void report(const Plan& plan, bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
+// what the three entry points do once their arguments have passed: boxes of mosaic texels of `lod` -> the plan -> its launches -> the report
+bt_status edit_boxes(bt_atlas* a, uint32_t ai, uint32_t lod, const std::vector<Box>& boxes, FirstStep& first, bt_tile_coordinate* changed, uint32_t changed_cap,
+                     bt_edit_stats* stats) {
+    const hipError_t e = hipSetDevice(a->ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    Plan plan;
+    build_plan(a, a->attachments[ai], lod, boxes, plan);
+    const bt_status rc = run_plan(a, ai, plan, first);
     for (uint32_t i = 0; i < plan.changed.size() && i < changed_cap; i++) changed[i] = plan.changed[i].first;
     if (stats) *stats = plan.stats;
+    return rc;
 }
 
 // what both edit calls check of the atlas: attachment, LOD, format and centre size
@@ -372,16 +421,79 @@ bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, bool brush,
     return BT_OK;
 }
 
-// a stamp's box (the header's BRUSH section), clipped to the face; nothing is added where it misses the face
-void add_stamp_box(std::vector<Box>& boxes, const Attachment& at, uint32_t lod, uint32_t side, const float center[2], float radius) {
-    const double size = double(uint64_t(at.meta.center_size) << lod);
-    double lo[2], hi[2];
-    for (int k = 0; k < 2; k++) {
-        lo[k] = std::max(0.0, std::floor(double(center[k]) - double(radius)));
-        hi[k] = std::min(size - 1.0, std::ceil(double(center[k]) + double(radius)));
-        if (lo[k] > hi[k]) return;
+// the fields of a stamp that only its own call has, in the place the call reports them: before_falloff or after the radius
+const char* bad_own(const bt_edit_stamp& s, bool before_falloff) {
+    if (before_falloff) return s.mode != BT_EDIT_ADD && s.mode != BT_EDIT_FLATTEN ? "mode" : nullptr;
+    return !std::isfinite(s.amount) ? "amount (not finite)" : nullptr;
+}
+const char* bad_own(const bt_smooth_stamp& s, bool before_falloff) {
+    if (before_falloff) return nullptr;
+    return !std::isfinite(s.strength) || !(s.strength > 0.0f) || !(s.strength <= 1.0f) ? "strength (finite, in (0, 1])" : nullptr;
+}
+
+// the first defect of a stamp that can be told without the atlas, in the order the calls report them
+template <typename Stamp>
+const char* bad_stamp(const Stamp& s) {
+    if (s.side >= 6u) return "side";
+    if (const char* bad = bad_own(s, true)) return bad;
+    if (s.falloff != BT_EDIT_FALLOFF_SMOOTH && s.falloff != BT_EDIT_FALLOFF_HARD) return "falloff";
+    if (!std::isfinite(s.center[0]) || !std::isfinite(s.center[1])) return "center (not finite)";
+    if (!std::isfinite(s.radius) || !(s.radius > 0.0f)) return "radius (finite and > 0)";
+    return bad_own(s, false);
+}
+
+// What bt_atlas_edit_height and bt_atlas_smooth_height (`what`) check alike, in the order they report it.  The stamps first: what can be
+// refused without the atlas is refused without it.  own(false) / own(true): the caller's checks of its other arguments that go before the
+// stamps are looked at / once the target has passed.
+template <typename Stamp, typename Own>
+bt_status check_stamps(const char* what, const bt_atlas* a, uint32_t ai, uint32_t lod, const Stamp* stamps, uint32_t count, const bt_tile_coordinate* changed,
+                       uint32_t changed_cap, Own own) {
+    if (count > BT_EDIT_MAX_STAMPS) {
+        set_error("%s: %u stamps, at most %u per call", what, count, BT_EDIT_MAX_STAMPS);
+        return BT_ERR_INVALID_ARGUMENT;
     }
-    boxes.push_back({side, {uint32_t(lo[0]), uint32_t(lo[1]), uint32_t(hi[0]), uint32_t(hi[1])}});
+    if (bt_status s = own(false)) return s;
+    if ((count && !stamps) || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", what, count && !stamps ? "stamps" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++)
+        if (const char* bad = bad_stamp(stamps[i])) {
+            set_error("%s: stamp %u: %s", what, i, bad);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (!a) {
+        set_error("%s: NULL atlas", what);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_target(a, ai, lod, true, what)) return s;
+    if (bt_status s = own(true)) return s;
+    const uint32_t sides = a->config.spherical ? 6u : 1u;
+    for (uint32_t i = 0; i < count; i++)
+        if (stamps[i].side >= sides) {
+            set_error("%s: stamp %u: side %u of %u", what, i, stamps[i].side, sides);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    return BT_OK;
+}
+
+// The stamps' boxes.  A stamp's box is [floor(center - radius), ceil(center + radius)], clipped to the face (nothing is added where it
+// misses the face): a texel outside it is at least radius + 1 away on one axis, and rounding is monotonic, so its d2 is not below r2 in
+// binary32 either.
+template <typename Stamp>
+std::vector<Box> stamp_boxes(const bt_atlas* a, uint32_t ai, uint32_t lod, const Stamp* stamps, uint32_t count) {
+    const double size = double(uint64_t(a->attachments[ai].meta.center_size) << lod);
+    std::vector<Box> boxes;
+    for (uint32_t i = 0; i < count; i++) {
+        const Stamp& s = stamps[i];
+        double lo[2], hi[2];
+        for (int k = 0; k < 2; k++) {
+            lo[k] = std::max(0.0, std::floor(double(s.center[k]) - double(s.radius)));
+            hi[k] = std::min(size - 1.0, std::ceil(double(s.center[k]) + double(s.radius)));
+        }
+        if (lo[0] <= hi[0] && lo[1] <= hi[1]) boxes.push_back({s.side, {uint32_t(lo[0]), uint32_t(lo[1]), uint32_t(hi[0]), uint32_t(hi[1])}});
+    }
+    return boxes;
 }
 
 }  // namespace
@@ -391,111 +503,32 @@ extern "C" {
 bt_status bt_atlas_edit_height(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_edit_stamp* stamps, uint32_t count, bt_tile_coordinate* changed,
                                uint32_t changed_cap, bt_edit_stats* stats) {
     if (stats) *stats = bt_edit_stats{};
-    // the stamps first: what can be refused without the atlas is refused without it
-    if (count > BT_EDIT_MAX_STAMPS) {
-        set_error("bt_atlas_edit_height: %u stamps, at most %u per call", count, BT_EDIT_MAX_STAMPS);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if ((count && !stamps) || (changed_cap && !changed)) {
-        set_error("bt_atlas_edit_height: NULL %s", count && !stamps ? "stamps" : "changed with changed_cap > 0");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    for (uint32_t i = 0; i < count; i++) {
-        const bt_edit_stamp& s = stamps[i];
-        const char* bad = nullptr;
-        if (s.side >= 6u) bad = "side";
-        else if (s.mode != BT_EDIT_ADD && s.mode != BT_EDIT_FLATTEN) bad = "mode";
-        else if (s.falloff != BT_EDIT_FALLOFF_SMOOTH && s.falloff != BT_EDIT_FALLOFF_HARD) bad = "falloff";
-        else if (!std::isfinite(s.center[0]) || !std::isfinite(s.center[1])) bad = "center (not finite)";
-        else if (!std::isfinite(s.radius) || !(s.radius > 0.0f)) bad = "radius (finite and > 0)";
-        else if (!std::isfinite(s.amount)) bad = "amount (not finite)";
-        if (bad) {
-            set_error("bt_atlas_edit_height: stamp %u: %s", i, bad);
-            return BT_ERR_INVALID_ARGUMENT;
-        }
-    }
-    if (!a) {
-        set_error("bt_atlas_edit_height: NULL atlas");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (bt_status s = check_target(a, ai, lod, true, "bt_atlas_edit_height")) return s;
-    const uint32_t sides = a->config.spherical ? 6u : 1u;
-    for (uint32_t i = 0; i < count; i++)
-        if (stamps[i].side >= sides) {
-            set_error("bt_atlas_edit_height: stamp %u: side %u of %u", i, stamps[i].side, sides);
-            return BT_ERR_INVALID_ARGUMENT;
-        }
+    if (bt_status s = check_stamps("bt_atlas_edit_height", a, ai, lod, stamps, count, changed, changed_cap, [](bool) { return BT_OK; })) return s;
     if (!count) return BT_OK;
-    const Attachment& at = a->attachments[ai];
-    // a stamp's box [floor(center - radius), ceil(center + radius)], clipped to the face: a texel outside it is at least radius + 1 away on
-    // one axis, and rounding is monotonic, so its d2 is not below r2 in binary32 either
-    std::vector<Box> boxes;
-    for (uint32_t i = 0; i < count; i++) add_stamp_box(boxes, at, lod, stamps[i].side, stamps[i].center, stamps[i].radius);
-    hipError_t e = hipSetDevice(a->ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    Plan plan;
-    build_plan(a, at, lod, boxes, plan);
-    const bt_status rc = run_plan(a, ai, plan, stamps, count, nullptr);
-    report(plan, changed, changed_cap, stats);
-    return rc;
+    FirstStep first{FirstStep::kBrush};
+    first.stamps = stamps, first.count = count;
+    return edit_boxes(a, ai, lod, stamp_boxes(a, ai, lod, stamps, count), first, changed, changed_cap, stats);
 }
 
 bt_status bt_atlas_smooth_height(bt_atlas* a, uint32_t ai, uint32_t lod, uint32_t kernel_radius, const bt_smooth_stamp* stamps, uint32_t count,
                                  bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
     if (stats) *stats = bt_edit_stats{};
-    // as bt_atlas_edit_height: what can be refused without the atlas is refused without it
-    if (count > BT_EDIT_MAX_STAMPS) {
-        set_error("bt_atlas_smooth_height: %u stamps, at most %u per call", count, BT_EDIT_MAX_STAMPS);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (kernel_radius == 0u || kernel_radius > BT_SMOOTH_MAX_KERNEL) {
-        set_error("bt_atlas_smooth_height: kernel_radius %u (1 .. %u)", kernel_radius, BT_SMOOTH_MAX_KERNEL);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if ((count && !stamps) || (changed_cap && !changed)) {
-        set_error("bt_atlas_smooth_height: NULL %s", count && !stamps ? "stamps" : "changed with changed_cap > 0");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    for (uint32_t i = 0; i < count; i++) {
-        const bt_smooth_stamp& s = stamps[i];
-        const char* bad = nullptr;
-        if (s.side >= 6u) bad = "side";
-        else if (s.falloff != BT_EDIT_FALLOFF_SMOOTH && s.falloff != BT_EDIT_FALLOFF_HARD) bad = "falloff";
-        else if (!std::isfinite(s.center[0]) || !std::isfinite(s.center[1])) bad = "center (not finite)";
-        else if (!std::isfinite(s.radius) || !(s.radius > 0.0f)) bad = "radius (finite and > 0)";
-        else if (!std::isfinite(s.strength) || !(s.strength > 0.0f) || !(s.strength <= 1.0f)) bad = "strength (finite, in (0, 1])";
-        if (bad) {
-            set_error("bt_atlas_smooth_height: stamp %u: %s", i, bad);
+    auto check_kernel = [&](bool with_target) {
+        if (!with_target && (kernel_radius == 0u || kernel_radius > BT_SMOOTH_MAX_KERNEL)) {
+            set_error("bt_atlas_smooth_height: kernel_radius %u (1 .. %u)", kernel_radius, BT_SMOOTH_MAX_KERNEL);
             return BT_ERR_INVALID_ARGUMENT;
         }
-    }
-    if (!a) {
-        set_error("bt_atlas_smooth_height: NULL atlas");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (bt_status s = check_target(a, ai, lod, true, "bt_atlas_smooth_height")) return s;
-    const Attachment& at = a->attachments[ai];
-    if (kernel_radius > at.meta.border_size) {
-        set_error("bt_atlas_smooth_height: kernel_radius %u beyond border_size %u: the box would leave the tile's layer", kernel_radius, at.meta.border_size);
-        return BT_ERR_UNSUPPORTED;
-    }
-    const uint32_t sides = a->config.spherical ? 6u : 1u;
-    for (uint32_t i = 0; i < count; i++)
-        if (stamps[i].side >= sides) {
-            set_error("bt_atlas_smooth_height: stamp %u: side %u of %u", i, stamps[i].side, sides);
-            return BT_ERR_INVALID_ARGUMENT;
+        if (with_target && kernel_radius > a->attachments[ai].meta.border_size) {
+            set_error("bt_atlas_smooth_height: kernel_radius %u beyond border_size %u: the box would leave the tile's layer", kernel_radius, a->attachments[ai].meta.border_size);
+            return BT_ERR_UNSUPPORTED;
         }
+        return BT_OK;
+    };
+    if (bt_status s = check_stamps("bt_atlas_smooth_height", a, ai, lod, stamps, count, changed, changed_cap, check_kernel)) return s;
     if (!count) return BT_OK;
-    std::vector<Box> boxes;
-    for (uint32_t i = 0; i < count; i++) add_stamp_box(boxes, at, lod, stamps[i].side, stamps[i].center, stamps[i].radius);
-    hipError_t e = hipSetDevice(a->ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    Plan plan;
-    build_plan(a, at, lod, boxes, plan);
-    const SmoothSource smooth = {stamps, kernel_radius};
-    const bt_status rc = run_plan(a, ai, plan, nullptr, count, nullptr, &smooth);
-    report(plan, changed, changed_cap, stats);
-    return rc;
+    FirstStep first{FirstStep::kSmooth};
+    first.stamps = stamps, first.count = count, first.kernel_radius = kernel_radius;
+    return edit_boxes(a, ai, lod, stamp_boxes(a, ai, lod, stamps, count), first, changed, changed_cap, stats);
 }
 
 bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
@@ -514,7 +547,7 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
         set_error("bt_atlas_write_region: side %u", side);
         return BT_ERR_INVALID_ARGUMENT;
     }
-    Attachment& at = a->attachments[ai];
+    const Attachment& at = a->attachments[ai];
     const uint64_t size = uint64_t(at.meta.center_size) << lod;
     if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
         set_error("bt_atlas_write_region: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", x0, x0 + width, y0, y0 + height, (unsigned long long)size);
@@ -527,43 +560,16 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
         set_error("bt_atlas_write_region: %s", !texels ? "NULL texels_host" : "row_pitch smaller than a row");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    bt_ctx* ctx = a->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    Plan plan;
-    build_plan(a, at, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, plan);
-    if (plan.levels.empty()) {  // the rectangle meets no tile the atlas holds
-        report(plan, changed, changed_cap, stats);
-        return BT_OK;
-    }
-    // the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
-    const uint64_t total = row_bytes * height;
-    if (bt_status s = region_scratch(ctx, total)) return s;
-    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
-        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
-    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
-    hipEvent_t copied[bt_ctx::kStagingBuffers] = {};
-    bt_status rc = BT_OK;
-    uint32_t chunk = 0;
-    for (uint32_t row = 0; row < height && rc == BT_OK; row += chunk_rows, chunk++) {
-        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
-        hipError_t e = copied[k] ? hipEventSynchronize(copied[k]) : hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
-        for (uint32_t r = 0; r < rows && e == hipSuccess; r++)
-            memcpy((uint8_t*)ctx->staging[k] + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region_dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(copied[k], ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "bt_atlas_write_region staging");
-    }
-    if (rc == BT_OK) {
-        const RegionSource src = {ctx->edit_region_dev, x0, y0, width};
-        rc = run_plan(a, ai, plan, nullptr, 0, &src);
-    }
-    for (hipEvent_t ev : copied)  // the staging buffers are free again once the copies have run: the one wait of this call
+    FirstStep first{FirstStep::kRegion};
+    first.texels = texels, first.row_pitch = row_pitch;
+    first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
+    bt_status rc = edit_boxes(a, ai, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, stats);
+    for (hipEvent_t ev : first.copied)  // the staging buffers are free again once the copies have run: the one wait of this call
         if (ev) {
             const hipError_t e = hipEventSynchronize(ev);
             if (e != hipSuccess && rc == BT_OK) rc = hip_fail(e, "bt_atlas_write_region staging");
             hipEventDestroy(ev);
         }
-    report(plan, changed, changed_cap, stats);
     return rc;
 }
 

@@ -3,9 +3,7 @@
 // An item is ONE tile's dirty rectangle of one launch: (layer, inclusive rectangle in centre texels, mosaic origin of the tile's centre).
 // grid = (items, row blocks of the tallest rectangle); a workgroup of four waves takes kEditRows rows of its item, a wave one row at a
 // time, lanes along x: a row is one coalesced run of dwords.
-//   R16: a lane owns one ALIGNED 32-bit pair of texels (T is even: an odd centre size is refused, so rows start on a dword).  At an odd
-//   rectangle edge half of the pair lies outside the rectangle (another centre texel, or an apron texel): the lane writes that half back
-//   from its own read.  Items of a launch are different layers and rows are different dwords, so no two lanes touch the same dword.
+//   R16: a lane owns one ALIGNED 32-bit pair of texels; the rule is stated, and carried out, at for_each_pair.
 //   Rgba8: a lane owns one texel.
 //
 // edit_brush_kernel   the stamps of bt_atlas_edit_height on the texels of the rectangle; the stamp array is indexed by the loop counter
@@ -31,18 +29,27 @@ namespace {
 constexpr uint32_t kEditThreads = 256;
 constexpr uint32_t kEditRows = 16;  // rows of a rectangle per workgroup: four per wave
 
-// t -> t' of one stamp that has passed the side test (the header's BRUSH section, line by line)
-__device__ __forceinline__ uint32_t stamp_texel(const bt_edit_stamp& s, float r2, float fx, float fy, uint32_t t) {
+// the disc test and the falloff weight of a stamp (bt_edit_stamp or bt_smooth_stamp) at texel (fx, fy), the header's BRUSH section line
+// by line: false outside the disc, else w
+template <typename Stamp>
+__device__ __forceinline__ bool stamp_weight(const Stamp& s, float r2, float fx, float fy, float& w) {
     const float dx = fx - s.center[0];
     const float dy = fy - s.center[1];
     const float d2 = (dx * dx) + (dy * dy);
-    if (!(d2 < r2) || t == 0u) return t;
-    float w = 1.0f;
+    if (!(d2 < r2)) return false;
+    w = 1.0f;
     if (s.falloff == BT_EDIT_FALLOFF_SMOOTH) {
         const float q = d2 / r2;
         const float sm = 1.0f - q;
         w = sm * sm;
     }
+    return true;
+}
+
+// t -> t' of one stamp that has passed the side test
+__device__ __forceinline__ uint32_t stamp_texel(const bt_edit_stamp& s, float r2, float fx, float fy, uint32_t t) {
+    float w;
+    if (!stamp_weight(s, r2, fx, fy, w) || t == 0u) return t;
     const float h = unorm16_to_float(t);  // == f32(t) / 65535 for every t (bt_selftest)
     const float hn = s.mode == BT_EDIT_FLATTEN ? h + (s.amount - h) * w : h + s.amount * w;
     return max(1u, float_to_unorm(hn, 65535.0f));
@@ -60,17 +67,33 @@ __device__ __forceinline__ void for_each_dword(const EditItem& it, uint32_t firs
         for (uint32_t p = first + lane; p <= last; p += 64u) body(y, p);
 }
 
-__global__ __launch_bounds__(kEditThreads) void edit_brush_kernel(AttachmentMeta m, uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
-                                                                  const bt_edit_stamp* __restrict__ stamps, uint32_t stamp_count) {
-    const EditItem it = items[blockIdx.x];
+__device__ __forceinline__ uint32_t pair_of(uint32_t t0, uint32_t t1) { return t0 | (t1 << 16); }
+
+// R16: a lane owns one ALIGNED 32-bit pair of texels, (px, px + 1) with px = 2p a column of the layer (T is even: an odd centre size is
+// refused, so rows start on a dword).  At an odd rectangle edge half of the pair lies outside the rectangle (another centre texel, or an
+// apron texel): the lane writes that half back from its own read; the read is skipped when both halves are inside, unless the body wants
+// the old texels (kAlwaysRead).  Items of a launch are different layers and rows are different dwords, so no two lanes touch the same
+// dword.  body(y, p, px, in0, in1, old) returns the fresh pair; what it puts in a half that is outside (in0 / in1 false) is dropped.
+template <bool kAlwaysRead, typename Body>
+__device__ __forceinline__ void for_each_pair(const AttachmentMeta& m, uint16_t* atlas, const EditItem& it, Body body) {
     const uint32_t Tsz = m.texture_size, b = m.border_size;
     uint32_t* tile = reinterpret_cast<uint32_t*>(atlas + uint64_t(it.layer) * Tsz * Tsz);
     const uint32_t px0 = b + it.x0, px1 = b + it.x1;
     for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
         uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
-        const uint32_t old = *dst;
         const uint32_t px = 2u * p;
         const bool in0 = px >= px0, in1 = px + 1u <= px1;  // (px <= px1 and px + 1 >= px0 hold for every dword of the range)
+        const uint32_t old = (kAlwaysRead || !(in0 && in1)) ? *dst : 0u;
+        const uint32_t fresh = body(y, p, px, in0, in1, old);
+        *dst = pair_of(in0 ? (fresh & 0xFFFFu) : (old & 0xFFFFu), in1 ? (fresh >> 16) : (old >> 16));
+    });
+}
+
+__global__ __launch_bounds__(kEditThreads) void edit_brush_kernel(AttachmentMeta m, uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
+                                                                  const bt_edit_stamp* __restrict__ stamps, uint32_t stamp_count) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t b = m.border_size;
+    for_each_pair<true>(m, atlas, it, [&](uint32_t y, uint32_t, uint32_t px, bool in0, bool in1, uint32_t old) {
         uint32_t t0 = old & 0xFFFFu, t1 = old >> 16;
         const float fy = float(it.gy0 + y);
         const float fx0 = float(it.gx0 + px - b), fx1 = float(it.gx0 + px + 1u - b);  // (the half outside the rectangle is not used)
@@ -81,7 +104,7 @@ __global__ __launch_bounds__(kEditThreads) void edit_brush_kernel(AttachmentMeta
             if (in0) t0 = stamp_texel(s, r2, fx0, fy, t0);
             if (in1) t1 = stamp_texel(s, r2, fx1, fy, t1);
         }
-        *dst = t0 | (t1 << 16);
+        return pair_of(t0, t1);
     });
 }
 
@@ -90,22 +113,15 @@ __global__ __launch_bounds__(kEditThreads) void edit_region_kernel(AttachmentMet
                                                                    const void* __restrict__ src_, uint32_t rx0, uint32_t ry0, uint32_t src_width) {
     const EditItem it = items[blockIdx.x];
     const uint32_t Tsz = m.texture_size, b = m.border_size;
-    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
     if constexpr (FORMAT == BT_FORMAT_R16) {
-        uint32_t* tile = reinterpret_cast<uint32_t*>((uint16_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz);
         const uint16_t* src = (const uint16_t*)src_;
-        for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
-            uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
-            const uint32_t old = *dst;
-            const uint32_t px = 2u * p;
-            const bool in0 = px >= px0, in1 = px + 1u <= px1;
+        for_each_pair<false>(m, (uint16_t*)atlas_, it, [&](uint32_t y, uint32_t, uint32_t px, bool in0, bool in1, uint32_t) {
             const uint16_t* row = src + uint64_t(it.gy0 + y - ry0) * src_width;
             // (the column of the half outside the rectangle may lie outside the staged rows: it is not read)
-            const uint32_t t0 = in0 ? uint32_t(row[it.gx0 + px - b - rx0]) : (old & 0xFFFFu);
-            const uint32_t t1 = in1 ? uint32_t(row[it.gx0 + px + 1u - b - rx0]) : (old >> 16);
-            *dst = t0 | (t1 << 16);
+            return pair_of(in0 ? uint32_t(row[it.gx0 + px - b - rx0]) : 0u, in1 ? uint32_t(row[it.gx0 + px + 1u - b - rx0]) : 0u);
         });
     } else {
+        const uint32_t px0 = b + it.x0, px1 = b + it.x1;
         uint32_t* tile = (uint32_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz;
         const uint32_t* src = (const uint32_t*)src_;
         for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) {
@@ -145,17 +161,8 @@ __device__ __forceinline__ uint32_t smooth_texel(const bt_smooth_stamp* __restri
     for (uint32_t k = 0; k < stamp_count; k++) {
         const bt_smooth_stamp s = stamps[k];
         if (s.side != side) continue;
-        const float r2 = s.radius * s.radius;
-        const float dx = fx - s.center[0];
-        const float dy = fy - s.center[1];
-        const float d2 = (dx * dx) + (dy * dy);
-        if (!(d2 < r2)) continue;
-        float w = 1.0f;
-        if (s.falloff == BT_EDIT_FALLOFF_SMOOTH) {
-            const float q = d2 / r2;
-            const float sm = 1.0f - q;
-            w = sm * sm;
-        }
+        float w;
+        if (!stamp_weight(s, s.radius * s.radius, fx, fy, w)) continue;
         const float a = s.strength * w;
         const float h = unorm16_to_float(t);
         const float hn = h + (mean - h) * a;
@@ -231,22 +238,13 @@ __global__ __launch_bounds__(kEditThreads) void edit_smooth_kernel(AttachmentMet
     }
 }
 
-// scratch -> layers: edit_region_kernel<R16>'s ownership of dwords, the source being item-relative
+// scratch -> layers, the source being item-relative
 __global__ __launch_bounds__(kEditThreads) void edit_smooth_copy_kernel(AttachmentMeta m, uint16_t* __restrict__ atlas, const EditItem* __restrict__ items,
                                                                         const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ scratch) {
     const EditItem it = items[blockIdx.x];
-    const uint32_t Tsz = m.texture_size, b = m.border_size;
-    uint32_t* tile = reinterpret_cast<uint32_t*>(atlas + uint64_t(it.layer) * Tsz * Tsz);
-    const uint32_t px0 = b + it.x0, px1 = b + it.x1, first = px0 >> 1, width = (px1 >> 1) - first + 1u;
+    const uint32_t b = m.border_size, first = (b + it.x0) >> 1, width = ((b + it.x1) >> 1) - first + 1u;
     const uint32_t* src = scratch + offsets[blockIdx.x];
-    for_each_dword(it, first, px1 >> 1, [&](uint32_t y, uint32_t p) {
-        uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
-        const uint32_t px = 2u * p;
-        const bool in0 = px >= px0, in1 = px + 1u <= px1;
-        const uint32_t fresh = src[uint64_t(y - it.y0) * width + (p - first)];
-        const uint32_t old = (in0 && in1) ? 0u : *dst;
-        *dst = (in0 ? (fresh & 0xFFFFu) : (old & 0xFFFFu)) | ((in1 ? (fresh >> 16) : (old >> 16)) << 16);
-    });
+    for_each_pair<false>(m, atlas, it, [&](uint32_t y, uint32_t p, uint32_t, bool, bool, uint32_t) { return src[uint64_t(y - it.y0) * width + (p - first)]; });
 }
 
 // centre texel (tx, ty) of a parent: the child it lies in and the 2x2 block of that child's centre (downsample_kernel's mapping).  The child
@@ -270,20 +268,13 @@ __global__ __launch_bounds__(kEditThreads) void edit_downsample_kernel(Attachmen
     const uint32_t Tsz = m.texture_size, b = m.border_size;
     T* base = (T*)atlas_;
     const EditChildren ch = {it.child[0], it.child[1], it.child[2], it.child[3]};
-    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
     if constexpr (FORMAT == BT_FORMAT_R16) {
-        uint32_t* tile = reinterpret_cast<uint32_t*>(base + uint64_t(it.layer) * Tsz * Tsz);
-        for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
-            uint32_t* dst = tile + (uint64_t(b + y) * Tsz) / 2u + p;
-            const uint32_t px = 2u * p;
-            const bool in0 = px >= px0, in1 = px + 1u <= px1;
-            // (the half of a dword outside the rectangle: its texel is computed from a clamped column and dropped, the parent's value kept)
-            const uint32_t t0 = parent_texel<FORMAT>(m, base, ch, in0 ? px - b : it.x0, y);
-            const uint32_t t1 = parent_texel<FORMAT>(m, base, ch, in1 ? px + 1u - b : it.x1, y);
-            const uint32_t old = (in0 && in1) ? 0u : *dst;
-            *dst = (in0 ? t0 : (old & 0xFFFFu)) | ((in1 ? t1 : (old >> 16)) << 16);
+        for_each_pair<false>(m, base, it, [&](uint32_t y, uint32_t, uint32_t px, bool in0, bool in1, uint32_t) {
+            // (the half of a dword outside the rectangle: its texel is computed from a clamped column and dropped)
+            return pair_of(parent_texel<FORMAT>(m, base, ch, in0 ? px - b : it.x0, y), parent_texel<FORMAT>(m, base, ch, in1 ? px + 1u - b : it.x1, y));
         });
     } else {
+        const uint32_t px0 = b + it.x0, px1 = b + it.x1;
         T* tile = base + uint64_t(it.layer) * Tsz * Tsz;
         for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) { tile[uint64_t(b + y) * Tsz + px] = parent_texel<FORMAT>(m, base, ch, px - b, y); });
     }
@@ -308,10 +299,8 @@ bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* a
 bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
                              const void* src, uint32_t rx0, uint32_t ry0, uint32_t src_width) {
     if (!n || !max_rows) return BT_OK;
-    if (m.format == BT_FORMAT_R16)
-        edit_region_kernel<BT_FORMAT_R16><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
-    else
-        edit_region_kernel<BT_FORMAT_RGBA8><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
+    const auto kernel = m.format == BT_FORMAT_R16 ? edit_region_kernel<BT_FORMAT_R16> : edit_region_kernel<BT_FORMAT_RGBA8>;
+    kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
     return edit_launched("edit_region_kernel");
 }
 
@@ -333,10 +322,8 @@ bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* 
 
 bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows) {
     if (!n || !max_rows) return BT_OK;
-    if (m.format == BT_FORMAT_R16)
-        edit_downsample_kernel<BT_FORMAT_R16><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
-    else
-        edit_downsample_kernel<BT_FORMAT_RGBA8><<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
+    const auto kernel = m.format == BT_FORMAT_R16 ? edit_downsample_kernel<BT_FORMAT_R16> : edit_downsample_kernel<BT_FORMAT_RGBA8>;
+    kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
     return edit_launched("edit_downsample_kernel");
 }
 

@@ -203,10 +203,10 @@ struct bt_ctx {
     // bt_tile_tree_raycast: the rays and the hits of one call on the device (grown on demand, kept until bt_ctx_trim)
     void* raycast_dev = nullptr;
     uint64_t raycast_bytes = 0;
-    // bt_atlas_edit_height / bt_atlas_write_region: the plans (items, stamps, stitch tasks) of the calls in flight, pinned and on the device,
-    // handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is recorded behind each
-    // call's copy and waited for when the ring wraps), and the staged rectangle of write_region / the new texels of smooth_height on the
-    // device (grown on demand, kept until bt_ctx_trim)
+    // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
+    // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
+    // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out.  Then the
+    // staged rectangle of write_region / the new texels of smooth_height on the device (grown on demand, kept until bt_ctx_trim)
     void* edit_dev = nullptr;
     void* edit_host = nullptr;
     uint64_t edit_bytes = 0, edit_used = 0;
@@ -411,8 +411,27 @@ struct HeightBoundsImpl {
     bool current = false;
 };
 inline HeightBoundsImpl* bounds_impl(bt_height_bounds* b) { return reinterpret_cast<HeightBoundsImpl*>(b); }
-// bt_edit.cpp: `need` bytes of the context's plan ring: pinned half to fill, device half the kernels read
-bt_status edit_scratch(bt_ctx* ctx, uint64_t need, uint8_t** host, uint8_t** dev);
+// bt_edit.cpp: the records of one call (an edit's plan, a bounds update's) on their way through the context's plan ring (bt_ctx::edit_*).
+// add() the host records, each 16-byte aligned; then, optionally, device_only() bytes behind them; every offset returned is relative to
+// the device base commit() hands back.  commit(), once: reserves pinned and device bytes of the ring, copies the records (they must still
+// be where add() saw them) into the pinned half, enqueues the ONE copy to the device half on the context's stream and records
+// edit_copied behind it, which the ring waits for before it wraps onto pinned records.
+class PlanRing {
+public:
+    uint64_t add(const void* src, uint64_t bytes);
+    template <typename T>
+    uint64_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
+    uint64_t device_only(uint64_t bytes) { return add(nullptr, bytes); }  // after the last add() of a host record
+    bt_status commit(bt_ctx* ctx, uint8_t** dev);
+
+private:
+    struct Record {
+        const void* src;  // NULL: device only
+        uint64_t bytes, at;
+    };
+    std::vector<Record> records;
+    uint64_t size = 0, upload = 0;  // of all records; of those up to the last host record: what the copy moves
+};
 }  // namespace bt
 
 namespace bt {

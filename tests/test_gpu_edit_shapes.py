@@ -29,7 +29,7 @@ from test_gpu_edit import ATLAS, R16, RGBA8, Snapshot, ancestors_levels, check_e
 F32 = np.float32
 LANES = 64      # bt_edit.hip, for_each_dword: p += 64u
 ROW_BLOCK = 16  # bt_edit.hip: kEditRows
-RING_BYTES = 1 << 20  # bt_edit.cpp, edit_scratch(): `std::max<uint64_t>(1ull << 20, 2u * need)`, the plan ring's initial size
+RING_BYTES = 1 << 20  # bt_edit.cpp, PlanRing::commit(): `std::max<uint64_t>(1ull << 20, 2u * need)`, the plan ring's initial size
 MAX_STAMPS = 256      # BT_EDIT_MAX_STAMPS
 
 

@@ -4,7 +4,7 @@ headline benchmark (bench.py).
 
 Per case (one SMOOTH ADD stamp of radius 4 / 32 / 256 / 2048 texels across a four-tile corner of the finest LOD, and 64 stamps of radius
 32): device time per call from a device-event pair around `--calls` back-to-back calls (no synchronise in between; the plan ring of the
-context serves the calls in flight) after a spin-up of the same calls, the median of `--repeats` such windows; `launches` and
+context serves the calls in flight) after a spin-up of the same calls, the median of `--repeats` such windows (and the windows themselves, `*_windows`); `launches` and
 `changed_count` of the call; host time per call (the planning + enqueue, a host clock around the same window ended by a synchronise).
 Successive calls of a window use the same stamps: the texels saturate after some calls, the work does not change.
 
@@ -164,6 +164,7 @@ def main():
                 atlas.upload_tile(0, i, t)
             round_trip.append((time.perf_counter() - t0) * 1e3)
         result[name] = {"stamps": len(stamps), "device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
+                        "device_ms_windows": [round(v, 4) for v in device_ms], "host_ms_windows": [round(v, 4) for v in host_ms],
                         "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"],
                         "download_upload_round_trip_wall_ms": round(median(round_trip), 3)}
     smooth_cases(device, atlas, index, args, result)
@@ -193,6 +194,7 @@ def smooth_cases(device, atlas, index, args, result):
                 host_ms.append((time.perf_counter() - t0) * 1e3 / args.calls)
                 device_ms.append(device.timer_end() / args.calls)
             result[f"smooth_r{r}_k{k}"] = {"device_ms_per_call": round(median(device_ms), 4), "host_ms_per_call": round(median(host_ms), 4),
+                                           "device_ms_windows": [round(v, 4) for v in device_ms], "host_ms_windows": [round(v, 4) for v in host_ms],
                                            "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"]}
         # the same tile set by hand: download the changed tiles, (filter), write the stamp's box back through write_region
         lo = [max(0, int(np.floor(corner[i] - r))) for i in range(2)]
