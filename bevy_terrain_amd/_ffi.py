@@ -159,6 +159,7 @@ EDIT_ADD, EDIT_FLATTEN = 0, 1
 EDIT_FALLOFF_SMOOTH, EDIT_FALLOFF_HARD = 0, 1
 EDIT_MAX_STAMPS = 256
 SMOOTH_MAX_KERNEL = 4
+PAINT_BLEND, PAINT_ADD = 0, 1
 
 
 class EditStampC(C.Structure):
@@ -168,6 +169,11 @@ class EditStampC(C.Structure):
 
 class SmoothStampC(C.Structure):
     _fields_ = [("side", C.c_uint32), ("falloff", C.c_uint32), ("center", C.c_float * 2), ("radius", C.c_float), ("strength", C.c_float)]
+
+
+class PaintStampC(C.Structure):
+    _fields_ = [("side", C.c_uint32), ("mode", C.c_uint32), ("falloff", C.c_uint32), ("channel_mask", C.c_uint32), ("center", C.c_float * 2),
+                ("radius", C.c_float), ("opacity", C.c_float), ("color", C.c_float * 4)]
 
 
 class EditStatsC(C.Structure):
@@ -244,6 +250,8 @@ PROTOTYPES = {
     "bt_atlas_tile_bounds": (_i32, [_vp, _u32, _P(_u32), _u32, _u32, _u32, _P(C.c_uint16), _u64]),
     "bt_atlas_edit_height": (_i32, [_vp, _u32, _u32, _P(EditStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_smooth_height": (_i32, [_vp, _u32, _u32, _u32, _P(SmoothStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_paint": (_i32, [_vp, _u32, _u32, _P(PaintStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_read_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(_u32)]),
     "bt_atlas_write_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),

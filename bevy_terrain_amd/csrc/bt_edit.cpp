@@ -1,4 +1,5 @@
-// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_write_region / bt_atlas_save_tiles: the host half of in-place editing.
+// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_write_region / bt_atlas_read_region / bt_atlas_save_tiles: the
+// host half of in-place editing.
 //
 // An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
 // include/bevy_terrain_amd.h): the ancestors' centres, the aprons of every written tile and of its existing neighbours, the mips.  The plan
@@ -94,12 +95,8 @@ EditItem make_item(const bt_tile_coordinate& c, const Dirty& d, uint32_t centre)
     return it;
 }
 
-// boxes of mosaic texels of `lod` -> the whole plan.  Host index arithmetic only.
-void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std::vector<Box>& boxes, Plan& plan) {
-    const uint32_t c = at.meta.center_size;
-    const bool spherical = a->config.spherical != 0;
-    DirtyTiles cur;
-    // the tiles of `lod` each box meets: existing ones get the box's part of their centre, the others are counted
+// the tiles of `lod` each box meets: existing ones get the box's part of their centre (`cur`), and all of them are counted (returned)
+uint64_t meet_tiles(const bt_atlas* a, uint32_t c, uint32_t lod, const std::vector<Box>& boxes, DirtyTiles& cur) {
     uint64_t met = 0;
     for (uint32_t side = 0; side < 6; side++) {
         std::vector<Rect> tile_rects;
@@ -131,6 +128,15 @@ void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std
             }
         }
     }
+    return met;
+}
+
+// boxes of mosaic texels of `lod` -> the whole plan.  Host index arithmetic only.
+void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std::vector<Box>& boxes, Plan& plan) {
+    const uint32_t c = at.meta.center_size;
+    const bool spherical = a->config.spherical != 0;
+    DirtyTiles cur;
+    const uint64_t met = meet_tiles(a, c, lod, boxes, cur);
     plan.stats.tiles_edited = uint32_t(cur.size());
     plan.stats.tiles_missing = uint32_t(std::min<uint64_t>(met - std::min<uint64_t>(met, cur.size()), 0xFFFFFFFFull));
     if (cur.empty()) return;
@@ -268,11 +274,11 @@ bt_status region_scratch(bt_ctx* ctx, uint64_t bytes) {
 }
 
 // The first step of a plan, the one that writes the rectangles of the edited tiles (the steps after it are the same for every call): the
-// brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps.  prepare() runs once the plan is known
+// brush or the paint brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps.  prepare() runs once the plan is known
 // to write something: it adds what the step wants in the ring and readies its device buffer; launch() follows the ring's commit.
 struct FirstStep {
-    enum Kind { kBrush, kRegion, kSmooth } kind;
-    // brush: bt_edit_stamp[count]; smooth: bt_smooth_stamp[count] and the box's kernel_radius
+    enum Kind { kBrush, kRegion, kSmooth, kPaint } kind;
+    // brush: bt_edit_stamp[count]; paint: bt_paint_stamp[count]; smooth: bt_smooth_stamp[count] and the box's kernel_radius
     const void* stamps = nullptr;
     uint32_t count = 0, kernel_radius = 0;
     // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart; copied: the events of the staging
@@ -294,6 +300,7 @@ struct FirstStep {
 bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::vector<EditItem>& items, PlanRing& ring) {
     switch (kind) {
         case kBrush: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_edit_stamp)); return BT_OK;
+        case kPaint: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_paint_stamp)); return BT_OK;
         case kRegion: return stage_region(ctx, uint64_t(width) * m.pixel_size);
         case kSmooth: {
             uint64_t scratch_dwords = 0;
@@ -333,6 +340,7 @@ bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
 bt_status FirstStep::launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ring, const EditItem* items, uint32_t n, uint32_t max_rows) const {
     switch (kind) {
         case kBrush: return launch_edit_brush(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_edit_stamp*)(ring + stamps_at), count);
+        case kPaint: return launch_edit_paint(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_paint_stamp*)(ring + stamps_at), count);
         case kRegion: return launch_edit_region(ctx->stream, at.meta, at.level0, items, n, max_rows, ctx->edit_region_dev, x0, y0, width);
         case kSmooth:
             return launch_edit_smooth(ctx->stream, at.meta, at.level0, items, (const uint64_t*)(ring + offsets_at), n, max_rows, (const bt_smooth_stamp*)(ring + stamps_at), count,
@@ -395,8 +403,9 @@ bt_status edit_boxes(bt_atlas* a, uint32_t ai, uint32_t lod, const std::vector<B
     return rc;
 }
 
-// what both edit calls check of the atlas: attachment, LOD, format and centre size
-bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, bool brush, const char* what) {
+// what the edit calls check of the atlas: attachment, LOD, format (the formats the call takes) and centre size
+enum Target { kHeights, kColours, kTexels };  // R16 (the height brushes), Rgba8 (the paint brush), both (the regions)
+bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, Target target, const char* what) {
     if (ai >= a->attachments.size()) {
         set_error("%s: attachment %u of %zu", what, ai, a->attachments.size());
         return BT_ERR_INVALID_ARGUMENT;
@@ -406,8 +415,9 @@ bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, bool brush,
         return BT_ERR_INVALID_ARGUMENT;
     }
     const AttachmentMeta& m = a->attachments[ai].meta;
-    if (m.format != BT_FORMAT_R16 && (brush || m.format != BT_FORMAT_RGBA8)) {
-        set_error("%s: attachment format %u (%s)", what, m.format, brush ? "the brush edits R16 heights" : "R16 and Rgba8 only");
+    if (!((m.format == BT_FORMAT_R16 && target != kColours) || (m.format == BT_FORMAT_RGBA8 && target != kHeights))) {
+        set_error("%s: attachment format %u (%s)", what, m.format,
+                  target == kHeights ? "the brush edits R16 heights" : target == kColours ? "the paint brush edits Rgba8" : "R16 and Rgba8 only");
         return BT_ERR_UNSUPPORTED;
     }
     if (m.center_size % 2u) {
@@ -426,6 +436,14 @@ const char* bad_own(const bt_edit_stamp& s, bool before_falloff) {
     if (before_falloff) return s.mode != BT_EDIT_ADD && s.mode != BT_EDIT_FLATTEN ? "mode" : nullptr;
     return !std::isfinite(s.amount) ? "amount (not finite)" : nullptr;
 }
+const char* bad_own(const bt_paint_stamp& s, bool before_falloff) {
+    if (before_falloff) return s.mode != BT_PAINT_BLEND && s.mode != BT_PAINT_ADD ? "mode" : nullptr;
+    if (s.channel_mask == 0u || s.channel_mask > 15u) return "channel_mask (1 .. 15)";
+    if (!std::isfinite(s.opacity) || !(s.opacity > 0.0f) || !(s.opacity <= 1.0f)) return "opacity (finite, in (0, 1])";
+    for (float v : s.color)
+        if (!std::isfinite(v)) return "color (not finite)";
+    return nullptr;
+}
 const char* bad_own(const bt_smooth_stamp& s, bool before_falloff) {
     if (before_falloff) return nullptr;
     return !std::isfinite(s.strength) || !(s.strength > 0.0f) || !(s.strength <= 1.0f) ? "strength (finite, in (0, 1])" : nullptr;
@@ -442,11 +460,11 @@ const char* bad_stamp(const Stamp& s) {
     return bad_own(s, false);
 }
 
-// What bt_atlas_edit_height and bt_atlas_smooth_height (`what`) check alike, in the order they report it.  The stamps first: what can be
+// What bt_atlas_edit_height, bt_atlas_smooth_height and bt_atlas_paint (`what`) check alike, in the order they report it.  The stamps first: what can be
 // refused without the atlas is refused without it.  own(false) / own(true): the caller's checks of its other arguments that go before the
 // stamps are looked at / once the target has passed.
 template <typename Stamp, typename Own>
-bt_status check_stamps(const char* what, const bt_atlas* a, uint32_t ai, uint32_t lod, const Stamp* stamps, uint32_t count, const bt_tile_coordinate* changed,
+bt_status check_stamps(const char* what, Target target, const bt_atlas* a, uint32_t ai, uint32_t lod, const Stamp* stamps, uint32_t count, const bt_tile_coordinate* changed,
                        uint32_t changed_cap, Own own) {
     if (count > BT_EDIT_MAX_STAMPS) {
         set_error("%s: %u stamps, at most %u per call", what, count, BT_EDIT_MAX_STAMPS);
@@ -466,7 +484,7 @@ bt_status check_stamps(const char* what, const bt_atlas* a, uint32_t ai, uint32_
         set_error("%s: NULL atlas", what);
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_target(a, ai, lod, true, what)) return s;
+    if (bt_status s = check_target(a, ai, lod, target, what)) return s;
     if (bt_status s = own(true)) return s;
     const uint32_t sides = a->config.spherical ? 6u : 1u;
     for (uint32_t i = 0; i < count; i++)
@@ -503,7 +521,7 @@ extern "C" {
 bt_status bt_atlas_edit_height(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_edit_stamp* stamps, uint32_t count, bt_tile_coordinate* changed,
                                uint32_t changed_cap, bt_edit_stats* stats) {
     if (stats) *stats = bt_edit_stats{};
-    if (bt_status s = check_stamps("bt_atlas_edit_height", a, ai, lod, stamps, count, changed, changed_cap, [](bool) { return BT_OK; })) return s;
+    if (bt_status s = check_stamps("bt_atlas_edit_height", kHeights, a, ai, lod, stamps, count, changed, changed_cap, [](bool) { return BT_OK; })) return s;
     if (!count) return BT_OK;
     FirstStep first{FirstStep::kBrush};
     first.stamps = stamps, first.count = count;
@@ -524,10 +542,20 @@ bt_status bt_atlas_smooth_height(bt_atlas* a, uint32_t ai, uint32_t lod, uint32_
         }
         return BT_OK;
     };
-    if (bt_status s = check_stamps("bt_atlas_smooth_height", a, ai, lod, stamps, count, changed, changed_cap, check_kernel)) return s;
+    if (bt_status s = check_stamps("bt_atlas_smooth_height", kHeights, a, ai, lod, stamps, count, changed, changed_cap, check_kernel)) return s;
     if (!count) return BT_OK;
     FirstStep first{FirstStep::kSmooth};
     first.stamps = stamps, first.count = count, first.kernel_radius = kernel_radius;
+    return edit_boxes(a, ai, lod, stamp_boxes(a, ai, lod, stamps, count), first, changed, changed_cap, stats);
+}
+
+bt_status bt_atlas_paint(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_paint_stamp* stamps, uint32_t count, bt_tile_coordinate* changed, uint32_t changed_cap,
+                         bt_edit_stats* stats) {
+    if (stats) *stats = bt_edit_stats{};
+    if (bt_status s = check_stamps("bt_atlas_paint", kColours, a, ai, lod, stamps, count, changed, changed_cap, [](bool) { return BT_OK; })) return s;
+    if (!count) return BT_OK;
+    FirstStep first{FirstStep::kPaint};
+    first.stamps = stamps, first.count = count;
     return edit_boxes(a, ai, lod, stamp_boxes(a, ai, lod, stamps, count), first, changed, changed_cap, stats);
 }
 
@@ -542,7 +570,7 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
         set_error("bt_atlas_write_region: NULL changed with changed_cap > 0");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_target(a, ai, lod, false, "bt_atlas_write_region")) return s;
+    if (bt_status s = check_target(a, ai, lod, kTexels, "bt_atlas_write_region")) return s;
     if (side >= (a->config.spherical ? 6u : 1u)) {
         set_error("bt_atlas_write_region: side %u", side);
         return BT_ERR_INVALID_ARGUMENT;
@@ -571,6 +599,89 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
             hipEventDestroy(ev);
         }
     return rc;
+}
+
+bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* texels,
+                               uint64_t row_pitch, uint32_t* tiles_missing) {
+    if (tiles_missing) *tiles_missing = 0;
+    if (!a) {
+        set_error("bt_atlas_read_region: NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_target(a, ai, lod, kTexels, "bt_atlas_read_region")) return s;
+    if (side >= (a->config.spherical ? 6u : 1u)) {
+        set_error("bt_atlas_read_region: side %u", side);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& at = a->attachments[ai];
+    const uint64_t size = uint64_t(at.meta.center_size) << lod;
+    if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
+        set_error("bt_atlas_read_region: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", x0, x0 + width, y0, y0 + height, (unsigned long long)size);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!width || !height) return BT_OK;
+    const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
+    if (!row_pitch) row_pitch = row_bytes;
+    if (!texels || row_pitch < row_bytes) {
+        set_error("bt_atlas_read_region: %s", !texels ? "NULL texels_host" : "row_pitch smaller than a row");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    // the items: the rectangle's part of every tile the atlas holds, as a write's first level
+    DirtyTiles tiles;
+    const uint64_t met = meet_tiles(a, at.meta.center_size, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, tiles);
+    const uint64_t missing = met - std::min<uint64_t>(met, tiles.size());
+    if (tiles_missing) *tiles_missing = uint32_t(std::min<uint64_t>(missing, 0xFFFFFFFFull));
+    std::vector<EditItem> items;
+    uint32_t max_rows = 0;
+    for (const auto& [coord, d] : tiles) {
+        items.push_back(make_item(coord, d, at.meta.center_size));
+        max_rows = std::max(max_rows, d.r.y1 - d.r.y0 + 1u);
+    }
+    // layers -> the staged rectangle on the device (what no tile covers: zeros, from a memset queued before the launch)
+    const uint64_t total = row_bytes * height;
+    if (bt_status s = region_scratch(ctx, total)) return s;
+    if (missing) BT_HIP(hipMemsetAsync(ctx->edit_region_dev, 0, total, ctx->stream));
+    if (!items.empty()) {
+        PlanRing ring;
+        const uint64_t items_at = ring.add(items);
+        uint8_t* dev = nullptr;
+        if (bt_status s = ring.commit(ctx, &dev)) return s;
+        if (bt_status s = launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, ctx->edit_region_dev, x0, y0, width))
+            return s;
+    }
+    // the staged rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
+    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
+        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
+    struct Landing {
+        hipEvent_t copied = nullptr;
+        uint32_t row = 0, rows = 0;  // rows != 0: a chunk is on its way into the buffer
+    } landing[bt_ctx::kStagingBuffers];
+    hipError_t e = hipSuccess;
+    auto empty = [&](uint32_t k) {
+        Landing& l = landing[k];
+        if (!l.rows || e != hipSuccess) return;
+        e = hipEventSynchronize(l.copied);
+        for (uint32_t r = 0; r < l.rows && e == hipSuccess; r++)
+            memcpy((uint8_t*)texels + (uint64_t(l.row) + r) * row_pitch, (const uint8_t*)ctx->staging[k] + r * row_bytes, row_bytes);
+        l.rows = 0;
+    };
+    uint32_t chunk = 0;
+    for (uint32_t row = 0; row < height && e == hipSuccess; row += chunk_rows, chunk++) {
+        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
+        empty(k);
+        if (e == hipSuccess && !landing[k].copied) e = hipEventCreateWithFlags(&landing[k].copied, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)ctx->edit_region_dev + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(landing[k].copied, ctx->stream);
+        if (e == hipSuccess) landing[k].row = row, landing[k].rows = rows;
+    }
+    for (uint32_t i = 0; i < bt_ctx::kStagingBuffers; i++) empty((chunk + i) % bt_ctx::kStagingBuffers);  // the oldest first
+    if (e != hipSuccess) hipStreamSynchronize(ctx->stream);  // nothing may still be landing in the context's buffers when the call returns
+    for (Landing& l : landing)
+        if (l.copied) hipEventDestroy(l.copied);
+    return e == hipSuccess ? BT_OK : hip_fail(e, "bt_atlas_read_region staging");
 }
 
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {

@@ -1,4 +1,4 @@
-// In-place editing of atlas layers (bt_atlas_edit_height / bt_atlas_write_region): the kernels.  The planning is in bt_edit.cpp.
+// In-place editing of atlas layers (bt_atlas_edit_height / bt_atlas_paint / bt_atlas_write_region / bt_atlas_read_region): the kernels.  The planning is in bt_edit.cpp.
 //
 // An item is ONE tile's dirty rectangle of one launch: (layer, inclusive rectangle in centre texels, mosaic origin of the tile's centre).
 // grid = (items, row blocks of the tallest rectangle); a workgroup of four waves takes kEditRows rows of its item, a wave one row at a
@@ -8,7 +8,10 @@
 //
 // edit_brush_kernel   the stamps of bt_atlas_edit_height on the texels of the rectangle; the stamp array is indexed by the loop counter
 //                     only (wave-uniform: scalar loads), and a stamp whose side is not the item's is skipped by the whole wave.
+// edit_paint_kernel   the stamps of bt_atlas_paint on the Rgba8 texels of the rectangle, in the same way: one dword read, four channels in
+//                     registers, one dword written.
 // edit_region_kernel  the same layout, copying from the staged rectangle of bt_atlas_write_region.
+// edit_gather_kernel  its mirror for bt_atlas_read_region: layers -> the staged rectangle.
 // edit_smooth_kernel<K>  the box mean of bt_atlas_smooth_height (kernel_radius K) and its stamps.  It READS the layers and writes the new dwords
 //                     of every item's rectangle into device scratch: other workgroups read the rows it would write (as halo), so nothing of
 //                     the call may land in a layer before every workgroup has read.  edit_smooth_copy_kernel, the next launch, moves them in.
@@ -53,6 +56,24 @@ __device__ __forceinline__ uint32_t stamp_texel(const bt_edit_stamp& s, float r2
     const float h = unorm16_to_float(t);  // == f32(t) / 65535 for every t (bt_selftest)
     const float hn = s.mode == BT_EDIT_FLATTEN ? h + (s.amount - h) * w : h + s.amount * w;
     return max(1u, float_to_unorm(hn, 65535.0f));
+}
+
+// u -> u' of one paint stamp that has passed the side test: the header's PAINT section line by line
+__device__ __forceinline__ uint32_t paint_texel(const bt_paint_stamp& s, float r2, float fx, float fy, uint32_t u) {
+    float w;
+    if ((u & 0x00FFFFFFu) == 0u || !stamp_weight(s, r2, fx, fy, w)) return u;
+    const float a = s.opacity * w;
+    uint32_t out = u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        if (!((s.channel_mask >> k) & 1u)) continue;
+        const float c = unorm8_to_float((u >> (8u * k)) & 0xFFu);  // == f32(u[k]) / 255 (bt_selftest)
+        const float cn = s.mode == BT_PAINT_BLEND ? c + (s.color[k] - c) * a : c + s.color[k] * a;
+        out = (out & ~(0xFFu << (8u * k))) | (float_to_unorm(cn, 255.0f) << (8u * k));
+    }
+    // never a hole: the channels of the mask among r, g, b (all 0 here) become 1
+    if ((out & 0x00FFFFFFu) == 0u) out |= (s.channel_mask & 1u) | ((s.channel_mask & 2u) << 7) | ((s.channel_mask & 4u) << 14);
+    return out;
 }
 
 // the rows and the dword range a workgroup's waves walk: calls body(row y, dword p) for every (row of this workgroup, dword of the row)
@@ -108,6 +129,24 @@ __global__ __launch_bounds__(kEditThreads) void edit_brush_kernel(AttachmentMeta
     });
 }
 
+__global__ __launch_bounds__(kEditThreads) void edit_paint_kernel(AttachmentMeta m, uint32_t* __restrict__ atlas, const EditItem* __restrict__ items,
+                                                                  const bt_paint_stamp* __restrict__ stamps, uint32_t stamp_count) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    uint32_t* tile = atlas + uint64_t(it.layer) * Tsz * Tsz;
+    for_each_dword(it, b + it.x0, b + it.x1, [&](uint32_t y, uint32_t px) {
+        uint32_t* dst = tile + uint64_t(b + y) * Tsz + px;
+        uint32_t u = *dst;
+        const float fx = float(it.gx0 + px - b), fy = float(it.gy0 + y);
+        for (uint32_t k = 0; k < stamp_count; k++) {
+            const bt_paint_stamp s = stamps[k];
+            if (s.side != it.side) continue;
+            u = paint_texel(s, s.radius * s.radius, fx, fy, u);
+        }
+        *dst = u;
+    });
+}
+
 template <uint32_t FORMAT>
 __global__ __launch_bounds__(kEditThreads) void edit_region_kernel(AttachmentMeta m, void* __restrict__ atlas_, const EditItem* __restrict__ items,
                                                                    const void* __restrict__ src_, uint32_t rx0, uint32_t ry0, uint32_t src_width) {
@@ -126,6 +165,34 @@ __global__ __launch_bounds__(kEditThreads) void edit_region_kernel(AttachmentMet
         const uint32_t* src = (const uint32_t*)src_;
         for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) {
             tile[uint64_t(b + y) * Tsz + px] = src[uint64_t(it.gy0 + y - ry0) * src_width + (it.gx0 + px - b - rx0)];
+        });
+    }
+}
+
+// The mirror of edit_region_kernel: the texels of every item's rectangle go from the layers into the staged rectangle (`dst_width` texels per
+// row, tightly packed, texel (0, 0) = mosaic texel (rx0, ry0)).  R16: a lane owns one aligned pair of the LAYER row and reads it as one dword;
+// the staged rectangle is written PER TEXEL (16-bit stores of the halves inside the rectangle), so an odd x0 or width, where the staged
+// rows are not dword-aligned with the layer's, needs no case of its own.  Rgba8: one dword in, one dword out.
+template <uint32_t FORMAT>
+__global__ __launch_bounds__(kEditThreads) void edit_gather_kernel(AttachmentMeta m, const void* __restrict__ atlas_, const EditItem* __restrict__ items,
+                                                                   void* __restrict__ dst_, uint32_t rx0, uint32_t ry0, uint32_t dst_width) {
+    const EditItem it = items[blockIdx.x];
+    const uint32_t Tsz = m.texture_size, b = m.border_size;
+    const uint32_t px0 = b + it.x0, px1 = b + it.x1;
+    if constexpr (FORMAT == BT_FORMAT_R16) {
+        const uint32_t* tile = reinterpret_cast<const uint32_t*>((const uint16_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz);
+        uint16_t* dst = (uint16_t*)dst_;
+        for_each_dword(it, px0 >> 1, px1 >> 1, [&](uint32_t y, uint32_t p) {
+            const uint32_t pair = tile[(uint64_t(b + y) * Tsz) / 2u + p], px = 2u * p;
+            uint16_t* row = dst + uint64_t(it.gy0 + y - ry0) * dst_width;
+            if (px >= px0) row[it.gx0 + px - b - rx0] = uint16_t(pair & 0xFFFFu);
+            if (px + 1u <= px1) row[it.gx0 + px + 1u - b - rx0] = uint16_t(pair >> 16);
+        });
+    } else {
+        const uint32_t* tile = (const uint32_t*)atlas_ + uint64_t(it.layer) * Tsz * Tsz;
+        uint32_t* dst = (uint32_t*)dst_;
+        for_each_dword(it, px0, px1, [&](uint32_t y, uint32_t px) {
+            dst[uint64_t(it.gy0 + y - ry0) * dst_width + (it.gx0 + px - b - rx0)] = tile[uint64_t(b + y) * Tsz + px];
         });
     }
 }
@@ -294,6 +361,21 @@ bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* a
     if (!n || !max_rows) return BT_OK;
     edit_brush_kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, (uint16_t*)atlas, items, stamps, stamp_count);
     return edit_launched("edit_brush_kernel");
+}
+
+bt_status launch_edit_paint(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                            const bt_paint_stamp* stamps, uint32_t stamp_count) {
+    if (!n || !max_rows) return BT_OK;
+    edit_paint_kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, (uint32_t*)atlas, items, stamps, stamp_count);
+    return edit_launched("edit_paint_kernel");
+}
+
+bt_status launch_edit_gather(hipStream_t stream, const AttachmentMeta& m, const void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                             void* dst, uint32_t rx0, uint32_t ry0, uint32_t dst_width) {
+    if (!n || !max_rows) return BT_OK;
+    const auto kernel = m.format == BT_FORMAT_R16 ? edit_gather_kernel<BT_FORMAT_R16> : edit_gather_kernel<BT_FORMAT_RGBA8>;
+    kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, dst, rx0, ry0, dst_width);
+    return edit_launched("edit_gather_kernel");
 }
 
 bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,

@@ -206,7 +206,7 @@ struct bt_ctx {
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
     // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out.  Then the
-    // staged rectangle of write_region / the new texels of smooth_height on the device (grown on demand, kept until bt_ctx_trim)
+    // staged rectangle of write_region and read_region / the new texels of smooth_height on the device (grown on demand, kept until bt_ctx_trim)
     void* edit_dev = nullptr;
     void* edit_host = nullptr;
     uint64_t edit_bytes = 0, edit_used = 0;
@@ -279,9 +279,14 @@ struct EditItem {
 };
 bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
                             const bt_edit_stamp* stamps, uint32_t stamp_count);
+bt_status launch_edit_paint(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                            const bt_paint_stamp* stamps, uint32_t stamp_count);
 // src: the staged rectangle (device, `src_width` texels per row, tightly packed) whose texel (0, 0) is mosaic texel (rx0, ry0)
 bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
                              const void* src, uint32_t rx0, uint32_t ry0, uint32_t src_width);
+// the other direction (bt_atlas_read_region): the items' rectangles of the layers -> the staged rectangle `dst`
+bt_status launch_edit_gather(hipStream_t stream, const AttachmentMeta& m, const void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
+                             void* dst, uint32_t rx0, uint32_t ry0, uint32_t dst_width);
 bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows);
 // bt_atlas_smooth_height, two launches: edit_smooth_kernel<kernel_radius> reads the layers and writes the new dwords of every item's rectangle
 // to `scratch` (device), the copy launch moves them into the layers.  offsets[i] (device): where item i's rectangle starts in `scratch`, in

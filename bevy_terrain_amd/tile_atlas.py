@@ -141,6 +141,35 @@ class SmoothStamp:
                                  (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.strength))
 
 
+@dataclass
+class PaintStamp:
+    """bt_paint_stamp: one stamp of TileAtlas.paint (Rgba8).  center / radius as EditStamp's; color is normalised (1 = 255): the target of
+    "blend", the signed delta of "add"; opacity in (0, 1] scales the falloff weight; channels selects what is painted: an iterable of
+    channel indices or letters out of "rgba" (channel k is byte k of the texel)."""
+    center: Tuple[float, float]
+    radius: float
+    color: Tuple[float, float, float, float]
+    opacity: float = 1.0
+    mode: str = "blend"      # "blend" | "add"
+    falloff: str = "smooth"  # "smooth": w = (1 - d^2 / r^2)^2 | "hard": w = 1
+    channels: object = "rgba"
+    side: int = 0
+
+    def channel_mask(self) -> int:
+        if isinstance(self.channels, int):
+            return self.channels
+        mask = 0
+        for ch in self.channels:
+            mask |= 1 << ("rgba".index(ch) if isinstance(ch, str) else int(ch))
+        return mask
+
+    def _c(self):
+        return _ffi.PaintStampC(self.side, {"blend": _ffi.PAINT_BLEND, "add": _ffi.PAINT_ADD}[self.mode],
+                                {"smooth": _ffi.EDIT_FALLOFF_SMOOTH, "hard": _ffi.EDIT_FALLOFF_HARD}[self.falloff], self.channel_mask(),
+                                (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.opacity),
+                                (C.c_float * 4)(*[float(v) for v in self.color]))
+
+
 def mosaic_position(uv, lod: int, center_size: int) -> Tuple[float, float]:
     """The mosaic position (EditStamp.center units) of face coordinate uv in [0, 1]^2 at `lod`: the face is 2^lod * center_size texels
     wide and texel g covers [g / n, (g + 1) / n) with its position at the integer g, so the middle of texel g maps to g."""
@@ -349,6 +378,26 @@ class TileAtlas:
         stamps = list(stamps)
         arr = (_ffi.SmoothStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
         return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_smooth_height(self._h, attachment_index, lod, kernel_radius, arr, len(stamps), changed, cap, stats))
+
+    def paint(self, attachment_index: int, stamps, lod: Optional[int] = None) -> Tuple[List[TileCoordinate], dict]:
+        """bt_atlas_paint: apply the PaintStamps, in list order, to the centre texels of the existing tiles of `lod` (default: the finest) of
+        an Rgba8 attachment, then restore the ancestors, the aprons and the mips as edit_height does, without synchronising.  Texels without
+        data (rgb == 0) are left alone and none is made.  Returns (changed, stats)."""
+        lod = self.lod_count - 1 if lod is None else lod
+        stamps = list(stamps)
+        arr = (_ffi.PaintStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
+        return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_paint(self._h, attachment_index, lod, arr, len(stamps), changed, cap, stats))
+
+    def read_region(self, attachment_index: int, x0: int, y0: int, w: int, h: int, lod: Optional[int] = None, side: int = 0) -> Tuple[np.ndarray, int]:
+        """bt_atlas_read_region: the w x h rectangle of centre texels at mosaic position (x0, y0) of `lod` on `side`, the inverse of
+        write_region: ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros where the atlas holds no tile, number of such tiles).
+        Ordered behind the queued work; synchronous."""
+        lod = self.lod_count - 1 if lod is None else lod
+        a = self.config.attachments[attachment_index]
+        out = np.zeros((h, w) if a.format == AttachmentFormat.R16 else (h, w, 4), dtype=texel_dtype(a.format))
+        missing = C.c_uint32()
+        _ffi.check(_ffi.lib().bt_atlas_read_region(self._h, attachment_index, side, lod, x0, y0, w, h, out.ctypes.data_as(C.c_void_p), 0, C.byref(missing)))
+        return out, missing.value
 
     def write_region(self, attachment_index: int, texels: np.ndarray, x0: int, y0: int, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_write_region: copy `texels` ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros allowed) verbatim over the centre

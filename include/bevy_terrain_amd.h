@@ -341,8 +341,8 @@ bt_status bt_atlas_tile_bounds(bt_atlas* atlas, uint32_t attachment_index, const
  * BT_OK with nothing touched: count == 0, width == 0 or height == 0.  BT_ERR_INVALID_ARGUMENT: NULL atlas or a NULL required pointer
  * (stamps, texels_host, changed with changed_cap > 0), attachment_index or lod >= lod_count out of range, side out of range (planar: 0;
  * cube: 0..5), a non-finite center or amount, a radius that is not finite or <= 0, an unknown mode or falloff, count > BT_EDIT_MAX_STAMPS,
- * a rectangle outside the mosaic, a row_pitch smaller than a row.  BT_ERR_UNSUPPORTED: an odd centre size c, Rg16 / Rgb8 attachments, a
- * brush on an Rgba8 attachment.  Neither call aborts. */
+ * a rectangle outside the mosaic, a row_pitch smaller than a row.  BT_ERR_UNSUPPORTED: an odd centre size c, Rg16 / Rgb8 attachments, this
+ * brush on an Rgba8 attachment (Rgba8 has its own: bt_atlas_paint below).  Neither call aborts. */
 enum { BT_EDIT_ADD = 0, BT_EDIT_FLATTEN = 1 };          /* bt_edit_stamp.mode */
 enum { BT_EDIT_FALLOFF_SMOOTH = 0, BT_EDIT_FALLOFF_HARD = 1 };
 #define BT_EDIT_MAX_STAMPS 256u
@@ -401,6 +401,56 @@ typedef struct bt_smooth_stamp {
 bt_status bt_atlas_smooth_height(bt_atlas* atlas, uint32_t attachment_index, uint32_t lod, uint32_t kernel_radius,
                                  const bt_smooth_stamp* stamps, uint32_t count,
                                  bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+/* PAINT (bt_atlas_paint; Rgba8 only): the brush of the colour format.  IEEE binary32, one rounding per written operation, no contraction.
+ * A centre texel (gx, gy) with bytes u[0..3] (u[k] = byte k of the texel: 0 r, 1 g, 2 b, 3 a) takes the stamps IN LIST ORDER, those whose
+ * `side` is the tile's:
+ *     the texel is skipped by every stamp when u[0] | u[1] | u[2] == 0: no data by the rule of downsample (rgb == 0, alpha ignored)
+ *     dx, dy, d2, r2, the test d2 < r2 and w exactly as in THE BRUSH
+ *     a = opacity * w
+ *     for every k whose bit is set in channel_mask:
+ *         c = f32(u[k]) / 255                                          the correctly rounded division
+ *         c' = c + (color[k] - c) * a (BT_PAINT_BLEND);  c' = c + color[k] * a (BT_PAINT_ADD)
+ *         u'[k] = floor(0.5 + 255 * clamp(c', 0, 1))
+ *     channels outside the mask keep their byte
+ *     if u'[0] | u'[1] | u'[2] == 0: u'[k] = 1 for every k < 3 of the mask           and u' is the u of the next stamp
+ * A stamp never produces a hole and never fills one: the hole mask is not the brush's to alter.  (The last line always finds a k: the texel
+ * had data before the stamp and the channels outside the mask did not move, so a channel of the mask went to 0.)
+ * Everything else is bt_atlas_edit_height's, word for word: a stamp is clipped to its face; the tiles a stamp can reach are those that meet
+ * its box [floor(center - radius), ceil(center + radius)]; tiles_edited / tiles_missing / tiles_with_children count as there and every
+ * existing tile of the box is written, changed or not; tiles finer than `lod` are not touched; `changed` has the same content and order;
+ * the call enqueues on the context's stream and returns without synchronising; every written layer counts as written for
+ * bt_run_stats.prev_zero_launches; the plan scratch stays in the context until bt_ctx_trim.  Launches: one paint launch, one downsample
+ * launch per LOD above, one stitch launch, then the mip launches.
+ * BT_ERR_INVALID_ARGUMENT (all checked before any device work): NULL atlas, NULL stamps with count > 0, NULL changed with changed_cap > 0,
+ * count > BT_EDIT_MAX_STAMPS, a bad side, mode or falloff, channel_mask 0 or above 15, a non-finite center or color, a radius that is not
+ * finite or <= 0, an opacity that is not finite or outside (0, 1], attachment_index or lod out of range.  BT_ERR_UNSUPPORTED: a non-Rgba8
+ * attachment, an odd centre size.  count == 0: BT_OK with nothing touched. */
+enum { BT_PAINT_BLEND = 0, BT_PAINT_ADD = 1 };            /* bt_paint_stamp.mode */
+typedef struct bt_paint_stamp {
+    uint32_t side, mode, falloff, channel_mask;  /* BT_EDIT_FALLOFF_*; bit k selects channel k (0 r, 1 g, 2 b, 3 a = byte k of the texel) */
+    float center[2];   /* mosaic texels of `lod` on `side`, as bt_edit_stamp */
+    float radius;      /* texels, finite, > 0 */
+    float opacity;     /* finite, 0 < opacity <= 1 */
+    float color[4];    /* normalised (1 = 255), finite: BLEND target, ADD signed delta */
+} bt_paint_stamp;      /* 48 bytes */
+bt_status bt_atlas_paint(bt_atlas* atlas, uint32_t attachment_index, uint32_t lod, const bt_paint_stamp* stamps, uint32_t count,
+                         bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+/* bt_atlas_read_region (R16 and Rgba8): the inverse of bt_atlas_write_region.  Reads the width x height rectangle of centre texels at
+ * mosaic (x0, y0) of `lod` on `side` into host memory, texels in the attachment's format, row_pitch bytes per row (0 = tightly packed;
+ * bytes of a row past its texels are not touched).  Texels of tiles the atlas holds no layer for read as 0 in every byte; *tiles_missing
+ * (may be NULL) counts those tiles of the rectangle.  Ordered behind the work queued on the context's stream (a read after an
+ * un-synchronised edit sees the edit); synchronous; a read: no layer is marked written.  A gather launch copies the layers' texels into the
+ * staged-rectangle buffer of bt_atlas_write_region on the device (absent tiles: a memset queued before it), from where the rows travel
+ * through the context's pinned staging buffers in chunks of whole rows.
+ * BT_ERR_INVALID_ARGUMENT: NULL atlas or texels_host, attachment_index, side or lod out of range, a rectangle outside [0, 2^lod * c)^2, a
+ * row_pitch smaller than a row.  BT_ERR_UNSUPPORTED: Rg16 / Rgb8, an odd centre size: the refusals of bt_atlas_write_region, so whatever
+ * can be read can be written back.  width == 0 or height == 0 (with valid arguments otherwise): BT_OK, nothing touched.
+ * UNDO of any of the four edit calls: read the edit's clipped box (a stamp's [floor(center - radius), ceil(center + radius)] cut to the
+ * face, or the written rectangle) before the edit, and write that rectangle back afterwards.  Zeros are legal there, so holes come back,
+ * and the write restores ancestors, aprons and mips from the same primary texels: provided F held before the edit, the atlas is then
+ * byte-identical to what it was. */
+bt_status bt_atlas_read_region(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                               uint32_t width, uint32_t height, void* texels_host, uint64_t row_pitch, uint32_t* tiles_missing /* may be NULL */);
 /* bt_atlas_save_attachment for a list of tiles (the `changed` list of an edit): writes "{directory}/{coord}.bin" of the listed tiles only.
  * A coordinate the atlas holds no layer for: BT_ERR_INVALID_ARGUMENT before anything is written.  count == 0: the directory is created. */
 bt_status bt_atlas_save_tiles(bt_atlas* atlas, uint32_t attachment_index, const char* directory, const bt_tile_coordinate* coords, uint32_t count);
