@@ -317,6 +317,8 @@ PROTOTYPES = {
     "bt_tile_tree_approximate_height": (_i32, [_vp, _vp, _P(C.c_float)]),
     "bt_tile_tree_view_state": (_i32, [_vp, _P(ViewStateC)]),
     "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
+    "bt_tile_tree_sample_normal": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_float), _P(C.c_float)]),
+    "bt_atlas_tile_normals": (_i32, [_vp, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(C.c_uint8), _u64]),
     "bt_frame_update": (_i32, [_vp, _vp, _vp, _P(C.c_double), C.c_uint32, _P(FrameInfoC)]),
     "bt_selftest": (_i32, [_vp, _P(_u32)]),
     "bt_synth_fbm_r16": (_i32, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _u32, _u32]),

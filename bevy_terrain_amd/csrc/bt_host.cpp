@@ -290,6 +290,7 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     if (ctx->bounds_dev) hipFree(ctx->bounds_dev);
     if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
     if (ctx->raycast_dev) hipFree(ctx->raycast_dev);
+    if (ctx->normal_dev) hipFree(ctx->normal_dev);
     if (ctx->edit_dev) hipFree(ctx->edit_dev);
     if (ctx->edit_host) hipHostFree(ctx->edit_host);
     if (ctx->edit_region_dev) hipFree(ctx->edit_region_dev);
@@ -350,6 +351,12 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
     }
     ctx->raycast_dev = nullptr;
     ctx->raycast_bytes = 0;
+    if (ctx->normal_dev) {
+        BT_HIP(hipFree(ctx->normal_dev));
+        freed += ctx->normal_bytes;
+    }
+    ctx->normal_dev = nullptr;
+    ctx->normal_bytes = 0;
     if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
     if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
     if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));

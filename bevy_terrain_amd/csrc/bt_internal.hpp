@@ -203,6 +203,10 @@ struct bt_ctx {
     // bt_tile_tree_raycast: the rays and the hits of one call on the device (grown on demand, kept until bt_ctx_trim)
     void* raycast_dev = nullptr;
     uint64_t raycast_bytes = 0;
+    // bt_tile_tree_sample_normal: the positions, normals and cosines of one call; bt_atlas_tile_normals: the tile list and up to three
+    // chunks of normal maps on their way to the pinned staging buffers (grown on demand, kept until bt_ctx_trim)
+    void* normal_dev = nullptr;
+    uint64_t normal_bytes = 0;
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
     // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out.  Then the

@@ -620,6 +620,55 @@ bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const 
     return BT_OK;
 }
 
+bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const double* positions, uint32_t count, float* normals, float* up_dot) {
+    if (!t || !a) {
+        set_error("bt_tile_tree_sample_normal: NULL %s", t ? "atlas" : "tile tree");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (t->ctx != a->ctx) {
+        set_error("bt_tile_tree_sample_normal: tile tree and atlas belong to different contexts");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (ai >= a->attachments.size()) {
+        set_error("bt_tile_tree_sample_normal: attachment index %u out of range", ai);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("bt_tile_tree_sample_normal: attachment %u is not R16", ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!count) return BT_OK;
+    if (!positions || !normals) {
+        set_error("bt_tile_tree_sample_normal: NULL %s", positions ? "out_normals_xyz" : "world_positions_xyz");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t in_bytes = sizeof(double) * 3 * uint64_t(count), n_bytes = 12 * uint64_t(count), d_bytes = 4 * uint64_t(count);
+    if (ctx->normal_bytes < in_bytes + n_bytes + d_bytes) {
+        BT_HIP(hipStreamSynchronize(s));
+        if (ctx->normal_dev) BT_HIP(hipFree(ctx->normal_dev));
+        ctx->normal_dev = nullptr;
+        ctx->normal_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->normal_dev, in_bytes + n_bytes + d_bytes));
+        ctx->normal_bytes = in_bytes + n_bytes + d_bytes;
+    }
+    uint8_t* dev = (uint8_t*)ctx->normal_dev;
+    BT_HIP(hipMemcpyAsync(dev, positions, in_bytes, hipMemcpyHostToDevice, s));
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    if (bt_status st = launch_sample_normal(s, make_params(t), t->d_entries, at.meta, at.level0, (const double*)dev, count, (float*)(dev + in_bytes),
+                                            up_dot ? (float*)(dev + in_bytes + n_bytes) : nullptr, t->d_height))
+        return st;
+    BT_HIP(hipMemcpyAsync(normals, dev + in_bytes, n_bytes, hipMemcpyDeviceToHost, s));
+    if (up_dot) BT_HIP(hipMemcpyAsync(up_dot, dev + in_bytes + n_bytes, d_bytes, hipMemcpyDeviceToHost, s));
+    BT_HIP(hipStreamSynchronize(s));
+    adopt_height(t);
+    t->table_copy_pending = false;
+    return BT_OK;
+}
+
 namespace {
 // TileTree::approximate_height (tile_tree.rs:372-386): sample_height of attachment 0 at the view position, kept on the device
 // (d_height[0]; the kernel reads the old value for its surface position, then overwrites it) and copied to pinned memory

@@ -24,6 +24,10 @@ struct TreeParams {
 // of approximate_height (may be NULL: P.approximate_height)
 bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
                          const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits, const float* height);
+// bt_normal.hip: the world normals (3 floats each) and, when up_dot is not NULL, their cosine against the mesh normal, of `count` world
+// positions (device) against the tree's entries and one R16 attachment; height as above
+bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                               const double* positions, uint32_t count, float* normals, float* up_dot, const float* height);
 
 #if defined(__HIPCC__)
 
@@ -43,9 +47,8 @@ struct Lookup {  // TileLookup (tile_tree.rs:67-81)
     float uv[2];
 };
 
-// TileTree::lookup_tile (tile_tree.rs:241-266)
-__device__ __forceinline__ Lookup lookup_tile(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, model::V3 world_position, uint32_t tree_lod) {
-    const model::Coordinate c = model::coordinate_from_world_position(world_position, P.model);
+// TileTree::lookup_tile (tile_tree.rs:241-266) from the coordinate of the world position on
+__device__ __forceinline__ Lookup lookup_tile_at(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, model::Coordinate c, uint32_t tree_lod) {
     const double tile_count = double(1u << tree_lod);
     const model::V2 t = model::compute_tree_xy(c, tile_count);
     const uint32_t ts = P.tree_size;
@@ -55,6 +58,23 @@ __device__ __forceinline__ Lookup lookup_tile(const TreeParams& P, const bt_tile
     const double div = double(1u << (tree_lod - e.atlas_lod));
     const double qx = t.x / div, qy = t.y / div;
     return {e.atlas_index, e.atlas_lod, {float(qx - trunc(qx)), float(qy - trunc(qy))}};  // `% 1.0`, as_vec2
+}
+__device__ __forceinline__ Lookup lookup_tile(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, model::V3 world_position, uint32_t tree_lod) {
+    return lookup_tile_at(P, entries, model::coordinate_from_world_position(world_position, P.model), tree_lod);
+}
+
+// The bilinear sample of a tile from texel space on (AttachmentData::sample, terrain_data/mod.rs:220-263), in three pieces shared by
+// sample_lookup and the tile normal (bt_normal_device.hpp): t = uv * T - 0.5 -> (rem, first texel); the clamped texel; the two lerps.
+__device__ __forceinline__ void texel_split(float t, float& rem, int& first) {
+    rem = fmodf(t, 1.0f);
+    first = int(t);
+}
+__device__ __forceinline__ uint32_t texel_clamp(int i, uint32_t T) { return uint32_t(min(max(i, 0), int(T) - 1)); }
+// v[x][y]: the four texels; rem[0] along x, rem[1] along y
+__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, float rem_x, float rem_y) {
+    const float a = v00 + (v01 - v00) * rem_y;
+    const float b = v10 + (v11 - v10) * rem_y;
+    return a + (b - a) * rem_x;
 }
 
 // AtlasAttachment::sample + AttachmentData::sample (tile_atlas.rs:249-258, terrain_data/mod.rs:220-263); the same
@@ -71,16 +91,14 @@ __device__ __forceinline__ void sample_lookup(const AttachmentMeta& m, const voi
 #pragma unroll
     for (int a = 0; a < 2; a++) {
         const float u = l.uv[a] * scale + offset;
-        const float uv = u * float(T) - 0.5f;
-        rem[a] = fmodf(uv, 1.0f);
-        ixy[a] = int(uv);
+        texel_split(u * float(T) - 0.5f, rem[a], ixy[a]);
     }
     float v[2][2][4];
 #pragma unroll
     for (int x = 0; x < 2; x++)
 #pragma unroll
         for (int y = 0; y < 2; y++) {
-            const uint32_t px = uint32_t(min(max(ixy[0] + x, 0), int(T) - 1)), py = uint32_t(min(max(ixy[1] + y, 0), int(T) - 1));
+            const uint32_t px = texel_clamp(ixy[0] + x, T), py = texel_clamp(ixy[1] + y, T);
             const uint64_t index = uint64_t(l.atlas_index) * T * T + uint64_t(py) * T + px;
             if (m.format == BT_FORMAT_R16) {
                 v[x][y][0] = unorm16_to_float(((const uint16_t*)atlas)[index]);
@@ -92,10 +110,21 @@ __device__ __forceinline__ void sample_lookup(const AttachmentMeta& m, const voi
             }
         }
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float a = v[0][0][k] + (v[0][1][k] - v[0][0][k]) * rem[1];
-        const float b = v[1][0][k] + (v[1][1][k] - v[1][0][k]) * rem[1];
-        r[k] = a + (b - a) * rem[0];
+    for (int k = 0; k < 4; k++) r[k] = bilerp(v[0][0][k], v[0][1][k], v[1][0][k], v[1][1][k], rem[0], rem[1]);
+}
+
+// TileTree::compute_blend (tile_tree.rs:223-239) of a surface position
+__device__ __forceinline__ void compute_blend(const TreeParams& P, model::V3 surface, uint32_t& lod, float& ratio) {
+    const double view_distance = model::distance3(P.view_world_position, surface);
+    const double cap = double(P.lod_count) - 0.00001;
+    const double l2 = log2(P.blend_distance / view_distance);
+    const float target_lod = float(l2 < cap ? l2 : cap);
+    lod = !(target_lod > 0.0f) ? 0u : uint32_t(target_lod);  // `as u32` saturates
+    ratio = 0.0f;
+    if (lod != 0) {  // inverse_mix(lod + blend_range, lod, target_lod) (util.rs:8-10)
+        const float a = float(lod) + P.blend_range, b = float(lod);
+        const float q = (target_lod - a) / (b - a);
+        ratio = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
     }
 }
 
@@ -103,18 +132,9 @@ __device__ __forceinline__ void sample_lookup(const AttachmentMeta& m, const voi
 // their samples and the blend.  surface = surface_position(model, sample position, approximate_height).
 __device__ __forceinline__ void sample_surface(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
                                                const void* __restrict__ atlas, model::V3 surface, float value[4]) {
-    // compute_blend (tile_tree.rs:223-239)
-    const double view_distance = model::distance3(P.view_world_position, surface);
-    const double cap = double(P.lod_count) - 0.00001;
-    const double l2 = log2(P.blend_distance / view_distance);
-    const float target_lod = float(l2 < cap ? l2 : cap);
-    const uint32_t lod = !(target_lod > 0.0f) ? 0u : uint32_t(target_lod);  // `as u32` saturates
-    float ratio = 0.0f;
-    if (lod != 0) {  // inverse_mix(lod + blend_range, lod, target_lod) (util.rs:8-10)
-        const float a = float(lod) + P.blend_range, b = float(lod);
-        const float q = (target_lod - a) / (b - a);
-        ratio = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
-    }
+    uint32_t lod;
+    float ratio;
+    compute_blend(P, surface, lod, ratio);
     sample_lookup(m, atlas, lookup_tile(P, entries, surface, lod), value);
     if (ratio > 0.0f) {
         float value2[4];

@@ -350,6 +350,20 @@ class TileAtlas:
             base += n * n
         return result
 
+    def tile_normals(self, attachment_index: int, coords) -> np.ndarray:
+        """bt_atlas_tile_normals: the tangent-space normal map of the centre texels of the listed tiles of an R16 attachment, for the
+        config's terrain model -> (n, c, c, 4) uint8: r, g, b = the normal's x, y, z as round(255 * (0.5 + 0.5 * v)), a = 255 where the
+        texel has data, (128, 128, 255, 0) where it has none.  Ordered behind the queued work; synchronous; a read."""
+        from .tile_tree import model_c
+        coords = list(coords)
+        a = self.config.attachments[attachment_index]
+        c = a.texture_size - 2 * a.border_size
+        arr = (_ffi.TileCoordinateC * max(len(coords), 1))(*[t._c() if hasattr(t, "_c") else _ffi.TileCoordinateC(*t) for t in coords])
+        out = np.zeros((len(coords), c, c, 4), dtype=np.uint8)
+        _ffi.check(_ffi.lib().bt_atlas_tile_normals(self._h, attachment_index, C.byref(model_c(self.config.model)), arr, len(coords),
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes))
+        return out
+
     def _edit_result(self, call) -> Tuple[List[TileCoordinate], dict]:
         """runs call(changed, cap, stats) and, if the list did not fit, is NOT run again: the first call sizes the list for any edit"""
         cap = max(self.atlas_size, 1)  # a call cannot write more tiles than the atlas has layers

@@ -114,9 +114,24 @@ class TileTree:
             out.ctypes.data_as(C.POINTER(C.c_float)), heights.ctypes.data_as(C.POINTER(C.c_float))))
         return out, heights
 
-    def raycast(self, attachment_index: int, origins, directions, t_min, t_max, steps: int = 256, refine_rounds: int = 2) -> np.ndarray:
+    def sample_normal(self, attachment_index: int, positions: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """bt_tile_tree_sample_normal: the world normals of the ground under a batch of world positions, the reference shader's (LOD blend
+        and best-loaded-tile fallback included), in one launch -> ((n, 3) float32 unit normals, (n,) float32 cosines of the slope against
+        the mesh normal); zeros for a position with a non-finite component."""
+        positions = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        n = len(positions)
+        normals = np.zeros((n, 3), np.float32)
+        up_dot = np.zeros(n, np.float32)
+        _ffi.check(_ffi.lib().bt_tile_tree_sample_normal(
+            self._h, self.atlas._h, attachment_index, positions.ctypes.data_as(C.POINTER(C.c_double)), n,
+            normals.ctypes.data_as(C.POINTER(C.c_float)), up_dot.ctypes.data_as(C.POINTER(C.c_float))))
+        return normals, up_dot
+
+    def raycast(self, attachment_index: int, origins, directions, t_min, t_max, steps: int = 256, refine_rounds: int = 2, normals: bool = False):
         """bt_tile_tree_raycast: one launch for the whole batch.  origins / directions (n, 3), t_min / t_max scalars or (n,); returns a
-        structured array (RAY_HIT_DTYPE): status (_ffi.RAY_*), step, t, t_above, position, height."""
+        structured array (RAY_HIT_DTYPE): status (_ffi.RAY_*), step, t, t_above, position, height.  normals=True: returns (hits, normals),
+        the second being sample_normal(attachment_index, hits["position"])[0] (one more launch; the position of a MISS or INVALID ray is
+        the zero vector and its row is whatever the ground under that point gives)."""
         origins = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
         n = len(origins)
         rays = np.zeros(n, RAY_DTYPE)
@@ -127,6 +142,8 @@ class TileTree:
         hits = np.zeros(n, RAY_HIT_DTYPE)
         _ffi.check(_ffi.lib().bt_tile_tree_raycast(self._h, self.atlas._h, attachment_index, rays.ctypes.data_as(C.POINTER(_ffi.RayC)), n, steps,
                                                    refine_rounds, hits.ctypes.data_as(C.POINTER(_ffi.RayHitC))))
+        if normals:
+            return hits, self.sample_normal(attachment_index, hits["position"])[0]
         return hits
 
     def approximate_height(self) -> float:
@@ -170,6 +187,11 @@ def sample_attachment(tile_tree: TileTree, tile_atlas: TileAtlas, attachment_ind
 
 def sample_height(tile_tree: TileTree, tile_atlas: TileAtlas, sample_world_position) -> float:
     return float(tile_tree.sample_attachment(0, np.asarray([sample_world_position]))[1][0])
+
+
+def sample_normal(tile_tree: TileTree, tile_atlas: TileAtlas, sample_world_position):
+    """the world normal of the ground (height attachment) under one world position, as a tuple"""
+    return tuple(float(v) for v in tile_tree.sample_normal(0, np.asarray([sample_world_position]))[0][0])
 
 
 def raycast_terrain(tile_tree: TileTree, tile_atlas: TileAtlas, origin, direction, max_distance: float, steps: int = 256, refine_rounds: int = 2):

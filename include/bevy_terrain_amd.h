@@ -170,7 +170,8 @@ bt_status bt_ctx_synchronize(bt_ctx* ctx);
 /* Gives back what the context keeps between queues: the device rasters finished queues released (kept so that the next queue's
  * sources need not be allocated again: 0.5 GB for a 16k R16 raster, six of 128 MB for a cube job; at most 8 buffers and 4 GiB) and
  * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds,
- * the device scratch of bt_tile_tree_raycast.
+ * the device scratch of bt_tile_tree_raycast, the device scratch of bt_tile_tree_sample_normal and bt_atlas_tile_normals (their pinned
+ * half is the staging buffers above).
  * Synchronises the context's stream first.  `freed_bytes` (may be NULL): device + pinned bytes released. */
 bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes);
 /* Host threads that write (bt_preprocessor_save / _run_streamed) and read (bt_atlas_load_tiles) tile files for this context.
@@ -982,6 +983,69 @@ typedef struct bt_ray_hit {
 } bt_ray_hit;
 bt_status bt_tile_tree_raycast(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_ray* rays, uint32_t count,
                                uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits_out);
+
+/* Surface normals ("which way does the ground face": collision response, slope limits and alignment of placed objects, slope-driven
+ * texturing).  The reference derives the normal only in its fragment shader (sample_normal, src/shaders/attachments.wgsl:51-107, blended
+ * over two LODs in render/fragment.wgsl:99-107); these two calls return that normal: bt_tile_tree_sample_normal for a batch of world
+ * positions, with the LOD blend and best-loaded-tile fallback of bt_tile_tree_sample_attachment, and bt_atlas_tile_normals as the
+ * tangent-space normal map of listed tiles.  Both evaluate ONE definition, in this order (IEEE binary32 unless marked f64, one rounding
+ * per written operation, no contraction):
+ *     dot3f(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *     norm3f(v)   : r = 1.0f / sqrtf(dot3f(v, v)); (v.x*r, v.y*r, v.z*r)
+ *     cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)
+ *
+ * TILE NORMAL s(layer L, lod, uv[2]) of an R16 attachment (T = texture_size, b = border_size, c = T - 2b) and a terrain model:
+ *     scale = f32(c) / f32(T); offset = f32(b) / f32(T); o = 0.5f / f32(c)   (the reference's 0.5 / attachments[0].size, size =
+ *             center_size, terrain_bind_group.rs:64, applied in texture uv: T / (2c) texels, the reference's choice)
+ *     u_a = uv_a * scale + offset
+ *     taps, in texture uv: left (u_x - o, u_y), up (u_x, u_y - o), right (u_x + o, u_y), down (u_x, u_y + o)
+ *     a tap (p, q): t_a = p_a * f32(T) - 0.5f; rem_a = fmodf(t_a, 1.0f); i_a = int(t_a) (truncating); texels
+ *             (clamp(i_x + x, 0, T-1), clamp(i_y + y, 0, T-1)) for x, y in {0, 1} of layer L, each converted by the exact unorm16 -> f32;
+ *             A = v00 + (v01 - v00) * rem_y; B = v10 + (v11 - v10) * rem_y; v = A + (B - A) * rem_x   (v[x][y]; the operations of
+ *             bt_tile_tree_sample_attachment's tile sample from uv * T - 0.5 on: one code)
+ *             (the kernels take rem_a as t_a - truncf(t_a), which is fmodf(t_a, 1.0f) for every finite t_a up to the sign of a zero, and
+ *             that sign does not reach v: a unorm value plus either zero is itself)
+ *     h = min_height + (max_height - min_height) * v
+ *     side_length = f32(model scale) for a planar model, (3.14159265359f / 4.0f) * f32(model scale) otherwise; the model scale is
+ *             TerrainModel::scale() in f64 (terrain_model.rs:183-193): side_length / 2 of a planar model, the radius of a sphere,
+ *             (major + minor) / 2 of an ellipsoid.  So a planar terrain's "side_length" is HALF its side: the reference's quirk, kept.
+ *     dist = side_length / (f32(c) * f32(1u << lod))
+ *     s = norm3f((h_left - h_right, h_down - h_up, dist))
+ *   L >= atlas_size (nothing loaded): s = (0, 0, 1).  Texels equal to 0 (no data) are read as heights, as the renderer reads them.
+ *
+ * WORLD NORMAL at world position p, with the tree's current state (view position, approximate height, entries):
+ *     1. f64, as bt_tile_tree_sample_attachment: local = position_world_to_local(model, p); surface = position_local_to_world(model,
+ *        local, approximate_height)
+ *     2. mesh normal: planar VN = (0, 1, 0); otherwise VN = f32(normalize3((local.x / scale.x, local.y / scale.y, local.z / scale.z)))
+ *        (f64, then cast): the reference's normal_local_to_world, local_from_world_transpose * local with identity rotation.  On an
+ *        ellipsoid this is NOT the direction along which heights displace the surface and bt_tile_tree_raycast measures altitude.
+ *     3. N = norm3f(VN)
+ *     4. planar: W(s) = (s.x, s.z, s.y).  Otherwise, side = the cube face of `surface` as lookup_tile sees it, face_up = (0, 1, 0) for
+ *        sides 0 and 1, (0, 0, -1) for 2 and 3, (-1, 0, 0) for 4 and 5 (attachments.wgsl:55-62): tan = cross(face_up, N); bit =
+ *        cross(N, tan); W(s)_k = (tan_k * s.x + bit_k * s.y) + N_k * s.z
+ *     5. (lod, ratio) = compute_blend(surface), as bt_tile_tree_sample_attachment
+ *     6. l1 = lookup_tile(surface, lod); n1 = norm3f(W(s(l1.atlas_index, l1.atlas_lod, l1.uv)))
+ *     7. ratio > 0: l2 = lookup_tile(surface, lod - 1), n2 likewise, n = n1 + (n2 - n1) * ratio per component; otherwise n = n1
+ *     8. out = norm3f(n) when dot3f(n, n) > 0, otherwise N
+ *     9. up_dot = dot3f(out, N): the cosine of the slope against the mesh normal
+ *    10. a position with a non-finite component: out = (0, 0, 0), up_dot = 0, decided before any lookup
+ *
+ * NORMAL MAP of a tile (side, lod, X, Y) held in layer L (raw texels S[row][column]), for its centre texel (i, j):
+ *     uv = ((f32(i) + 0.5f) / f32(c), (f32(j) + 0.5f) / f32(c)); s = s(L, lod, uv)
+ *     enc(v) = u8(floor(0.5f + 255.0f * clamp(0.5f + 0.5f * v, 0, 1))); bytes r, g, b = enc(s.x), enc(s.y), enc(s.z); a = 255 when
+ *     S[b + j][b + i] != 0, otherwise the texel is (128, 128, 255, 0).  Per entry of `coords`, in list order: c x c texels, j major, 4 bytes.
+ *
+ * Both calls: ordered behind the work queued on the context's stream; synchronous (host arrays in and out); a read (no layer is marked
+ * written for bt_run_stats.prev_zero_launches); scratch stays in the context until bt_ctx_trim.  count == 0: BT_OK, nothing touched.
+ * Non-R16 attachments: BT_ERR_UNSUPPORTED.  BT_ERR_INVALID_ARGUMENT, before anything is queued: NULL handles, NULL required arrays with
+ * count > 0, attachment_index out of range.  bt_tile_tree_sample_normal is one launch; out_up_dot may be NULL.
+ * bt_atlas_tile_normals also refuses, before any device work: a NULL or malformed model, out_bytes < count * c * c * 4, a coordinate with a
+ * bad side, lod or x / y or one the atlas holds no layer for (all BT_ERR_INVALID_ARGUMENT; out_host is left untouched), and an attachment
+ * with border_size 0 (BT_ERR_UNSUPPORTED: the taps of an edge texel need the neighbour's texels).  It runs one launch per 32 MiB of output. */
+bt_status bt_tile_tree_sample_normal(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const double* world_positions_xyz,
+                                     uint32_t count, float* out_normals_xyz /* 3 per position */, float* out_up_dot /* may be NULL */);
+bt_status bt_atlas_tile_normals(bt_atlas* atlas, uint32_t attachment_index, const bt_terrain_model* model, const bt_tile_coordinate* coords,
+                                uint32_t count, uint8_t* out_host, uint64_t out_bytes);
 
 /* One frame of one view (src/plugin.rs:46-56: TileTree::compute_requests -> TileAtlas::update's release / request half ->
  * TileTree::adjust_to_tile_atlas -> TileTree::approximate_height -> TilingPrepassNode::run) as ONE call with ONE host
