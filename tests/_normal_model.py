@@ -52,13 +52,16 @@ def stack_layers(layers, texture_size):
     return out
 
 
-def tap(stack, layer, p, q):
-    """one tap at texture uv (p, q) of layers `layer` (arrays of one length): steps 1 - 8 of the definition"""
+def tap(stack, layer, p, q, seen=None):
+    """one tap at texture uv (p, q) of layers `layer` (arrays of one length): steps 1 - 8 of the definition.  seen: a list that receives
+    which elements took the tap's edge paths (see edge_counts); the values do not depend on it"""
     T = stack.shape[1]
     p, q, layer = f32(p), f32(q), np.asarray(layer, dtype=np.int64)
     tx, ty = p * F(T) - F(0.5), q * F(T) - F(0.5)
     rx, ry = np.fmod(tx, F(1.0)), np.fmod(ty, F(1.0))
     ix, iy = np.trunc(tx).astype(np.int64), np.trunc(ty).astype(np.int64)
+    if seen is not None:
+        seen.append(dict(negative=(tx < 0) | (ty < 0), high=(ix + 1 > T - 1) | (iy + 1 > T - 1), minus_one=(ix == -1) | (iy == -1)))
 
     def texel(x, y):  # the exact unorm16 -> f32: the correctly rounded quotient
         raw = stack[layer, np.clip(iy + y, 0, T - 1), np.clip(ix + x, 0, T - 1)]
@@ -70,25 +73,31 @@ def tap(stack, layer, p, q):
     return a + (b - a) * rx
 
 
-def taps(stack, border_size, layer, uv, o=None):
+def taps(stack, border_size, layer, uv, o=None, seen=None):
     """the four taps (left, up, right, down) of centre uv (2 arrays); o: the offset in texture uv (default: the definition's 0.5 / c)"""
     T = stack.shape[1]
     c = T - 2 * border_size
     scale, offset = F(c) / F(T), F(border_size) / F(T)
     o = F(0.5) / F(c) if o is None else F(o)
     ux, uy = f32(uv[0]) * scale + offset, f32(uv[1]) * scale + offset
-    return tap(stack, layer, ux - o, uy), tap(stack, layer, ux, uy - o), tap(stack, layer, ux + o, uy), tap(stack, layer, ux, uy + o)
+    return tap(stack, layer, ux - o, uy, seen), tap(stack, layer, ux, uy - o, seen), tap(stack, layer, ux + o, uy, seen), tap(stack, layer, ux, uy + o, seen)
 
 
-def tile_normal(model, stack, border_size, layer, lod, uv):
-    """TILE NORMAL s for arrays of (layer, lod, uv); a layer >= len(stack) (nothing loaded) gives (0, 0, 1)"""
+def tile_normal(model, stack, border_size, layer, lod, uv, edges=None):
+    """TILE NORMAL s for arrays of (layer, lod, uv); a layer >= len(stack) (nothing loaded) gives (0, 0, 1).  edges: a dict whose
+    "negative" / "high" / "minus_one" arrays are or-ed with the elements that hold a layer and one of whose four taps has a negative
+    coordinate t / a pair first + 1 beyond T - 1 / a first texel of -1 after the truncation"""
     T = stack.shape[1]
     c = T - 2 * border_size
     layer, lod = np.asarray(layer, dtype=np.int64), np.asarray(lod, dtype=np.int64)
     held = layer < len(stack)
     safe_layer, safe_lod = np.where(held, layer, 0), np.where(held, lod, 0)
     lo, hi = F(model.min_height), F(model.max_height)
-    left, up, right, down = [lo + (hi - lo) * v for v in taps(stack, border_size, safe_layer, uv)]
+    seen = None if edges is None else []
+    left, up, right, down = [lo + (hi - lo) * v for v in taps(stack, border_size, safe_layer, uv, seen=seen)]
+    if edges is not None:
+        for name in ("negative", "high", "minus_one"):
+            edges[name] = edges[name] | (held & np.logical_or.reduce([t[name] for t in seen]))
     dist = side_length(model) / (F(c) * np.ldexp(F(1.0), safe_lod).astype(np.float32))
     s = norm3f([left - right, down - up, dist + np.zeros_like(left)])
     return [np.where(held, s[0], F(0.0)), np.where(held, s[1], F(0.0)), np.where(held, s[2], F(1.0))]
@@ -194,9 +203,11 @@ def world_normals(model, otree, approximate_height, texture_size, border_size, l
             return [s[0], s[2], s[1]]
         return [(tan[k] * s[0] + bit[k] * s[1]) + N[k] * s[2] for k in range(3)]
 
+    first = {name: np.zeros(n, bool) for name in ("negative", "high", "minus_one")}  # per position: the edge paths its taps took
+    second = {name: np.zeros(n, bool) for name in first}
     with np.errstate(all="ignore"):
-        n1 = norm3f(through_tbn(tile_normal(model, stack, border_size, look[0]["layer"], look[0]["lod"], (look[0]["u"], look[0]["v"]))))
-        n2 = norm3f(through_tbn(tile_normal(model, stack, border_size, look[1]["layer"], look[1]["lod"], (look[1]["u"], look[1]["v"]))))
+        n1 = norm3f(through_tbn(tile_normal(model, stack, border_size, look[0]["layer"], look[0]["lod"], (look[0]["u"], look[0]["v"]), edges=first)))
+        n2 = norm3f(through_tbn(tile_normal(model, stack, border_size, look[1]["layer"], look[1]["lod"], (look[1]["u"], look[1]["v"]), edges=second)))
         blended = [np.where(ratio > 0, n1[k] + (n2[k] - n1[k]) * ratio, n1[k]) for k in range(3)]
         unit = norm3f(blended)
         keep = dot3f(blended, blended) > 0
@@ -205,4 +216,5 @@ def world_normals(model, otree, approximate_height, texture_size, border_size, l
     normals = np.stack(out, axis=1).astype(np.float32)
     normals[~finite] = 0.0
     up_dot = np.where(finite, up_dot, F(0.0)).astype(np.float32)
-    return normals, up_dot, dict(ratio=ratio, side=side, layer=look[0]["layer"], lod=look[0]["lod"], N=np.stack(N, axis=1))
+    edges = {"tap_" + name: finite & (first[name] | (second[name] & (ratio > 0))) for name in first}  # the second lookup counts where it is blended in
+    return normals, up_dot, dict(ratio=ratio, side=side, layer=look[0]["layer"], lod=look[0]["lod"], N=np.stack(N, axis=1), **edges)

@@ -122,12 +122,12 @@ def assert_hits_equal(got, exp):
 class Streamed:
     """a terrain streamed into a device tree and the oracle's tree in lock step (the loop of test_streaming_loop_entries_and_heights)"""
 
-    def __init__(self, device, tmp_path, kind, frames=12):
+    def __init__(self, device, tmp_path, kind, frames=12, texture_size=T, border_size=B):
         self.model, self.omodel = MODELS[kind]
-        root, cfg, tiles = build_terrain(device, tmp_path, self.model, LODS, T, B)
+        root, cfg, tiles = build_terrain(device, tmp_path, self.model, LODS, texture_size, border_size)
         atlas_size = 256 if kind == "planar" else 512
         scfg = bt.TerrainConfig(lod_count=LODS, atlas_size=atlas_size, path=cfg.path, model=self.model)
-        scfg.add_attachment(bt.AttachmentConfig(name="height", texture_size=T, border_size=B, format=bt.AttachmentFormat.R16))
+        scfg.add_attachment(bt.AttachmentConfig(name="height", texture_size=texture_size, border_size=border_size, format=bt.AttachmentFormat.R16))
         self.atlas = bt.TileAtlas.new(scfg, device)
         self.atlas.load_tile_config(root)
         kw = dict(tree_size=4, load_distance=1.2, blend_distance=1.0)
@@ -152,7 +152,7 @@ class Streamed:
         known = coords[:, 1] != O.INVALID
         assert len(set(entries[known, 1])) >= 3  # the entries mix LODs ...
         assert (entries[known, 1] < coords[known, 1]).any()  # ... and some nodes fall back to an ancestor
-        self.sample = RM.sampler(self.otree, T, B, self.layers)
+        self.sample = RM.sampler(self.otree, texture_size, border_size, self.layers)
 
     def f(self, pts):
         """f(p) through the EXISTING device call: the model's altitude, the heights of tree.sample_attachment"""
