@@ -924,7 +924,9 @@ bt_status bt_tile_tree_read(bt_tile_tree* tree, bt_tile_tree_entry* entries, uin
 /* sample_height / sample_attachment (terrain_data/mod.rs:265-307) for a batch of world positions: surface projection,
  * TileTree::compute_blend (:223-239), lookup_tile (:241-266) at lod and lod - 1, bilinear tile samples
  * (AtlasAttachment::sample) and their blend, on the GPU against the tree's entries and the atlas in HBM.
- * out_vec4: 4 floats per position (the attachment value); heights (optional): lerp(min_height, max_height, value.x). */
+ * out_vec4: 4 floats per position (the attachment value: R16 -> (unorm16, 0, 0, 0), Rgba8 -> the four unorm8 channels, all through the
+ * same lerps); heights (optional, may be NULL): lerp(min_height, max_height, value.x).  Heights of an Rgba8 attachment equal
+ * lerp(min_height, max_height, red). */
 bt_status bt_tile_tree_sample_attachment(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index,
                                          const double* world_positions_xyz, uint32_t count, float* out_vec4, float* heights);
 /* TileTree::approximate_height (:376-386): sample_height at the view position of the last update; also kept by the tree

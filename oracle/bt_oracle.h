@@ -242,6 +242,8 @@ uint32_t orc_tile_tree_node_count(const orc_tile_tree* t);
 /* entries / node coordinates / node states in [side][lod][x][y] slot order; origins [side][lod][2] */
 void orc_tile_tree_read(const orc_tile_tree* t, orc_tree_entry* entries, uint32_t* origins, orc_coord* nodes, uint32_t* requested);
 void orc_tile_tree_set_approximate_height(orc_tile_tree* t, float h);
+/* the best-tile table as given, in orc_tile_tree_read's order: what adjust_to_tile_atlas would write from a stream in that state */
+void orc_tile_tree_set_entries(orc_tile_tree* t, const orc_tree_entry* entries);
 /* compute_blend (:223-239) */
 void orc_tile_tree_compute_blend(const orc_tile_tree* t, const double sample_world_position[3], uint32_t* lod, float* ratio);
 /* sample_attachment / sample_height (terrain_data/mod.rs:265-307).  layers[atlas_index] = level-0 texels of that slot

@@ -748,6 +748,11 @@ void orc_tile_tree_read(const orc_tile_tree* t, orc_tree_entry* entries, uint32_
     }
     if (origins) memcpy(origins, t->origins, (size_t)t->sides * t->lod_count * 2 * sizeof(uint32_t));
 }
+/* the best-tile table as given (a test's loaded set): what adjust_to_tile_atlas would write from a stream in that state */
+void orc_tile_tree_set_entries(orc_tile_tree* t, const orc_tree_entry* entries) {
+    uint32_t n = orc_tile_tree_node_count(t);
+    for (uint32_t i = 0; i < n; i++) t->data[i] = entries[i];
+}
 
 /* util.rs:8-10 */
 static float inverse_mix(float a, float b, float value) {

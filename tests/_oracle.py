@@ -201,6 +201,8 @@ def lib():
     L.orc_tile_tree_node_count.restype = u32
     L.orc_tile_tree_read.argtypes = [vp, vp, vp, vp, vp]
     L.orc_tile_tree_read.restype = None
+    L.orc_tile_tree_set_entries.argtypes = [vp, vp]
+    L.orc_tile_tree_set_entries.restype = None
     L.orc_tile_tree_set_approximate_height.argtypes = [vp, C.c_float]
     L.orc_tile_tree_set_approximate_height.restype = None
     L.orc_tile_tree_compute_blend.argtypes = [vp, dp, C.POINTER(u32), C.POINTER(C.c_float)]
@@ -547,6 +549,11 @@ class TileTree:
         requested = np.zeros(self.nodes, np.uint32)
         lib().orc_tile_tree_read(self._h, _np_ptr(entries), _np_ptr(origins), _np_ptr(coords), _np_ptr(requested))
         return entries, origins, coords, requested
+
+    def set_entries(self, entries):
+        """the best-tile table as given: (nodes, 2) u32 = (atlas_index, atlas_lod) in the table's order"""
+        entries = np.ascontiguousarray(entries, dtype=np.uint32).reshape(self.nodes, 2)
+        lib().orc_tile_tree_set_entries(self._h, _np_ptr(entries))
 
     def set_approximate_height(self, h):
         lib().orc_tile_tree_set_approximate_height(self._h, C.c_float(h))

@@ -7,7 +7,11 @@ numpy array operations instead of replayed pushes and per-node loops — so that
   TileTreeModel                        terrain_data/tile_tree.rs:175-333 + math/coordinate.rs:69-160 + math/terrain_model.rs:130-153
   generate_mipmaps                     terrain_data/mod.rs:143-219
   tc_encode                            formats/mod.rs:8-35 (bincode 2 `config::standard()`: little endian, variable-length integers)
+  sample_attachment (+ its trace)      terrain_data/mod.rs:220-307 + tile_tree.rs:223-266 + tile_atlas.rs:249-258, R16 and Rgba8
+  StreamModel                          terrain_data/tile_atlas.rs:300-500
 """
+import collections
+
 import numpy as np
 
 INVALID = 0xFFFFFFFF
@@ -91,7 +95,7 @@ def _saturating_u32(x):
 
 class TileTreeModel:
     """TileTree::update (tile_tree.rs:268-333) on whole tables.  kind: "planar" (scale = side length) or "sphere" (scale = radius);
-    an ellipsoid (scale = (a, b, a)) takes its view coordinate from outside (the projection onto the ellipsoid is not restated here)."""
+    an ellipsoid (scale = (a, b, a)) takes its view coordinate, or `project` (the projection onto the ellipsoid, not restated here), from outside."""
 
     def __init__(self, kind, position, scale, min_height, max_height, lod_count, tree_size, load_distance):
         self.kind, self.t = kind, np.asarray(position, np.float64)
@@ -106,13 +110,31 @@ class TileTreeModel:
         self.coords = np.full((self.sides, lod_count, tree_size, tree_size, 4), INVALID, np.uint32)
         self.requested = np.zeros((self.sides, lod_count, tree_size, tree_size), bool)
         self.origins = np.zeros((self.sides, lod_count, 2), np.uint32)
+        self.project = None  # ellipsoid only: project_point_ellipsoid(e, y) (math/ellipsoid.rs), supplied by the caller
 
     # Coordinate::from_world_position (coordinate.rs:69-107) for the planar and the spherical model
+    def local_position(self, p):
+        """TerrainModel::position_world_to_local (terrain_model.rs:144-169)"""
+        p = np.asarray(p, np.float64)
+        if self.kind == "ellipsoid":  # the closest point of the ellipsoid (major, major, minor) to p - translation: self.project, from outside
+            p = np.asarray(self.project(tuple((self.scale[0], self.scale[0], self.scale[1])), tuple(p - self.t)), np.float64)
+        local = (p - self.t) / self.scale
+        if not self.spherical:
+            return np.array([1.0, 0.0, 1.0]) * local
+        return local * (1.0 / np.sqrt(local[0] * local[0] + local[1] * local[1] + local[2] * local[2]))
+
+    def clamped(self, p):
+        """planar: Coordinate::from_world_position's clamp of the uv to [0, 1] changes it"""
+        if self.spherical:
+            return False
+        local = self.local_position(p)
+        return bool(local[0] + 0.5 < 0.0 or local[0] + 0.5 > 1.0 or local[2] + 0.5 < 0.0 or local[2] + 0.5 > 1.0)
+
     def view_coordinate(self, p):
-        local = (np.asarray(p, np.float64) - self.t) / self.scale
+        local = self.local_position(p)
         if not self.spherical:
             return 0, np.clip(np.array([local[0] + 0.5, local[2] + 0.5]), 0.0, 1.0)
-        n = local * (1.0 / np.sqrt(local[0] * local[0] + local[1] * local[1] + local[2] * local[2]))
+        n = local
         a = np.abs(n)
         if a[0] > a[1] and a[0] > a[2]:
             side, uv = (0, np.array([-n[2] / n[0], n[1] / n[0]])) if n[0] < 0.0 else (3, np.array([-n[1] / n[0], n[2] / n[0]]))
@@ -238,66 +260,131 @@ def tc_encode(tiles):
 
 
 # ------------------------------------------------------------------------------------------------ sample_attachment (f4)
-def sample_attachment_r16(model, view_position, approximate_height, blend_distance, blend_range, lod_count, entries, layers, T, b, positions):
-    """sample_attachment / sample_height (terrain_data/mod.rs:265-307) of an R16 attachment for the planar and the spherical model, one
-    sample at a time in the reference's order: surface_position (terrain_model.rs:130-173), compute_blend and lookup_tile
-    (tile_tree.rs:223-266), AtlasAttachment::sample (tile_atlas.rs:249-258) and AttachmentData::sample (terrain_data/mod.rs:220-257).
-    model: a TileTreeModel (its transform and cube-sphere warp); entries: (sides, lods, tree, tree, 2) u32 = (atlas_index, atlas_lod);
-    layers: {atlas_index: (T, T) u16}.  Returns ((n, 4) f32 values, (n,) f32 heights; min / max height from `model.heights`)."""
+FORMAT_RGBA8, FORMAT_R16 = 0, 1  # AttachmentFormat ids (the values of include/bevy_terrain_amd.h)
+INVALID_LOD = 0xFFFFFFFF
+
+# one lookup_tile of a sample: the entry it read, how many levels above the node's own LOD that tile is (None: no loaded ancestor),
+# the slot of the node table it read (the tile's coordinate % tree_size), the first of the 2 x 2 texels (None without a tile), and
+# the tile's coordinate itself (the slot differs from it where the table wraps)
+Lookup = collections.namedtuple("Lookup", "atlas_index atlas_lod depth slot_x slot_y ix iy tile_x tile_y")
+# one sample: side and uv of its coordinate, the f64 log2 compute_blend took, lod / target_lod / ratio, its one or two lookups, and
+# whether the planar clamp of the coordinate to [0, 1] changed it
+Trace = collections.namedtuple("Trace", "side uv l2 lod target_lod ratio lookups clamped")
+
+
+def blend_of_l2(l2, lod_count, blend_range):
+    """TileTree::compute_blend (tile_tree.rs:223-239) from the f64 log2 on -> (target_lod f32, lod, ratio f32, l2 < cap, target > 0)"""
     f32 = np.float32
-    INVALID_LOD = 0xFFFFFFFF
+    cap = float(lod_count) - 0.00001
+    below = bool(l2 < cap)
+    target = f32(l2 if below else cap)
+    positive = bool(target > 0)
+    lod = int(target) if positive else 0  # `as u32`
+    ratio = f32(0.0)
+    if lod != 0:  # inverse_mix(lod + blend_range, lod, target_lod) (util.rs:8-10)
+        a, c = f32(lod) + f32(blend_range), f32(lod)
+        ratio = f32(min(max(f32(f32(target - a) / f32(c - a)), f32(0.0)), f32(1.0)))
+    return target, lod, ratio, below, positive
+
+
+def blend_is_admissible(l2, lod_count, blend_range, steps=2):
+    """True when a log2 up to `steps` representable doubles away from l2 on either side gives the same f32 target_lod, the same verdicts
+    of `< cap` and `> 0`, the same lod and the same bits of the clamped ratio: the platform's log2 (at most 1 ulp from libm's) cannot
+    change the sample."""
+    key = lambda r: (r[0].tobytes(), r[1], r[2].tobytes(), r[3], r[4])
+    here = key(blend_of_l2(l2, lod_count, blend_range))
+    for direction in (-np.inf, np.inf):
+        x = np.float64(l2)
+        for _ in range(steps):
+            x = np.nextafter(x, direction)
+            if key(blend_of_l2(float(x), lod_count, blend_range)) != here:
+                return False
+    return True
+
+
+def surface_position(model, p, height):
+    """TerrainModel::surface_position (terrain_model.rs:130-180): p onto the terrain's shape, then `height` along the normal"""
+    local = model.local_position(p)  # position_world_to_local
+    direction = local * model.scale if model.spherical else np.array([0.0, 1.0, 0.0]) * model.scale
+    world = local * model.scale + model.t
+    normal = direction * (1.0 / np.sqrt(direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2]))
+    return world + np.float64(height) * normal
+
+
+def blend_log2(view_position, blend_distance, surface):
+    """the f64 log2(blend_distance / view_distance) of compute_blend for a surface position (numpy's log2: the C library's)"""
+    d = surface - np.asarray(view_position, np.float64)
+    view_distance = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    with np.errstate(divide="ignore"):
+        return float(np.log2(np.float64(blend_distance) / view_distance))
+
+
+def sample_attachment(fmt, model, view_position, approximate_height, blend_distance, blend_range, lod_count, entries, layers, T, b, positions):
+    """sample_attachment / sample_height (terrain_data/mod.rs:265-307) of an R16 or Rgba8 attachment, one sample at a time in the
+    reference's order: surface_position (terrain_model.rs:130-173), compute_blend and lookup_tile (tile_tree.rs:223-266),
+    AtlasAttachment::sample (tile_atlas.rs:249-258) and AttachmentData::sample (terrain_data/mod.rs:220-257).  An R16 texel is
+    f32(t) / 65535 in channel 0 (the others 0), an Rgba8 texel f32(byte) / 255 per channel; all four channels take the same lerps.
+    model: a TileTreeModel (its transform and cube-sphere warp; an ellipsoid needs model.project, the closest point on the ellipsoid,
+    which is NOT restated here); entries: (sides, lods, tree, tree, 2) u32 = (atlas_index, atlas_lod); layers: {atlas_index: (T, T) u16
+    or (T, T, 4) u8}.  Returns ((n, 4) f32 values, (n,) f32 heights = lerp(min_height, max_height, values[:, 0]) with min / max from
+    `model.heights`, a Trace per sample), every field of the trace from this function's own arithmetic."""
+    f32 = np.float32
     view = np.asarray(view_position, np.float64)
     scale, offset = f32(T - 2 * b) / f32(T), f32(b) / f32(T)
     ts = entries.shape[2]
+    unit = f32(65535.0) if fmt == FORMAT_R16 else f32(255.0)
 
-    def surface(p):
-        local = (np.asarray(p, np.float64) - model.t) / model.scale  # local_from_world
-        if model.spherical:
-            local = local * (1.0 / np.sqrt(local[0] * local[0] + local[1] * local[1] + local[2] * local[2]))
-            direction = local * model.scale
+    def lerp(a, c, t):  # Vec4::lerp / f32::lerp, per channel
+        return (a + (c - a) * t).astype(f32)
+
+    def texel(data, x, y):
+        x, y = min(max(x, 0), T - 1), min(max(y, 0), T - 1)  # (the library and the oracle clamp where the reference would index out of the tile)
+        v = np.zeros(4, f32)
+        if fmt == FORMAT_R16:
+            v[0] = f32(data[y, x]) / unit
         else:
-            local = np.array([1.0, 0.0, 1.0]) * local
-            direction = np.array([0.0, 1.0, 0.0]) * model.scale
-        world = local * model.scale + model.t
-        normal = direction * (1.0 / np.sqrt(direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2]))
-        return world + np.float64(approximate_height) * normal
-
-    def lerp(a, c, t):  # Vec4::lerp / f32::lerp
-        return f32(a + f32(f32(c - a) * t))
+            v[:] = data[y, x].astype(f32) / unit
+        return v
 
     def lookup_and_sample(p, lod):
         side, uv = model.view_coordinate(p)
         count = float(1 << lod)
         tree_xy = np.minimum(uv * count, count - 0.000001)
-        index, atlas_lod = entries[side, lod, int(tree_xy[0]) % ts, int(tree_xy[1]) % ts]
-        if atlas_lod == INVALID_LOD or index == 0xFFFFFFFF:
-            return f32(0.0)
-        atlas_uv = np.fmod(tree_xy / float(1 << (lod - int(atlas_lod))), 1.0).astype(f32)
-        uv32 = atlas_uv * scale + offset
-        uvs = uv32 * f32(T) - f32(0.5)
+        tx, ty = int(tree_xy[0]), int(tree_xy[1])
+        index, atlas_lod = (int(v) for v in entries[side, lod, tx % ts, ty % ts])
+        if atlas_lod == INVALID_LOD or index == INVALID:
+            return np.zeros(4, f32), Lookup(index, atlas_lod, None, tx % ts, ty % ts, None, None, tx, ty)
+        atlas_uv = np.fmod(tree_xy / float(1 << (lod - atlas_lod)), 1.0).astype(f32)
+        uvs = (atlas_uv * scale + offset) * f32(T) - f32(0.5)
         rem = np.fmod(uvs, f32(1.0))
         ix, iy = int(uvs[0]), int(uvs[1])  # as_ivec2 truncates
-        data = layers[int(index)].reshape(-1)
-        v = [[f32(data[(iy + y) * T + ix + x]) / f32(65535.0) for y in range(2)] for x in range(2)]
-        return lerp(lerp(v[0][0], v[0][1], rem[1]), lerp(v[1][0], v[1][1], rem[1]), rem[0])
+        data = layers[index]
+        v = [[texel(data, ix + x, iy + y) for y in range(2)] for x in range(2)]
+        value = lerp(lerp(v[0][0], v[0][1], rem[1]), lerp(v[1][0], v[1][1], rem[1]), rem[0])
+        return value, Lookup(index, atlas_lod, lod - atlas_lod, tx % ts, ty % ts, ix, iy, tx, ty)
 
     values = np.zeros((len(positions), 4), f32)
+    trace = []
     for i, p in enumerate(positions):
-        s = surface(p)
-        d = s - view
-        view_distance = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
-        target = f32(min(np.log2(blend_distance / view_distance), float(lod_count) - 0.00001))
-        lod = 0 if not target > 0 else int(target)
-        value = lookup_and_sample(s, lod)
-        if lod != 0:
-            a, c = f32(lod) + f32(blend_range), f32(lod)
-            ratio = f32(f32(target - a) / f32(c - a))
-            ratio = f32(min(max(ratio, f32(0.0)), f32(1.0)))
-            if ratio > 0:
-                value = lerp(value, lookup_and_sample(s, lod - 1), ratio)
-        values[i, 0] = value
+        s = surface_position(model, p, approximate_height)
+        l2 = blend_log2(view, blend_distance, s)
+        target, lod, ratio, _, _ = blend_of_l2(l2, lod_count, blend_range)
+        value, first = lookup_and_sample(s, lod)
+        lookups = [first]
+        if ratio > 0:
+            value2, second = lookup_and_sample(s, lod - 1)
+            value = lerp(value, value2, ratio)
+            lookups.append(second)
+        values[i] = value
+        side, uv = model.view_coordinate(s)
+        trace.append(Trace(side, (float(uv[0]), float(uv[1])), l2, lod, target, ratio, lookups, model.clamped(p)))
     lo, hi = f32(model.heights[0]), f32(model.heights[1])
-    return values, (lo + f32(hi - lo) * values[:, 0]).astype(f32)
+    return values, (lo + f32(hi - lo) * values[:, 0]).astype(f32), trace
+
+
+def sample_attachment_r16(model, view_position, approximate_height, blend_distance, blend_range, lod_count, entries, layers, T, b, positions):
+    """sample_attachment of an R16 attachment -> (values, heights)"""
+    return sample_attachment(FORMAT_R16, model, view_position, approximate_height, blend_distance, blend_range, lod_count, entries, layers, T, b, positions)[:2]
 
 
 # ------------------------------------------------------------------------------------------------ streaming state machine
@@ -346,10 +433,13 @@ class StreamModel:
     def pending_loads(self):
         return len(self.to_load)
 
-    def finish_loads(self, n):
+    def finish_loads(self, n, missing=()):
+        """the next n queued loads; one of a tile in `missing` (no file) returns its load slot and leaves the tile Loading (:202-204)"""
         done = []
         for _ in range(n):
             c, index, a = self.to_load.popleft()
+            if c in missing:
+                continue
             st = self.states[c]
             st[1] -= 1
             done.append((c, index))

@@ -343,11 +343,14 @@ def test_degenerate_inputs(device):
         assert int(a.download_tile(0, 0)[8, 8]) == 12345
 
 
+@pytest.mark.parametrize("T,b", [(32, 2), (20, 1), (12, 0), (16, 4)])
 @pytest.mark.parametrize("fmt", [O.FORMAT_R16, O.FORMAT_RGBA8])
-def test_atlas_sample_matches_the_cpu_sampling(device, fmt):
+def test_atlas_sample_matches_the_cpu_sampling(device, fmt, T, b):
     """SURVEY §8f row 4, the atlas half: TileAtlas::sample_attachment as a batched query on the tiles in HBM ==
-    the reference's CPU sampling (oracle restatement) bit for bit, INVALID lookups give zero."""
-    T, b = 32, 2
+    the reference's CPU sampling (oracle restatement) bit for bit, INVALID lookups give zero.  Tile shapes: the usual one, the reference's
+    default border (1), no border (only there the first or the second texel of a tap leaves the tile and is clamped to 0 or T - 1), and a
+    border a quarter of the tile.  uv stays inside [0, 1] (outside it `int(uv)` of the CPU sampling is undefined) and meets 0 and 1 exactly
+    on each axis, alone and together."""
     src = K.random_raster(fmt, 200, 200, seed=41)
     atlas, _ = K.product_planar(device, src, 3, T, b, fmt)
     rng = np.random.default_rng(9)
@@ -355,6 +358,10 @@ def test_atlas_sample_matches_the_cpu_sampling(device, fmt):
     idx = rng.integers(0, 21, size=n).astype(np.uint32)
     uv = rng.random((n, 2), dtype=np.float32)
     uv[:8] = [[0, 0], [1, 1], [0, 1], [1, 0], [0.5, 0.5], [1e-7, 0.999999], [0.25, 0.75], [0.999, 0.001]]
+    uv[8:16, 0], uv[16:24, 0], uv[24:32, 1], uv[32:40, 1] = 0.0, 1.0, 0.0, 1.0  # exactly on each of the four sides, anywhere along it
+    uv[40:56] = 1.0 - rng.random((16, 2), dtype=np.float32) * np.float32(0.4 / T)  # within the last half texel of both axes
+    uv[56:72] = rng.random((16, 2), dtype=np.float32) * np.float32(0.4 / T)  # within the first
+    assert uv.min() == 0.0 and uv.max() == 1.0
     idx[-1] = 0xFFFFFFFF
     ours = atlas.sample(0, idx, uv)
     tiles = atlas.download_tiles(0, 0, 21)
@@ -362,8 +369,21 @@ def test_atlas_sample_matches_the_cpu_sampling(device, fmt):
         exp = O.sample_tile(fmt, b, tiles[idx[i]], uv[i])
         assert np.array_equal(ours[i], exp), (i, idx[i], uv[i], ours[i], exp)
     assert np.array_equal(ours[-1], np.zeros(4, np.float32))
+    # the texel clamp, from the oracle's arithmetic (orc_sample_tile: t = (uv * (T - 2 b) / T + b / T) * T - 0.5 in f32, first texel int(t)):
+    # without a border the second texel of a tap is T (clamped to T - 1) near uv = 1; with one no tap leaves the tile
+    f32 = np.float32
+    t = (uv[:-1] * (f32(T - 2 * b) / f32(T)) + f32(b) / f32(T)) * f32(T) - f32(0.5)
+    first = t.astype(np.int32)  # truncation
+    clamped_high = int(((first + 1 == T).any(axis=1)).sum())
+    clamped_low = int(((t < 0).any(axis=1)).sum())  # (first == 0 for -0.5 <= t < 0: no clamp of the index, a negative remainder)
     if fmt == O.FORMAT_R16:  # sample_height = lerp(min_height, max_height, value.x): heights stay inside the texel range
-        assert ours[:-1, 0].min() >= tiles.min() / 65535.0 - 1e-6 and ours[:-1, 0].max() <= tiles.max() / 65535.0 + 1e-6
+        inside = (t >= 0).all(axis=1)  # (t < 0, without a border only: the remainder is negative and the reference's lerp extrapolates)
+        assert inside.all() or b == 0
+        assert ours[:-1, 0][inside].min() >= tiles.min() / 65535.0 - 1e-6 and ours[:-1, 0][inside].max() <= tiles.max() / 65535.0 + 1e-6
+    if b == 0:
+        assert clamped_high >= 8 and clamped_low >= 8, (clamped_high, clamped_low)
+    else:
+        assert clamped_high == 0 and clamped_low == 0 and first.min() >= 0 and first.max() + 1 <= T - 1
 
 
 @pytest.mark.parametrize("lod_count,T,W", [(1, 64, 100), (2, 64, 150), (8, 16, 1600)])
