@@ -144,6 +144,15 @@ class RayHitC(C.Structure):
                 ("height", C.c_float), ("_padding", C.c_uint32)]
 
 
+GEOMETRY_GRID, GEOMETRY_NO_MORPH, GEOMETRY_NO_BLEND = 1, 2, 4
+GEOMETRY_MAX_GRID = 32
+
+
+class TerrainVertexC(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("height", C.c_float), ("normal", C.c_float * 3), ("tile_index", C.c_uint32),
+                ("coordinate_uv", C.c_float * 2), ("view_distance", C.c_float), ("blend_ratio", C.c_float)]
+
+
 class CullViewC(C.Structure):
     _fields_ = [("planes", (C.c_float * 4) * 5), ("plane_count", C.c_uint32), ("margin", C.c_float), ("min_height", C.c_float),
                 ("max_height", C.c_float)]
@@ -319,6 +328,8 @@ PROTOTYPES = {
     "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
     "bt_tile_tree_sample_normal": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_float), _P(C.c_float)]),
     "bt_atlas_tile_normals": (_i32, [_vp, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(C.c_uint8), _u64]),
+    "bt_tile_tree_build_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _vp, _u32, _vp, _u64]),
+    "bt_tile_tree_tile_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _P(TileCoordinateC), _u32, _u32, _P(TerrainVertexC), _u64]),
     "bt_frame_update": (_i32, [_vp, _vp, _vp, _P(C.c_double), C.c_uint32, _P(FrameInfoC)]),
     "bt_selftest": (_i32, [_vp, _P(_u32)]),
     "bt_synth_fbm_r16": (_i32, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _u32, _u32]),

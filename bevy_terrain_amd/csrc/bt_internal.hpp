@@ -448,4 +448,6 @@ namespace bt {
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain
 bt_status tiling_prepass_enqueue(bt_tiling_prepass* t, const bt_view_state* view, const float* device_height, uint32_t form);
 bt_ctx* tiling_prepass_ctx(const bt_tiling_prepass* t);  // the context (stream) its kernels run on
+// the final tile list on the device, the word that holds its length (as the last run left it) and the buffer's capacity in tiles
+void tiling_prepass_final(const bt_tiling_prepass* t, const bt_tile_coordinate** final_tiles, const uint32_t** final_count, uint32_t* capacity);
 }  // namespace bt

@@ -16,6 +16,7 @@
 // Arithmetic contract: IEEE binary32, one rounding per written operation (-ffp-contract=off), same
 // operation order as oracle/bt_oracle.c (functions.wgsl:14-29,73-96,117-188).
 #include "bt_internal.hpp"
+#include "bt_surface_device.hpp"  // Coordinate, coordinate_change_lod, length3, SurfacePoint, tile_surface
 
 struct bt_tiling_prepass {
     bt_ctx* ctx = nullptr;
@@ -41,89 +42,6 @@ namespace {
 
 constexpr uint32_t kThreads = 1024;
 constexpr uint32_t kWaves = kThreads / 64;
-
-struct Coordinate {  // types.wgsl:31-40
-    uint32_t side, lod, x, y;
-    float u, v;
-};
-
-// functions.wgsl:164-188; pow(2.0, f32(d)) is exact (ldexpf)
-__device__ __forceinline__ void coordinate_change_lod(Coordinate& c, uint32_t new_lod) {
-    const int d = int(new_lod) - int(c.lod);
-    if (d == 0) return;
-    const uint32_t delta_count = 1u << uint32_t(d < 0 ? -d : d);
-    const float delta_size = ldexpf(1.0f, d);
-    c.lod = new_lod;
-    if (d > 0) {
-        const float su = c.u * delta_size, sv = c.v * delta_size;
-        c.x = c.x * delta_count + uint32_t(su);
-        c.y = c.y * delta_count + uint32_t(sv);
-        c.u = su - truncf(su);
-        c.v = sv - truncf(sv);
-    } else {
-        const uint32_t x = c.x, y = c.y, sh = uint32_t(-d);  // delta_count = 2^sh: quotient and remainder by shift and mask
-        c.x = x >> sh;
-        c.y = y >> sh;
-        c.u = (float(x & (delta_count - 1u)) + c.u) * delta_size;
-        c.v = (float(y & (delta_count - 1u)) + c.v) * delta_size;
-    }
-}
-
-__device__ __forceinline__ float length3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
-
-// A point of a tile's surface and the normal there: compute_local_position (functions.wgsl:73-96) of the tile coordinate (u, w) =
-// (tile xy + uv) / tile_count, then position_local_to_world / normal_local_to_world (:117-121).  point(tile, uv, h) = world + h * normal:
-// the divide test's and the culling test's (include/bevy_terrain_amd.h).  l is the local position itself (the unit sphere's when spherical):
-// the horizon test works from it.
-struct SurfacePoint {
-    float wx, wy, wz, nx, ny, nz, lx, ly, lz;
-};
-
-__device__ __forceinline__ SurfacePoint tile_surface(const bt_view_state& v, uint32_t side, float u, float w) {
-    float lx, ly, lz;
-    if (v.spherical) {
-        const float C_SQR = 0.87f * 0.87f;
-        u = (u - 0.5f) * 2.0f;
-        w = (w - 0.5f) * 2.0f;
-        u = u / sqrtf(1.0f + C_SQR - C_SQR * u * u);
-        w = w / sqrtf(1.0f + C_SQR - C_SQR * w * w);
-        switch (side) {
-            case 0: lx = -1.0f; ly = -w; lz = u; break;
-            case 1: lx = u; ly = -w; lz = 1.0f; break;
-            case 2: lx = u; ly = 1.0f; lz = w; break;
-            case 3: lx = 1.0f; ly = -u; lz = w; break;
-            case 4: lx = w; ly = -u; lz = -1.0f; break;
-            case 5: lx = w; ly = -1.0f; lz = u; break;
-            default: lx = ly = lz = 0.0f; break;
-        }
-        const float l = length3(lx, ly, lz);
-        lx = lx / l;
-        ly = ly / l;
-        lz = lz / l;
-    } else {
-        lx = u - 0.5f;
-        ly = 0.0f;
-        lz = w - 0.5f;
-    }
-    SurfacePoint p;
-    const float* m = v.world_from_local;  // 3 columns + translation
-    p.wx = (m[0] * lx + m[3] * ly + m[6] * lz) + m[9];
-    p.wy = (m[1] * lx + m[4] * ly + m[7] * lz) + m[10];
-    p.wz = (m[2] * lx + m[5] * ly + m[8] * lz) + m[11];
-    const float nx0 = v.spherical ? lx : 0.0f, ny0 = v.spherical ? ly : 1.0f, nz0 = v.spherical ? lz : 0.0f;
-    const float* t = v.local_from_world_transpose;
-    const float nx = t[0] * nx0 + t[3] * ny0 + t[6] * nz0;
-    const float ny = t[1] * nx0 + t[4] * ny0 + t[7] * nz0;
-    const float nz = t[2] * nx0 + t[5] * ny0 + t[8] * nz0;
-    const float nl = length3(nx, ny, nz);
-    p.nx = nx / nl;
-    p.ny = ny / nl;
-    p.nz = nz / nl;
-    p.lx = lx;
-    p.ly = ly;
-    p.lz = lz;
-    return p;
-}
 
 // refine_tiles.wgsl:17-22 -> compute_subdivision_coordinate (functions.wgsl:133-154) ->
 // approximate_view_distance (:117-131) -> compute_local_position (:73-96)
@@ -646,6 +564,11 @@ using namespace bt;
 
 namespace bt {
 bt_ctx* tiling_prepass_ctx(const bt_tiling_prepass* t) { return t ? t->ctx : nullptr; }
+void tiling_prepass_final(const bt_tiling_prepass* t, const bt_tile_coordinate** final_tiles, const uint32_t** final_count, uint32_t* capacity) {
+    *final_tiles = t->final_tiles;
+    *final_count = t->counters;  // counters[0]: what prepare_render counted (it may exceed the capacity after an overflow)
+    *capacity = t->capacity;
+}
 }  // namespace bt
 
 extern "C" {

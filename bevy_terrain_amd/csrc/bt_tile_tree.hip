@@ -670,6 +670,150 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
 }
 
 namespace {
+// what both geometry calls refuse before any device work, and what they hand the kernel: the tree's parameters (TerrainViewConfigUniform:
+// the f64 distances x TerrainModel::scale(), `as f32`) and the view (the caller's, or the tree's own)
+bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, uint32_t flags, GeometryParams* G, bt_view_state* v) {
+    if (!t || !a) {
+        set_error("%s: NULL %s", who, t ? "atlas" : "tile tree");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (t->ctx != a->ctx) {
+        set_error("%s: tile tree and atlas belong to different contexts", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (ai >= a->attachments.size()) {
+        set_error("%s: attachment index %u out of range", who, ai);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (flags & ~uint32_t(BT_GEOMETRY_GRID | BT_GEOMETRY_NO_MORPH | BT_GEOMETRY_NO_BLEND)) {
+        set_error("%s: unknown flags 0x%x", who, flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (a->attachments[ai].meta.format != BT_FORMAT_R16) {
+        set_error("%s: attachment %u is not R16", who, ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    const bt_terrain_view_config& vc = t->view_config;
+    if (vc.grid_size == 0u || vc.grid_size > uint32_t(BT_GEOMETRY_MAX_GRID)) {
+        set_error("%s: grid_size %u (1 .. %u)", who, vc.grid_size, unsigned(BT_GEOMETRY_MAX_GRID));
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!(flags & BT_GEOMETRY_NO_MORPH) && !(std::isfinite(vc.morph_range) && vc.morph_range > 0.0f)) {
+        set_error("%s: morph_range %g (finite, > 0, or BT_GEOMETRY_NO_MORPH)", who, double(vc.morph_range));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(flags & BT_GEOMETRY_NO_BLEND) && !(std::isfinite(vc.blend_range) && vc.blend_range > 0.0f)) {
+        set_error("%s: blend_range %g (finite, > 0, or BT_GEOMETRY_NO_BLEND)", who, double(vc.blend_range));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (view) {
+        *v = *view;
+    } else if (bt_status s = bt_tile_tree_view_state(t, v)) {
+        return s;
+    }
+    if ((v->spherical ? 6u : 1u) != t->sides) {
+        set_error("%s: a view of %u side(s) for a tile tree of %u", who, v->spherical ? 6u : 1u, t->sides);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    G->grid_size = vc.grid_size;
+    G->tree_size = vc.tree_size;
+    G->lod_count = t->lod_count;
+    G->sides = t->sides;
+    G->flags = flags;
+    G->morph_distance = float(t->morph_distance);
+    G->blend_distance = float(t->blend_distance);
+    G->morph_range = vc.morph_range;
+    G->blend_range = vc.blend_range;
+    G->min_height = t->model_c.min_height;
+    G->max_height = t->model_c.max_height;
+    return BT_OK;
+}
+
+uint64_t geometry_slots(const GeometryParams& G) {
+    const uint64_t g = G.grid_size;
+    return (G.flags & BT_GEOMETRY_GRID) ? (g + 1u) * (g + 1u) : 2u * g * (g + 2u);
+}
+}  // namespace
+
+bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tiling_prepass* prepass, uint32_t flags,
+                                      void* vertices_device, uint64_t vertex_capacity) {
+    GeometryParams G{};
+    bt_view_state v{};
+    if (bt_status s = geometry_check("bt_tile_tree_build_geometry", t, a, ai, view, flags, &G, &v)) return s;
+    if (!prepass || bt::tiling_prepass_ctx(prepass) != t->ctx) {
+        // the kernel reads the list the prepass kernels leave: ordered only on one stream
+        set_error("bt_tile_tree_build_geometry: %s", prepass ? "tile tree and tiling prepass belong to different contexts" : "NULL prepass");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!vertex_capacity) return BT_OK;
+    if (!vertices_device || (uintptr_t(vertices_device) & 15u)) {
+        set_error("bt_tile_tree_build_geometry: vertices_device is %s", vertices_device ? "not 16-byte aligned" : "NULL");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bt_tile_coordinate* tiles;
+    const uint32_t* count;
+    uint32_t capacity;
+    bt::tiling_prepass_final(prepass, &tiles, &count, &capacity);
+    BT_HIP(hipSetDevice(t->ctx->device));
+    // a read of the atlas: level0 is passed on without marking any layer written
+    const Attachment& at = a->attachments[ai];
+    return launch_geometry(t->ctx->stream, v, G, t->d_entries, at.meta, at.level0, tiles, count, capacity, 0u, vertices_device, vertex_capacity);
+}
+
+bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tile_coordinate* tiles, uint32_t count,
+                                     uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    static_assert(sizeof(bt_terrain_vertex) == 48, "three 16-byte stores per vertex");
+    GeometryParams G{};
+    bt_view_state v{};
+    if (bt_status s = geometry_check("bt_tile_tree_tile_geometry", t, a, ai, view, flags, &G, &v)) return s;
+    if (!count) return BT_OK;
+    if (!tiles || !out) {
+        set_error("bt_tile_tree_tile_geometry: NULL %s", tiles ? "out_host" : "tiles");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t slots = geometry_slots(G), tile_bytes = slots * sizeof(bt_terrain_vertex);
+    if (out_bytes < uint64_t(count) * tile_bytes) {
+        set_error("bt_tile_tree_tile_geometry: out_bytes %llu < %u tiles x %llu vertices x 48", (unsigned long long)out_bytes, count, (unsigned long long)slots);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_tile_coordinate& c = tiles[i];
+        if (c.side >= t->sides || c.lod >= t->lod_count || c.x >= (1u << c.lod) || c.y >= (1u << c.lod)) {
+            set_error("bt_tile_tree_tile_geometry: tile %u (%u, %u, %u, %u) is not a tile of this terrain", i, c.side, c.lod, c.x, c.y);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // one launch per 32 MiB of vertices (at least one tile); the scratch is the normals' (bt_ctx::normal_dev), until bt_ctx_trim
+    const uint32_t chunk = uint32_t(std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / tile_bytes)));
+    const uint64_t in_bytes = (sizeof(bt_tile_coordinate) * uint64_t(chunk) + 15u) & ~15ull, need = in_bytes + uint64_t(chunk) * tile_bytes;
+    if (ctx->normal_bytes < need) {
+        BT_HIP(hipStreamSynchronize(s));
+        if (ctx->normal_dev) BT_HIP(hipFree(ctx->normal_dev));
+        ctx->normal_dev = nullptr;
+        ctx->normal_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->normal_dev, need));
+        ctx->normal_bytes = need;
+    }
+    uint8_t* dev = (uint8_t*)ctx->normal_dev;
+    const Attachment& at = a->attachments[ai];
+    for (uint32_t first = 0; first < count; first += chunk) {
+        const uint32_t n = std::min(chunk, count - first);
+        BT_HIP(hipMemcpyAsync(dev, tiles + first, sizeof(bt_tile_coordinate) * size_t(n), hipMemcpyHostToDevice, s));
+        // a read of the atlas: level0 is passed on without marking any layer written
+        if (bt_status st = launch_geometry(s, v, G, t->d_entries, at.meta, at.level0, (const bt_tile_coordinate*)dev, nullptr, n, first, dev + in_bytes, uint64_t(n) * slots))
+            return st;
+        BT_HIP(hipMemcpyAsync((uint8_t*)out + uint64_t(first) * tile_bytes, dev + in_bytes, uint64_t(n) * tile_bytes, hipMemcpyDeviceToHost, s));
+        BT_HIP(hipStreamSynchronize(s));  // (the next chunk reuses the scratch, and `tiles` / `out` are pageable)
+    }
+    adopt_height(t);
+    t->table_copy_pending = false;
+    return BT_OK;
+}
+
+namespace {
 // TileTree::approximate_height (tile_tree.rs:372-386): sample_height of attachment 0 at the view position, kept on the device
 // (d_height[0]; the kernel reads the old value for its surface position, then overwrites it) and copied to pinned memory
 bt_status enqueue_height(bt_tile_tree* t, bt_atlas* a) {

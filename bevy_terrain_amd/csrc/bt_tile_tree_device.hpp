@@ -29,6 +29,18 @@ bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_
 bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
                                const double* positions, uint32_t count, float* normals, float* up_dot, const float* height);
 
+// bt_geometry.hip: what TERRAIN GEOMETRY (include/bevy_terrain_amd.h) takes from the tree besides its entries
+struct GeometryParams {
+    uint32_t grid_size, tree_size, lod_count, sides, flags;  // flags: BT_GEOMETRY_*
+    float morph_distance, blend_distance, morph_range, blend_range, min_height, max_height;
+};
+// the vertices (bt_terrain_vertex, device) of the tiles of a device list, in list order.  device_count != NULL: the list's length is read
+// on the device, min(*device_count, count); otherwise it is `count`.  Tile k writes slots k * slots_per_tile .. of `vertices` and carries
+// tile_index tile_base + k; a tile whose last slot lies beyond vertex_capacity is left out.
+bt_status launch_geometry(hipStream_t stream, const bt_view_state& view, const GeometryParams& G, const bt_tile_tree_entry* entries, const AttachmentMeta& m,
+                          const void* atlas, const bt_tile_coordinate* tiles, const uint32_t* device_count, uint32_t count, uint32_t tile_base,
+                          void* vertices, uint64_t vertex_capacity);
+
 #if defined(__HIPCC__)
 
 __device__ __forceinline__ float unorm16_to_float(uint32_t t) {

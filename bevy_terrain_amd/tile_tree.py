@@ -5,7 +5,7 @@ The node tables live on the GPU; this module is a thin ctypes mirror used by the
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -52,6 +52,15 @@ def view_state_from_config(model: TerrainModel, view_config: TerrainViewConfig, 
 RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("direction", np.float64, 3), ("t_min", np.float64), ("t_max", np.float64)])
 RAY_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.float64), ("t_above", np.float64), ("position", np.float64, 3),
                           ("height", np.float32), ("_padding", np.uint32)])
+
+
+# numpy mirror of bt_terrain_vertex
+TERRAIN_VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("height", np.float32), ("normal", np.float32, 3), ("tile_index", np.uint32),
+                                 ("coordinate_uv", np.float32, 2), ("view_distance", np.float32), ("blend_ratio", np.float32)])
+
+
+def _geometry_flags(grid: bool, morph: bool, blend: bool) -> int:
+    return (_ffi.GEOMETRY_GRID if grid else 0) | (0 if morph else _ffi.GEOMETRY_NO_MORPH) | (0 if blend else _ffi.GEOMETRY_NO_BLEND)
 
 
 class TileTree:
@@ -145,6 +154,47 @@ class TileTree:
         if normals:
             return hits, self.sample_normal(attachment_index, hits["position"])[0]
         return hits
+
+    def vertices_per_tile(self, grid: bool = False) -> int:
+        """slots a tile takes in either geometry layout: the strip's 2 g (g + 2) (bt_view_state.vertices_per_tile) or the grid's (g + 1)^2"""
+        g = self.view_config.grid_size
+        return (g + 1) ** 2 if grid else 2 * g * (g + 2)
+
+    def tile_geometry(self, attachment_index: int, tiles, view=None, *, grid: bool = False, morph: bool = True, blend: bool = True) -> np.ndarray:
+        """bt_tile_tree_tile_geometry: the reference's vertex stage for the listed tiles ((n, 4) [side, lod, x, y] or TileCoordinates)
+        -> an (n, vertices_per_tile(grid)) structured array (TERRAIN_VERTEX_DTYPE): position, height, the mesh normal, tile_index (the
+        row), the morphed uv, view_distance, blend_ratio.  view: a bt_view_state (default: view_state()).  Synchronous; a read."""
+        tiles = np.ascontiguousarray([(t.side, t.lod, t.x, t.y) if isinstance(t, TileCoordinate) else tuple(t) for t in tiles], dtype=np.uint32).reshape(-1, 4)
+        out = np.zeros((len(tiles), self.vertices_per_tile(grid)), TERRAIN_VERTEX_DTYPE)
+        _ffi.check(_ffi.lib().bt_tile_tree_tile_geometry(
+            self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None, tiles.ctypes.data_as(C.POINTER(_ffi.TileCoordinateC)),
+            len(tiles), _geometry_flags(grid, morph, blend), out.ctypes.data_as(C.POINTER(_ffi.TerrainVertexC)), out.nbytes))
+        return out
+
+    def build_geometry(self, prepass, attachment_index: int = 0, view=None, *, vertices: Optional[int] = None, vertex_capacity: int = 0,
+                       grid: bool = False, morph: bool = True, blend: bool = True):
+        """bt_tile_tree_build_geometry: the vertices of the final tiles `prepass` last produced, in list order.  Pass the view the prepass
+        ran with (default: view_state()).
+        With vertices (a 16-byte aligned device pointer, e.g. Device.malloc's) and vertex_capacity (in vertices): one asynchronous
+        launch behind that run, no host synchronisation; a tile that does not fit whole is skipped; returns None.
+        Without: the convenience form — reads the list's length (one synchronisation), builds into a buffer of its own and returns the
+        (tiles, vertices_per_tile(grid)) structured array (TERRAIN_VERTEX_DTYPE)."""
+        flags = _geometry_flags(grid, morph, blend)
+        call = lambda ptr, capacity: _ffi.check(_ffi.lib().bt_tile_tree_build_geometry(
+            self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None, prepass._h, flags, C.c_void_p(ptr), capacity))
+        if vertices is not None:
+            call(vertices, vertex_capacity)
+            return None
+        shape = (len(prepass.read()[0]), self.vertices_per_tile(grid))
+        if shape[0] == 0:
+            return np.zeros(shape, TERRAIN_VERTEX_DTYPE)
+        device = self.atlas.device
+        ptr = device.malloc(shape[0] * shape[1] * TERRAIN_VERTEX_DTYPE.itemsize)
+        try:
+            call(ptr, shape[0] * shape[1])
+            return device.download(ptr, shape, TERRAIN_VERTEX_DTYPE)
+        finally:
+            device.free(ptr)
 
     def approximate_height(self) -> float:
         h = C.c_float()

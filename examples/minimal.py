@@ -64,6 +64,11 @@ def main():
             ground = sample_height(tile_tree, tile_atlas, (view_position[0], 0.0, view_position[2]))
             print(f"frame {frame:4d}: view y {view_position[1]:7.1f}  requested {info.requested_count:3d} released {info.released_count:3d} "
                   f"loaded {loaded:3d}  final tiles {len(tiles):5d} (draw: {indirect[0]} vertices x {indirect[1]} instances)  height below the view {ground:6.1f}")
+    # what a draw of the last frame's list would shade: the vertex stage (morph, LOD blend, displacement) as a compute pass, for a host
+    # without the renderer (colliders, export); the view is the tree's own, whose height lags the prepass's by a frame
+    vertices = tile_tree.build_geometry(prepass)
+    if vertices.size:
+        print(f"geometry of the last frame: {vertices.size} vertices of {len(vertices)} tiles, heights {vertices['height'].min():.1f} .. {vertices['height'].max():.1f}")
     print(f"{args.frames} frames, {requested_total} tile requests, {loaded_total} tile loads ({failed_total} failed), pending {tile_atlas.pending_loads()}, "
           f"{1e3 * t_frames / args.frames:.3f} ms of host time per frame (loads included)")
 

@@ -1049,6 +1049,86 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* tree, bt_atlas* atlas, uint32
 bt_status bt_atlas_tile_normals(bt_atlas* atlas, uint32_t attachment_index, const bt_terrain_model* model, const bt_tile_coordinate* coords,
                                 uint32_t count, uint8_t* out_host, uint64_t out_bytes);
 
+/* Terrain geometry ("where are the vertices of the tiles the prepass selected": colliders for the visible tiles, mesh export, a renderer
+ * that is not wgpu).  bt_frame_update ends with final_tiles and indirect arguments whose vertex_count counts vertices of the reference's
+ * vertex stage (src/shaders/render/vertex.wgsl: compute_tile_uv, compute_local_position, compute_morph, compute_blend, lookup_tile through
+ * the tree's entries, sample_height with the two-LOD blend, the displacement along the mesh normal).  These two calls run that stage as
+ * a compute pass: bt_tile_tree_build_geometry expands the prepass's final tiles on the device, bt_tile_tree_tile_geometry a listed set of
+ * tiles into host memory.  The clip-space transform is left to the caller; the surface normal of a vertex is bt_tile_tree_sample_normal's.
+ * The reference's HIGH_PRECISION and TILE_TREE_LOD branches are not built: the Taylor coefficients of TerrainModelApproximation are out
+ * of scope here.
+ *
+ * Parameters.  From the tree (bt_tile_tree_create): grid_size g, tree_size, lod_count, morph_range, blend_range, min_height, max_height,
+ * and morph_distance / blend_distance = f32(view_config value * TerrainModel::scale()) (tile_tree.rs:145-146, `as f32` as in
+ * terrain_view_bind_group.rs:107-108).  From `view` (NULL: bt_tile_tree_view_state(tree)): what refine_tiles reads, i.e. spherical,
+ * approximate_height, world_position and the two mesh matrices.
+ *
+ * TERRAIN GEOMETRY, the definition.  IEEE binary32 unless marked f64, one rounding per written operation, no contraction:
+ *     mix(a, b, t) = a*(1 - t) + b*t        (the form oracle/wgsl_ref/wgsl_rt.hpp uses for the reference's WGSL)
+ *     sat(x)       = x < 0 ? 0 : (x > 1 ? 1 : x)
+ *     min(a, b)    = a < b ? a : b
+ *     length3 and POINT: as in "frustum and height-bounds culling" above; POINT's pair (world, n) at (u, w) is its world position and
+ *     normal before the displacement
+ * With G = f32(g) and the tile (side, lod, x, y), the k-th of its list:
+ *   1. grid vertex (cx, cy), 0 <= cx, cy <= g: tile_uv = (f32(cx) / G, f32(cy) / G).  In the strip layout slot gi of the tile holds the
+ *      grid vertex of compute_tile_uv: vpr = 2*(g + 2); r = clamp(gi % vpr, 1, vpr - 2) - 1; col = gi / vpr; (cx, cy) = (col + (r & 1), r >> 1)
+ *   2. (world0, n0) = POINT's pair at ((f32(x) + tile_uv.x) / 2^lod, (f32(y) + tile_uv.y) / 2^lod);
+ *      d = length3((world0 + approximate_height * n0) - view.world_position), componentwise
+ *   3. morph (BT_GEOMETRY_NO_MORPH: uv = tile_uv): per axis a, even_a = f32(u32(tile_uv_a * G) & ~1u) / G — the product is rounded,
+ *      then truncated, so for a G that is not a power of two it can land below cx: the reference's behaviour, kept;
+ *      target = f32(log2(f64((2.0f * morph_distance) / d)));
+ *      ratio = lod == 0 ? 0 : sat((target - (f32(lod) + morph_range)) / (f32(lod) - (f32(lod) + morph_range)));
+ *      uv_a = mix(tile_uv_a, even_a, ratio)
+ *      (world, n) = POINT's pair at ((f32(x) + uv.x) / 2^lod, (f32(y) + uv.y) / 2^lod)
+ *   4. blend, from the unmorphed d as the shader does: t = min(f32(log2(f64(blend_distance / d))), f32(lod_count) - 0.00001f);
+ *      bl = u32(t), saturating (0 for a t that is not > 0);
+ *      ratio_b = (bl == 0 || BT_GEOMETRY_NO_BLEND) ? 0 : sat((t - (f32(bl) + blend_range)) / (f32(bl) - (f32(bl) + blend_range)))
+ *   5. lookup(o), for o = 0 and, when ratio_b > 0, o = 1: the coordinate (side, lod, x, y, uv) through coordinate_change_lod
+ *      (functions.wgsl:164-188, the prepass's) to L = bl - o, giving (X, Y, uv'); entry = entries[((side * lod_count + L) * tree_size +
+ *      X % tree_size) * tree_size + Y % tree_size].  entry.atlas_lod == BT_INVALID_LOD: value = 0, decided before any further step (the
+ *      reference leaves this case undefined).  Otherwise coordinate_change_lod to entry.atlas_lod, u_a = uv''_a * scale + offset (the
+ *      attachment uv of bt_tile_tree_sample_attachment's tile sample), and value = channel x of that sample's bilinear tail from
+ *      u * f32(T) - 0.5f on: one code with it (an atlas_index >= atlas_size samples as 0 there).  h_o = mix(min_height, max_height, value)
+ *   6. height = ratio_b > 0 ? mix(h_0, h_1, ratio_b) : h_0;  position = world + height * n, componentwise;  normal = n;
+ *      tile_index = k; coordinate_uv = uv; view_distance = d; blend_ratio = ratio_b
+ * The two log2 are the platform's f64 log2 (OCML on the device), the convention bt_tile_tree_sample_attachment's compute_blend already
+ * has; OCML and libm may differ in the last place of a double, which can move the f32 result only when the double sits at an f32
+ * rounding boundary.
+ *
+ * Layouts.  Default (strip): slot k * vertices_per_tile + gi, vertices_per_tile = 2 g (g + 2), holds the vertex the reference's shader
+ * computes for vertex_index = k * vertices_per_tile + gi — the first and the last vertex of each strip row twice, for the degenerate
+ * triangles — so bt_indirect.vertex_count vertices drawn as one triangle strip are the reference's draw.  BT_GEOMETRY_GRID: (g + 1)^2
+ * vertices per tile, slot k * (g + 1)^2 + cy * (g + 1) + cx: the same vertices without the doubles, for consumers that index them.
+ *
+ * bt_tile_tree_build_geometry (device form): one launch of a fixed size on the context's stream, asynchronous, no host synchronisation;
+ * the kernel reads the number of final tiles on the device from what the prepass's last run left (at most the prepass's capacity) and
+ * takes the tiles in list order; a tile whose last slot would fall beyond vertex_capacity (in vertices) is skipped whole.
+ * vertices_device is 16-byte aligned.  vertex_capacity == 0: BT_OK, nothing touched.  Pass the view the prepass ran with: after
+ * bt_frame_update the height the prepass used stays on the device, one frame ahead of what bt_tile_tree_view_state reports.
+ * bt_tile_tree_tile_geometry (host form): synchronous, host arrays in and out, one launch per 32 MiB of vertices; count == 0: BT_OK,
+ * nothing touched.  Both are reads (no layer is marked written for bt_run_stats.prev_zero_launches); the host form's scratch stays in
+ * the context until bt_ctx_trim.
+ * Refusals, all before any device work.  BT_ERR_INVALID_ARGUMENT: NULL handles (the prepass of the device form included, or one of
+ * another context), NULL required arrays with a count / capacity > 0, attachment_index out of range, unknown flags, a view whose
+ * `spherical` does not match the tree's model, a tile of the host list with a bad side, lod >= lod_count or x / y >= 2^lod, out_bytes
+ * too small, a morph_range / blend_range that is not finite and > 0 while its stage is on.  BT_ERR_UNSUPPORTED: a non-R16 attachment;
+ * grid_size 0 or above BT_GEOMETRY_MAX_GRID (a tile's (g + 1)^2 vertices are staged in LDS; the reference's default is 16). */
+typedef struct bt_terrain_vertex { /* 48 bytes: three 16-byte stores per vertex */
+    float position[3];      /* world + height * n (vertex_output's world_position) */
+    float height;           /* the blended height */
+    float normal[3];        /* n: the mesh normal (info.world_normal), not the surface normal */
+    uint32_t tile_index;    /* index into the tile list */
+    float coordinate_uv[2]; /* the morphed uv */
+    float view_distance;    /* d (approximate_view_distance) */
+    float blend_ratio;      /* ratio_b */
+} bt_terrain_vertex;
+enum { BT_GEOMETRY_GRID = 1, BT_GEOMETRY_NO_MORPH = 2, BT_GEOMETRY_NO_BLEND = 4 };
+enum { BT_GEOMETRY_MAX_GRID = 32 };
+bt_status bt_tile_tree_build_geometry(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_view_state* view /* NULL: bt_tile_tree_view_state */,
+                                      const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity);
+bt_status bt_tile_tree_tile_geometry(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_view_state* view /* NULL: bt_tile_tree_view_state */,
+                                     const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out_host, uint64_t out_bytes);
+
 /* One frame of one view (src/plugin.rs:46-56: TileTree::compute_requests -> TileAtlas::update's release / request half ->
  * TileTree::adjust_to_tile_atlas -> TileTree::approximate_height -> TilingPrepassNode::run) as ONE call with ONE host
  * synchronisation — the one the structure forces: the atlas's streaming state machine is host code and needs the two lists,
