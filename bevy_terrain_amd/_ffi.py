@@ -146,11 +146,21 @@ class RayHitC(C.Structure):
 
 GEOMETRY_GRID, GEOMETRY_NO_MORPH, GEOMETRY_NO_BLEND = 1, 2, 4
 GEOMETRY_MAX_GRID = 32
+GEOMETRY_VIEW_RELATIVE = 8  # the _hp calls only
 
 
 class TerrainVertexC(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("height", C.c_float), ("normal", C.c_float * 3), ("tile_index", C.c_uint32),
                 ("coordinate_uv", C.c_float * 2), ("view_distance", C.c_float), ("blend_ratio", C.c_float)]
+
+
+class SideCoefficientsC(C.Structure):
+    _fields_ = [("c", C.c_float * 3), ("c_s", C.c_float * 3), ("c_t", C.c_float * 3), ("c_ss", C.c_float * 3), ("c_st", C.c_float * 3),
+                ("c_tt", C.c_float * 3)]
+
+
+class ModelApproximationC(C.Structure):
+    _fields_ = [("sides", SideCoefficientsC * 6), ("precision_threshold_distance", C.c_float), ("origin_lod", C.c_uint32), ("_padding", C.c_uint32 * 2)]
 
 
 class CullViewC(C.Structure):
@@ -330,6 +340,10 @@ PROTOTYPES = {
     "bt_atlas_tile_normals": (_i32, [_vp, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(C.c_uint8), _u64]),
     "bt_tile_tree_build_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _vp, _u32, _vp, _u64]),
     "bt_tile_tree_tile_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _P(TileCoordinateC), _u32, _u32, _P(TerrainVertexC), _u64]),
+    "bt_model_approximation_from_config": (_i32, [_P(TerrainModelC), _P(TerrainViewConfigC), _P(C.c_double), _P(ModelApproximationC)]),
+    "bt_tile_tree_model_approximation": (_i32, [_vp, _P(ModelApproximationC)]),
+    "bt_tile_tree_build_geometry_hp": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _P(ModelApproximationC), _vp, _u32, _vp, _u64]),
+    "bt_tile_tree_tile_geometry_hp": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _P(ModelApproximationC), _P(TileCoordinateC), _u32, _u32, _P(TerrainVertexC), _u64]),
     "bt_frame_update": (_i32, [_vp, _vp, _vp, _P(C.c_double), C.c_uint32, _P(FrameInfoC)]),
     "bt_selftest": (_i32, [_vp, _P(_u32)]),
     "bt_synth_fbm_r16": (_i32, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _u32, _u32]),

@@ -14,6 +14,12 @@
 // bt_tile_tree_device.hpp (bt_tile_tree_sample_attachment's own).  The view travels as an unmodified by-value argument (see
 // should_be_divided in bt_refine.hip on what writing into it costs).
 //
+// HIGH PRECISION (bt_tile_tree_build_geometry_hp / _tile_geometry_hp) is an instantiation of its own (template <bool kHighPrecision>, as kCull
+// in bt_refine.hip): the kernel the plain calls run is what it was.  A vertex nearer than precision_threshold_distance takes its position
+// from REL (bt_surface_device.hpp), the reference's second-order series around the view, instead of scale * local + translation; the
+// coefficients travel as a by-value argument of their own (448 bytes), never written, indexed by the tile's side, which is workgroup-
+// uniform: they are read with scalar loads and stay out of the VGPRs.
+//
 // Arithmetic contract: IEEE binary32 unless marked, one rounding per written operation (-ffp-contract=off); the two log2 are OCML's f64.
 #include "bt_internal.hpp"
 #include "bt_surface_device.hpp"
@@ -44,10 +50,19 @@ __device__ __forceinline__ float lookup_value(const GeometryParams& G, const bt_
     return r[0];
 }
 
-// one grid vertex (cx, cy) of tile `tile`, the tile_index-th of its list: steps 1 - 6 of the definition -> the three 16-byte parts
-__device__ __forceinline__ void grid_vertex(const bt_view_state& view, const GeometryParams& G, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
-                                            const void* __restrict__ atlas, const bt_tile_coordinate& tile, uint32_t tile_index, uint32_t cx, uint32_t cy,
-                                            f32x4* __restrict__ out) {
+template <bool kHighPrecision>
+struct HpArgs {};
+template <>
+struct HpArgs<true> {
+    bt_model_approximation approximation;
+};
+
+// one grid vertex (cx, cy) of tile `tile`, the tile_index-th of its list: steps 1 - 6 of the definition (kHighPrecision: with steps 2h and
+// 3h) -> the three 16-byte parts
+template <bool kHighPrecision>
+__device__ __forceinline__ void grid_vertex(const bt_view_state& view, const HpArgs<kHighPrecision>& hpa, const GeometryParams& G, const bt_tile_tree_entry* __restrict__ entries,
+                                            const AttachmentMeta& m, const void* __restrict__ atlas, const bt_tile_coordinate& tile, uint32_t tile_index, uint32_t cx,
+                                            uint32_t cy, f32x4* __restrict__ out) {
     const float g = float(G.grid_size);
     const float tu = float(cx) / g, tv = float(cy) / g;
     // 2: x / 2^lod == x * 2^-lod bit for bit (see should_be_divided)
@@ -56,7 +71,16 @@ __device__ __forceinline__ void grid_vertex(const bt_view_state& view, const Geo
     const float dx = (p.wx + view.approximate_height * p.nx) - view.world_position[0];
     const float dy = (p.wy + view.approximate_height * p.ny) - view.world_position[1];
     const float dz = (p.wz + view.approximate_height * p.nz) - view.world_position[2];
-    const float d = length3(dx, dy, dz);
+    float d = length3(dx, dy, dz);
+    // 2h: the distance once more, from the series
+    bool hp = false;
+    if constexpr (kHighPrecision) {
+        hp = d < hpa.approximation.precision_threshold_distance;
+        if (hp) {
+            const Rel r = relative_position(view, hpa.approximation, Coordinate{tile.side, tile.lod, tile.x, tile.y, tu, tv});
+            d = length3(r.x + view.approximate_height * p.nx, r.y + view.approximate_height * p.ny, r.z + view.approximate_height * p.nz);
+        }
+    }
     // 3
     float u = tu, v = tv;
     if (!(G.flags & BT_GEOMETRY_NO_MORPH)) {
@@ -66,7 +90,17 @@ __device__ __forceinline__ void grid_vertex(const bt_view_state& view, const Geo
         const float ratio = tile.lod == 0u ? 0.0f : satf((target - a) / (float(tile.lod) - a));
         u = mixf(tu, eu, ratio);
         v = mixf(tv, ev, ratio);
-        p = tile_surface(view, tile.side, (float(tile.x) + u) * inv_tc, (float(tile.y) + v) * inv_tc);
+        if (!hp) p = tile_surface(view, tile.side, (float(tile.x) + u) * inv_tc, (float(tile.y) + v) * inv_tc);  // (3h keeps n0)
+    }
+    // 3h: world = view.world_position + REL at the morphed uv; the normal stays the unmorphed one (vertex.wgsl:55)
+    Rel rel{0.0f, 0.0f, 0.0f};
+    if constexpr (kHighPrecision) {
+        if (hp) {
+            rel = relative_position(view, hpa.approximation, Coordinate{tile.side, tile.lod, tile.x, tile.y, u, v});
+            p.wx = view.world_position[0] + rel.x;
+            p.wy = view.world_position[1] + rel.y;
+            p.wz = view.world_position[2] + rel.z;
+        }
     }
     // 4
     const float l2 = float(log2(double(G.blend_distance / d))), cap = float(G.lod_count) - 0.00001f;
@@ -84,6 +118,14 @@ __device__ __forceinline__ void grid_vertex(const bt_view_state& view, const Geo
         const float h1 = mixf(G.min_height, G.max_height, lookup_value(G, entries, m, atlas, c, bl - 1u));
         height = mixf(height, h1, ratio_b);
     }
+    if constexpr (kHighPrecision) {
+        if (G.flags & BT_GEOMETRY_VIEW_RELATIVE) {  // the base of the displacement relative to the view: the series itself where it was taken
+            if (!hp) rel = Rel{p.wx - view.world_position[0], p.wy - view.world_position[1], p.wz - view.world_position[2]};
+            p.wx = rel.x;
+            p.wy = rel.y;
+            p.wz = rel.z;
+        }
+    }
     out[0] = f32x4{p.wx + height * p.nx, p.wy + height * p.ny, p.wz + height * p.nz, height};
     out[1] = f32x4{p.nx, p.ny, p.nz, __builtin_bit_cast(float, tile_index)};
     out[2] = f32x4{u, v, d, ratio_b};
@@ -91,10 +133,11 @@ __device__ __forceinline__ void grid_vertex(const bt_view_state& view, const Geo
 
 // tiles [0, n) of the list, n = min(*device_count, count) when device_count is given; tile k's vertices go to slots (k * slots_per_tile ..),
 // its tile_index is tile_base + k
+template <bool kHighPrecision>
 __global__ __launch_bounds__(kGeometryThreads) void geometry_kernel(bt_view_state view, GeometryParams G, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                     const void* __restrict__ atlas, const bt_tile_coordinate* __restrict__ tiles,
                                                                     const uint32_t* __restrict__ device_count, uint32_t count, uint32_t tile_base,
-                                                                    f32x4* __restrict__ vertices, uint64_t vertex_capacity) {
+                                                                    f32x4* __restrict__ vertices, uint64_t vertex_capacity, HpArgs<kHighPrecision> hpa) {
     extern __shared__ __attribute__((aligned(16))) f32x4 s_vertex[];  // [(g + 1)^2][3]
     const uint32_t g = G.grid_size, row = g + 1u, grid_vertices = row * row;
     const bool grid_layout = (G.flags & BT_GEOMETRY_GRID) != 0u;
@@ -105,7 +148,7 @@ __global__ __launch_bounds__(kGeometryThreads) void geometry_kernel(bt_view_stat
         const bt_tile_coordinate tile = tiles[k];
         for (uint32_t vi = threadIdx.x; vi < grid_vertices; vi += kGeometryThreads) {
             const uint32_t cy = vi / row, cx = vi - cy * row;
-            grid_vertex(view, G, entries, m, atlas, tile, tile_base + k, cx, cy, s_vertex + 3u * vi);
+            grid_vertex<kHighPrecision>(view, hpa, G, entries, m, atlas, tile, tile_base + k, cx, cy, s_vertex + 3u * vi);
         }
         __syncthreads();
         f32x4* __restrict__ dst = vertices + uint64_t(k) * slots * 3u;
@@ -126,11 +169,16 @@ __global__ __launch_bounds__(kGeometryThreads) void geometry_kernel(bt_view_stat
 
 bt_status launch_geometry(hipStream_t stream, const bt_view_state& view, const GeometryParams& G, const bt_tile_tree_entry* entries, const AttachmentMeta& m,
                           const void* atlas, const bt_tile_coordinate* tiles, const uint32_t* device_count, uint32_t count, uint32_t tile_base,
-                          void* vertices, uint64_t vertex_capacity) {
+                          void* vertices, uint64_t vertex_capacity, const bt_model_approximation* approximation) {
     if (!count) return BT_OK;
     const uint32_t row = G.grid_size + 1u, lds = row * row * 3u * uint32_t(sizeof(f32x4));
     const uint32_t blocks = device_count ? kGeometryBlocks : std::min(count, kGeometryBlocks);
-    geometry_kernel<<<blocks, kGeometryThreads, lds, stream>>>(view, G, entries, m, atlas, tiles, device_count, count, tile_base, (f32x4*)vertices, vertex_capacity);
+    if (approximation)
+        geometry_kernel<true><<<blocks, kGeometryThreads, lds, stream>>>(view, G, entries, m, atlas, tiles, device_count, count, tile_base, (f32x4*)vertices, vertex_capacity,
+                                                                         HpArgs<true>{*approximation});
+    else
+        geometry_kernel<false><<<blocks, kGeometryThreads, lds, stream>>>(view, G, entries, m, atlas, tiles, device_count, count, tile_base, (f32x4*)vertices, vertex_capacity,
+                                                                          HpArgs<false>{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "geometry_kernel");
     return BT_OK;

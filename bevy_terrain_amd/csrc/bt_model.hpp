@@ -258,6 +258,73 @@ BT_HD Coordinate coordinate_project_to_side(Coordinate c, uint32_t side, const M
     return {side, {pick(i0), pick(i1)}};
 }
 
+// ---- TerrainModelApproximation::compute (math/terrain_model.rs:263-360): the Taylor coefficients of one side, f64 ----------------
+// Our definition of the reference's powi (it leaves the multiplication order to the compiler): left to right.
+BT_HD double cube(double x) { return x * x * x; }
+BT_HD double pow5(double x) { return (x * x) * (x * x) * x; }
+// SIDE_MATRICES[side] * (a, b, c) (terrain_model.rs:14-21; glam: x_axis * a + y_axis * b + z_axis * c)
+BT_HD V3 side_vector(uint32_t side, double a, double b, double c) {
+    const double m[6][9] = {{-1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, 0.0}, {0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, -1.0, 0.0}, {0.0, 1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0},
+                            {1.0, 0.0, 0.0, 0.0, -1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, -1.0, 0.0, -1.0, 0.0, 1.0, 0.0, 0.0}, {0.0, -1.0, 0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 0.0}};
+    const double* k = m[side];
+    return {(k[0] * a + k[3] * b) + k[6] * c, (k[1] * a + k[4] * b) + k[7] * c, (k[2] * a + k[5] * b) + k[8] * c};
+}
+BT_HD V3 div3(V3 a, double d) { return {a.x / d, a.y / d, a.z / d}; }
+// the six vectors of a side's series in world space, before the casts: p (a point), p_s, p_t, p_ss, p_st, p_tt (vectors; the halving of
+// p_ss and p_tt is the caller's).  The definition, operation by operation: include/bevy_terrain_amd.h, HIGH PRECISION.
+struct SideSeries {
+    V3 p, p_s, p_t, p_ss, p_st, p_tt;
+};
+BT_HD SideSeries side_series(uint32_t side, V2 st, const Model& m) {
+    const double s = st.x, t = st.y;
+    const double u_denom = sqrt(1.0 - 4.0 * kCSqr * s * (s - 1.0));
+    const double u = (2.0 * s - 1.0) / u_denom;
+    const double u_ds = 2.0 * (kCSqr + 1.0) / cube(u_denom);
+    const double u_dss = 12.0 * kCSqr * (kCSqr + 1.0) * (2.0 * s - 1.0) / pow5(u_denom);
+
+    const double v_denom = sqrt(1.0 - 4.0 * kCSqr * t * (t - 1.0));
+    const double v = (2.0 * t - 1.0) / v_denom;
+    const double v_dt = 2.0 * (kCSqr + 1.0) / cube(v_denom);
+    const double v_dtt = 12.0 * kCSqr * (kCSqr + 1.0) * (2.0 * t - 1.0) / pow5(v_denom);
+
+    const double l = sqrt(1.0 + u * u + v * v);
+    const double l_ds = u * u_ds / l;
+    const double l_dt = v * v_dt / l;
+    const double l_dss = (u * u_dss * l * l + (v * v + 1.0) * u_ds * u_ds) / cube(l);
+    const double l_dst = -(u * v * u_ds * v_dt) / cube(l);
+    const double l_dtt = (v * v_dtt * l * l + (u * u + 1.0) * v_dt * v_dt) / cube(l);
+
+    const double a = 1.0;
+    const double a_ds = -l_ds;
+    const double a_dt = -l_dt;
+    const double a_dss = 2.0 * l_ds * l_ds - l * l_dss;
+    const double a_dst = 2.0 * l_ds * l_dt - l * l_dst;
+    const double a_dtt = 2.0 * l_dt * l_dt - l * l_dtt;
+
+    const double b = u;
+    const double b_ds = -u * l_ds + l * u_ds;
+    const double b_dt = -u * l_dt;
+    const double b_dss = 2.0 * u * l_ds * l_ds - l * (2.0 * u_ds * l_ds + u * l_dss) + u_dss * l * l;
+    const double b_dst = 2.0 * u * l_ds * l_dt - l * (u_ds * l_dt + u * l_dst);
+    const double b_dtt = 2.0 * u * l_dt * l_dt - l * u * l_dtt;
+
+    const double c = v;
+    const double c_ds = -v * l_ds;
+    const double c_dt = -v * l_dt + l * v_dt;
+    const double c_dss = 2.0 * v * l_ds * l_ds - l * v * l_dss;
+    const double c_dst = 2.0 * v * l_ds * l_dt - l * (v_dt * l_ds + v * l_dst);
+    const double c_dtt = 2.0 * v * l_dt * l_dt - l * (2.0 * v_dt * l_dt + v * l_dtt) + v_dtt * l * l;
+
+    SideSeries o;
+    o.p = transform_point(m, div3(side_vector(side, a, b, c), l));
+    o.p_s = transform_vector(m, div3(side_vector(side, a_ds, b_ds, c_ds), l * l));
+    o.p_t = transform_vector(m, div3(side_vector(side, a_dt, b_dt, c_dt), l * l));
+    o.p_ss = transform_vector(m, div3(side_vector(side, a_dss, b_dss, c_dss), cube(l)));
+    o.p_st = transform_vector(m, div3(side_vector(side, a_dst, b_dst, c_dst), cube(l)));
+    o.p_tt = transform_vector(m, div3(side_vector(side, a_dtt, b_dtt, c_dtt), cube(l)));
+    return o;
+}
+
 // ---- TileTree helpers (terrain_data/tile_tree.rs) ---------------------------------------------------------
 // `as u32` / as_uvec2: saturating, NaN -> 0
 BT_HD uint32_t saturating_u32(double v) { return !(v > 0.0) ? 0u : (v >= 4294967295.0 ? 0xFFFFFFFFu : uint32_t(v)); }

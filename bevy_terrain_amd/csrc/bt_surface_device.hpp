@@ -43,6 +43,27 @@ __device__ __forceinline__ void coordinate_change_lod(Coordinate& c, uint32_t ne
 
 __device__ __forceinline__ float length3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
 
+// REL(coordinate) (include/bevy_terrain_amd.h, HIGH PRECISION): compute_relative_position (functions.wgsl:98-115), the position of a
+// coordinate relative to the view from the second-order series of its side.  The coordinate goes to origin_lod, its offset from the view's
+// coordinate is taken in integers first (i32, wrapping), and the series is summed left to right as the WGSL expression is, componentwise.  The side indexes
+// two by-value kernel arguments; callers pass a workgroup-uniform side (>= 6 cannot come from a list of the view's terrain: read as 5).
+struct Rel {
+    float x, y, z;
+};
+__device__ __forceinline__ Rel relative_position(const bt_view_state& v, const bt_model_approximation& a, Coordinate c) {
+    coordinate_change_lod(c, a.origin_lod);
+    const uint32_t side = c.side < 6u ? c.side : 5u;
+    const bt_side_parameter& o = v.sides[side];
+    const bt_side_coefficients& k = a.sides[side];
+    const float inv_oc = __builtin_bit_cast(float, (127u - a.origin_lod) << 23);  // x / 2^origin_lod == x * 2^-origin_lod bit for bit
+    const float s = ((float(int32_t(c.x - uint32_t(o.view_xy[0]))) + c.u) - o.view_uv[0]) * inv_oc;
+    const float t = ((float(int32_t(c.y - uint32_t(o.view_xy[1]))) + c.v) - o.view_uv[1]) * inv_oc;
+    float r[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] = ((((k.c[i] + k.c_s[i] * s) + k.c_t[i] * t) + (k.c_ss[i] * s) * s) + (k.c_st[i] * s) * t) + (k.c_tt[i] * t) * t;
+    return {r[0], r[1], r[2]};
+}
+
 // A point of a tile's surface and the normal there: compute_local_position (functions.wgsl:73-96) of the tile coordinate (u, w) =
 // (tile xy + uv) / tile_count, then position_local_to_world / normal_local_to_world (:117-121).  point(tile, uv, h) = world + h * normal:
 // the divide test's and the culling test's (include/bevy_terrain_amd.h).  l is the local position itself (the unit sphere's when spherical):

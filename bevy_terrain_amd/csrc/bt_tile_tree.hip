@@ -295,6 +295,45 @@ bt_status bt_view_state_from_config(const bt_terrain_model* model, const bt_terr
     return BT_OK;
 }
 
+// TerrainModelApproximation::compute (terrain_model.rs:263-360) in f64, `as f32` at the end: the definition is the header's (HIGH PRECISION)
+bt_status bt_model_approximation_from_config(const bt_terrain_model* model, const bt_terrain_view_config* vc, const double view_world_position[3],
+                                             bt_model_approximation* out) {
+    if (!model || !vc || !view_world_position || !out) {
+        set_error("bt_model_approximation_from_config: NULL %s", !model ? "model" : (!vc ? "view_config" : (!out ? "out" : "view_world_position")));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_model(model)) return s;
+    if (model->kind == BT_MODEL_PLANAR) {
+        set_error("bt_model_approximation_from_config: a planar model has no series (the reference's coefficients are the cube sphere's there)");
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!std::isfinite(view_world_position[0]) || !std::isfinite(view_world_position[1]) || !std::isfinite(view_world_position[2]) || vc->origin_lod > 31u) {
+        set_error("bt_model_approximation_from_config: a non-finite position, or origin_lod %u (<= 31)", vc->origin_lod);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Model m = make_model(*model);
+    const V3 view = {view_world_position[0], view_world_position[1], view_world_position[2]};
+    const Coordinate c = coordinate_from_world_position(view, m);
+    bt_model_approximation a{};
+    for (uint32_t side = 0; side < 6; side++) {
+        const SideSeries q = side_series(side, coordinate_project_to_side(c, side, m).uv, m);
+        bt_side_coefficients& k = a.sides[side];
+        const V3 rel = {q.p.x - view.x, q.p.y - view.y, q.p.z - view.z};
+        const V3 half_ss = div3(q.p_ss, 2.0), half_tt = div3(q.p_tt, 2.0);
+        const V3* src[6] = {&rel, &q.p_s, &q.p_t, &half_ss, &q.p_st, &half_tt};
+        float* dst[6] = {k.c, k.c_s, k.c_t, k.c_ss, k.c_st, k.c_tt};
+        for (int i = 0; i < 6; i++) {
+            dst[i][0] = float(src[i]->x);
+            dst[i][1] = float(src[i]->y);
+            dst[i][2] = float(src[i]->z);
+        }
+    }
+    a.precision_threshold_distance = float(vc->precision_threshold_distance * model_scale(m));  // tile_tree.rs:153, terrain_view_bind_group.rs:111
+    a.origin_lod = vc->origin_lod;
+    *out = a;
+    return BT_OK;
+}
+
 // f64 -> f32 with a directed rounding (the nearest value, stepped back when it lies on the wrong side)
 static float f32_toward_zero(double d) {
     const float f = float(d);
@@ -672,7 +711,9 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
 namespace {
 // what both geometry calls refuse before any device work, and what they hand the kernel: the tree's parameters (TerrainViewConfigUniform:
 // the f64 distances x TerrainModel::scale(), `as f32`) and the view (the caller's, or the tree's own)
-bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, uint32_t flags, GeometryParams* G, bt_view_state* v) {
+// hp: the HIGH PRECISION calls, which also accept BT_GEOMETRY_VIEW_RELATIVE and check the approximation they were given
+bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, uint32_t flags, GeometryParams* G, bt_view_state* v,
+                         bool hp = false, const bt_model_approximation* approximation = nullptr) {
     if (!t || !a) {
         set_error("%s: NULL %s", who, t ? "atlas" : "tile tree");
         return BT_ERR_INVALID_ARGUMENT;
@@ -685,7 +726,7 @@ bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t
         set_error("%s: attachment index %u out of range", who, ai);
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (flags & ~uint32_t(BT_GEOMETRY_GRID | BT_GEOMETRY_NO_MORPH | BT_GEOMETRY_NO_BLEND)) {
+    if (flags & ~uint32_t(BT_GEOMETRY_GRID | BT_GEOMETRY_NO_MORPH | BT_GEOMETRY_NO_BLEND | (hp ? BT_GEOMETRY_VIEW_RELATIVE : 0))) {
         set_error("%s: unknown flags 0x%x", who, flags);
         return BT_ERR_INVALID_ARGUMENT;
     }
@@ -715,6 +756,22 @@ bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t
         set_error("%s: a view of %u side(s) for a tile tree of %u", who, v->spherical ? 6u : 1u, t->sides);
         return BT_ERR_INVALID_ARGUMENT;
     }
+    if (hp) {
+        if (!approximation) {
+            set_error("%s: NULL approximation", who);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        if (t->sides != 6u) {
+            set_error("%s: a planar terrain has no model approximation", who);
+            return BT_ERR_UNSUPPORTED;
+        }
+        const float th = approximation->precision_threshold_distance;
+        if (approximation->origin_lod != v->origin_lod || approximation->origin_lod > 31u || !std::isfinite(th) || th < 0.0f) {
+            set_error("%s: approximation of origin_lod %u for a view of %u (equal, <= 31), or precision_threshold_distance %g (finite, >= 0)", who,
+                      approximation->origin_lod, v->origin_lod, double(th));
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
     G->grid_size = vc.grid_size;
     G->tree_size = vc.tree_size;
     G->lod_count = t->lod_count;
@@ -735,19 +792,21 @@ uint64_t geometry_slots(const GeometryParams& G) {
 }
 }  // namespace
 
-bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tiling_prepass* prepass, uint32_t flags,
-                                      void* vertices_device, uint64_t vertex_capacity) {
+namespace {
+// both forms, plain (hp false, approximation NULL) and HIGH PRECISION
+bt_status build_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
     GeometryParams G{};
     bt_view_state v{};
-    if (bt_status s = geometry_check("bt_tile_tree_build_geometry", t, a, ai, view, flags, &G, &v)) return s;
+    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
     if (!prepass || bt::tiling_prepass_ctx(prepass) != t->ctx) {
         // the kernel reads the list the prepass kernels leave: ordered only on one stream
-        set_error("bt_tile_tree_build_geometry: %s", prepass ? "tile tree and tiling prepass belong to different contexts" : "NULL prepass");
+        set_error("%s: %s", who, prepass ? "tile tree and tiling prepass belong to different contexts" : "NULL prepass");
         return BT_ERR_INVALID_ARGUMENT;
     }
     if (!vertex_capacity) return BT_OK;
     if (!vertices_device || (uintptr_t(vertices_device) & 15u)) {
-        set_error("bt_tile_tree_build_geometry: vertices_device is %s", vertices_device ? "not 16-byte aligned" : "NULL");
+        set_error("%s: vertices_device is %s", who, vertices_device ? "not 16-byte aligned" : "NULL");
         return BT_ERR_INVALID_ARGUMENT;
     }
     const bt_tile_coordinate* tiles;
@@ -757,29 +816,30 @@ bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai,
     BT_HIP(hipSetDevice(t->ctx->device));
     // a read of the atlas: level0 is passed on without marking any layer written
     const Attachment& at = a->attachments[ai];
-    return launch_geometry(t->ctx->stream, v, G, t->d_entries, at.meta, at.level0, tiles, count, capacity, 0u, vertices_device, vertex_capacity);
+    return launch_geometry(t->ctx->stream, v, G, t->d_entries, at.meta, at.level0, tiles, count, capacity, 0u, vertices_device, vertex_capacity, approximation);
 }
 
-bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tile_coordinate* tiles, uint32_t count,
-                                     uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+bt_status tile_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
     static_assert(sizeof(bt_terrain_vertex) == 48, "three 16-byte stores per vertex");
+    static_assert(sizeof(bt_model_approximation) == 448, "a by-value kernel argument, a multiple of 16 bytes");
     GeometryParams G{};
     bt_view_state v{};
-    if (bt_status s = geometry_check("bt_tile_tree_tile_geometry", t, a, ai, view, flags, &G, &v)) return s;
+    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
     if (!count) return BT_OK;
     if (!tiles || !out) {
-        set_error("bt_tile_tree_tile_geometry: NULL %s", tiles ? "out_host" : "tiles");
+        set_error("%s: NULL %s", who, tiles ? "out_host" : "tiles");
         return BT_ERR_INVALID_ARGUMENT;
     }
     const uint64_t slots = geometry_slots(G), tile_bytes = slots * sizeof(bt_terrain_vertex);
     if (out_bytes < uint64_t(count) * tile_bytes) {
-        set_error("bt_tile_tree_tile_geometry: out_bytes %llu < %u tiles x %llu vertices x 48", (unsigned long long)out_bytes, count, (unsigned long long)slots);
+        set_error("%s: out_bytes %llu < %u tiles x %llu vertices x 48", who, (unsigned long long)out_bytes, count, (unsigned long long)slots);
         return BT_ERR_INVALID_ARGUMENT;
     }
     for (uint32_t i = 0; i < count; i++) {
         const bt_tile_coordinate& c = tiles[i];
         if (c.side >= t->sides || c.lod >= t->lod_count || c.x >= (1u << c.lod) || c.y >= (1u << c.lod)) {
-            set_error("bt_tile_tree_tile_geometry: tile %u (%u, %u, %u, %u) is not a tile of this terrain", i, c.side, c.lod, c.x, c.y);
+            set_error("%s: tile %u (%u, %u, %u, %u) is not a tile of this terrain", who, i, c.side, c.lod, c.x, c.y);
             return BT_ERR_INVALID_ARGUMENT;
         }
     }
@@ -803,7 +863,8 @@ bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
         const uint32_t n = std::min(chunk, count - first);
         BT_HIP(hipMemcpyAsync(dev, tiles + first, sizeof(bt_tile_coordinate) * size_t(n), hipMemcpyHostToDevice, s));
         // a read of the atlas: level0 is passed on without marking any layer written
-        if (bt_status st = launch_geometry(s, v, G, t->d_entries, at.meta, at.level0, (const bt_tile_coordinate*)dev, nullptr, n, first, dev + in_bytes, uint64_t(n) * slots))
+        if (bt_status st = launch_geometry(s, v, G, t->d_entries, at.meta, at.level0, (const bt_tile_coordinate*)dev, nullptr, n, first, dev + in_bytes, uint64_t(n) * slots,
+                                           approximation))
             return st;
         BT_HIP(hipMemcpyAsync((uint8_t*)out + uint64_t(first) * tile_bytes, dev + in_bytes, uint64_t(n) * tile_bytes, hipMemcpyDeviceToHost, s));
         BT_HIP(hipStreamSynchronize(s));  // (the next chunk reuses the scratch, and `tiles` / `out` are pageable)
@@ -811,6 +872,27 @@ bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
     adopt_height(t);
     t->table_copy_pending = false;
     return BT_OK;
+}
+}  // namespace
+
+bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tiling_prepass* prepass, uint32_t flags,
+                                      void* vertices_device, uint64_t vertex_capacity) {
+    return build_geometry("bt_tile_tree_build_geometry", false, t, a, ai, view, nullptr, prepass, flags, vertices_device, vertex_capacity);
+}
+
+bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tile_coordinate* tiles, uint32_t count,
+                                     uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    return tile_geometry("bt_tile_tree_tile_geometry", false, t, a, ai, view, nullptr, tiles, count, flags, out, out_bytes);
+}
+
+bt_status bt_tile_tree_build_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
+    return build_geometry("bt_tile_tree_build_geometry_hp", true, t, a, ai, view, approximation, prepass, flags, vertices_device, vertex_capacity);
+}
+
+bt_status bt_tile_tree_tile_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    return tile_geometry("bt_tile_tree_tile_geometry_hp", true, t, a, ai, view, approximation, tiles, count, flags, out, out_bytes);
 }
 
 namespace {
@@ -882,6 +964,14 @@ bt_status bt_frame_update(bt_tile_tree* t, bt_atlas* a, bt_tiling_prepass* prepa
 bt_status bt_tile_tree_view_state(const bt_tile_tree* t, bt_view_state* out) {
     if (!t || !out) return BT_ERR_INVALID_ARGUMENT;
     return bt_view_state_from_config(&t->model_c, &t->view_config, t->view_world_position, t->approximate_height, out);
+}
+
+bt_status bt_tile_tree_model_approximation(bt_tile_tree* t, bt_model_approximation* out) {
+    if (!t || !out) {
+        set_error("bt_tile_tree_model_approximation: NULL %s", t ? "out" : "tile tree");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    return bt_model_approximation_from_config(&t->model_c, &t->view_config, t->view_world_position, out);
 }
 
 }  // extern "C"

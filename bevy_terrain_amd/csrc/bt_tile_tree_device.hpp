@@ -36,10 +36,11 @@ struct GeometryParams {
 };
 // the vertices (bt_terrain_vertex, device) of the tiles of a device list, in list order.  device_count != NULL: the list's length is read
 // on the device, min(*device_count, count); otherwise it is `count`.  Tile k writes slots k * slots_per_tile .. of `vertices` and carries
-// tile_index tile_base + k; a tile whose last slot lies beyond vertex_capacity is left out.
+// tile_index tile_base + k; a tile whose last slot lies beyond vertex_capacity is left out.  approximation != NULL: the HIGH PRECISION
+// instantiation (the only one that reads BT_GEOMETRY_VIEW_RELATIVE); NULL: the plain one.
 bt_status launch_geometry(hipStream_t stream, const bt_view_state& view, const GeometryParams& G, const bt_tile_tree_entry* entries, const AttachmentMeta& m,
                           const void* atlas, const bt_tile_coordinate* tiles, const uint32_t* device_count, uint32_t count, uint32_t tile_base,
-                          void* vertices, uint64_t vertex_capacity);
+                          void* vertices, uint64_t vertex_capacity, const bt_model_approximation* approximation);
 
 #if defined(__HIPCC__)
 

@@ -48,6 +48,15 @@ def view_state_from_config(model: TerrainModel, view_config: TerrainViewConfig, 
     return v
 
 
+def model_approximation_from_config(model: TerrainModel, view_config: TerrainViewConfig, view_world_position: Sequence[float]) -> _ffi.ModelApproximationC:
+    """bt_model_approximation_from_config: the Taylor coefficients of the high-precision geometry (TerrainModelApproximation::compute) for a
+    view position, f64 in the library, `as f32` at the end; derive the view (view_state_from_config) from the same position."""
+    a = _ffi.ModelApproximationC()
+    pos = (C.c_double * 3)(*view_world_position)
+    _ffi.check(_ffi.lib().bt_model_approximation_from_config(C.byref(model_c(model)), C.byref(view_config_c(view_config)), pos, C.byref(a)))
+    return a
+
+
 # numpy mirrors of bt_ray / bt_ray_hit (include/bevy_terrain_amd.h)
 RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("direction", np.float64, 3), ("t_min", np.float64), ("t_max", np.float64)])
 RAY_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.float64), ("t_above", np.float64), ("position", np.float64, 3),
@@ -59,8 +68,11 @@ TERRAIN_VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("height", np.floa
                                  ("coordinate_uv", np.float32, 2), ("view_distance", np.float32), ("blend_ratio", np.float32)])
 
 
-def _geometry_flags(grid: bool, morph: bool, blend: bool) -> int:
-    return (_ffi.GEOMETRY_GRID if grid else 0) | (0 if morph else _ffi.GEOMETRY_NO_MORPH) | (0 if blend else _ffi.GEOMETRY_NO_BLEND)
+def _geometry_flags(grid: bool, morph: bool, blend: bool, approximation=None, view_relative: bool = False) -> int:
+    if view_relative and approximation is None:
+        raise ValueError("view_relative=True needs approximation= (BT_GEOMETRY_VIEW_RELATIVE is the high-precision calls')")
+    return (_ffi.GEOMETRY_GRID if grid else 0) | (0 if morph else _ffi.GEOMETRY_NO_MORPH) | (0 if blend else _ffi.GEOMETRY_NO_BLEND) | \
+        (_ffi.GEOMETRY_VIEW_RELATIVE if view_relative else 0)
 
 
 class TileTree:
@@ -160,28 +172,40 @@ class TileTree:
         g = self.view_config.grid_size
         return (g + 1) ** 2 if grid else 2 * g * (g + 2)
 
-    def tile_geometry(self, attachment_index: int, tiles, view=None, *, grid: bool = False, morph: bool = True, blend: bool = True) -> np.ndarray:
+    def tile_geometry(self, attachment_index: int, tiles, view=None, *, grid: bool = False, morph: bool = True, blend: bool = True, approximation=None,
+                      view_relative: bool = False) -> np.ndarray:
         """bt_tile_tree_tile_geometry: the reference's vertex stage for the listed tiles ((n, 4) [side, lod, x, y] or TileCoordinates)
         -> an (n, vertices_per_tile(grid)) structured array (TERRAIN_VERTEX_DTYPE): position, height, the mesh normal, tile_index (the
-        row), the morphed uv, view_distance, blend_ratio.  view: a bt_view_state (default: view_state()).  Synchronous; a read."""
+        row), the morphed uv, view_distance, blend_ratio.  view: a bt_view_state (default: view_state()).  Synchronous; a read.
+        approximation (a bt_model_approximation of the same position as the view: model_approximation() / model_approximation_from_config):
+        bt_tile_tree_tile_geometry_hp, the reference's HIGH_PRECISION branch — vertices nearer than its precision_threshold_distance come
+        from the Taylor series around the view; view_relative=True: positions relative to the view (BT_GEOMETRY_VIEW_RELATIVE)."""
         tiles = np.ascontiguousarray([(t.side, t.lod, t.x, t.y) if isinstance(t, TileCoordinate) else tuple(t) for t in tiles], dtype=np.uint32).reshape(-1, 4)
         out = np.zeros((len(tiles), self.vertices_per_tile(grid)), TERRAIN_VERTEX_DTYPE)
-        _ffi.check(_ffi.lib().bt_tile_tree_tile_geometry(
-            self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None, tiles.ctypes.data_as(C.POINTER(_ffi.TileCoordinateC)),
-            len(tiles), _geometry_flags(grid, morph, blend), out.ctypes.data_as(C.POINTER(_ffi.TerrainVertexC)), out.nbytes))
+        flags = _geometry_flags(grid, morph, blend, approximation, view_relative)
+        head = (self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None)
+        tail = (tiles.ctypes.data_as(C.POINTER(_ffi.TileCoordinateC)), len(tiles), flags, out.ctypes.data_as(C.POINTER(_ffi.TerrainVertexC)), out.nbytes)
+        if approximation is None:
+            _ffi.check(_ffi.lib().bt_tile_tree_tile_geometry(*head, *tail))
+        else:
+            _ffi.check(_ffi.lib().bt_tile_tree_tile_geometry_hp(*head, C.byref(approximation), *tail))
         return out
 
     def build_geometry(self, prepass, attachment_index: int = 0, view=None, *, vertices: Optional[int] = None, vertex_capacity: int = 0,
-                       grid: bool = False, morph: bool = True, blend: bool = True):
+                       grid: bool = False, morph: bool = True, blend: bool = True, approximation=None, view_relative: bool = False):
         """bt_tile_tree_build_geometry: the vertices of the final tiles `prepass` last produced, in list order.  Pass the view the prepass
         ran with (default: view_state()).
         With vertices (a 16-byte aligned device pointer, e.g. Device.malloc's) and vertex_capacity (in vertices): one asynchronous
         launch behind that run, no host synchronisation; a tile that does not fit whole is skipped; returns None.
         Without: the convenience form — reads the list's length (one synchronisation), builds into a buffer of its own and returns the
-        (tiles, vertices_per_tile(grid)) structured array (TERRAIN_VERTEX_DTYPE)."""
-        flags = _geometry_flags(grid, morph, blend)
-        call = lambda ptr, capacity: _ffi.check(_ffi.lib().bt_tile_tree_build_geometry(
-            self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None, prepass._h, flags, C.c_void_p(ptr), capacity))
+        (tiles, vertices_per_tile(grid)) structured array (TERRAIN_VERTEX_DTYPE).
+        approximation / view_relative: bt_tile_tree_build_geometry_hp, as in tile_geometry."""
+        flags = _geometry_flags(grid, morph, blend, approximation, view_relative)
+        head = (self._h, self.atlas._h, attachment_index, C.byref(view) if view is not None else None)
+        if approximation is None:
+            call = lambda ptr, capacity: _ffi.check(_ffi.lib().bt_tile_tree_build_geometry(*head, prepass._h, flags, C.c_void_p(ptr), capacity))
+        else:
+            call = lambda ptr, capacity: _ffi.check(_ffi.lib().bt_tile_tree_build_geometry_hp(*head, C.byref(approximation), prepass._h, flags, C.c_void_p(ptr), capacity))
         if vertices is not None:
             call(vertices, vertex_capacity)
             return None
@@ -217,6 +241,12 @@ class TileTree:
         v = _ffi.ViewStateC()
         _ffi.check(_ffi.lib().bt_tile_tree_view_state(self._h, C.byref(v)))
         return v
+
+    def model_approximation(self) -> _ffi.ModelApproximationC:
+        """bt_tile_tree_model_approximation: the Taylor coefficients of the tree's last view position (the companion of view_state())"""
+        a = _ffi.ModelApproximationC()
+        _ffi.check(_ffi.lib().bt_tile_tree_model_approximation(self._h, C.byref(a)))
+        return a
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1055,8 +1055,8 @@ bt_status bt_atlas_tile_normals(bt_atlas* atlas, uint32_t attachment_index, cons
  * the tree's entries, sample_height with the two-LOD blend, the displacement along the mesh normal).  These two calls run that stage as
  * a compute pass: bt_tile_tree_build_geometry expands the prepass's final tiles on the device, bt_tile_tree_tile_geometry a listed set of
  * tiles into host memory.  The clip-space transform is left to the caller; the surface normal of a vertex is bt_tile_tree_sample_normal's.
- * The reference's HIGH_PRECISION and TILE_TREE_LOD branches are not built: the Taylor coefficients of TerrainModelApproximation are out
- * of scope here.
+ * These two run the stage with HIGH_PRECISION off; bt_tile_tree_build_geometry_hp / bt_tile_tree_tile_geometry_hp below run it with the
+ * branch on (the reference's default: the Taylor series of TerrainModelApproximation).  The TILE_TREE_LOD branch is not built.
  *
  * Parameters.  From the tree (bt_tile_tree_create): grid_size g, tree_size, lod_count, morph_range, blend_range, min_height, max_height,
  * and morph_distance / blend_distance = f32(view_config value * TerrainModel::scale()) (tile_tree.rs:145-146, `as f32` as in
@@ -1128,6 +1128,81 @@ bt_status bt_tile_tree_build_geometry(bt_tile_tree* tree, bt_atlas* atlas, uint3
                                       const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity);
 bt_status bt_tile_tree_tile_geometry(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_view_state* view /* NULL: bt_tile_tree_view_state */,
                                      const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out_host, uint64_t out_bytes);
+
+/* HIGH PRECISION terrain geometry: the HIGH_PRECISION branch of the vertex stage (vertex.wgsl:40-61), which the reference turns on by
+ * default (DebugTerrain::high_precision).  The plain stage computes world = scale * local + translation in binary32: on a planet (one ulp
+ * of 6.4e6 m is 0.5 m) every vertex near the camera sits on a half-metre lattice.  TerrainModelApproximation (terrain_model.rs:222-361) is
+ * the reference's answer: per cube side a second-order Taylor series of the surface around the point under the view, computed in f64 on
+ * the host and evaluated in f32 RELATIVE TO THE VIEW for every vertex nearer than precision_threshold_distance.
+ *
+ * THE COEFFICIENTS, bt_model_approximation_from_config.  IEEE binary64, one rounding per written operation, the expressions as written
+ * (left to right, the usual precedence), C = 0.87 * 0.87.  OUR DEFINITION of the reference's powi, whose multiplication order it leaves
+ * to the compiler: cube(x) = x*x*x and pow5(x) = (x*x)*(x*x)*x, both left to right; powi(2) = x*x.
+ *   view = Coordinate::from_world_position(view_world_position, model); per side: (s, t) = view.project_to_side(side).uv (the functions
+ *   bt_view_state_from_config uses for view_xy / view_uv), then
+ *     ud = sqrt(1.0 - 4.0*C*s*(s - 1.0));  u = (2.0*s - 1.0)/ud;  u_s = 2.0*(C + 1.0)/cube(ud);  u_ss = 12.0*C*(C + 1.0)*(2.0*s - 1.0)/pow5(ud)
+ *     vd, v, v_t, v_tt: the same of t
+ *     l = sqrt(1.0 + u*u + v*v);  l_s = u*u_s/l;  l_t = v*v_t/l;
+ *     l_ss = (u*u_ss*l*l + (v*v + 1.0)*u_s*u_s)/cube(l);  l_st = -(u*v*u_s*v_t)/cube(l);  l_tt = (v*v_tt*l*l + (u*u + 1.0)*v_t*v_t)/cube(l)
+ *     a = 1.0;  a_s = -l_s;  a_t = -l_t;  a_ss = 2.0*l_s*l_s - l*l_ss;  a_st = 2.0*l_s*l_t - l*l_st;  a_tt = 2.0*l_t*l_t - l*l_tt
+ *     b = u;  b_s = -u*l_s + l*u_s;  b_t = -u*l_t;  b_ss = 2.0*u*l_s*l_s - l*(2.0*u_s*l_s + u*l_ss) + u_ss*l*l;
+ *     b_st = 2.0*u*l_s*l_t - l*(u_s*l_t + u*l_st);  b_tt = 2.0*u*l_t*l_t - l*u*l_tt
+ *     c = v;  c_s = -v*l_s;  c_t = -v*l_t + l*v_t;  c_ss = 2.0*v*l_s*l_s - l*v*l_ss;  c_st = 2.0*v*l_s*l_t - l*(v_t*l_s + v*l_st);
+ *     c_tt = 2.0*v*l_t*l_t - l*(2.0*v_t*l_t + v*l_tt) + v_tt*l*l
+ *   SM(a, b, c) = SIDE_MATRICES[side] * (a, b, c) (terrain_model.rs:14-21), each component (m_x*a + m_y*b) + m_z*c with the matrix's
+ *   entries 0.0, 1.0, -1.0; W = world_from_local = scale * x (+ model.position for a point), componentwise;
+ *     p = W_point(SM(a, b, c)/l);  p_s = W(SM(a_s, b_s, c_s)/(l*l));  p_t = W(SM(a_t, b_t, c_t)/(l*l));
+ *     p_ss = W(SM(a_ss, b_ss, c_ss)/cube(l));  p_st, p_tt likewise over cube(l)
+ *   sides[side]: c = f32(p - view_world_position), c_s = f32(p_s), c_t = f32(p_t), c_ss = f32(p_ss/2.0), c_st = f32(p_st),
+ *   c_tt = f32(p_tt/2.0), componentwise.  precision_threshold_distance = f32(view_config.precision_threshold_distance *
+ *   TerrainModel::scale()) (tile_tree.rs:153, terrain_view_bind_group.rs:111); origin_lod = view_config.origin_lod.
+ * BT_ERR_INVALID_ARGUMENT: NULL arguments, a malformed model, a non-finite position, origin_lod > 31.  BT_ERR_UNSUPPORTED: a planar
+ * model — the reference fills the structure with the cube sphere's derivatives there, which describe no plane (and its planar terrains
+ * are small enough for binary32).  bt_tile_tree_model_approximation: the same of the tree's model, view configuration and last view
+ * position (bt_tile_tree_update / bt_frame_update), like bt_tile_tree_view_state.
+ *
+ * REL(coordinate) = compute_relative_position (functions.wgsl:98-115), IEEE binary32, one rounding per written operation:
+ *   (side, X, Y, uv') = coordinate_change_lod(coordinate, origin_lod); per axis a with view_xy / view_uv of view.sides[side]:
+ *     st_a = ((f32(i32(XY_a) - view_xy_a) + uv'_a) - view_uv_a) / 2^origin_lod;  (s, t) = st
+ *   REL = ((((c + c_s*s) + c_t*t) + (c_ss*s)*s) + (c_st*s)*t) + (c_tt*t)*t, componentwise, with the coefficients of sides[side]
+ *
+ * THE VERTEX.  Steps 1, 2 of TERRAIN GEOMETRY as they are (d0 = step 2's d), then
+ *   2h. hp = d0 < precision_threshold_distance.  Not hp: steps 3 - 6 as they are (d = d0).  hp: rel0 = REL(tile, tile_uv);
+ *       d = length3(rel0 + approximate_height * n0), componentwise
+ *   3h. (hp) morph as step 3 with this d; rel = REL(tile, uv); world = view.world_position + rel, componentwise; n = n0, the normal at the
+ *       UNMORPHED tile_uv, as vertex.wgsl:55 has it
+ *   4 - 6 with this d (blend ratio, view_distance) and this (world, n).
+ * The reference's view.world_position + rel throws the series' precision away again in binary32: it relies on big_space keeping the
+ * camera near the origin.  BT_GEOMETRY_VIEW_RELATIVE is the form a consumer without big_space needs: position is relative to the view,
+ *   hp vertex: position = rel + height * n;   any other vertex: position = (world - view.world_position) + height * n, componentwise
+ * and the consumer adds its own f64 view position.  Every other field is the same in both forms.
+ * precision_threshold_distance == 0: no vertex is hp, and without VIEW_RELATIVE the output is the plain calls' byte for byte.
+ *
+ * The two calls take the plain calls' arguments plus the approximation, and behave as they do (layouts, capacity, launch per 32 MiB,
+ * reads).  Pass an approximation and a view derived from the SAME position (bt_model_approximation_from_config and
+ * bt_view_state_from_config, or bt_tile_tree_model_approximation and bt_tile_tree_view_state): REL offsets the view's view_xy / view_uv.
+ * Refusals: the plain calls', plus BT_ERR_INVALID_ARGUMENT for a NULL approximation, an origin_lod that differs from the view's, a
+ * precision_threshold_distance that is not finite or is negative; BT_ERR_UNSUPPORTED for the tree of a planar model.  The plain calls
+ * keep refusing BT_GEOMETRY_VIEW_RELATIVE. */
+typedef struct bt_side_coefficients {
+    float c[3], c_s[3], c_t[3], c_ss[3], c_st[3], c_tt[3];
+} bt_side_coefficients;
+typedef struct bt_model_approximation { /* 448 bytes: a kernel argument of its own */
+    bt_side_coefficients sides[6];
+    float precision_threshold_distance; /* f32(view_config.precision_threshold_distance * TerrainModel::scale()) */
+    uint32_t origin_lod;                /* the origin_lod the coefficients (and the view's view_xy / view_uv) belong to */
+    uint32_t _padding[2];
+} bt_model_approximation;
+enum { BT_GEOMETRY_VIEW_RELATIVE = 8 }; /* the _hp calls only */
+bt_status bt_model_approximation_from_config(const bt_terrain_model* model, const bt_terrain_view_config* view_config,
+                                             const double view_world_position[3], bt_model_approximation* out);
+bt_status bt_tile_tree_model_approximation(bt_tile_tree* tree, bt_model_approximation* out);
+bt_status bt_tile_tree_build_geometry_hp(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_view_state* view /* NULL: bt_tile_tree_view_state */,
+                                         const bt_model_approximation* approximation, const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device,
+                                         uint64_t vertex_capacity);
+bt_status bt_tile_tree_tile_geometry_hp(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_view_state* view /* NULL: bt_tile_tree_view_state */,
+                                        const bt_model_approximation* approximation, const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags,
+                                        bt_terrain_vertex* out_host, uint64_t out_bytes);
 
 /* One frame of one view (src/plugin.rs:46-56: TileTree::compute_requests -> TileAtlas::update's release / request half ->
  * TileTree::adjust_to_tile_atlas -> TileTree::approximate_height -> TilingPrepassNode::run) as ONE call with ONE host
