@@ -7,7 +7,10 @@ every side, and three explicit views (near, middle, far) that put those tiles at
 above.  The tree's table is derived on the CPU from the second models (_second_models.TileTreeModel / StreamModel), the tiles by the CPU
 oracle; the GPU test streams the same terrain and asserts that the device's table and layers are these.
 
-scene(kind, grid, loaded) computes once per process: the parameters, the views, the tiles, the entries and the layers."""
+scene(kind, grid, loaded) computes once per process: the parameters, the views, the tiles, the entries and the layers.
+
+At the end, for test_gpu_geometry_trips.py: the scenes' tiles as lists longer than one launch's 1024 workgroups and than the host form's
+32 MiB launches (long_tiles, LONG), and a 9-LOD tree whose prepass list is longer than 1024 (deep_scene)."""
 import functools
 import types
 
@@ -161,3 +164,133 @@ def expected(kind, grid, loaded, view, flags):
 COMPARED = ([(kind, 4, True, 0) for kind in MODELS] + [("planar", 5, True, 0), ("sphere", 12, True, 0), ("ellipsoid", 16, True, 0), ("planar", 32, True, 0)]
             + [("sphere", 5, True, GM.GRID), ("planar", 12, True, GM.GRID | GM.NO_MORPH), ("ellipsoid", 4, True, GM.NO_BLEND), ("planar", 16, True, GM.NO_MORPH | GM.NO_BLEND)]
             + [("planar", 4, False, 0), ("sphere", 4, False, GM.GRID)])
+
+
+# ---- long lists: later trips of the workgroup loop, the host form's chunks, the capacity cut ------------------------------------------------
+# (test_gpu_geometry_trips.py; test_geometry_model.py asserts without a GPU that they reach what they claim)
+TRIP = 1024  # workgroups of one launch: tile k and tile k + TRIP are the same workgroup's, one trip apart
+VERTEX_BYTES = 48
+LONG_MAX = 2060  # the longest list: the shorter ones are its head
+
+
+def slots_of(grid, flags):
+    return (grid + 1) ** 2 if flags & GM.GRID else 2 * grid * (grid + 2)
+
+
+def chunk_tiles(grid, flags):
+    """tiles per launch of the host form, from the header's rule (one launch per 32 MiB of vertices, at least one tile)"""
+    return max(1, (32 << 20) // (slots_of(grid, flags) * VERTEX_BYTES))
+
+
+@functools.lru_cache(maxsize=None)
+def long_rows(kind, seed):
+    """rows of tiles(kind) for a list of LONG_MAX tiles: the scene over and over, each round in a permuted order of its own, such that
+    positions k and k + 1024, and k and k + 2048, hold tiles of different LOD or side, and positions k and k + 1 different tiles.
+    (One order repeated cannot do it: on the planar scene 32 of the 37 tiles are of two LODs, and the three positions of a workgroup that
+    takes three trips need a third LOD each.)  Every round is drawn from `seed`; then, while a pair clashes, one of its two positions
+    changes places with another of its round, and the exchange is kept unless it adds clashes"""
+    t = tiles(kind)
+    m = len(t)
+    cls = t[:, 0].astype(np.int64) * 64 + t[:, 1]
+    rng = np.random.default_rng(seed)
+    k1, k2 = np.arange(LONG_MAX - TRIP), np.arange(LONG_MAX - 2 * TRIP)
+
+    def clashing(r):
+        c = cls[r]
+        one, two = k1[c[k1] == c[k1 + TRIP]], k2[c[k2] == c[k2 + 2 * TRIP]]
+        return np.concatenate([one, one + TRIP, two, two + 2 * TRIP, np.flatnonzero(r[1:] == r[:-1])])
+
+    for attempt in range(32):  # (a draw whose repair comes to rest on a few clashes is drawn again)
+        rows = np.concatenate([rng.permutation(m) for _ in range(-(-LONG_MAX // m))])[:LONG_MAX]
+        bad = clashing(rows)
+        for _ in range(4000):
+            if not len(bad):
+                return rows
+            i = int(bad[rng.integers(len(bad))])
+            j = min(i // m * m + int(rng.integers(m)), LONG_MAX - 1)
+            rows[i], rows[j] = rows[j], rows[i]
+            after = clashing(rows)
+            if len(after) <= len(bad):
+                bad = after
+            else:
+                rows[i], rows[j] = rows[j], rows[i]
+    raise AssertionError((kind, seed, len(bad)))
+
+
+def long_index(kind, count, seed=3):
+    """row of tiles(kind) that position k of the long list holds"""
+    assert count <= LONG_MAX
+    return long_rows(kind, seed)[:count]
+
+
+def long_tiles(kind, count, seed=3):
+    """tiles(kind) in a fixed permuted order, round after round until `count`: every tile of the scene the same number of times +- 1"""
+    return np.ascontiguousarray(tiles(kind)[long_index(kind, count, seed)])
+
+
+def gather(expectation, index):
+    """a model's (vertices, trace, admissible) of the scene's tiles -> (vertices, admissible) of the long list: the rows gathered to list
+    order, tile_index the list's own"""
+    vertices, _, admissible = expectation
+    vertices = vertices[index].copy()
+    vertices["tile_index"] = np.arange(len(index), dtype=np.uint32)[:, None]
+    return vertices, admissible[index]
+
+
+def long_expected(kind, grid, view, flags, count, seed=3):
+    return gather(expected(kind, grid, True, view, flags), long_index(kind, count, seed))
+
+
+# the host form's long calls, near view, loaded scenes: (kind, grid, flags, count, launches).  launches: the tiles of each launch, by the
+# header's rule; more than 1024 in one launch is a later trip of the workgroup loop
+LONG = [
+    ("planar", 4, 0, 2060, (2060,)),                    # second and third trip; 12 workgroups take three
+    ("sphere", 4, GM.GRID | GM.NO_MORPH, 1025, (1025,)),  # exactly one workgroup takes a second trip
+    ("planar", 4, 0, 1024, (1024,)),                    # the boundary: nobody takes a second trip
+    ("ellipsoid", 16, 0, 1300, (1213, 87)),             # a second trip inside chunk 0 (289 grid vertices: the thread loop's second trip too)
+    ("planar", 32, 0, 330, (321, 9)),                   # a chunk boundary at the LDS cap
+    ("sphere", 32, GM.GRID, 1290, (641, 641, 8)),       # three chunks: the scratch reused twice
+]
+
+
+def launches_of(grid, flags, count):
+    chunk = chunk_tiles(grid, flags)
+    return tuple(min(chunk, count - first) for first in range(0, count, chunk))
+
+
+# ---- the device form on a list longer than 1024: a deeper tree on the same atlas, never adjusted (every entry invalid) ---------------------
+DEEP_LODS = 9
+DEEP_KW = dict(tree_size=4, morph_distance=6.0, blend_distance=1.0, grid_size=4, refinement_count=8, geometry_tile_count=4096)
+
+
+def deep_view_config(**more):
+    kw = dict(DEEP_KW, **more)
+    return bt.TerrainViewConfig(**kw), O.make_view_config(**kw)
+
+
+@functools.lru_cache(maxsize=None)
+def deep_scene(kind):
+    """the near view over a tree of DEEP_LODS LODs: the oracle's prepass list (measured: 1416 tiles on the sphere, 1415 on the ellipsoid, LODs
+    2 .. 8), the parameters and the all-invalid table"""
+    c = types.SimpleNamespace(kind=kind)
+    c.model, c.omodel = MODELS[kind]
+    c.view_config, c.oview_config = deep_view_config()
+    c.position = SPECS[kind]["views"][0]
+    c.view = O.view_state_from_config(c.omodel, c.oview_config, c.position, approximate_height(kind))
+    c.tiles, c.indirect, _ = O.refine(c.view)
+    c.P = GM.params(c.model, c.view_config, DEEP_LODS)
+    c.entries = np.full(((1 if kind == "planar" else 6) * DEEP_LODS * DEEP_KW["tree_size"] ** 2, 2), GM.INVALID, np.uint32)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def deep_expected(kind, flags):
+    c = deep_scene(kind)
+    return GM.geometry(c.view, c.P, c.entries, {}, T, B, c.tiles, flags)
+
+
+def cuts(n, slots):
+    """(vertex_capacity, the first tile left out) of the capacity-cut test on a list of n tiles: in a second trip with tiles behind it;
+    no partial tile and every second trip cut (24 workgroups already at their first: tiles 1000 .. 1023); the first trip whole and the
+    second cut whole; everything"""
+    return [(1100 * slots + slots - 1, 1100), (1000 * slots, 1000), (1024 * slots + 1, 1024), (n * slots, n)]

@@ -7,7 +7,9 @@ coordinate_change_lod UP (tile LODs 0 .. 2) and nowhere (LOD 3), origin_lod 10 U
 
 The deep scene sends it DOWN and is the one the accuracy is measured on: lod_count 16, nothing loaded, min_height 0 (every height is
 exactly 0, so `position` is the surface point itself), grid 16, LOD 15 tiles (about 300 m) under and around a view 2 m above the ground, out
-to the default threshold (0.001 scales, about 6.4 km) and just beyond it, the reference's default view configuration otherwise."""
+to the default threshold (0.001 scales, about 6.4 km) and just beyond it, the reference's default view configuration otherwise.
+
+At the end, for test_gpu_geometry_trips.py: _geometry_cases' long lists with a threshold and an origin_lod (LONG, long_device_scene)."""
 import functools
 import types
 
@@ -99,4 +101,46 @@ def deep_scene(kind):
 @functools.lru_cache(maxsize=None)
 def deep_expected(kind, flags):
     c = deep_scene(kind)
+    return HM.geometry(c.view, c.approximation, c.P, c.entries, {}, GC.T, GC.B, c.tiles, flags)
+
+
+# ---- long lists (test_gpu_geometry_trips.py): _geometry_cases' long lists through the kHighPrecision instantiation --------------------------
+# (kind, grid, threshold, origin_lod, flags, view, count, launches)
+LONG = [
+    ("sphere", 4, SPLIT, 3, 0, NEAR, 2060, (2060,)),                         # later trips, hp and other vertices mixed
+    ("ellipsoid", 32, ALL, 10, HM.VIEW_RELATIVE, MIDDLE, 330, (321, 9)),  # the hp form across a chunk boundary
+]
+
+
+def long_expected(kind, grid, threshold, origin_lod, flags, n, count, seed=3):
+    """(vertices, admissible) of the long list, (hp per vertex) of the scene's own tiles"""
+    e = expected(kind, grid, threshold, origin_lod, flags, n)
+    return GC.gather(e, GC.long_index(kind, count, seed)) + (e[1]["hp"],)
+
+
+# the device form on _geometry_cases.deep_scene's list (more than 1024 tiles of LODs 2 .. 8 in that order, nothing loaded).  Chosen from the
+# model's trace: the nearest vertex of the near view's list is 0.026 scales away and the median 0.25; at 0.1 scales a quarter of the vertices
+# are hp, 4 in 100 of the first 1024 tiles' and 86 in 100 of the later tiles', which are the workgroups' second trip, and some forty tiles
+# of that trip hold both kinds.  The hp vertices belong to tiles of LODs 7 and 8: with origin_lod 7 coordinate_change_lod goes nowhere and DOWN
+LONG_DEVICE_THRESHOLD, LONG_DEVICE_ORIGIN = 0.1, 7
+
+
+def long_device_view_config():
+    return GC.deep_view_config(precision_threshold_distance=LONG_DEVICE_THRESHOLD, origin_lod=LONG_DEVICE_ORIGIN)
+
+
+@functools.lru_cache(maxsize=None)
+def long_device_scene(kind):
+    """_geometry_cases.deep_scene with the threshold and origin_lod above: its view, approximation and the oracle's prepass list"""
+    c = types.SimpleNamespace(**vars(GC.deep_scene(kind)))
+    c.view_config, c.oview_config = long_device_view_config()
+    c.view = O.view_state_from_config(c.omodel, c.oview_config, c.position, GC.approximate_height(kind))
+    c.approximation = HM.approximation(c.model, c.view_config, c.position)
+    c.tiles, c.indirect, _ = O.refine(c.view)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def long_device_expected(kind, flags):
+    c = long_device_scene(kind)
     return HM.geometry(c.view, c.approximation, c.P, c.entries, {}, GC.T, GC.B, c.tiles, flags)

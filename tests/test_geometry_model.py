@@ -6,7 +6,10 @@ grid; every lookup's height against the oracle's tile sample; flat terrains agai
 The scenes: the union of their traces reaches every value the GPU comparison is there for — coordinate_change_lod up, down and not at all
 for either lookup, the second lookup taken and not, morph ratio 0, between and 1, own, ancestor's and no entry, every cube side — and at
 most 1 vertex in 1000 is inadmissible (a log2 two doubles away would change one of its bits; both sides use this machine's libm here: the
-rule is about the device's)."""
+rule is about the device's).
+The long lists of test_gpu_geometry_trips.py: their lengths against 1024, 2048 and the chunk sizes the header's rule gives, tiles one and two
+trips apart and on either side of a chunk boundary different in LOD or side and in the model's positions, the oracle's prepass list on the
+9-LOD tree longer than 1024, the same cap on inadmissible vertices."""
 import numpy as np
 import pytest
 
@@ -213,3 +216,80 @@ def test_admissibility_flag():
         assert not flagged.ravel()[at] and flagged.sum() == flagged.size - 1, (key, at)
         planted[key][at] = float(F(logs[key][at]))  # the middle of its rounding interval
         assert GM.geometry(*args, logs=planted)[2].all()
+
+
+# ---- the long lists of test_gpu_geometry_trips.py ------------------------------------------------------------------------------------------
+
+def position_rows(vertices):
+    """per tile, the bits of every vertex's position"""
+    return bits(vertices["position"]).reshape(len(vertices), -1)
+
+
+def assert_list_conditions(tiles, launches):
+    """what makes a vertex written to another trip's slots, or a chunk that began again at the list's head, differ from the expected one in
+    more than tile_index: tiles one and two trips apart are of different LOD or side, the tiles on either side of a chunk boundary differ,
+    and so do the list's first tile and the first of every later chunk"""
+    count = len(tiles)
+    for step in (GC.TRIP, 2 * GC.TRIP):
+        a, b = tiles[:max(0, count - step)], tiles[step:]
+        assert ((a[:, 0] != b[:, 0]) | (a[:, 1] != b[:, 1])).all(), step
+    assert sum(launches) == count
+    for c in np.cumsum(launches)[:-1]:
+        assert (tiles[c - 1] != tiles[c]).any() and (tiles[0] != tiles[c]).any(), c
+
+
+def test_long_lists_reach_later_trips_and_chunk_boundaries():
+    by_hand = {(16, 0): 1213, (32, 0): 321, (32, GM.GRID): 641, (4, 0): 14563}
+    for (grid, flags), chunk in by_hand.items():
+        slots = (grid + 1) ** 2 if flags & GM.GRID else 2 * grid * (grid + 2)
+        assert max(1, (32 << 20) // (slots * 48)) == chunk == GC.chunk_tiles(grid, flags)
+    reached = []
+    for kind, grid, flags, count, launches in GC.LONG:
+        tiles = GC.long_tiles(kind, count)
+        assert tiles.shape == (count, 4) and launches == GC.launches_of(grid, flags, count)
+        # every tile of the scene, the same number of times +- 1
+        rows = GC.long_index(kind, count)
+        times = np.bincount(rows, minlength=len(GC.tiles(kind)))
+        assert times.max() - times.min() <= 1 and times.min() >= 1 and np.array_equal(tiles, GC.tiles(kind)[rows])
+        assert_list_conditions(tiles, launches)
+        # what a launch of n tiles reaches: min(n, 1024) workgroups, of which n - 1024 take a second trip and n - 2048 a third
+        reached.append(tuple((n, min(n, GC.TRIP), max(0, min(n - GC.TRIP, GC.TRIP)), max(0, n - 2 * GC.TRIP)) for n in launches))
+        exp, admissible = GC.long_expected(kind, grid, 0, flags, count)
+        assert exp.shape == (count, GC.slots_of(grid, flags)) and np.array_equal(exp["tile_index"][:, 0], np.arange(count))
+        position = position_rows(exp)
+        for step in (GC.TRIP, 2 * GC.TRIP):  # a tile written by the wrong trip is seen in its positions
+            if count > step:
+                assert (position[:count - step] != position[step:]).any(axis=1).all(), (kind, grid, step)
+        for c in np.cumsum(launches)[:-1]:  # and so is a chunk that began again at the head of the list
+            assert (position[0] != position[c]).any() and (position[c - 1] != position[c]).any()
+        skipped = int((~admissible).sum())
+        print(kind, grid, flags, count, "vertices", admissible.size, "inadmissible", skipped)
+        assert skipped * 1000 <= admissible.size
+    assert reached == [((2060, 1024, 1024, 12),), ((1025, 1024, 1, 0),), ((1024, 1024, 0, 0),), ((1213, 1024, 189, 0), (87, 87, 0, 0)), ((321, 321, 0, 0), (9, 9, 0, 0)),
+                       ((641, 641, 0, 0), (641, 641, 0, 0), (8, 8, 0, 0))]
+    assert (16 + 1) ** 2 > 256  # the 1300-tile case: a second trip of the thread loop inside a workgroup's second trip
+
+
+def test_deep_scene_gives_the_device_form_a_list_longer_than_1024():
+    """the oracle's prepass list on the 9-LOD tree at the near view (measured: 1416 tiles on the sphere, LODs 2 .. 8, 1415 on the ellipsoid):
+    more than one trip of the device form's 1024 workgroups, fewer than three; the cut capacities of the GPU test lie where they claim"""
+    lengths = {}
+    for kind in ("sphere", "ellipsoid"):
+        c = GC.deep_scene(kind)
+        n = lengths[kind] = len(c.tiles)
+        assert GC.TRIP < n <= 2 * GC.TRIP and n <= GC.DEEP_KW["geometry_tile_count"] and c.tiles[:, 1].max() < GC.DEEP_LODS
+        assert c.indirect[0] == n * 48 and len(np.unique(c.tiles, axis=0)) == n  # (grid 4: 48 strip slots a tile)
+        for flags in (0, GM.GRID):
+            exp, trace, admissible = GC.deep_expected(kind, flags)
+            assert (trace["state0"] == GM.NO_ENTRY).all()
+            position = position_rows(exp)
+            assert (position[:n - GC.TRIP] != position[GC.TRIP:]).any(axis=1).all()
+            print(kind, flags, "tiles", n, "by LOD", np.bincount(c.tiles[:, 1], minlength=GC.DEEP_LODS).tolist(), "inadmissible", int((~admissible).sum()))
+            assert (~admissible).sum() * 1000 <= admissible.size
+    assert lengths == {"sphere": 1416, "ellipsoid": 1415}
+    assert np.bincount(GC.deep_scene("sphere").tiles[:, 1], minlength=GC.DEEP_LODS).tolist() == [0, 0, 27, 190, 266, 235, 233, 233, 232]
+    # the cuts: tile c is the first left out
+    n, slots = lengths["sphere"], 48
+    for capacity, c in GC.cuts(n, slots):
+        assert c == min(n, capacity // slots), (capacity, c)
+    assert [c for _, c in GC.cuts(n, slots)] == [1100, 1000, 1024, n] and 1000 + GC.TRIP > n >= 1100

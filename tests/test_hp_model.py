@@ -1,7 +1,7 @@
 """The high-precision terrain geometry without a GPU: bt_model_approximation_from_config (host code, f64) byte for byte against the model
 of its definition (tests/_hp_model.py), the model's coefficients against central differences of the f64 surface function, the accuracy of
 the hp vertex against f64 truth next to the plain vertex's, the model at threshold 0 against _geometry_model, and the reach of the scenes
-test_gpu_hp_geometry.py compares (tests/_hp_cases.py)."""
+test_gpu_hp_geometry.py compares (tests/_hp_cases.py), and of the long lists test_gpu_geometry_trips.py sends through the hp calls."""
 import ctypes as C
 
 import numpy as np
@@ -187,3 +187,47 @@ def test_python_keywords():
         bt.tile_tree._geometry_flags(False, True, True, None, True)
     assert bt.tile_tree._geometry_flags(True, False, True, object(), True) == 1 | 2 | 8 == _ffi.GEOMETRY_GRID | _ffi.GEOMETRY_NO_MORPH | _ffi.GEOMETRY_VIEW_RELATIVE
     assert bt.tile_tree._geometry_flags(False, True, True) == 0
+
+
+# ---- the long lists of test_gpu_geometry_trips.py ------------------------------------------------------------------------------------------
+
+def test_long_hp_lists():
+    from test_geometry_model import assert_list_conditions, position_rows
+    for kind, grid, threshold, origin_lod, flags, n, count, launches in HC.LONG:
+        tiles = GC.long_tiles(kind, count)
+        assert launches == GC.launches_of(grid, flags, count)
+        assert_list_conditions(tiles, launches)
+        exp, admissible, hp = HC.long_expected(kind, grid, threshold, origin_lod, flags, n, count)
+        hp = hp[GC.long_index(kind, count)]
+        assert exp.shape == hp.shape == (count, GC.slots_of(grid, flags))
+        position = position_rows(exp)
+        for step in (GC.TRIP, 2 * GC.TRIP):
+            if count > step:
+                assert (position[:count - step] != position[step:]).any(axis=1).all(), (kind, grid, step)
+                # hp and plain vertices in the later trips too
+                assert threshold != HC.SPLIT or (hp[step:].any() and not hp[step:].all() and (hp[step:].any(axis=1) & ~hp[step:].all(axis=1)).any())
+        for c in np.cumsum(launches)[:-1]:
+            assert (position[0] != position[c]).any() and (position[c - 1] != position[c]).any()
+        assert hp.all() if threshold == HC.ALL else (hp.any() and not hp.all())
+        print(kind, grid, threshold, count, "vertices", hp.size, "hp", int(hp.sum()), "inadmissible", int((~admissible).sum()))
+        assert (~admissible).sum() * 1000 <= admissible.size
+    assert [c[6:] for c in HC.LONG] == [(2060, (2060,)), (330, (321, 9))]
+
+
+def test_long_device_list_mixes_hp_and_plain_vertices():
+    """the threshold and origin_lod of the device form's long hp list change nothing in the prepass's list; between one vertex in ten and all
+    of them are hp, in the first trip of the 1024 workgroups and in the second, where tiles hold both kinds"""
+    for kind in HC.KINDS:
+        c = HC.long_device_scene(kind)
+        assert np.array_equal(c.tiles, GC.deep_scene(kind).tiles) and len(c.tiles) > GC.TRIP
+        assert c.view.origin_lod == HC.LONG_DEVICE_ORIGIN == c.approximation.origin_lod
+        for flags in (GM.GRID | HM.VIEW_RELATIVE, 0):
+            exp, trace, admissible = HC.long_device_expected(kind, flags)
+            share = trace["hp"].mean()
+            print(kind, flags, "tiles", len(c.tiles), "hp share %.3f" % share, "inadmissible", int((~admissible).sum()))
+            assert 0.1 < share < 1
+            assert set(np.unique(trace["dir_origin"][trace["hp"]]).tolist()) == {GM.NONE, GM.DOWN}
+            for part in (trace["hp"][:GC.TRIP], trace["hp"][GC.TRIP:]):
+                assert part.any() and not part.all()
+            assert (trace["hp"][GC.TRIP:].any(axis=1) & ~trace["hp"][GC.TRIP:].all(axis=1)).sum() >= 16
+            assert (~admissible).sum() * 1000 <= admissible.size
