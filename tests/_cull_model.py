@@ -174,16 +174,20 @@ def overflows(passes, final_count, capacity):
     return final_count > capacity or any(visited + 4 * dividing > capacity for visited, dividing in passes)
 
 
-def build_table(sides, levels, held):
+def build_table(sides, levels, held, own=None):
     """bt_height_bounds_build: held = {(side, lod, x, y): the tile's (T, T) uint16 layer}.  own = min / max of the whole layer
     (_bounds_model.tile_bounds at grid 1); a tile that is not held takes own of its parent, a root the whole range; then every entry is
-    united with its children's."""
+    united with its children's.  own: {coord: (min, max)} of the held tiles, computed by the caller (for tens of thousands of tiles,
+    where one tile_bounds call each takes seconds); held is not looked at then."""
     table = Table(sides, levels)
-    own = {}
-    for (side, lod, x, y), layer in held.items():
-        if lod < levels:
-            mn, mx = B.tile_bounds(np.asarray(layer)[None], 1)[0][0, 0, 0]
-            own[(side, lod, x, y)] = (int(mn), int(mx))
+    if own is not None:
+        own = {c: (int(mn), int(mx)) for c, (mn, mx) in own.items() if c[1] < levels}
+    else:
+        own = {}
+        for (side, lod, x, y), layer in held.items():
+            if lod < levels:
+                mn, mx = B.tile_bounds(np.asarray(layer)[None], 1)[0][0, 0, 0]
+                own[(side, lod, x, y)] = (int(mn), int(mx))
     for lod in range(levels):
         for side in range(sides):
             for y in range(1 << lod):

@@ -1,12 +1,15 @@
 """CPU checks of bt_height_bounds_update: the entry point's export, the stats struct's size and the NULL-table status, and a small numpy
 restatement of the incremental plan (U, ancestors, fill roots, walk-up, bottom-up) against the definition, _cull_model.build_table, on
 random sparse held sets with random changes.  The GPU comparisons are in test_gpu_bounds_update.py, which takes its entries_written cap
-from here."""
+from here.  The last tests check the inputs of test_gpu_bounds_update_shapes.py (_bounds_update_cases.py): every case reaches the branch
+it is named for, on the numpy plan alone."""
 import ctypes as C
 import os
 
 import numpy as np
 
+import _bounds_model as B
+import _bounds_update_cases as BC
 import _cull_model as M
 from bevy_terrain_amd import _ffi
 
@@ -28,7 +31,8 @@ def children(c):
 def plan(levels, listed, is_held):
     """-> (U, the ancestors of U outside U, the distinct fill roots): index arithmetic only"""
     U = list(dict.fromkeys(c for c in listed if c[1] < levels))
-    up = list(dict.fromkeys(a for c in U for a in ancestors(c) if a not in set(U)))
+    in_U = set(U)
+    up = list(dict.fromkeys(a for c in U for a in ancestors(c) if a not in in_U))
     roots = list(dict.fromkeys(ch for c in U for ch in children(c) if ch[1] < levels and not is_held(ch)))
     return U, up, roots
 
@@ -156,3 +160,153 @@ def test_incremental_plan_agrees_with_the_definition():
             assert written <= cap
             within_cap += 1
     assert min(shrank, grew, flipped) > 50 and within_cap == 720
+
+
+# ---- the inputs of test_gpu_bounds_update_shapes.py: every case reaches the branch it is named for, on the numpy plan alone ------------
+
+def test_vectorised_own_ranges_are_tile_bounds_at_grid_1():
+    """the big cases hand build_table own ranges computed for all layers at once: the same numbers as one tile_bounds call per layer,
+    and the same table"""
+    rng = np.random.default_rng(3)
+    coords, layers = BC.big_initial()
+    assert len(coords) == len(layers) == 21845 and layers.dtype == np.uint16 and layers.shape[1:] == (BC.T, BC.T)
+    sample = np.concatenate([[0, 1, 4, 5, 20, 21, 84, 85, 21844], rng.integers(0, 21845, 48)])
+    ranges = BC.own_ranges(layers)
+    for i in sample:
+        assert tuple(ranges[i]) == tuple(int(v) for v in B.tile_bounds(layers[i], 1)[0][0, 0, 0]), i
+    assert ranges[:, 0].min() >= BC.BIG_BASE[0] and ranges[:, 1].max() <= BC.BIG_BASE[1]
+    lo, hi = rng.integers(0, 60000, 40), rng.integers(0, 5000, 40)
+    hi[:3] = 0  # a flat layer
+    made = BC.layers_with(rng, lo, lo + hi)
+    assert np.array_equal(BC.own_ranges(made), np.stack([lo, lo + hi], axis=1))
+    one = BC.layer_with(rng, 17, 60001)
+    assert tuple(B.tile_bounds(one, 1)[0][0, 0, 0]) == (17, 60001)
+    held = {c: l for c, l in zip(coords[:85], layers[:85]) if rng.random() < 0.6}
+    assert np.array_equal(M.build_table(1, 5, held).data, M.build_table(1, 5, None, own=BC.own_of(held)).data)
+
+
+def check_one_writer(reach):
+    entries = BC.window_entries(reach.windows)
+    assert len(entries) == len(set(entries)) == reach.total and set(entries) == reach.affected
+
+
+def test_sparse_scripts_reach():
+    """case 1: the scripts replayed on the numpy plan equal the definition after every step, stay in the one-workgroup form, and between
+    them reach the walk-ups, the whole-range entries, the nested roots and the covered listed tiles the GPU test sums up"""
+    assert 12 <= len(BC.SPARSE) <= 16
+    assert {lv for s, lv, _ in BC.SPARSE if s == 1} == set(range(1, 7)) and {lv for s, lv, _ in BC.SPARSE if s == 6} >= set(range(1, 5))
+    assert sum(s == 6 and lv == 5 for s, lv, _ in BC.SPARSE) >= 2 and {d for _, _, d in BC.SPARSE} == {-1, 0, 1}
+    seen, kinds, densities = dict(), set(), set()
+    for seed in range(len(BC.SPARSE)):
+        script = BC.sparse_script(seed)
+        densities.add(script.density)
+        table = M.build_table(script.sides, script.levels, None, own=BC.own_of(script.initial))
+        shadow = {c: r for c, r in BC.own_of(script.initial).items() if c[1] < script.levels}
+        assert len(script.steps) == 3
+        for step, reach, held in BC.replay(script):
+            own = BC.own_of(held)
+            before = table.data.copy()
+            written = incremental_update(table, shadow, step.listed, own)
+            assert np.array_equal(table.data, M.build_table(script.sides, script.levels, None, own=own).data), seed
+            assert written == reach.total == len(reach.affected) and reach.small_form and reach.launches() == 1
+            check_one_writer(reach)
+            assert len(step.listed) == len(set(step.listed)) + 1 and any(c[1] >= script.levels for c in step.listed)
+            kinds |= set(step.kinds)
+            for name, hit in BC.sparse_reach(reach, held).items():
+                seen[name] = seen.get(name, 0) + hit
+            seen["differs"] = seen.get("differs", 0) + (not np.array_equal(before, table.data))
+    assert densities == set(BC.DENSITIES) and kinds == {"narrow", "move", "evict", "hold", "load"}
+    assert all(seen[name] >= 2 for name in ("walks_two", "whole_range_beside_held", "nested_roots", "listed_under_a_root")), seen
+    assert seen["differs"] == 3 * len(BC.SPARSE), seen  # every step shows something
+
+
+def test_second_trip_inputs():
+    """case 2: (a) more than 1024 scatter records, windows, affected entries and level-6 entries, at most 4096 in all, no fill root;
+    (b) one entry and no work on any deeper level"""
+    listed = BC.second_trip_list()
+    reach = BC.Reach(BC.BIG_LEVELS, listed, lambda c: True)
+    assert len(set(listed)) == len(listed) == 1104 and not reach.roots
+    assert BC.SMALL_THREADS < reach.work[6] == len(reach.U) == 1104 and reach.work[7] == 0
+    assert BC.SMALL_THREADS < reach.window_count == reach.total <= BC.SMALL_FORM_MAX and reach.launches() == 1
+    assert reach.work[:6] == [1, 2, 6, 19, 69, 276]
+    check_one_writer(reach)
+    coords, layers = BC.big_initial()
+    new, unions = BC.second_trip_layers(np.random.default_rng(1), listed, dict(zip(coords, BC.own_ranges(layers))))
+    ranges = BC.own_ranges(new)
+    wide, flat = ranges[0::2], ranges[1::2]  # both kinds on either side of entry 1024
+    assert len({tuple(r) for r in wide}) == 552 and wide[:, 0].max() < BC.BIG_BASE[0] and wide[:, 1].min() > BC.BIG_BASE[1]
+    assert (flat[:, 0] == flat[:, 1]).all() and (unions[1::2, 0] < flat[:, 0]).all() and (flat[:, 1] < unions[1::2, 1]).all()
+    root = BC.Reach(BC.BIG_LEVELS, [(0, 0, 0, 0)], lambda c: True)
+    assert root.total == 1 and root.work == [1] + [0] * 7 and not root.roots
+
+
+def test_form_edge_arithmetic():
+    """case 3: 3072 level-7 tiles and their ancestors are 4097 entries, one more than the one-workgroup form takes; without one of the
+    tiles 4096, whose windows (single entries all) are exactly 65 536 bytes"""
+    listed = BC.form_edge_list()
+    assert len(set(listed)) == 3072 and all(c[1] == 7 for c in listed)
+    wide = BC.Reach(BC.BIG_LEVELS, listed, lambda c: True)
+    small = BC.Reach(BC.BIG_LEVELS, listed[:-1], lambda c: True)
+    assert wide.total == 3 * 1365 + 2 == 4097 == BC.SMALL_FORM_MAX + 1 and not wide.small_form and wide.launches() == 2 + 7
+    assert small.total == 4096 == BC.SMALL_FORM_MAX and small.small_form and len(small.U) == 3071
+    for reach in (wide, small):
+        assert not reach.roots and reach.window_count == reach.total and all(s == 0 for level in reach.windows for _, s, _, _ in level)
+        check_one_writer(reach)
+    assert small.window_count * 16 == 65536
+    assert wide.work == [1, 1, 3, 12, 48, 192, 768, 3072] and -(-len(wide.U) // BC.WIDE_THREADS) == 12
+    old = BC.big_initial()[1][:200]
+    new = BC.own_ranges(BC.moved_layers(np.random.default_rng(2), old))
+    assert (new != BC.own_ranges(old)).all()
+
+
+def test_cube_case_reach():
+    """case 4: the wide form, more than one workgroup of scatter records, a level with single windows and squares of two shifts, five
+    sides affected and one untouched"""
+    initial, ops, listed = BC.cube_case()
+    held, loading = dict(initial), set()
+    step = BC.Step()
+    step.ops = ops
+    BC.apply_step(held, loading, step)
+    assert 0.4 < len(initial) / len(BC.pyramid(BC.CUBE_LODS, 6)) < 0.6
+    reach = BC.Reach(BC.CUBE_LEVELS, listed, held.__contains__)
+    assert reach.total > BC.SMALL_FORM_MAX and reach.launches() > 2 and len(reach.U) > BC.WIDE_THREADS
+    check_one_writer(reach)
+    mixes = [{s for _, s, _, _ in level} for level in reach.windows]
+    assert any(0 in m and len(m - {0}) >= 2 for m in mixes), mixes
+    assert any(sum(1 for _, s, _, _ in level if s == 0) > 64 for level in reach.windows)  # a long list for the search
+    assert {c[0] for c in reach.affected} == set(range(6)) - {BC.CUBE_UNTOUCHED}
+    roots_listed = [c for c in listed if c[1] == 0]
+    assert len(roots_listed) >= 2 and all(0 < sum(ch in held for ch in children(c)) < 4 for c in roots_listed)
+    assert {c[1] for c in listed} == {0, 2, 3, BC.CUBE_LEVELS - 1}
+    last = [c for c in reach.U if c[1] == BC.CUBE_LEVELS - 1]
+    under = set(reach.listed_under_a_root())
+    assert any(c in under for c in last) and any(c not in under for c in last)
+    depths = reach.depths()
+    assert {d for d in depths.values()} >= {0, 1, 2, 3, 4}
+    table = M.build_table(6, BC.CUBE_LEVELS, None, own=BC.own_of(initial))
+    shadow = {c: r for c, r in BC.own_of(initial).items()}
+    assert incremental_update(table, shadow, listed, BC.own_of(held)) == reach.total
+    assert np.array_equal(table.data, M.build_table(6, BC.CUBE_LEVELS, None, own=BC.own_of(held)).data)
+
+
+def test_deep_walk_reach():
+    """case 5: fill roots at level 3 under an 8-level table; their entries walk up 1 to 5 levels below a held LOD-2 tile and 2 to 6
+    below an evicted one"""
+    initial, ops, listed = BC.deep_walk_case()
+    held, loading = dict(initial), set()
+    step = BC.Step()
+    step.ops = ops
+    BC.apply_step(held, loading, step)
+    assert {c[1] for c in initial} == {0, 1, 2} and 0 < sum(c[1] == 2 for c in held) < 16 and all(c[1] == 2 for c in listed)
+    reach = BC.Reach(BC.DEEP_LEVELS, listed, held.__contains__)
+    assert reach.total > BC.SMALL_FORM_MAX and reach.launches() == 2 + 7
+    assert len(reach.roots) == 4 * len(listed) and all(r[1] == 3 for r in reach.roots) and not reach.nested_roots()
+    check_one_writer(reach)
+    depths = reach.depths()
+    below_held = {depths[c] for c in reach.affected if c[1] >= 3 and (0, 2, c[2] >> (c[1] - 2), c[3] >> (c[1] - 2)) in held}
+    below_evicted = {depths[c] for c in reach.affected if c[1] >= 3 and (0, 2, c[2] >> (c[1] - 2), c[3] >> (c[1] - 2)) not in held}
+    assert below_held == {1, 2, 3, 4, 5} and below_evicted == {2, 3, 4, 5, 6}
+    table = M.build_table(1, BC.DEEP_LEVELS, None, own=BC.own_of(initial))
+    shadow = dict(BC.own_of(initial))
+    assert incremental_update(table, shadow, listed, BC.own_of(held)) == reach.total
+    assert np.array_equal(table.data, M.build_table(1, BC.DEEP_LEVELS, None, own=BC.own_of(held)).data)
