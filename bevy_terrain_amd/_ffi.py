@@ -144,6 +144,20 @@ class RayHitC(C.Structure):
                 ("height", C.c_float), ("_padding", C.c_uint32)]
 
 
+RENDER_ORTHOGRAPHIC, RENDER_LIGHTING = 1, 2
+RENDER_MAX_STEPS, RENDER_MAX_PIXELS, RENDER_NO_ALBEDO = 4096, 1 << 24, 0xFFFFFFFF
+
+
+class RenderCameraC(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("forward", C.c_double * 3), ("right", C.c_double * 3), ("up", C.c_double * 3), ("t_min", C.c_double),
+                ("t_max", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("albedo_attachment", C.c_uint32),
+                ("sun", C.c_float * 3), ("ambient", C.c_float), ("background", C.c_uint8 * 4), ("_padding", C.c_uint32)]
+
+
+class RenderStatsC(C.Structure):
+    _fields_ = [("launches", C.c_uint32), ("hit_pixels", C.c_uint32), ("inside_pixels", C.c_uint32), ("miss_pixels", C.c_uint32)]
+
+
 GEOMETRY_GRID, GEOMETRY_NO_MORPH, GEOMETRY_NO_BLEND = 1, 2, 4
 GEOMETRY_MAX_GRID = 32
 GEOMETRY_VIEW_RELATIVE = 8  # the _hp calls only
@@ -336,6 +350,7 @@ PROTOTYPES = {
     "bt_tile_tree_approximate_height": (_i32, [_vp, _vp, _P(C.c_float)]),
     "bt_tile_tree_view_state": (_i32, [_vp, _P(ViewStateC)]),
     "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
+    "bt_tile_tree_render": (_i32, [_vp, _vp, _u32, _P(RenderCameraC), _u32, _u32, _P(C.c_double), _P(C.c_uint8), _P(C.c_float), _P(C.c_uint8), _P(RenderStatsC)]),
     "bt_tile_tree_sample_normal": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_float), _P(C.c_float)]),
     "bt_atlas_tile_normals": (_i32, [_vp, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(C.c_uint8), _u64]),
     "bt_tile_tree_build_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _vp, _u32, _vp, _u64]),

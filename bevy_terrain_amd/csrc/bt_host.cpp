@@ -291,6 +291,7 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
     if (ctx->raycast_dev) hipFree(ctx->raycast_dev);
     if (ctx->normal_dev) hipFree(ctx->normal_dev);
+    if (ctx->render_dev) hipFree(ctx->render_dev);
     if (ctx->edit_dev) hipFree(ctx->edit_dev);
     if (ctx->edit_host) hipHostFree(ctx->edit_host);
     if (ctx->edit_region_dev) hipFree(ctx->edit_region_dev);
@@ -357,6 +358,12 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
     }
     ctx->normal_dev = nullptr;
     ctx->normal_bytes = 0;
+    if (ctx->render_dev) {
+        BT_HIP(hipFree(ctx->render_dev));
+        freed += ctx->render_bytes;
+    }
+    ctx->render_dev = nullptr;
+    ctx->render_bytes = 0;
     if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
     if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
     if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));

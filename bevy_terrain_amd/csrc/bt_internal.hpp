@@ -207,6 +207,9 @@ struct bt_ctx {
     // chunks of normal maps on their way to the pinned staging buffers (grown on demand, kept until bt_ctx_trim)
     void* normal_dev = nullptr;
     uint64_t normal_bytes = 0;
+    // bt_tile_tree_render: the pixel counters and the planes of one call on the device (grown on demand, kept until bt_ctx_trim)
+    void* render_dev = nullptr;
+    uint64_t render_bytes = 0;
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
     // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out.  Then the

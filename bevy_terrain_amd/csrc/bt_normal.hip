@@ -23,19 +23,7 @@ namespace {
 
 // ---- the query ---------------------------------------------------------------------------------------------------
 
-// n_i of WORLD NORMAL: the tile's tangent-space normal through the TBN of the position, normalised
-__device__ __forceinline__ F3 lookup_normal(const AttachmentMeta& m, const uint16_t* __restrict__ atlas, const NormalModel& nm, const Lookup& l, bool spherical, F3 tan,
-                                            F3 bit, F3 N) {
-    F3 s = {0.0f, 0.0f, 1.0f};  // nothing loaded: every tap samples 0
-    if (l.atlas_index < m.atlas_size) {
-        const uint32_t T = m.texture_size;
-        const uint16_t* tile = atlas + uint64_t(l.atlas_index) * T * T;
-        const NormalTaps tp = normal_taps(m);
-        s = tile_normal(tp, nm, normal_dist(m, nm, l.atlas_lod), tap_split(tp, l.uv), [&](uint32_t px, uint32_t py) -> uint32_t { return tile[uint64_t(py) * T + px]; });
-    }
-    if (!spherical) return norm3f({s.x, s.z, s.y});
-    return norm3f({(tan.x * s.x + bit.x * s.y) + N.x * s.z, (tan.y * s.x + bit.y * s.y) + N.y * s.z, (tan.z * s.x + bit.z * s.y) + N.z * s.z});
-}
+// (WORLD NORMAL itself: world_normal of bt_normal_device.hpp, shared with the render kernel of bt_render.hip)
 
 __global__ __launch_bounds__(128) void tile_tree_normal_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                const uint16_t* __restrict__ atlas, NormalModel nm, const double* __restrict__ positions,
@@ -44,39 +32,9 @@ __global__ __launch_bounds__(128) void tile_tree_normal_kernel(TreeParams P, con
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const V3 p = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
-    F3 out = {0.0f, 0.0f, 0.0f};
-    float cosine = 0.0f;
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-        const float approximate_height = height ? *height : P.approximate_height;
-        const bool spherical = is_spherical(P.model);
-        const V3 local = position_world_to_local(P.model, p);
-        const V3 surface = position_local_to_world(P.model, local, double(approximate_height));
-        // normal_local_to_world: local_from_world_transpose * local, identity rotation
-        F3 VN = {0.0f, 1.0f, 0.0f};
-        if (spherical) {
-            const V3 v = normalize3({local.x / P.model.scale.x, local.y / P.model.scale.y, local.z / P.model.scale.z});
-            VN = {float(v.x), float(v.y), float(v.z)};
-        }
-        const F3 N = norm3f(VN);
-        const Coordinate c = coordinate_from_world_position(surface, P.model);
-        F3 tan = {0.0f, 0.0f, 0.0f}, bit = tan;
-        if (spherical) {
-            const uint32_t pair = c.side >> 1;  // FACE_UP (attachments.wgsl:55-62)
-            const F3 face_up = {pair == 2u ? -1.0f : 0.0f, pair == 0u ? 1.0f : 0.0f, pair == 1u ? -1.0f : 0.0f};
-            tan = cross3f(face_up, N);
-            bit = cross3f(N, tan);
-        }
-        uint32_t lod;
-        float ratio;
-        compute_blend(P, surface, lod, ratio);
-        F3 n = lookup_normal(m, atlas, nm, lookup_tile_at(P, entries, c, lod), spherical, tan, bit, N);
-        if (ratio > 0.0f) {
-            const F3 n2 = lookup_normal(m, atlas, nm, lookup_tile_at(P, entries, c, lod - 1u), spherical, tan, bit, N);
-            n = {n.x + (n2.x - n.x) * ratio, n.y + (n2.y - n.y) * ratio, n.z + (n2.z - n.z) * ratio};
-        }
-        out = dot3f(n, n) > 0.0f ? norm3f(n) : N;
-        cosine = dot3f(out, N);
-    }
+    const float approximate_height = height ? *height : P.approximate_height;
+    float cosine;
+    const F3 out = world_normal(P, entries, m, atlas, nm, p, approximate_height, cosine);
     normals[3 * uint64_t(i)] = out.x;
     normals[3 * uint64_t(i) + 1] = out.y;
     normals[3 * uint64_t(i) + 2] = out.z;

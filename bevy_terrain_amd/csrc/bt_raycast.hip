@@ -12,7 +12,9 @@
 // A sample whose altitude is above lerp(min_height, max_height, 1.0f) has f > 0 whatever the atlas holds: a bilinear sample of unorm
 // texels and the blend of two of them stay within [0, 1] (rounding is monotone and every weight is in [0, 1] once the tile has a border,
 // border_size >= 1) and the f32 lerp is monotone in its weight for max_height >= min_height.  Such a sample fetches nothing.
-#include "bt_tile_tree_device.hpp"
+//
+// The per-sample evaluation (ray_eval) lives in bt_raycast_device.hpp, shared with the render kernel (bt_render.hip).
+#include "bt_raycast_device.hpp"
 
 namespace bt {
 
@@ -22,34 +24,6 @@ namespace {
 
 constexpr uint32_t kRaycastThreads = 256;  // four rays per workgroup, no LDS, no barrier
 constexpr uint32_t kRaysPerGroup = kRaycastThreads / 64u;
-
-struct RayEval {
-    bool below;    // f(p) <= 0
-    float height;  // h(p), when it was sampled (always when below)
-};
-
-__device__ __forceinline__ V3 ray_point(const bt_ray& r, double t) {
-    return {r.origin[0] + t * r.direction[0], r.origin[1] + t * r.direction[1], r.origin[2] + t * r.direction[2]};
-}
-
-__device__ __forceinline__ RayEval ray_eval(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
-                                            const void* __restrict__ atlas, V3 p, double approximate_height, bool skip_above, double ceiling) {
-    const Model& model = P.model;
-    const V3 local = position_world_to_local(model, p);
-    const V3 n = normalize3(transform_vector(model, is_spherical(model) ? local : V3{0.0, 1.0, 0.0}));
-    const V3 ground0 = position_local_to_world(model, local, 0.0);
-    const double altitude = dot3({p.x - ground0.x, p.y - ground0.y, p.z - ground0.z}, n);
-    if (skip_above && altitude > ceiling) return {false, 0.0f};
-    // surface_position(model, p, approximate_height) with the local position at hand
-    const V3 surface = position_local_to_world(model, local, approximate_height);
-    float value[4];
-    sample_surface(P, entries, m, atlas, surface, value);
-    const float h = height_of_value(model, value[0]);
-    const double f = altitude - double(h);
-    return {f <= 0.0, h};
-}
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN and the infinities
 
 __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                   const void* __restrict__ atlas, const bt_ray* __restrict__ rays, uint32_t count,
@@ -83,7 +57,7 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
     float h_hit = 0.0f;
     for (uint32_t base = 0; base <= steps && !found; base += 64u) {
         const uint32_t i = base + lane;
-        RayEval e = {false, 0.0f};
+        RayEval e = {false, 0.0f, 0.0f};
         if (i <= steps) e = ray_eval(P, entries, m, atlas, ray_point(ray, ray.t_min + double(i) * dt), approximate_height, skip_above, ceiling);
         const unsigned long long bits = __ballot(e.below);
         if (bits) {
@@ -109,7 +83,7 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
         // refinement: lane k evaluates u_k, k = 1 .. 63
         for (uint32_t round = 0; round < refine_rounds; round++) {
             const double width = hi - lo;
-            RayEval e = {false, 0.0f};
+            RayEval e = {false, 0.0f, 0.0f};
             if (lane != 0) e = ray_eval(P, entries, m, atlas, ray_point(ray, lo + width * (double(lane) / 64.0)), approximate_height, skip_above, ceiling);
             const unsigned long long bits = __ballot(e.below);
             const uint32_t k = bits ? uint32_t(__ffsll(bits)) - 1u : 64u;

@@ -1,0 +1,166 @@
+// A camera's view of the terrain, ray-cast image-order (bt_tile_tree_render; the definition is in include/bevy_terrain_amd.h).
+//
+// Every plane is made of the library's existing definitions: a pixel's ray is marched as bt_tile_tree_raycast marches it (ray_eval of
+// bt_raycast_device.hpp, ceiling skip included), the normal at the hit is WORLD NORMAL (world_normal of bt_normal_device.hpp), the colour
+// is the attachment value sample_surface returns there (bt_tile_tree_device.hpp).  So the image agrees with the point queries bit for bit.
+//
+// One lane per pixel, one wave per 8 x 8 block of pixels, four blocks per workgroup; no LDS, no barrier.  Neighbouring pixels visit the
+// same tiles and leave the march at similar steps, so a wave's lanes share their fetches' cache lines and idle little behind the slowest
+// of them.  A lane runs the definition as it is written: the smallest i with f <= 0, then per refinement round the smallest k in 1 .. 63;
+// nothing crosses lanes until the pixel counters at the very end, which every lane of the wave reaches: lanes of pixels outside the
+// image, of finished rays and of INVALID rays skip the work, never the ballots.  The hit's value and height come from the evaluation that
+// found it.  Shading and the stores of the planes the caller asked for happen in the same launch.
+#include "bt_normal_device.hpp"
+#include "bt_raycast_device.hpp"
+
+namespace bt {
+
+using namespace bt::model;
+
+namespace {
+
+__device__ __forceinline__ uint32_t enc8(float v) {
+    const float c = v > 0.0f ? (v > 1.0f ? 1.0f : v) : 0.0f;  // (a NaN encodes as 0)
+    return uint32_t(floorf(0.5f + 255.0f * c));
+}
+
+__global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
+                                                                const void* __restrict__ atlas, AttachmentMeta albedo_meta, const void* __restrict__ albedo,
+                                                                NormalModel nm, RenderArgs a, const float* __restrict__ height) {
+    const bt_render_camera& cam = a.camera;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t in_launch = blockIdx.x * kRenderBlocksPerGroup + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    // the wave's 8 x 8 block, the lane's pixel in it (row-major: lane & 7 along x)
+    const uint32_t block = a.first_block + in_launch;
+    const uint32_t by = block / a.blocks_x, bx = block - by * a.blocks_x;
+    const uint32_t x = bx * 8u + (lane & 7u), y = by * 8u + (lane >> 3);
+    const bool active = in_launch < a.block_count && x < cam.width && y < cam.height;
+    uint32_t status = BT_RAY_INVALID;
+
+    if (active) {
+        const float approximate_height = height ? *height : P.approximate_height;
+        const bool skip_above = m.border_size >= 1u && P.model.max_height >= P.model.min_height;
+        const double ceiling = double(height_of_value(P.model, 1.0f));
+        // PIXEL RAY
+        const double sx = (2.0 * (double(x) + 0.5)) / double(cam.width) - 1.0;
+        const double sy = 1.0 - (2.0 * (double(y) + 0.5)) / double(cam.height);
+        bt_ray ray;
+        for (int k = 0; k < 3; k++) {
+            if (cam.flags & BT_RENDER_ORTHOGRAPHIC) {
+                ray.origin[k] = (cam.origin[k] + sx * cam.right[k]) + sy * cam.up[k];
+                ray.direction[k] = cam.forward[k];
+            } else {
+                ray.origin[k] = cam.origin[k];
+                ray.direction[k] = (cam.forward[k] + sx * cam.right[k]) + sy * cam.up[k];
+            }
+        }
+        ray.t_min = cam.t_min;
+        ray.t_max = cam.t_max;
+        bool valid = finite(ray.t_min) && finite(ray.t_max) && ray.t_max >= ray.t_min;
+        bool nonzero = false;
+        for (int k = 0; k < 3; k++) {
+            valid = valid && finite(ray.origin[k]) && finite(ray.direction[k]);
+            nonzero = nonzero || ray.direction[k] != 0.0;
+        }
+
+        double t = 0.0;
+        float value = 0.0f;
+        if (valid && nonzero) {
+            // MARCH, the lane's own: coarse steps 0 .. steps until the first at or under the ground
+            const double dt = (ray.t_max - ray.t_min) / double(a.steps);
+            status = BT_RAY_MISS;
+            uint32_t step = 0;
+            for (uint32_t i = 0; i <= a.steps; i++) {
+                const RayEval e = ray_eval(P, entries, m, atlas, ray_point(ray, ray.t_min + double(i) * dt), double(approximate_height), skip_above, ceiling);
+                if (e.below) {
+                    status = i == 0u ? BT_RAY_INSIDE : BT_RAY_HIT;
+                    step = i;
+                    value = e.value;
+                    break;
+                }
+            }
+            if (status == BT_RAY_INSIDE) t = ray.t_min;
+            if (status == BT_RAY_HIT) {
+                double lo = ray.t_min + double(step - 1u) * dt, hi = ray.t_min + double(step) * dt;
+                for (uint32_t round = 0; round < a.refine_rounds; round++) {
+                    const double width = hi - lo;
+                    uint32_t k = 1;
+                    for (; k < 64u; k++) {
+                        const RayEval e = ray_eval(P, entries, m, atlas, ray_point(ray, lo + width * (double(k) / 64.0)), double(approximate_height), skip_above, ceiling);
+                        if (e.below) {
+                            value = e.value;
+                            break;
+                        }
+                    }
+                    const double new_hi = k == 64u ? hi : lo + width * (double(k) / 64.0);
+                    const double new_lo = k == 1u ? lo : lo + width * (double(k - 1u) / 64.0);
+                    hi = new_hi;
+                    lo = new_lo;
+                }
+                t = hi;
+            }
+        }
+
+        // the fragment stage at p(t), and the planes the caller asked for
+        const bool hit = status == BT_RAY_HIT || status == BT_RAY_INSIDE;
+        const bool lighting = (cam.flags & BT_RENDER_LIGHTING) != 0u;
+        const uint64_t pixel = uint64_t(y) * cam.width + x;
+        const V3 p = ray_point(ray, t);
+        F3 n = {0.0f, 0.0f, 0.0f};
+        if (hit && (a.normal || (a.rgba && lighting))) {
+            float cosine;
+            n = world_normal(P, entries, m, (const uint16_t*)atlas, nm, p, approximate_height, cosine);
+        }
+        if (a.t) a.t[pixel] = t;
+        if (a.status) a.status[pixel] = uint8_t(status);
+        if (a.normal) {
+            a.normal[3u * pixel] = n.x;
+            a.normal[3u * pixel + 1u] = n.y;
+            a.normal[3u * pixel + 2u] = n.z;
+        }
+        if (a.rgba) {
+            uint32_t texel = uint32_t(cam.background[0]) | (uint32_t(cam.background[1]) << 8) | (uint32_t(cam.background[2]) << 16) | (uint32_t(cam.background[3]) << 24);
+            if (hit) {
+                float base[4];
+                if (albedo) {
+                    sample_surface(P, entries, albedo_meta, albedo, surface_position(P.model, p, double(approximate_height)), base);
+                } else {
+                    const float g = 0.5f * value;  // sample_color (attachments.wgsl:109-113)
+                    base[0] = base[1] = base[2] = g;
+                    base[3] = 1.0f;
+                }
+                if (lighting) {  // a plain Lambert term
+                    const float d = dot3f(n, {cam.sun[0], cam.sun[1], cam.sun[2]});
+                    const float l = d > 0.0f ? d : 0.0f;
+                    const float k = cam.ambient + (1.0f - cam.ambient) * l;
+                    for (int c = 0; c < 3; c++) base[c] = base[c] * k;
+                }
+                texel = enc8(base[0]) | (enc8(base[1]) << 8) | (enc8(base[2]) << 16) | (enc8(base[3]) << 24);
+            }
+            a.rgba[pixel] = texel;
+        }
+    }
+
+    // the pixel counters: the whole wave is here, whatever its lanes did above
+    const unsigned long long hits = __ballot(active && status == BT_RAY_HIT);
+    const unsigned long long insides = __ballot(active && status == BT_RAY_INSIDE);
+    const unsigned long long misses = __ballot(active && status == BT_RAY_MISS);
+    if (lane == 0u) {
+        if (hits) atomicAdd(&a.counters[0], uint32_t(__popcll(hits)));
+        if (insides) atomicAdd(&a.counters[1], uint32_t(__popcll(insides)));
+        if (misses) atomicAdd(&a.counters[2], uint32_t(__popcll(misses)));
+    }
+}
+
+}  // namespace
+
+bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height) {
+    if (!a.block_count) return BT_OK;
+    const NormalModel nm = {P.model.min_height, P.model.max_height, normal_side_length(P.model)};
+    render_kernel<<<(a.block_count + kRenderBlocksPerGroup - 1u) / kRenderBlocksPerGroup, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BT_OK : hip_fail(e, "render_kernel");
+}
+
+}  // namespace bt

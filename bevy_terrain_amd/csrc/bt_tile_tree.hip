@@ -14,6 +14,7 @@
 //
 // Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
 // where the reference defers to glam / libm.  compute_blend's log2 is the platform's (OCML here, libm in the oracle).
+#include <cmath>
 #include <cstring>
 
 #include "bt_internal.hpp"
@@ -656,6 +657,113 @@ bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const 
     BT_HIP(hipStreamSynchronize(s));
     adopt_height(t);
     t->table_copy_pending = false;
+    return BT_OK;
+}
+
+bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
+                              uint8_t* out_status, float* out_normal, uint8_t* out_rgba, bt_render_stats* stats) {
+    const char* who = "bt_tile_tree_render";
+    if (!t || !a || !camera) {
+        set_error("%s: NULL %s", who, !t ? "tile tree" : (!a ? "atlas" : "camera"));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (t->ctx != a->ctx) {
+        set_error("%s: tile tree and atlas belong to different contexts", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!out_t && !out_status && !out_normal && !out_rgba) {
+        set_error("%s: every plane is NULL", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bt_render_camera& cam = *camera;
+    const uint64_t pixels = uint64_t(cam.width) * cam.height;
+    if (!cam.width || !cam.height || pixels > uint64_t(BT_RENDER_MAX_PIXELS)) {
+        set_error("%s: %u x %u pixels (each at least 1, at most %u in all)", who, cam.width, cam.height, unsigned(BT_RENDER_MAX_PIXELS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (steps < 1u || steps > uint32_t(BT_RENDER_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
+        set_error("%s: steps %u (1 .. %u) / refine_rounds %u (at most %u)", who, steps, unsigned(BT_RENDER_MAX_STEPS), refine_rounds, unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool has_albedo = cam.albedo_attachment != BT_RENDER_NO_ALBEDO;
+    if (ai >= a->attachments.size() || (has_albedo && cam.albedo_attachment >= a->attachments.size())) {
+        set_error("%s: %s attachment index %u out of range", who, ai >= a->attachments.size() ? "height" : "albedo", ai >= a->attachments.size() ? ai : cam.albedo_attachment);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (cam.flags & ~uint32_t(BT_RENDER_ORTHOGRAPHIC | BT_RENDER_LIGHTING)) {
+        set_error("%s: unknown flag bits 0x%x", who, cam.flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!std::isfinite(cam.ambient) || !std::isfinite(cam.sun[0]) || !std::isfinite(cam.sun[1]) || !std::isfinite(cam.sun[2])) {
+        set_error("%s: non-finite ambient / sun", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("%s: height attachment %u is not R16", who, ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    const Attachment& albedo = a->attachments[has_albedo ? cam.albedo_attachment : ai];
+    if (has_albedo && albedo.meta.format != BT_FORMAT_RGBA8) {
+        set_error("%s: albedo attachment %u is not Rgba8", who, cam.albedo_attachment);
+        return BT_ERR_UNSUPPORTED;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary
+    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
+    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad(12u * pixels) : 0u),
+                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), need = s_off + (out_status ? pad(pixels) : 0u);
+    if (ctx->render_bytes < need) {
+        BT_HIP(hipStreamSynchronize(s));
+        if (ctx->render_dev) BT_HIP(hipFree(ctx->render_dev));
+        ctx->render_dev = nullptr;
+        ctx->render_bytes = 0;
+        BT_HIP(hipMalloc(&ctx->render_dev, need));
+        ctx->render_bytes = need;
+    }
+    uint8_t* dev = (uint8_t*)ctx->render_dev;
+    RenderArgs args{};
+    args.camera = cam;
+    args.steps = steps;
+    args.refine_rounds = refine_rounds;
+    args.blocks_x = (cam.width + 7u) / 8u;
+    args.counters = (uint32_t*)dev;
+    args.t = out_t ? (double*)(dev + t_off) : nullptr;
+    args.normal = out_normal ? (float*)(dev + n_off) : nullptr;
+    args.rgba = out_rgba ? (uint32_t*)(dev + c_off) : nullptr;
+    args.status = out_status ? dev + s_off : nullptr;
+    // a launch: whole 8 x 8 blocks whose worst case stays within BT_RAYCAST_MAX_SAMPLES (at least one fits: 64 * 4349 samples at most), cut to
+    // whole 8-row bands when it holds one
+    const uint32_t blocks = args.blocks_x * ((cam.height + 7u) / 8u);
+    const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds);
+    uint32_t per_launch = uint32_t(std::min<uint64_t>(blocks, uint64_t(BT_RAYCAST_MAX_SAMPLES) / block_samples));
+    if (per_launch >= args.blocks_x) per_launch -= per_launch % args.blocks_x;
+    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
+    const TreeParams P = make_params(t);
+    uint32_t launches = 0;
+    for (uint32_t first = 0; first < blocks; first += per_launch, launches++) {
+        args.first_block = first;
+        args.block_count = std::min(per_launch, blocks - first);
+        // a read of the atlas: level0 is passed on without marking any layer written
+        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height)) {
+            (void)hipStreamSynchronize(s);
+            return st;
+        }
+    }
+    // nothing is copied back before the last launch has been queued
+    uint32_t counters[4] = {};
+    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_t) e = hipMemcpyAsync(out_t, args.t, 8u * pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_status) e = hipMemcpyAsync(out_status, args.status, pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, args.normal, 12u * pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_rgba) e = hipMemcpyAsync(out_rgba, args.rgba, 4u * pixels, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
+    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
+    adopt_height(t);
+    t->table_copy_pending = false;
+    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
     return BT_OK;
 }
 

@@ -1,5 +1,5 @@
 // Device half of sample_attachment / sample_height (terrain_data/mod.rs:265-307) shared by the kernels that sample the
-// terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip) and raycast_kernel (bt_raycast.hip).  One
+// terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip), raycast_kernel (bt_raycast.hip), render_kernel (bt_render.hip).  One
 // definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there, bit for bit.
 //
 // Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
@@ -28,6 +28,25 @@ bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_
 // positions (device) against the tree's entries and one R16 attachment; height as above
 bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
                                const double* positions, uint32_t count, float* normals, float* up_dot, const float* height);
+
+// bt_render.hip: one launch of bt_tile_tree_render.  A wave renders one 8 x 8 block of pixels, a workgroup kRenderBlocksPerGroup of them;
+// the launch covers blocks first_block .. first_block + block_count - 1 of the image's blocks_x x ceil(height / 8) blocks, row-major.
+constexpr uint32_t kRenderThreads = 256;
+constexpr uint32_t kRenderBlocksPerGroup = kRenderThreads / 64u;
+struct RenderArgs {
+    bt_render_camera camera;
+    uint32_t steps, refine_rounds;
+    uint32_t blocks_x, first_block, block_count;
+    // the planes (device, width * height pixels each; NULL: not wanted) and the HIT / INSIDE / MISS pixel counters
+    double* t;
+    uint8_t* status;
+    float* normal;
+    uint32_t* rgba;
+    uint32_t* counters;
+};
+// albedo == NULL: the grey of the height attachment (BT_RENDER_NO_ALBEDO); height as above
+bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height);
 
 // bt_geometry.hip: what TERRAIN GEOMETRY (include/bevy_terrain_amd.h) takes from the tree besides its entries
 struct GeometryParams {

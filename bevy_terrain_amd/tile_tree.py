@@ -63,6 +63,77 @@ RAY_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.f
                           ("height", np.float32), ("_padding", np.uint32)])
 
 
+class RenderCamera:
+    """bt_render_camera (include/bevy_terrain_amd.h): the camera of TileTree.render.  origin, forward, right and up are used as given (f64):
+    pixel (x, y) looks along forward + sx * right + sy * up (perspective) or starts at origin + sx * right + sy * up and looks along
+    forward (orthographic), sx, sy in (-1, 1) at the pixel centres, y down.  Build one with perspective() or orthographic()."""
+
+    def __init__(self, origin, forward, right, up, width: int, height: int, t_min: float, t_max: float, *, orthographic: bool = False,
+                 lighting: bool = False, albedo_attachment: Optional[int] = None, sun=(0.0, 1.0, 0.0), ambient: float = 0.25, background=(0, 0, 0, 0)):
+        self.origin, self.forward, self.right, self.up = (np.array(v, dtype=np.float64).reshape(3) for v in (origin, forward, right, up))
+        self.width, self.height, self.t_min, self.t_max = int(width), int(height), float(t_min), float(t_max)
+        self.orthographic, self.lighting, self.albedo_attachment = bool(orthographic), bool(lighting), albedo_attachment
+        self.sun, self.ambient, self.background = tuple(float(v) for v in sun), float(ambient), tuple(int(v) for v in background)
+
+    @staticmethod
+    def _frame(forward, up):
+        f = np.asarray(forward, dtype=np.float64)
+        f = f / np.linalg.norm(f)
+        r = np.cross(f, np.asarray(up, dtype=np.float64))
+        r = r / np.linalg.norm(r)
+        return f, r, np.cross(r, f)
+
+    @staticmethod
+    def perspective(position, forward, up, fov_y: float, width: int, height: int, t_min: float, t_max: float, **kw) -> "RenderCamera":
+        """a pinhole camera at `position` looking along `forward` (normalised here) with `up` roughly up and a vertical field of view of
+        fov_y radians; t is then linear view depth"""
+        f, r, u = RenderCamera._frame(forward, up)
+        tan = np.tan(0.5 * float(fov_y))
+        return RenderCamera(position, f, r * (tan * (float(width) / float(height))), u * tan, width, height, t_min, t_max, **kw)
+
+    @staticmethod
+    def orthographic(position, forward, up, half_width: float, half_height: float, width: int, height: int, t_min: float, t_max: float, **kw) -> "RenderCamera":
+        """parallel rays along `forward` (normalised here) from a window of 2 half_width x 2 half_height world units centred on `position`"""
+        f, r, u = RenderCamera._frame(forward, up)
+        return RenderCamera(position, f, r * float(half_width), u * float(half_height), width, height, t_min, t_max, orthographic=True, **kw)
+
+    def c(self) -> _ffi.RenderCameraC:
+        cam = _ffi.RenderCameraC()
+        for i in range(3):
+            cam.origin[i], cam.forward[i], cam.right[i], cam.up[i], cam.sun[i] = self.origin[i], self.forward[i], self.right[i], self.up[i], self.sun[i]
+        cam.t_min, cam.t_max, cam.width, cam.height = self.t_min, self.t_max, self.width, self.height
+        cam.flags = (_ffi.RENDER_ORTHOGRAPHIC if self.orthographic else 0) | (_ffi.RENDER_LIGHTING if self.lighting else 0)
+        cam.albedo_attachment = _ffi.RENDER_NO_ALBEDO if self.albedo_attachment is None else self.albedo_attachment
+        cam.ambient = self.ambient
+        for i in range(4):
+            cam.background[i] = self.background[i]
+        return cam
+
+
+def render_rays(camera: RenderCamera) -> Tuple[np.ndarray, np.ndarray]:
+    """PIXEL RAY of include/bevy_terrain_amd.h for every pixel of a camera, row-major, y down: (origins, directions), each
+    (height * width, 3) float64, operation by operation as the kernel computes them; march them from camera.t_min to camera.t_max"""
+    w, h = camera.width, camera.height
+    x, y = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
+    sx = np.tile((2.0 * (x + 0.5)) / np.float64(w) - 1.0, h)
+    sy = np.repeat(1.0 - (2.0 * (y + 0.5)) / np.float64(h), w)
+    with np.errstate(all="ignore"):
+        base, other = (camera.origin, camera.forward) if camera.orthographic else (camera.forward, camera.origin)
+        moved = (base[None, :] + sx[:, None] * camera.right[None, :]) + sy[:, None] * camera.up[None, :]
+    fixed = np.tile(other, (w * h, 1))
+    return (moved, fixed) if camera.orthographic else (fixed, moved)
+
+
+def write_ppm(path: str, rgba: np.ndarray):
+    """an (height, width, 3 or 4) uint8 image (TileTree.render's "rgba" plane) as a binary PPM (P6; alpha is dropped): no library needed"""
+    rgba = np.asarray(rgba)
+    if rgba.dtype != np.uint8 or rgba.ndim != 3 or rgba.shape[2] not in (3, 4):
+        raise ValueError("write_ppm wants an (height, width, 3 or 4) uint8 array")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgba.shape[1], rgba.shape[0]))
+        f.write(np.ascontiguousarray(rgba[:, :, :3]).tobytes())
+
+
 # numpy mirror of bt_terrain_vertex
 TERRAIN_VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("height", np.float32), ("normal", np.float32, 3), ("tile_index", np.uint32),
                                  ("coordinate_uv", np.float32, 2), ("view_distance", np.float32), ("blend_ratio", np.float32)])
@@ -166,6 +237,25 @@ class TileTree:
         if normals:
             return hits, self.sample_normal(attachment_index, hits["position"])[0]
         return hits
+
+    def render(self, camera: RenderCamera, steps: int = 256, refine_rounds: int = 2, planes=("t", "status", "normal", "rgba"), attachment_index: int = 0):
+        """bt_tile_tree_render: the camera's view of the terrain, one ray per pixel marched on the device as raycast() marches it, shaded
+        at the hit.  Returns a dict with the planes asked for — "t" (height, width) float64 (0 where nothing was met), "status"
+        (height, width) uint8 (_ffi.RAY_*), "normal" (height, width, 3) float32, "rgba" (height, width, 4) uint8 — and "stats"
+        (launches, hit_pixels, inside_pixels, miss_pixels).  attachment_index: the R16 height attachment."""
+        unknown = set(planes) - {"t", "status", "normal", "rgba"}
+        if unknown:
+            raise ValueError(f"unknown planes {sorted(unknown)}")
+        w, h = camera.width, camera.height
+        shapes = {"t": ((h, w), np.float64, C.c_double), "status": ((h, w), np.uint8, C.c_uint8), "normal": ((h, w, 3), np.float32, C.c_float),
+                  "rgba": ((h, w, 4), np.uint8, C.c_uint8)}
+        out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in shapes if name in planes}
+        ptr = lambda name: out[name].ctypes.data_as(C.POINTER(shapes[name][2])) if name in out else None
+        stats = _ffi.RenderStatsC()
+        _ffi.check(_ffi.lib().bt_tile_tree_render(self._h, self.atlas._h, attachment_index, C.byref(camera.c()), steps, refine_rounds, ptr("t"), ptr("status"),
+                                                  ptr("normal"), ptr("rgba"), C.byref(stats)))
+        out["stats"] = {name: getattr(stats, name) for name, _ in _ffi.RenderStatsC._fields_}
+        return out
 
     def vertices_per_tile(self, grid: bool = False) -> int:
         """slots a tile takes in either geometry layout: the strip's 2 g (g + 2) (bt_view_state.vertices_per_tile) or the grid's (g + 1)^2"""

@@ -5,7 +5,9 @@ atlas streams the requested tiles from `data/height/*.bin` (mip chains built on 
 the tiling prepass (refine_tiles) that leaves the final tile list and the indirect draw arguments in HBM for whatever draws the terrain.
 The debug camera of the reference is replaced by a scripted fly-over.
 
-    python examples/preprocess_planar.py && python examples/minimal.py [--assets DIR] [--frames 120]
+    python examples/preprocess_planar.py && python examples/minimal.py [--assets DIR] [--frames 120] [--render FILE.ppm]
+
+--render writes what the last frame's camera sees, ray-cast on the GPU (TileTree.render), as a binary PPM.
 """
 import argparse
 import math
@@ -29,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--assets", default="assets")
     ap.add_argument("--frames", type=int, default=120)
+    ap.add_argument("--render", metavar="FILE.ppm", help="write the last frame's view, ray-cast on the GPU, as a binary PPM")
     args = ap.parse_args()
     if not os.path.exists(os.path.join(args.assets, PATH, "config.tc")):
         sys.exit(f"{args.assets}/{PATH}/config.tc not found: run examples/preprocess_planar.py first")
@@ -69,6 +72,13 @@ def main():
     vertices = tile_tree.build_geometry(prepass)
     if vertices.size:
         print(f"geometry of the last frame: {vertices.size} vertices of {len(vertices)} tiles, heights {vertices['height'].min():.1f} .. {vertices['height'].max():.1f}")
+    if args.render:
+        # the picture of the last frame: from the view position towards the middle of the terrain, lit by a plain Lambert term
+        camera = bt.RenderCamera.perspective(view_position, (-math.cos(phi), -0.35, -math.sin(phi)), (0.0, 1.0, 0.0), math.radians(60.0), 640, 360, 0.0, 2.0 * TERRAIN_SIZE,
+                                             lighting=True, sun=(0.4, 0.8, 0.45), ambient=0.3, background=(120, 170, 230, 255))
+        image = tile_tree.render(camera, steps=512, refine_rounds=2, planes=("rgba",))
+        bt.write_ppm(args.render, image["rgba"])
+        print(f"rendered {camera.width} x {camera.height} to {args.render}: {image['stats']}")
     print(f"{args.frames} frames, {requested_total} tile requests, {loaded_total} tile loads ({failed_total} failed), pending {tile_atlas.pending_loads()}, "
           f"{1e3 * t_frames / args.frames:.3f} ms of host time per frame (loads included)")
 

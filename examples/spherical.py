@@ -4,7 +4,9 @@ approaching from three radii out (the reference's DebugCameraBundle starts at -X
 per frame: TileTree::update over 6 sides x 16 LODs, tile requests / releases, streamed tile loads with their mip chains, adjust_to_tile_atlas,
 approximate_height, and the tiling prepass that leaves the final tile list + indirect draw arguments in HBM.
 
-    python examples/preprocess_spherical.py && python examples/spherical.py [--assets DIR] [--frames 120]
+    python examples/preprocess_spherical.py && python examples/spherical.py [--assets DIR] [--frames 120] [--render FILE.ppm]
+
+--render writes what the last frame's camera sees, ray-cast on the GPU (TileTree.render), as a binary PPM.
 """
 import argparse
 import math
@@ -31,6 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--assets", default="assets")
     ap.add_argument("--frames", type=int, default=120)
+    ap.add_argument("--render", metavar="FILE.ppm", help="write the last frame's view, ray-cast on the GPU, as a binary PPM")
     args = ap.parse_args()
     if not os.path.exists(os.path.join(args.assets, PATH, "config.tc")):
         sys.exit(f"{args.assets}/{PATH}/config.tc not found: run examples/preprocess_spherical.py first")
@@ -67,6 +70,15 @@ def main():
             lods = sorted({int(l) for l in tiles[:, 1]}) if len(tiles) else []
             print(f"frame {frame:4d}: altitude {(distance - RADIUS) / 1000.0:9.1f} km  requested {info.requested_count:3d} released {info.released_count:3d} loaded {loaded:3d}  "
                   f"final tiles {len(tiles):5d} on LODs {lods[0] if lods else '-'}..{lods[-1] if lods else '-'} (draw: {indirect[0]} vertices)  approximate height {info.approximate_height:8.1f}")
+    if args.render:
+        # the picture of the last frame: from 5 km up towards the horizon, the local vertical up, lit by a plain Lambert term
+        up = [v / distance for v in view_position]
+        ahead = (-math.sin(phi), 0.0, math.cos(phi))  # the direction of flight
+        camera = bt.RenderCamera.perspective(view_position, [a - 0.3 * u for a, u in zip(ahead, up)], up, math.radians(60.0), 480, 270, 0.0, 4.0e5,
+                                             lighting=True, sun=[0.5 * a + 0.8 * u for a, u in zip(ahead, up)], ambient=0.3, background=(120, 170, 230, 255))
+        image = tile_tree.render(camera, steps=512, refine_rounds=2, planes=("rgba",))
+        bt.write_ppm(args.render, image["rgba"])
+        print(f"rendered {camera.width} x {camera.height} to {args.render}: {image['stats']}")
     print(f"{args.frames} frames, {requested_total} tile requests, {loaded_total} tile loads ({failed_total} failed), pending {tile_atlas.pending_loads()}, "
           f"{1e3 * t_frames / args.frames:.3f} ms of host time per frame (loads included)")
 

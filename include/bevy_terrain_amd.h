@@ -171,7 +171,7 @@ bt_status bt_ctx_synchronize(bt_ctx* ctx);
  * sources need not be allocated again: 0.5 GB for a 16k R16 raster, six of 128 MB for a cube job; at most 8 buffers and 4 GiB) and
  * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds,
  * the device scratch of bt_tile_tree_raycast, the device scratch of bt_tile_tree_sample_normal and bt_atlas_tile_normals (their pinned
- * half is the staging buffers above).
+ * half is the staging buffers above), the device planes of bt_tile_tree_render.
  * Synchronises the context's stream first.  `freed_bytes` (may be NULL): device + pinned bytes released. */
 bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes);
 /* Host threads that write (bt_preprocessor_save / _run_streamed) and read (bt_atlas_load_tiles) tile files for this context.
@@ -1048,6 +1048,79 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* tree, bt_atlas* atlas, uint32
                                      uint32_t count, float* out_normals_xyz /* 3 per position */, float* out_up_dot /* may be NULL */);
 bt_status bt_atlas_tile_normals(bt_atlas* atlas, uint32_t attachment_index, const bt_terrain_model* model, const bt_tile_coordinate* coords,
                                 uint32_t count, uint8_t* out_host, uint64_t out_bytes);
+
+/* Rendering ("what does the terrain look like from here": preview thumbnails of a preprocessed dataset, headless visual checks of an
+ * edit, a depth or normal image for a tool that is not wgpu, top-down maps).  The reference's renderer is Bevy / wgpu and stays out of
+ * scope; this call casts one ray per pixel on the device and evaluates the fragment stage at the hit, so every plane is defined by the
+ * definitions above: the march of bt_tile_tree_raycast, WORLD NORMAL, bt_tile_tree_sample_attachment.
+ *
+ * Arithmetic: IEEE binary64 unless marked f32, one rounding per written operation, no contraction.
+ *
+ * PIXEL RAY of pixel (x, y), x = 0 .. width - 1 from the left, y = 0 .. height - 1 from the top:
+ *     sx = (2.0 * (double(x) + 0.5)) / double(width) - 1.0
+ *     sy = 1.0 - (2.0 * (double(y) + 0.5)) / double(height)
+ *     perspective:  o = origin;  d_a = (forward_a + sx * right_a) + sy * up_a
+ *     orthographic (BT_RENDER_ORTHOGRAPHIC):  o_a = (origin_a + sx * right_a) + sy * up_a;  d = forward
+ *   forward, right and up are used as given and d is not normalised: a perspective caller scales right by tan(fov_y / 2) * aspect and up
+ *   by tan(fov_y / 2); with a unit forward and right, up orthogonal to it, t is linear view depth.
+ *
+ * MARCH: status, step, t, t_above, position p(t) and height are exactly what bt_tile_tree_raycast returns for the ray {o, d, t_min, t_max}
+ *   with the same steps and refine_rounds against height_attachment (the definition is that one, not restated).  A camera with non-finite
+ *   vectors or bounds, or t_max < t_min, is no error: its pixels are BT_RAY_INVALID, as the ray definition says.
+ *     out_t[y * width + x]      = t (0 for BT_RAY_MISS and BT_RAY_INVALID)
+ *     out_status[y * width + x] = BT_RAY_*
+ *
+ * NORMAL PLANE, 3 floats per pixel: BT_RAY_HIT and BT_RAY_INSIDE: `out` of WORLD NORMAL (steps 1 - 10 above) at p(t); otherwise (0, 0, 0).
+ *
+ * COLOUR PLANE, 4 bytes per pixel, all f32:
+ *     base: albedo_attachment == BT_RENDER_NO_ALBEDO: (g, g, g, 1.0f), g = 0.5f * v, v the first component bt_tile_tree_sample_attachment(
+ *           height_attachment) returns at p(t) (the reference's sample_color, attachments.wgsl:109-113, under its two-LOD blend: x 0.5 is
+ *           exact, so blending first gives the same value); otherwise the four components bt_tile_tree_sample_attachment(albedo_attachment)
+ *           returns at p(t)
+ *     BT_RENDER_LIGHTING: n = the NORMAL PLANE's value; d = dot3f(n, sun); l = d > 0.0f ? d : 0.0f; k = ambient + (1.0f - ambient) * l;
+ *           rgb_c = base_c * k for c = 0, 1, 2; alpha unchanged.  sun is the direction TOWARDS the light, used as given (not normalised).
+ *           This is a plain Lambert term.  It is NOT the reference's apply_pbr_lighting, which lives in bevy_pbr and not in the reference.
+ *     bytes: enc8(v) = u8(floorf(0.5f + 255.0f * c)), c = v > 0.0f ? (v > 1.0f ? 1.0f : v) : 0.0f (a NaN encodes as 0)
+ *     BT_RAY_MISS and BT_RAY_INVALID pixels get `background`.
+ *
+ * All four planes are host arrays, row-major, y down; each may be NULL (it then costs no store and no device memory), but not all.
+ * stats (may be NULL): launches, and the number of BT_RAY_HIT, BT_RAY_INSIDE and BT_RAY_MISS pixels (the rest are BT_RAY_INVALID).
+ *
+ * The kernel gives a pixel to a lane and an 8 x 8 block of pixels to a wave; a lane marches its ray sample by sample and stops at its
+ * hit.  One launch is a run of whole 8 x 8 blocks, in row-major block order, whose worst case, 64 * (steps + 1 + 63 * refine_rounds)
+ * samples per block, stays within BT_RAYCAST_MAX_SAMPLES, the bound bt_tile_tree_raycast works under (the longest such launch is measured
+ * in DESIGN.md 3.11); a run that holds a whole 8-row band of the image is cut to whole bands.  A larger image is several launches
+ * (stats->launches); nothing is copied back before the last one has been queued.
+ *
+ * Refused before anything is queued, the planes untouched.  BT_ERR_INVALID_ARGUMENT: NULL handles or camera; handles of different
+ * contexts; all planes NULL; width or height 0, or width * height > BT_RENDER_MAX_PIXELS; steps outside 1 .. BT_RENDER_MAX_STEPS;
+ * refine_rounds > BT_RAYCAST_MAX_REFINE_ROUNDS; height_attachment or albedo_attachment (unless BT_RENDER_NO_ALBEDO) out of range;
+ * a non-finite ambient or sun component; unknown flag bits.  BT_ERR_UNSUPPORTED: a height attachment that is not R16, an albedo attachment
+ * that is not Rgba8.
+ * Ordered behind the work queued on the context's stream; synchronous (host arrays out); a read (no layer is marked written for
+ * bt_run_stats.prev_zero_launches).  Scratch (up to 25 bytes of device memory per pixel of the largest image so far, less without some
+ * planes) stays in the context until bt_ctx_trim. */
+enum { BT_RENDER_ORTHOGRAPHIC = 1, BT_RENDER_LIGHTING = 2 };
+enum { BT_RENDER_MAX_STEPS = 4096, BT_RENDER_MAX_PIXELS = 16777216 };
+#define BT_RENDER_NO_ALBEDO 0xFFFFFFFFu
+typedef struct bt_render_camera {
+    double origin[3];
+    double forward[3], right[3], up[3]; /* used as given; perspective callers scale right / up by tan(fov/2) (x aspect) */
+    double t_min, t_max;
+    uint32_t width, height;
+    uint32_t flags;             /* BT_RENDER_ORTHOGRAPHIC | BT_RENDER_LIGHTING */
+    uint32_t albedo_attachment; /* an Rgba8 attachment index, or BT_RENDER_NO_ALBEDO */
+    float sun[3];               /* direction TOWARDS the light, used as given */
+    float ambient;
+    uint8_t background[4];
+    uint32_t _padding;
+} bt_render_camera;
+typedef struct bt_render_stats {
+    uint32_t launches, hit_pixels, inside_pixels, miss_pixels;
+} bt_render_stats;
+bt_status bt_tile_tree_render(bt_tile_tree* tree, bt_atlas* atlas, uint32_t height_attachment, const bt_render_camera* camera,
+                              uint32_t steps, uint32_t refine_rounds, double* out_t, uint8_t* out_status,
+                              float* out_normal_xyz /* 3 per pixel */, uint8_t* out_rgba /* 4 per pixel */, bt_render_stats* stats);
 
 /* Terrain geometry ("where are the vertices of the tiles the prepass selected": colliders for the visible tiles, mesh export, a renderer
  * that is not wgpu).  bt_frame_update ends with final_tiles and indirect arguments whose vertex_count counts vertices of the reference's
