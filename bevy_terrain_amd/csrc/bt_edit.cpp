@@ -261,17 +261,7 @@ bt_status bt::PlanRing::commit(bt_ctx* ctx, uint8_t** dev) {
 
 namespace {
 
-// the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height
-bt_status region_scratch(bt_ctx* ctx, uint64_t bytes) {
-    if (bytes <= ctx->edit_region_bytes) return BT_OK;
-    if (ctx->edit_region_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // a launch in flight uses the buffer that goes away
-    if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
-    ctx->edit_region_dev = nullptr;
-    ctx->edit_region_bytes = 0;
-    BT_HIP(hipMalloc(&ctx->edit_region_dev, bytes));
-    ctx->edit_region_bytes = bytes;
-    return BT_OK;
-}
+// (bt_ctx::edit_region is the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height)
 
 // The first step of a plan, the one that writes the rectangles of the edited tiles (the steps after it are the same for every call): the
 // brush or the paint brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps.  prepare() runs once the plan is known
@@ -308,7 +298,7 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
                 offsets.push_back(scratch_dwords);
                 scratch_dwords += smooth_item_dwords(it, m.border_size);
             }
-            if (bt_status s = region_scratch(ctx, scratch_dwords * sizeof(uint32_t))) return s;
+            if (bt_status s = ctx->edit_region.reserve(ctx, scratch_dwords * sizeof(uint32_t))) return s;
             stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_smooth_stamp));
             offsets_at = ring.add(offsets);
             return BT_OK;
@@ -320,7 +310,7 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
 // the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
 bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
     const uint64_t total = row_bytes * height;
-    if (bt_status s = region_scratch(ctx, total)) return s;
+    if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
     if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
         if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
     const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
@@ -330,7 +320,7 @@ bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
         hipError_t e = copied[k] ? hipEventSynchronize(copied[k]) : hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
         for (uint32_t r = 0; r < rows && e == hipSuccess; r++)
             memcpy((uint8_t*)ctx->staging[k] + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region_dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region.dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(copied[k], ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "bt_atlas_write_region staging");
     }
@@ -341,10 +331,10 @@ bt_status FirstStep::launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ri
     switch (kind) {
         case kBrush: return launch_edit_brush(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_edit_stamp*)(ring + stamps_at), count);
         case kPaint: return launch_edit_paint(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_paint_stamp*)(ring + stamps_at), count);
-        case kRegion: return launch_edit_region(ctx->stream, at.meta, at.level0, items, n, max_rows, ctx->edit_region_dev, x0, y0, width);
+        case kRegion: return launch_edit_region(ctx->stream, at.meta, at.level0, items, n, max_rows, ctx->edit_region.dev, x0, y0, width);
         case kSmooth:
             return launch_edit_smooth(ctx->stream, at.meta, at.level0, items, (const uint64_t*)(ring + offsets_at), n, max_rows, (const bt_smooth_stamp*)(ring + stamps_at), count,
-                                      kernel_radius, ctx->edit_region_dev);
+                                      kernel_radius, ctx->edit_region.dev);
     }
     return BT_OK;
 }
@@ -641,14 +631,14 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
     }
     // layers -> the staged rectangle on the device (what no tile covers: zeros, from a memset queued before the launch)
     const uint64_t total = row_bytes * height;
-    if (bt_status s = region_scratch(ctx, total)) return s;
-    if (missing) BT_HIP(hipMemsetAsync(ctx->edit_region_dev, 0, total, ctx->stream));
+    if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
+    if (missing) BT_HIP(hipMemsetAsync(ctx->edit_region.dev, 0, total, ctx->stream));
     if (!items.empty()) {
         PlanRing ring;
         const uint64_t items_at = ring.add(items);
         uint8_t* dev = nullptr;
         if (bt_status s = ring.commit(ctx, &dev)) return s;
-        if (bt_status s = launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, ctx->edit_region_dev, x0, y0, width))
+        if (bt_status s = launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, ctx->edit_region.dev, x0, y0, width))
             return s;
     }
     // the staged rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
@@ -673,7 +663,7 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
         const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
         empty(k);
         if (e == hipSuccess && !landing[k].copied) e = hipEventCreateWithFlags(&landing[k].copied, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)ctx->edit_region_dev + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)ctx->edit_region.dev + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(landing[k].copied, ctx->stream);
         if (e == hipSuccess) landing[k].row = row, landing[k].rows = rows;
     }

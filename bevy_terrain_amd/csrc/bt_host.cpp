@@ -239,6 +239,29 @@ bt_status ctx_staging(bt_ctx* ctx, size_t bytes) {
     return BT_OK;
 }
 
+bt_status Scratch::reserve(bt_ctx* ctx, uint64_t need, bool with_pinned_twin) {
+    if (bytes >= need) return BT_OK;
+    if (dev) BT_HIP(hipStreamSynchronize(ctx->stream));  // work in flight may use the buffer that goes away
+    hipError_t e = hipSuccess;
+    release(&e);
+    if (e == hipSuccess) e = hipMalloc(&dev, need);
+    if (e == hipSuccess && with_pinned_twin) e = hipHostMalloc(&host, need, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        release();
+        return hip_fail(e, "scratch buffer");
+    }
+    bytes = need;
+    return BT_OK;
+}
+
+uint64_t Scratch::release(hipError_t* error) {
+    const hipError_t d = dev ? hipFree(dev) : hipSuccess, h = host ? hipHostFree(host) : hipSuccess;
+    const uint64_t freed = (dev ? bytes : 0u) + (host ? bytes : 0u);
+    *this = Scratch{};
+    if (error && *error == hipSuccess) *error = d != hipSuccess ? d : h;
+    return freed;
+}
+
 }  // namespace bt
 
 using namespace bt;
@@ -287,14 +310,9 @@ void bt_ctx_destroy(bt_ctx* ctx) {
     if (ctx->ev_end) hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     for (auto& kept : ctx->spare_rasters) hipFree(kept.first);
-    if (ctx->bounds_dev) hipFree(ctx->bounds_dev);
-    if (ctx->bounds_host) hipHostFree(ctx->bounds_host);
-    if (ctx->raycast_dev) hipFree(ctx->raycast_dev);
-    if (ctx->normal_dev) hipFree(ctx->normal_dev);
-    if (ctx->render_dev) hipFree(ctx->render_dev);
+    for (bt::Scratch* s : ctx->scratch()) s->release();
     if (ctx->edit_dev) hipFree(ctx->edit_dev);
     if (ctx->edit_host) hipHostFree(ctx->edit_host);
-    if (ctx->edit_region_dev) hipFree(ctx->edit_region_dev);
     if (ctx->edit_copied) hipEventDestroy(ctx->edit_copied);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->save_stream) hipStreamDestroy(ctx->save_stream);
@@ -341,35 +359,14 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
             freed += ctx->staging_bytes;
         }
     ctx->staging_bytes = 0;
-    if (ctx->bounds_dev) BT_HIP(hipFree(ctx->bounds_dev));
-    if (ctx->bounds_host) BT_HIP(hipHostFree(ctx->bounds_host));
-    if (ctx->bounds_dev || ctx->bounds_host) freed += 2u * ctx->bounds_bytes;
-    ctx->bounds_dev = ctx->bounds_host = nullptr;
-    ctx->bounds_bytes = 0;
-    if (ctx->raycast_dev) {
-        BT_HIP(hipFree(ctx->raycast_dev));
-        freed += ctx->raycast_bytes;
-    }
-    ctx->raycast_dev = nullptr;
-    ctx->raycast_bytes = 0;
-    if (ctx->normal_dev) {
-        BT_HIP(hipFree(ctx->normal_dev));
-        freed += ctx->normal_bytes;
-    }
-    ctx->normal_dev = nullptr;
-    ctx->normal_bytes = 0;
-    if (ctx->render_dev) {
-        BT_HIP(hipFree(ctx->render_dev));
-        freed += ctx->render_bytes;
-    }
-    ctx->render_dev = nullptr;
-    ctx->render_bytes = 0;
+    hipError_t failed = hipSuccess;
+    for (bt::Scratch* s : ctx->scratch()) freed += s->release(&failed);
+    BT_HIP(failed);
     if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
     if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
-    if (ctx->edit_region_dev) BT_HIP(hipFree(ctx->edit_region_dev));
-    freed += 2u * ctx->edit_bytes + ctx->edit_region_bytes;
-    ctx->edit_dev = ctx->edit_host = ctx->edit_region_dev = nullptr;
-    ctx->edit_bytes = ctx->edit_used = ctx->edit_region_bytes = 0;
+    freed += 2u * ctx->edit_bytes;
+    ctx->edit_dev = ctx->edit_host = nullptr;
+    ctx->edit_bytes = ctx->edit_used = 0;
     if (freed_bytes) *freed_bytes = freed;
     return BT_OK;
 }
@@ -1034,18 +1031,9 @@ bt_status bt_atlas_tile_bounds(bt_atlas* a, uint32_t ai, const uint32_t* layers,
     const uint32_t chunk = uint32_t(std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / (cells * 4u + 4u))));
     const uint64_t list_bytes = (uint64_t(chunk) * 4u + 255u) & ~255ull, need = list_bytes + uint64_t(chunk) * cells * 4u;
     BT_HIP(hipSetDevice(ctx->device));
-    if (ctx->bounds_bytes < need) {
-        BT_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->bounds_dev) BT_HIP(hipFree(ctx->bounds_dev));
-        if (ctx->bounds_host) BT_HIP(hipHostFree(ctx->bounds_host));
-        ctx->bounds_dev = ctx->bounds_host = nullptr;
-        ctx->bounds_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->bounds_dev, need));
-        BT_HIP(hipHostMalloc(&ctx->bounds_host, need, hipHostMallocDefault));
-        ctx->bounds_bytes = need;
-    }
-    uint32_t* list = (uint32_t*)ctx->bounds_host;
-    uint8_t* dev = (uint8_t*)ctx->bounds_dev;
+    if (bt_status s = ctx->bounds.reserve(ctx, need, true)) return s;
+    uint32_t* list = (uint32_t*)ctx->bounds.host;
+    uint8_t* dev = (uint8_t*)ctx->bounds.dev;
     for (uint32_t first = 0; first < count; first += chunk) {
         const uint32_t n = std::min(chunk, count - first);
         for (uint32_t i = 0; i < n; i++) list[i] = layers ? layers[first + i] : first + i;
@@ -1053,9 +1041,9 @@ bt_status bt_atlas_tile_bounds(bt_atlas* a, uint32_t ai, const uint32_t* layers,
         if (bt_status s = launch_tile_bounds(ctx->stream, at.level0, T, (const uint32_t*)dev, n, grid, flags & BT_BOUNDS_SKIP_ZERO,
                                              (uint32_t*)(dev + list_bytes)))
             return s;
-        BT_HIP(hipMemcpyAsync((uint8_t*)ctx->bounds_host + list_bytes, dev + list_bytes, n * cells * 4u, hipMemcpyDeviceToHost, ctx->stream));
+        BT_HIP(hipMemcpyAsync((uint8_t*)ctx->bounds.host + list_bytes, dev + list_bytes, n * cells * 4u, hipMemcpyDeviceToHost, ctx->stream));
         BT_HIP(hipStreamSynchronize(ctx->stream));
-        memcpy(out + uint64_t(first) * cells * 2u, (const uint8_t*)ctx->bounds_host + list_bytes, n * cells * 4u);
+        memcpy(out + uint64_t(first) * cells * 2u, (const uint8_t*)ctx->bounds.host + list_bytes, n * cells * 4u);
     }
     return BT_OK;  // a read: Attachment::written stays as it is
 }

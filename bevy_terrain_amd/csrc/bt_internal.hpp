@@ -16,11 +16,14 @@
 #include "bevy_terrain_amd.h"
 
 struct bt_preprocessor;
+struct bt_ctx;
 
 namespace bt {
 
 void set_error(const char* fmt, ...);
 bt_status hip_fail(hipError_t e, const char* what);
+// kind and axes of a caller's terrain model (bt_tile_tree.hip); `who`: the entry point the refusal names
+bt_status check_model(const bt_terrain_model* m, const char* who);
 
 #define BT_HIP(expr)                                          \
     do {                                                      \
@@ -150,6 +153,19 @@ struct Raster {
     uint64_t alloc_bytes = 0;  // size of the owned device allocation
 };
 
+// A device buffer, optionally with a pinned twin of the same size, that only grows and is kept until bt_ctx_trim: a per-frame caller pays
+// no allocation (bt_host.cpp)
+struct Scratch {
+    void* dev = nullptr;
+    void* host = nullptr;
+    uint64_t bytes = 0;
+    // at least `need` bytes; a buffer that is too small is replaced once the context's stream has drained (work in flight may use it).
+    // A failed allocation leaves the scratch empty
+    bt_status reserve(bt_ctx* ctx, uint64_t need, bool with_pinned_twin = false);
+    // frees both halves and returns the bytes given back (`bytes` per half that existed); *error keeps the first failure
+    uint64_t release(hipError_t* error = nullptr);
+};
+
 }  // namespace bt
 
 struct bt_ctx {
@@ -195,31 +211,26 @@ struct bt_ctx {
         }
     }
     uint32_t io_threads = 0;  // writer / reader threads of the save and load paths; 0 = automatic (bt_ctx_set_io_threads)
-    // bt_atlas_tile_bounds: the layer list and the pyramids of one chunk of layers, on the device and pinned (grown on demand, kept until
-    // bt_ctx_trim: a per-frame caller pays no allocation)
-    void* bounds_dev = nullptr;
-    void* bounds_host = nullptr;
-    uint64_t bounds_bytes = 0;
-    // bt_tile_tree_raycast: the rays and the hits of one call on the device (grown on demand, kept until bt_ctx_trim)
-    void* raycast_dev = nullptr;
-    uint64_t raycast_bytes = 0;
+    // The scratch of the query calls: each grown on demand by its call (bt::Scratch::reserve), kept until bt_ctx_trim
+    // bt_atlas_tile_bounds: the layer list and the pyramids of one chunk of layers, on the device and pinned
+    bt::Scratch bounds;
+    // bt_tile_tree_raycast: the rays and the hits of one call on the device
+    bt::Scratch raycast;
     // bt_tile_tree_sample_normal: the positions, normals and cosines of one call; bt_atlas_tile_normals: the tile list and up to three
-    // chunks of normal maps on their way to the pinned staging buffers (grown on demand, kept until bt_ctx_trim)
-    void* normal_dev = nullptr;
-    uint64_t normal_bytes = 0;
-    // bt_tile_tree_render: the pixel counters and the planes of one call on the device (grown on demand, kept until bt_ctx_trim)
-    void* render_dev = nullptr;
-    uint64_t render_bytes = 0;
+    // chunks of normal maps on their way to the pinned staging buffers; bt_tile_tree_tile_geometry(_hp): the tile list and the vertices of one chunk
+    bt::Scratch normal;
+    // bt_tile_tree_render: the pixel counters and the planes of one call on the device
+    bt::Scratch render;
+    // the staged rectangle of write_region and read_region / the new texels of smooth_height on the device
+    bt::Scratch edit_region;
+    std::array<bt::Scratch*, 5> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
-    // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out.  Then the
-    // staged rectangle of write_region and read_region / the new texels of smooth_height on the device (grown on demand, kept until bt_ctx_trim)
+    // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out (kept until bt_ctx_trim)
     void* edit_dev = nullptr;
     void* edit_host = nullptr;
     uint64_t edit_bytes = 0, edit_used = 0;
     hipEvent_t edit_copied = nullptr;
-    void* edit_region_dev = nullptr;
-    uint64_t edit_region_bytes = 0;
 };
 
 namespace bt {
@@ -245,6 +256,10 @@ struct bt_atlas {
 };
 
 namespace bt {
+
+// the R16 attachment a height query reads (bt_tile_tree_query.cpp): an index out of range is BT_ERR_INVALID_ARGUMENT, another format
+// BT_ERR_UNSUPPORTED, each with a message that starts with `who`
+bt_status height_attachment(const char* who, const bt_atlas* a, uint32_t ai, const Attachment** height);
 
 // One launch of the compiled plan.
 enum LaunchKind : uint32_t { kLaunchSplit, kLaunchDownsample, kLaunchStitch, kLaunchFusedMain, kLaunchFusedTail, kLaunchFusedDirect, kLaunchFusedTodo };

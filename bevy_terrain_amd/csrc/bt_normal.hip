@@ -118,14 +118,6 @@ __global__ __launch_bounds__(kBakeThreads) void tile_normals_kernel(BakeArgs a) 
 // of the tap position
 uint32_t bake_halo(const AttachmentMeta& m) { return m.texture_size / (2u * m.center_size) + 2u; }
 
-bt_status check_model(const bt_terrain_model* m, const char* who) {
-    if (!m || m->kind > BT_MODEL_ELLIPSOIDAL || !(m->a > 0.0) || (m->kind == BT_MODEL_ELLIPSOIDAL && !(m->b > 0.0))) {
-        set_error("%s: %s", who, m ? "terrain model: kind / axes" : "NULL model");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    return BT_OK;
-}
-
 }  // namespace
 
 namespace bt {
@@ -144,15 +136,13 @@ bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt
 extern "C" bt_status bt_atlas_tile_normals(bt_atlas* a, uint32_t ai, const bt_terrain_model* model_c, const bt_tile_coordinate* coords, uint32_t count,
                                            uint8_t* out, uint64_t out_bytes) {
     const char* who = "bt_atlas_tile_normals";
-    if (!a || ai >= a->attachments.size()) {
-        set_error("%s: %s", who, a ? "attachment index out of range" : "NULL atlas");
+    if (!a) {
+        set_error("%s: NULL atlas", who);
         return BT_ERR_INVALID_ARGUMENT;
     }
-    const Attachment& at = a->attachments[ai];
-    if (at.meta.format != BT_FORMAT_R16) {
-        set_error("%s: attachment %u is not R16", who, ai);
-        return BT_ERR_UNSUPPORTED;
-    }
+    const Attachment* height;
+    if (bt_status s = height_attachment(who, a, ai, &height)) return s;
+    const Attachment& at = *height;
     if (!count) return BT_OK;
     if (bt_status s = check_model(model_c, who)) return s;
     if (!coords || !out) {
@@ -193,19 +183,12 @@ extern "C" bt_status bt_atlas_tile_normals(bt_atlas* a, uint32_t ai, const bt_te
     const uint64_t chunk_bytes = chunk * tile_bytes, list_bytes = (uint64_t(count) * sizeof(BakeTile) + 255u) & ~255ull;
     const uint32_t chunks = uint32_t((count + chunk - 1u) / chunk);
     const uint64_t need = list_bytes + std::min<uint64_t>(kBuffers, chunks) * chunk_bytes;
-    if (ctx->normal_bytes < need) {
-        BT_HIP(hipStreamSynchronize(s));
-        if (ctx->normal_dev) BT_HIP(hipFree(ctx->normal_dev));
-        ctx->normal_dev = nullptr;
-        ctx->normal_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->normal_dev, need));
-        ctx->normal_bytes = need;
-    }
+    if (bt_status st = ctx->normal.reserve(ctx, need)) return st;
     if (ctx->staging_bytes < chunk_bytes || !ctx->staging[0]) {
         BT_HIP(hipStreamSynchronize(s));  // (no copy may be in flight when the staging buffers are replaced)
         if (bt_status st = ctx_staging(ctx, std::max<size_t>(32ull << 20, chunk_bytes))) return st;
     }
-    uint8_t* dev = (uint8_t*)ctx->normal_dev;
+    uint8_t* dev = (uint8_t*)ctx->normal.dev;
     BakeArgs args{};
     args.atlas = (const uint16_t*)at.level0;  // a read: no layer is marked written
     args.m = at.meta;

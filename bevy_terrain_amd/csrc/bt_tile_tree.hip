@@ -17,9 +17,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "bt_internal.hpp"
-#include "bt_model.hpp"
-#include "bt_tile_tree_device.hpp"
+#include "bt_tile_tree_host.hpp"
 
 using namespace bt;
 using namespace bt::model;
@@ -29,18 +27,6 @@ namespace {
 constexpr uint32_t kThreads = 1024;
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
-
-struct NodeState {  // TileState of the tree (tile_tree.rs:28-43)
-    bt_tile_coordinate coordinate;
-    uint32_t requested;  // RequestState::Requested
-};
-
-// One device copy of TileAtlasState::tile_states: open addressing, linear probing; key = coordinate
-struct StateSlot {
-    bt_tile_coordinate coordinate;  // side == kInvalid: empty
-    uint32_t atlas_index;
-    uint32_t loaded;
-};
 
 __host__ __device__ __forceinline__ uint32_t hash_coordinate(bt_tile_coordinate c) {
     uint64_t h = (uint64_t(c.side) << 59) ^ (uint64_t(c.lod) << 53) ^ (uint64_t(c.x) << 26) ^ uint64_t(c.y);
@@ -190,39 +176,7 @@ __global__ __launch_bounds__(128) void tile_tree_sample_kernel(TreeParams P, con
 
 }  // namespace
 
-struct bt_tile_tree {
-    bt_ctx* ctx = nullptr;
-    bt_terrain_model model_c{};
-    bt_terrain_view_config view_config{};
-    Model model{};
-    uint32_t lod_count = 0, sides = 0, nodes = 0;
-    // TileTree::new (tile_tree.rs:135-173)
-    double morph_distance = 0, blend_distance = 0, load_distance = 0, subdivision_distance = 0, precision_threshold_distance = 0;
-    double view_world_position[3] = {0, 0, 0};
-    float approximate_height = 0;
-    // device tables
-    NodeState* d_nodes = nullptr;
-    bt_tile_tree_entry* d_entries = nullptr;
-    uint32_t* d_origins = nullptr;
-    float* d_height = nullptr;  // [0] approximate_height (what the kernels read), [4..8) the vec4 sample behind it
-    StateSlot* d_table = nullptr;
-    uint32_t table_capacity = 0;
-    uint64_t table_version = 0;
-    const bt_atlas* table_atlas = nullptr;
-    // the last update's lists: pinned host memory the update kernel writes directly (one synchronisation, no copies)
-    bt_tile_coordinate *h_released = nullptr, *h_requested = nullptr;
-    uint32_t* h_counts = nullptr;
-    uint32_t released_count = 0, requested_count = 0;
-    // bt_frame_update: pinned staging of the view position, of the height read back one frame late, and of the atlas's tile states
-    double* h_view_position = nullptr;
-    float* h_height = nullptr;
-    bool height_in_flight = false;  // an asynchronous copy d_height -> h_height was enqueued after the last synchronisation
-    StateSlot* h_table = nullptr;
-    uint32_t h_table_capacity = 0;
-    bool table_copy_pending = false;  // h_table -> d_table enqueued since the last synchronisation
-};
-
-namespace {
+namespace bt {
 
 TreeParams make_params(const bt_tile_tree* t) {
     TreeParams P{};
@@ -240,15 +194,28 @@ TreeParams make_params(const bt_tile_tree* t) {
     return P;
 }
 
-bt_status check_model(const bt_terrain_model* m) {
+bt_status check_model(const bt_terrain_model* m, const char* who) {
     if (!m || m->kind > BT_MODEL_ELLIPSOIDAL || !(m->a > 0.0) || (m->kind == BT_MODEL_ELLIPSOIDAL && !(m->b > 0.0))) {
-        set_error("terrain model: kind / axes");
+        set_error("%s: %s", who, m ? "terrain model: kind / axes" : "NULL model");
         return BT_ERR_INVALID_ARGUMENT;
     }
     return BT_OK;
 }
 
-}  // namespace
+// the host's mirror of the tree's height: refreshed whenever the stream has just been synchronised
+static void adopt_height(bt_tile_tree* t) {
+    if (t->height_in_flight) {
+        t->approximate_height = *t->h_height;
+        t->height_in_flight = false;
+    }
+}
+
+void synchronised(bt_tile_tree* t) {
+    adopt_height(t);
+    t->table_copy_pending = false;
+}
+
+}  // namespace bt
 
 extern "C" {
 
@@ -260,7 +227,7 @@ void bt_terrain_view_config_default(bt_terrain_view_config* out) {
 bt_status bt_view_state_from_config(const bt_terrain_model* model, const bt_terrain_view_config* vc, const double view_world_position[3],
                                     float approximate_height, bt_view_state* out) {
     if (!vc || !view_world_position || !out) return BT_ERR_INVALID_ARGUMENT;
-    if (bt_status s = check_model(model)) return s;
+    if (bt_status s = check_model(model, "bt_view_state_from_config")) return s;
     const Model m = make_model(*model);
     bt_view_state v{};
     v.spherical = is_spherical(m) ? 1u : 0u;
@@ -303,7 +270,7 @@ bt_status bt_model_approximation_from_config(const bt_terrain_model* model, cons
         set_error("bt_model_approximation_from_config: NULL %s", !model ? "model" : (!vc ? "view_config" : (!out ? "out" : "view_world_position")));
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_model(model)) return s;
+    if (bt_status s = check_model(model, "bt_model_approximation_from_config")) return s;
     if (model->kind == BT_MODEL_PLANAR) {
         set_error("bt_model_approximation_from_config: a planar model has no series (the reference's coefficients are the cube sphere's there)");
         return BT_ERR_UNSUPPORTED;
@@ -350,7 +317,7 @@ bt_status bt_cull_horizon(const bt_terrain_model* model, const double view_world
         set_error("bt_cull_horizon: NULL %s", !out ? "out" : "view_world_position");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_model(model)) return s;
+    if (bt_status s = check_model(model, "bt_cull_horizon")) return s;
     if (model->kind == BT_MODEL_PLANAR) {
         set_error("bt_cull_horizon: a planar model has no horizon");
         return BT_ERR_UNSUPPORTED;
@@ -382,7 +349,7 @@ bt_status bt_cull_horizon(const bt_terrain_model* model, const double view_world
 bt_status bt_tile_tree_create(bt_ctx* ctx, const bt_terrain_model* model, uint32_t lod_count, const bt_terrain_view_config* vc, bt_tile_tree** out) {
     if (!ctx || !vc || !out) return BT_ERR_INVALID_ARGUMENT;
     *out = nullptr;
-    if (bt_status s = check_model(model)) return s;
+    if (bt_status s = check_model(model, "bt_tile_tree_create")) return s;
     if (lod_count == 0 || lod_count > 31 || vc->tree_size == 0 || vc->tree_size > 64) {
         set_error("tile tree: lod_count %u / tree_size %u", lod_count, vc->tree_size);
         return BT_ERR_INVALID_ARGUMENT;
@@ -445,14 +412,6 @@ void bt_tile_tree_destroy(bt_tile_tree* t) {
 }
 
 namespace {
-// the host's mirror of the tree's height: refreshed whenever the stream has just been synchronised
-void adopt_height(bt_tile_tree* t) {
-    if (t->height_in_flight) {
-        t->approximate_height = *t->h_height;
-        t->height_in_flight = false;
-    }
-}
-
 // TileTree::update as one launch; the kernel writes both lists and their lengths straight into pinned host memory
 bt_status enqueue_update(bt_tile_tree* t, const double view_world_position[3]) {
     for (int i = 0; i < 3; i++) t->view_world_position[i] = view_world_position[i];
@@ -464,8 +423,7 @@ bt_status enqueue_update(bt_tile_tree* t, const double view_world_position[3]) {
 
 bt_status finish_update(bt_tile_tree* t) {
     BT_HIP(hipStreamSynchronize(t->ctx->stream));
-    adopt_height(t);
-    t->table_copy_pending = false;
+    synchronised(t);
     t->released_count = t->h_counts[0];
     t->requested_count = t->h_counts[1];
     return BT_OK;
@@ -567,8 +525,7 @@ bt_status bt_tile_tree_read(bt_tile_tree* t, bt_tile_tree_entry* entries, uint32
         BT_HIP(hipMemcpyAsync(nodes.data(), t->d_nodes, sizeof(NodeState) * t->nodes, hipMemcpyDeviceToHost, s));
     }
     BT_HIP(hipStreamSynchronize(s));
-    adopt_height(t);
-    t->table_copy_pending = false;
+    synchronised(t);
     for (uint32_t i = 0; i < uint32_t(nodes.size()) && i < entry_cap; i++) {
         if (node_coordinates) node_coordinates[i] = nodes[i].coordinate;
         if (node_requested) node_requested[i] = nodes[i].requested;
@@ -600,409 +557,6 @@ bt_status bt_tile_tree_sample_attachment(bt_tile_tree* t, bt_atlas* a, uint32_t 
     return BT_OK;
 }
 
-bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds,
-                               bt_ray_hit* hits) {
-    if (!t || !a) {
-        set_error("bt_tile_tree_raycast: NULL %s", t ? "atlas" : "tile tree");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (t->ctx != a->ctx) {
-        set_error("bt_tile_tree_raycast: tile tree and atlas belong to different contexts");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (ai >= a->attachments.size()) {
-        set_error("bt_tile_tree_raycast: attachment index %u out of range", ai);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const Attachment& at = a->attachments[ai];
-    if (at.meta.format != BT_FORMAT_R16) {
-        set_error("bt_tile_tree_raycast: attachment %u is not R16", ai);
-        return BT_ERR_UNSUPPORTED;
-    }
-    if (steps < 1u || steps > uint32_t(BT_RAYCAST_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
-        set_error("bt_tile_tree_raycast: steps %u (1 .. %u) / refine_rounds %u (at most %u)", steps, unsigned(BT_RAYCAST_MAX_STEPS), refine_rounds,
-                  unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    // a ray costs whole rounds of 64 samples (one wave per ray): that is what the cap counts
-    const uint64_t rounds = (uint64_t(steps) + 1u + 63u) / 64u;
-    if (uint64_t(count) * rounds * 64u > uint64_t(BT_RAYCAST_MAX_SAMPLES)) {
-        set_error("bt_tile_tree_raycast: %u rays x %u rounds of 64 samples exceed BT_RAYCAST_MAX_SAMPLES (%u): split the batch", count, unsigned(rounds),
-                  unsigned(BT_RAYCAST_MAX_SAMPLES));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (!count) return BT_OK;
-    if (!rays || !hits) {
-        set_error("bt_tile_tree_raycast: NULL %s", rays ? "hits_out" : "rays");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    bt_ctx* ctx = t->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const uint64_t in_bytes = sizeof(bt_ray) * uint64_t(count), out_bytes = sizeof(bt_ray_hit) * uint64_t(count);
-    if (ctx->raycast_bytes < in_bytes + out_bytes) {
-        if (ctx->raycast_dev) BT_HIP(hipFree(ctx->raycast_dev));
-        ctx->raycast_dev = nullptr;
-        ctx->raycast_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->raycast_dev, in_bytes + out_bytes));
-        ctx->raycast_bytes = in_bytes + out_bytes;
-    }
-    uint8_t* dev = (uint8_t*)ctx->raycast_dev;
-    BT_HIP(hipMemcpyAsync(dev, rays, in_bytes, hipMemcpyHostToDevice, s));
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    if (bt_status st = launch_raycast(s, make_params(t), t->d_entries, at.meta, at.level0, (const bt_ray*)dev, count, steps, refine_rounds,
-                                      (bt_ray_hit*)(dev + in_bytes), t->d_height))
-        return st;
-    BT_HIP(hipMemcpyAsync(hits, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
-    BT_HIP(hipStreamSynchronize(s));
-    adopt_height(t);
-    t->table_copy_pending = false;
-    return BT_OK;
-}
-
-bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
-                              uint8_t* out_status, float* out_normal, uint8_t* out_rgba, bt_render_stats* stats) {
-    const char* who = "bt_tile_tree_render";
-    if (!t || !a || !camera) {
-        set_error("%s: NULL %s", who, !t ? "tile tree" : (!a ? "atlas" : "camera"));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (t->ctx != a->ctx) {
-        set_error("%s: tile tree and atlas belong to different contexts", who);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (!out_t && !out_status && !out_normal && !out_rgba) {
-        set_error("%s: every plane is NULL", who);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const bt_render_camera& cam = *camera;
-    const uint64_t pixels = uint64_t(cam.width) * cam.height;
-    if (!cam.width || !cam.height || pixels > uint64_t(BT_RENDER_MAX_PIXELS)) {
-        set_error("%s: %u x %u pixels (each at least 1, at most %u in all)", who, cam.width, cam.height, unsigned(BT_RENDER_MAX_PIXELS));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (steps < 1u || steps > uint32_t(BT_RENDER_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
-        set_error("%s: steps %u (1 .. %u) / refine_rounds %u (at most %u)", who, steps, unsigned(BT_RENDER_MAX_STEPS), refine_rounds, unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const bool has_albedo = cam.albedo_attachment != BT_RENDER_NO_ALBEDO;
-    if (ai >= a->attachments.size() || (has_albedo && cam.albedo_attachment >= a->attachments.size())) {
-        set_error("%s: %s attachment index %u out of range", who, ai >= a->attachments.size() ? "height" : "albedo", ai >= a->attachments.size() ? ai : cam.albedo_attachment);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (cam.flags & ~uint32_t(BT_RENDER_ORTHOGRAPHIC | BT_RENDER_LIGHTING)) {
-        set_error("%s: unknown flag bits 0x%x", who, cam.flags);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (!std::isfinite(cam.ambient) || !std::isfinite(cam.sun[0]) || !std::isfinite(cam.sun[1]) || !std::isfinite(cam.sun[2])) {
-        set_error("%s: non-finite ambient / sun", who);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const Attachment& at = a->attachments[ai];
-    if (at.meta.format != BT_FORMAT_R16) {
-        set_error("%s: height attachment %u is not R16", who, ai);
-        return BT_ERR_UNSUPPORTED;
-    }
-    const Attachment& albedo = a->attachments[has_albedo ? cam.albedo_attachment : ai];
-    if (has_albedo && albedo.meta.format != BT_FORMAT_RGBA8) {
-        set_error("%s: albedo attachment %u is not Rgba8", who, cam.albedo_attachment);
-        return BT_ERR_UNSUPPORTED;
-    }
-    bt_ctx* ctx = t->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary
-    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
-    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad(12u * pixels) : 0u),
-                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), need = s_off + (out_status ? pad(pixels) : 0u);
-    if (ctx->render_bytes < need) {
-        BT_HIP(hipStreamSynchronize(s));
-        if (ctx->render_dev) BT_HIP(hipFree(ctx->render_dev));
-        ctx->render_dev = nullptr;
-        ctx->render_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->render_dev, need));
-        ctx->render_bytes = need;
-    }
-    uint8_t* dev = (uint8_t*)ctx->render_dev;
-    RenderArgs args{};
-    args.camera = cam;
-    args.steps = steps;
-    args.refine_rounds = refine_rounds;
-    args.blocks_x = (cam.width + 7u) / 8u;
-    args.counters = (uint32_t*)dev;
-    args.t = out_t ? (double*)(dev + t_off) : nullptr;
-    args.normal = out_normal ? (float*)(dev + n_off) : nullptr;
-    args.rgba = out_rgba ? (uint32_t*)(dev + c_off) : nullptr;
-    args.status = out_status ? dev + s_off : nullptr;
-    // a launch: whole 8 x 8 blocks whose worst case stays within BT_RAYCAST_MAX_SAMPLES (at least one fits: 64 * 4349 samples at most), cut to
-    // whole 8-row bands when it holds one
-    const uint32_t blocks = args.blocks_x * ((cam.height + 7u) / 8u);
-    const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds);
-    uint32_t per_launch = uint32_t(std::min<uint64_t>(blocks, uint64_t(BT_RAYCAST_MAX_SAMPLES) / block_samples));
-    if (per_launch >= args.blocks_x) per_launch -= per_launch % args.blocks_x;
-    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
-    const TreeParams P = make_params(t);
-    uint32_t launches = 0;
-    for (uint32_t first = 0; first < blocks; first += per_launch, launches++) {
-        args.first_block = first;
-        args.block_count = std::min(per_launch, blocks - first);
-        // a read of the atlas: level0 is passed on without marking any layer written
-        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height)) {
-            (void)hipStreamSynchronize(s);
-            return st;
-        }
-    }
-    // nothing is copied back before the last launch has been queued
-    uint32_t counters[4] = {};
-    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_t) e = hipMemcpyAsync(out_t, args.t, 8u * pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_status) e = hipMemcpyAsync(out_status, args.status, pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, args.normal, 12u * pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_rgba) e = hipMemcpyAsync(out_rgba, args.rgba, 4u * pixels, hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
-    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
-    adopt_height(t);
-    t->table_copy_pending = false;
-    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
-    return BT_OK;
-}
-
-bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const double* positions, uint32_t count, float* normals, float* up_dot) {
-    if (!t || !a) {
-        set_error("bt_tile_tree_sample_normal: NULL %s", t ? "atlas" : "tile tree");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (t->ctx != a->ctx) {
-        set_error("bt_tile_tree_sample_normal: tile tree and atlas belong to different contexts");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (ai >= a->attachments.size()) {
-        set_error("bt_tile_tree_sample_normal: attachment index %u out of range", ai);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const Attachment& at = a->attachments[ai];
-    if (at.meta.format != BT_FORMAT_R16) {
-        set_error("bt_tile_tree_sample_normal: attachment %u is not R16", ai);
-        return BT_ERR_UNSUPPORTED;
-    }
-    if (!count) return BT_OK;
-    if (!positions || !normals) {
-        set_error("bt_tile_tree_sample_normal: NULL %s", positions ? "out_normals_xyz" : "world_positions_xyz");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    bt_ctx* ctx = t->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const uint64_t in_bytes = sizeof(double) * 3 * uint64_t(count), n_bytes = 12 * uint64_t(count), d_bytes = 4 * uint64_t(count);
-    if (ctx->normal_bytes < in_bytes + n_bytes + d_bytes) {
-        BT_HIP(hipStreamSynchronize(s));
-        if (ctx->normal_dev) BT_HIP(hipFree(ctx->normal_dev));
-        ctx->normal_dev = nullptr;
-        ctx->normal_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->normal_dev, in_bytes + n_bytes + d_bytes));
-        ctx->normal_bytes = in_bytes + n_bytes + d_bytes;
-    }
-    uint8_t* dev = (uint8_t*)ctx->normal_dev;
-    BT_HIP(hipMemcpyAsync(dev, positions, in_bytes, hipMemcpyHostToDevice, s));
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    if (bt_status st = launch_sample_normal(s, make_params(t), t->d_entries, at.meta, at.level0, (const double*)dev, count, (float*)(dev + in_bytes),
-                                            up_dot ? (float*)(dev + in_bytes + n_bytes) : nullptr, t->d_height))
-        return st;
-    BT_HIP(hipMemcpyAsync(normals, dev + in_bytes, n_bytes, hipMemcpyDeviceToHost, s));
-    if (up_dot) BT_HIP(hipMemcpyAsync(up_dot, dev + in_bytes + n_bytes, d_bytes, hipMemcpyDeviceToHost, s));
-    BT_HIP(hipStreamSynchronize(s));
-    adopt_height(t);
-    t->table_copy_pending = false;
-    return BT_OK;
-}
-
-namespace {
-// what both geometry calls refuse before any device work, and what they hand the kernel: the tree's parameters (TerrainViewConfigUniform:
-// the f64 distances x TerrainModel::scale(), `as f32`) and the view (the caller's, or the tree's own)
-// hp: the HIGH PRECISION calls, which also accept BT_GEOMETRY_VIEW_RELATIVE and check the approximation they were given
-bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, uint32_t flags, GeometryParams* G, bt_view_state* v,
-                         bool hp = false, const bt_model_approximation* approximation = nullptr) {
-    if (!t || !a) {
-        set_error("%s: NULL %s", who, t ? "atlas" : "tile tree");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (t->ctx != a->ctx) {
-        set_error("%s: tile tree and atlas belong to different contexts", who);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (ai >= a->attachments.size()) {
-        set_error("%s: attachment index %u out of range", who, ai);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (flags & ~uint32_t(BT_GEOMETRY_GRID | BT_GEOMETRY_NO_MORPH | BT_GEOMETRY_NO_BLEND | (hp ? BT_GEOMETRY_VIEW_RELATIVE : 0))) {
-        set_error("%s: unknown flags 0x%x", who, flags);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (a->attachments[ai].meta.format != BT_FORMAT_R16) {
-        set_error("%s: attachment %u is not R16", who, ai);
-        return BT_ERR_UNSUPPORTED;
-    }
-    const bt_terrain_view_config& vc = t->view_config;
-    if (vc.grid_size == 0u || vc.grid_size > uint32_t(BT_GEOMETRY_MAX_GRID)) {
-        set_error("%s: grid_size %u (1 .. %u)", who, vc.grid_size, unsigned(BT_GEOMETRY_MAX_GRID));
-        return BT_ERR_UNSUPPORTED;
-    }
-    if (!(flags & BT_GEOMETRY_NO_MORPH) && !(std::isfinite(vc.morph_range) && vc.morph_range > 0.0f)) {
-        set_error("%s: morph_range %g (finite, > 0, or BT_GEOMETRY_NO_MORPH)", who, double(vc.morph_range));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (!(flags & BT_GEOMETRY_NO_BLEND) && !(std::isfinite(vc.blend_range) && vc.blend_range > 0.0f)) {
-        set_error("%s: blend_range %g (finite, > 0, or BT_GEOMETRY_NO_BLEND)", who, double(vc.blend_range));
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (view) {
-        *v = *view;
-    } else if (bt_status s = bt_tile_tree_view_state(t, v)) {
-        return s;
-    }
-    if ((v->spherical ? 6u : 1u) != t->sides) {
-        set_error("%s: a view of %u side(s) for a tile tree of %u", who, v->spherical ? 6u : 1u, t->sides);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (hp) {
-        if (!approximation) {
-            set_error("%s: NULL approximation", who);
-            return BT_ERR_INVALID_ARGUMENT;
-        }
-        if (t->sides != 6u) {
-            set_error("%s: a planar terrain has no model approximation", who);
-            return BT_ERR_UNSUPPORTED;
-        }
-        const float th = approximation->precision_threshold_distance;
-        if (approximation->origin_lod != v->origin_lod || approximation->origin_lod > 31u || !std::isfinite(th) || th < 0.0f) {
-            set_error("%s: approximation of origin_lod %u for a view of %u (equal, <= 31), or precision_threshold_distance %g (finite, >= 0)", who,
-                      approximation->origin_lod, v->origin_lod, double(th));
-            return BT_ERR_INVALID_ARGUMENT;
-        }
-    }
-    G->grid_size = vc.grid_size;
-    G->tree_size = vc.tree_size;
-    G->lod_count = t->lod_count;
-    G->sides = t->sides;
-    G->flags = flags;
-    G->morph_distance = float(t->morph_distance);
-    G->blend_distance = float(t->blend_distance);
-    G->morph_range = vc.morph_range;
-    G->blend_range = vc.blend_range;
-    G->min_height = t->model_c.min_height;
-    G->max_height = t->model_c.max_height;
-    return BT_OK;
-}
-
-uint64_t geometry_slots(const GeometryParams& G) {
-    const uint64_t g = G.grid_size;
-    return (G.flags & BT_GEOMETRY_GRID) ? (g + 1u) * (g + 1u) : 2u * g * (g + 2u);
-}
-}  // namespace
-
-namespace {
-// both forms, plain (hp false, approximation NULL) and HIGH PRECISION
-bt_status build_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
-                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
-    GeometryParams G{};
-    bt_view_state v{};
-    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
-    if (!prepass || bt::tiling_prepass_ctx(prepass) != t->ctx) {
-        // the kernel reads the list the prepass kernels leave: ordered only on one stream
-        set_error("%s: %s", who, prepass ? "tile tree and tiling prepass belong to different contexts" : "NULL prepass");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (!vertex_capacity) return BT_OK;
-    if (!vertices_device || (uintptr_t(vertices_device) & 15u)) {
-        set_error("%s: vertices_device is %s", who, vertices_device ? "not 16-byte aligned" : "NULL");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const bt_tile_coordinate* tiles;
-    const uint32_t* count;
-    uint32_t capacity;
-    bt::tiling_prepass_final(prepass, &tiles, &count, &capacity);
-    BT_HIP(hipSetDevice(t->ctx->device));
-    // a read of the atlas: level0 is passed on without marking any layer written
-    const Attachment& at = a->attachments[ai];
-    return launch_geometry(t->ctx->stream, v, G, t->d_entries, at.meta, at.level0, tiles, count, capacity, 0u, vertices_device, vertex_capacity, approximation);
-}
-
-bt_status tile_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
-                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
-    static_assert(sizeof(bt_terrain_vertex) == 48, "three 16-byte stores per vertex");
-    static_assert(sizeof(bt_model_approximation) == 448, "a by-value kernel argument, a multiple of 16 bytes");
-    GeometryParams G{};
-    bt_view_state v{};
-    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
-    if (!count) return BT_OK;
-    if (!tiles || !out) {
-        set_error("%s: NULL %s", who, tiles ? "out_host" : "tiles");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    const uint64_t slots = geometry_slots(G), tile_bytes = slots * sizeof(bt_terrain_vertex);
-    if (out_bytes < uint64_t(count) * tile_bytes) {
-        set_error("%s: out_bytes %llu < %u tiles x %llu vertices x 48", who, (unsigned long long)out_bytes, count, (unsigned long long)slots);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    for (uint32_t i = 0; i < count; i++) {
-        const bt_tile_coordinate& c = tiles[i];
-        if (c.side >= t->sides || c.lod >= t->lod_count || c.x >= (1u << c.lod) || c.y >= (1u << c.lod)) {
-            set_error("%s: tile %u (%u, %u, %u, %u) is not a tile of this terrain", who, i, c.side, c.lod, c.x, c.y);
-            return BT_ERR_INVALID_ARGUMENT;
-        }
-    }
-    bt_ctx* ctx = t->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // one launch per 32 MiB of vertices (at least one tile); the scratch is the normals' (bt_ctx::normal_dev), until bt_ctx_trim
-    const uint32_t chunk = uint32_t(std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / tile_bytes)));
-    const uint64_t in_bytes = (sizeof(bt_tile_coordinate) * uint64_t(chunk) + 15u) & ~15ull, need = in_bytes + uint64_t(chunk) * tile_bytes;
-    if (ctx->normal_bytes < need) {
-        BT_HIP(hipStreamSynchronize(s));
-        if (ctx->normal_dev) BT_HIP(hipFree(ctx->normal_dev));
-        ctx->normal_dev = nullptr;
-        ctx->normal_bytes = 0;
-        BT_HIP(hipMalloc(&ctx->normal_dev, need));
-        ctx->normal_bytes = need;
-    }
-    uint8_t* dev = (uint8_t*)ctx->normal_dev;
-    const Attachment& at = a->attachments[ai];
-    for (uint32_t first = 0; first < count; first += chunk) {
-        const uint32_t n = std::min(chunk, count - first);
-        BT_HIP(hipMemcpyAsync(dev, tiles + first, sizeof(bt_tile_coordinate) * size_t(n), hipMemcpyHostToDevice, s));
-        // a read of the atlas: level0 is passed on without marking any layer written
-        if (bt_status st = launch_geometry(s, v, G, t->d_entries, at.meta, at.level0, (const bt_tile_coordinate*)dev, nullptr, n, first, dev + in_bytes, uint64_t(n) * slots,
-                                           approximation))
-            return st;
-        BT_HIP(hipMemcpyAsync((uint8_t*)out + uint64_t(first) * tile_bytes, dev + in_bytes, uint64_t(n) * tile_bytes, hipMemcpyDeviceToHost, s));
-        BT_HIP(hipStreamSynchronize(s));  // (the next chunk reuses the scratch, and `tiles` / `out` are pageable)
-    }
-    adopt_height(t);
-    t->table_copy_pending = false;
-    return BT_OK;
-}
-}  // namespace
-
-bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tiling_prepass* prepass, uint32_t flags,
-                                      void* vertices_device, uint64_t vertex_capacity) {
-    return build_geometry("bt_tile_tree_build_geometry", false, t, a, ai, view, nullptr, prepass, flags, vertices_device, vertex_capacity);
-}
-
-bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tile_coordinate* tiles, uint32_t count,
-                                     uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
-    return tile_geometry("bt_tile_tree_tile_geometry", false, t, a, ai, view, nullptr, tiles, count, flags, out, out_bytes);
-}
-
-bt_status bt_tile_tree_build_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
-                                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
-    return build_geometry("bt_tile_tree_build_geometry_hp", true, t, a, ai, view, approximation, prepass, flags, vertices_device, vertex_capacity);
-}
-
-bt_status bt_tile_tree_tile_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
-                                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
-    return tile_geometry("bt_tile_tree_tile_geometry_hp", true, t, a, ai, view, approximation, tiles, count, flags, out, out_bytes);
-}
-
 namespace {
 // TileTree::approximate_height (tile_tree.rs:372-386): sample_height of attachment 0 at the view position, kept on the device
 // (d_height[0]; the kernel reads the old value for its surface position, then overwrites it) and copied to pinned memory
@@ -1025,8 +579,7 @@ bt_status bt_tile_tree_approximate_height(bt_tile_tree* t, bt_atlas* a, float* h
     BT_HIP(hipSetDevice(t->ctx->device));
     if (bt_status s = enqueue_height(t, a)) return s;
     BT_HIP(hipStreamSynchronize(t->ctx->stream));
-    adopt_height(t);
-    t->table_copy_pending = false;
+    synchronised(t);
     if (height) *height = t->approximate_height;
     return BT_OK;
 }

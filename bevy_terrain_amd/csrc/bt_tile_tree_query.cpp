@@ -1,0 +1,374 @@
+// The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_render, bt_tile_tree_sample_normal and the
+// geometry calls.  Each validates, stages its inputs in scratch of the context (bt::Scratch: grown on demand, kept until bt_ctx_trim),
+// calls the launcher of its kernel file (bt_raycast.hip, bt_render.hip, bt_normal.hip, bt_geometry.hip) and copies the results back.
+#include <cmath>
+
+#include "bt_tile_tree_host.hpp"
+
+using namespace bt;
+
+namespace bt {
+
+bt_status query_handles(const char* who, const bt_tile_tree* t, const bt_atlas* a) {
+    if (!t || !a) {
+        set_error("%s: NULL %s", who, t ? "atlas" : "tile tree");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (t->ctx != a->ctx) {
+        set_error("%s: tile tree and atlas belong to different contexts", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    return BT_OK;
+}
+
+bt_status height_attachment(const char* who, const bt_atlas* a, uint32_t ai, const Attachment** height) {
+    if (ai >= a->attachments.size()) {
+        set_error("%s: attachment index %u out of range", who, ai);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (a->attachments[ai].meta.format != BT_FORMAT_R16) {
+        set_error("%s: attachment %u is not R16", who, ai);
+        return BT_ERR_UNSUPPORTED;
+    }
+    *height = &a->attachments[ai];
+    return BT_OK;
+}
+
+bt_status query_check(const char* who, const bt_tile_tree* t, const bt_atlas* a, uint32_t ai, const Attachment** height) {
+    if (bt_status s = query_handles(who, t, a)) return s;
+    return height_attachment(who, a, ai, height);
+}
+
+}  // namespace bt
+
+extern "C" {
+
+bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds,
+                               bt_ray_hit* hits) {
+    const Attachment* height;
+    if (bt_status s = query_check("bt_tile_tree_raycast", t, a, ai, &height)) return s;
+    const Attachment& at = *height;
+    if (steps < 1u || steps > uint32_t(BT_RAYCAST_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
+        set_error("bt_tile_tree_raycast: steps %u (1 .. %u) / refine_rounds %u (at most %u)", steps, unsigned(BT_RAYCAST_MAX_STEPS), refine_rounds,
+                  unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a ray costs whole rounds of 64 samples (one wave per ray): that is what the cap counts
+    const uint64_t rounds = (uint64_t(steps) + 1u + 63u) / 64u;
+    if (uint64_t(count) * rounds * 64u > uint64_t(BT_RAYCAST_MAX_SAMPLES)) {
+        set_error("bt_tile_tree_raycast: %u rays x %u rounds of 64 samples exceed BT_RAYCAST_MAX_SAMPLES (%u): split the batch", count, unsigned(rounds),
+                  unsigned(BT_RAYCAST_MAX_SAMPLES));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!count) return BT_OK;
+    if (!rays || !hits) {
+        set_error("bt_tile_tree_raycast: NULL %s", rays ? "hits_out" : "rays");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t in_bytes = sizeof(bt_ray) * uint64_t(count), out_bytes = sizeof(bt_ray_hit) * uint64_t(count);
+    if (bt_status st = ctx->raycast.reserve(ctx, in_bytes + out_bytes)) return st;
+    uint8_t* dev = (uint8_t*)ctx->raycast.dev;
+    BT_HIP(hipMemcpyAsync(dev, rays, in_bytes, hipMemcpyHostToDevice, s));
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    if (bt_status st = launch_raycast(s, make_params(t), t->d_entries, at.meta, at.level0, (const bt_ray*)dev, count, steps, refine_rounds,
+                                      (bt_ray_hit*)(dev + in_bytes), t->d_height))
+        return st;
+    BT_HIP(hipMemcpyAsync(hits, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
+    BT_HIP(hipStreamSynchronize(s));
+    synchronised(t);
+    return BT_OK;
+}
+
+bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
+                              uint8_t* out_status, float* out_normal, uint8_t* out_rgba, bt_render_stats* stats) {
+    const char* who = "bt_tile_tree_render";
+    if (t && a && !camera) {  // (refused before two contexts are)
+        set_error("%s: NULL camera", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status st = query_handles(who, t, a)) return st;
+    if (!out_t && !out_status && !out_normal && !out_rgba) {
+        set_error("%s: every plane is NULL", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bt_render_camera& cam = *camera;
+    const uint64_t pixels = uint64_t(cam.width) * cam.height;
+    if (!cam.width || !cam.height || pixels > uint64_t(BT_RENDER_MAX_PIXELS)) {
+        set_error("%s: %u x %u pixels (each at least 1, at most %u in all)", who, cam.width, cam.height, unsigned(BT_RENDER_MAX_PIXELS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (steps < 1u || steps > uint32_t(BT_RENDER_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
+        set_error("%s: steps %u (1 .. %u) / refine_rounds %u (at most %u)", who, steps, unsigned(BT_RENDER_MAX_STEPS), refine_rounds, unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool has_albedo = cam.albedo_attachment != BT_RENDER_NO_ALBEDO;
+    if (has_albedo && cam.albedo_attachment >= a->attachments.size()) {
+        set_error("%s: albedo attachment index %u out of range", who, cam.albedo_attachment);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (cam.flags & ~uint32_t(BT_RENDER_ORTHOGRAPHIC | BT_RENDER_LIGHTING)) {
+        set_error("%s: unknown flag bits 0x%x", who, cam.flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!std::isfinite(cam.ambient) || !std::isfinite(cam.sun[0]) || !std::isfinite(cam.sun[1]) || !std::isfinite(cam.sun[2])) {
+        set_error("%s: non-finite ambient / sun", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // (the height's index is refused here, behind the other invalid arguments and before either format)
+    const Attachment* height;
+    if (bt_status st = height_attachment(who, a, ai, &height)) return st;
+    const Attachment& at = *height;
+    const Attachment& albedo = a->attachments[has_albedo ? cam.albedo_attachment : ai];
+    if (has_albedo && albedo.meta.format != BT_FORMAT_RGBA8) {
+        set_error("%s: albedo attachment %u is not Rgba8", who, cam.albedo_attachment);
+        return BT_ERR_UNSUPPORTED;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary
+    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
+    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad(12u * pixels) : 0u),
+                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), need = s_off + (out_status ? pad(pixels) : 0u);
+    if (bt_status st = ctx->render.reserve(ctx, need)) return st;
+    uint8_t* dev = (uint8_t*)ctx->render.dev;
+    RenderArgs args{};
+    args.camera = cam;
+    args.steps = steps;
+    args.refine_rounds = refine_rounds;
+    args.blocks_x = (cam.width + 7u) / 8u;
+    args.counters = (uint32_t*)dev;
+    args.t = out_t ? (double*)(dev + t_off) : nullptr;
+    args.normal = out_normal ? (float*)(dev + n_off) : nullptr;
+    args.rgba = out_rgba ? (uint32_t*)(dev + c_off) : nullptr;
+    args.status = out_status ? dev + s_off : nullptr;
+    // a launch: whole 8 x 8 blocks whose worst case stays within BT_RAYCAST_MAX_SAMPLES (at least one fits: 64 * 4349 samples at most), cut to
+    // whole 8-row bands when it holds one
+    const uint32_t blocks = args.blocks_x * ((cam.height + 7u) / 8u);
+    const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds);
+    uint32_t per_launch = uint32_t(std::min<uint64_t>(blocks, uint64_t(BT_RAYCAST_MAX_SAMPLES) / block_samples));
+    if (per_launch >= args.blocks_x) per_launch -= per_launch % args.blocks_x;
+    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
+    const TreeParams P = make_params(t);
+    uint32_t launches = 0;
+    for (uint32_t first = 0; first < blocks; first += per_launch, launches++) {
+        args.first_block = first;
+        args.block_count = std::min(per_launch, blocks - first);
+        // a read of the atlas: level0 is passed on without marking any layer written
+        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height)) {
+            (void)hipStreamSynchronize(s);
+            return st;
+        }
+    }
+    // nothing is copied back before the last launch has been queued
+    uint32_t counters[4] = {};
+    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_t) e = hipMemcpyAsync(out_t, args.t, 8u * pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_status) e = hipMemcpyAsync(out_status, args.status, pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, args.normal, 12u * pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_rgba) e = hipMemcpyAsync(out_rgba, args.rgba, 4u * pixels, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
+    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
+    synchronised(t);
+    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
+    return BT_OK;
+}
+
+bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const double* positions, uint32_t count, float* normals, float* up_dot) {
+    const Attachment* height;
+    if (bt_status s = query_check("bt_tile_tree_sample_normal", t, a, ai, &height)) return s;
+    const Attachment& at = *height;
+    if (!count) return BT_OK;
+    if (!positions || !normals) {
+        set_error("bt_tile_tree_sample_normal: NULL %s", positions ? "out_normals_xyz" : "world_positions_xyz");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t in_bytes = sizeof(double) * 3 * uint64_t(count), n_bytes = 12 * uint64_t(count), d_bytes = 4 * uint64_t(count);
+    if (bt_status st = ctx->normal.reserve(ctx, in_bytes + n_bytes + d_bytes)) return st;
+    uint8_t* dev = (uint8_t*)ctx->normal.dev;
+    BT_HIP(hipMemcpyAsync(dev, positions, in_bytes, hipMemcpyHostToDevice, s));
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    if (bt_status st = launch_sample_normal(s, make_params(t), t->d_entries, at.meta, at.level0, (const double*)dev, count, (float*)(dev + in_bytes),
+                                            up_dot ? (float*)(dev + in_bytes + n_bytes) : nullptr, t->d_height))
+        return st;
+    BT_HIP(hipMemcpyAsync(normals, dev + in_bytes, n_bytes, hipMemcpyDeviceToHost, s));
+    if (up_dot) BT_HIP(hipMemcpyAsync(up_dot, dev + in_bytes + n_bytes, d_bytes, hipMemcpyDeviceToHost, s));
+    BT_HIP(hipStreamSynchronize(s));
+    synchronised(t);
+    return BT_OK;
+}
+
+namespace {
+// what both geometry calls refuse before any device work, and what they hand the kernel: the tree's parameters (TerrainViewConfigUniform:
+// the f64 distances x TerrainModel::scale(), `as f32`) and the view (the caller's, or the tree's own)
+// hp: the HIGH PRECISION calls, which also accept BT_GEOMETRY_VIEW_RELATIVE and check the approximation they were given
+bt_status geometry_check(const char* who, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, uint32_t flags, GeometryParams* G, bt_view_state* v,
+                         bool hp = false, const bt_model_approximation* approximation = nullptr) {
+    if (bt_status s = query_handles(who, t, a)) return s;
+    // (unknown flags are refused before the attachment's format)
+    if (flags & ~uint32_t(BT_GEOMETRY_GRID | BT_GEOMETRY_NO_MORPH | BT_GEOMETRY_NO_BLEND | (hp ? BT_GEOMETRY_VIEW_RELATIVE : 0))) {
+        set_error("%s: unknown flags 0x%x", who, flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment* height;  // (the callers take it from the atlas again once they launch)
+    if (bt_status s = height_attachment(who, a, ai, &height)) return s;
+    const bt_terrain_view_config& vc = t->view_config;
+    if (vc.grid_size == 0u || vc.grid_size > uint32_t(BT_GEOMETRY_MAX_GRID)) {
+        set_error("%s: grid_size %u (1 .. %u)", who, vc.grid_size, unsigned(BT_GEOMETRY_MAX_GRID));
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!(flags & BT_GEOMETRY_NO_MORPH) && !(std::isfinite(vc.morph_range) && vc.morph_range > 0.0f)) {
+        set_error("%s: morph_range %g (finite, > 0, or BT_GEOMETRY_NO_MORPH)", who, double(vc.morph_range));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(flags & BT_GEOMETRY_NO_BLEND) && !(std::isfinite(vc.blend_range) && vc.blend_range > 0.0f)) {
+        set_error("%s: blend_range %g (finite, > 0, or BT_GEOMETRY_NO_BLEND)", who, double(vc.blend_range));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (view) {
+        *v = *view;
+    } else if (bt_status s = bt_tile_tree_view_state(t, v)) {
+        return s;
+    }
+    if ((v->spherical ? 6u : 1u) != t->sides) {
+        set_error("%s: a view of %u side(s) for a tile tree of %u", who, v->spherical ? 6u : 1u, t->sides);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (hp) {
+        if (!approximation) {
+            set_error("%s: NULL approximation", who);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        if (t->sides != 6u) {
+            set_error("%s: a planar terrain has no model approximation", who);
+            return BT_ERR_UNSUPPORTED;
+        }
+        const float th = approximation->precision_threshold_distance;
+        if (approximation->origin_lod != v->origin_lod || approximation->origin_lod > 31u || !std::isfinite(th) || th < 0.0f) {
+            set_error("%s: approximation of origin_lod %u for a view of %u (equal, <= 31), or precision_threshold_distance %g (finite, >= 0)", who,
+                      approximation->origin_lod, v->origin_lod, double(th));
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    G->grid_size = vc.grid_size;
+    G->tree_size = vc.tree_size;
+    G->lod_count = t->lod_count;
+    G->sides = t->sides;
+    G->flags = flags;
+    G->morph_distance = float(t->morph_distance);
+    G->blend_distance = float(t->blend_distance);
+    G->morph_range = vc.morph_range;
+    G->blend_range = vc.blend_range;
+    G->min_height = t->model_c.min_height;
+    G->max_height = t->model_c.max_height;
+    return BT_OK;
+}
+
+uint64_t geometry_slots(const GeometryParams& G) {
+    const uint64_t g = G.grid_size;
+    return (G.flags & BT_GEOMETRY_GRID) ? (g + 1u) * (g + 1u) : 2u * g * (g + 2u);
+}
+}  // namespace
+
+namespace {
+// both forms, plain (hp false, approximation NULL) and HIGH PRECISION
+bt_status build_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
+    GeometryParams G{};
+    bt_view_state v{};
+    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
+    if (!prepass || bt::tiling_prepass_ctx(prepass) != t->ctx) {
+        // the kernel reads the list the prepass kernels leave: ordered only on one stream
+        set_error("%s: %s", who, prepass ? "tile tree and tiling prepass belong to different contexts" : "NULL prepass");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!vertex_capacity) return BT_OK;
+    if (!vertices_device || (uintptr_t(vertices_device) & 15u)) {
+        set_error("%s: vertices_device is %s", who, vertices_device ? "not 16-byte aligned" : "NULL");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bt_tile_coordinate* tiles;
+    const uint32_t* count;
+    uint32_t capacity;
+    bt::tiling_prepass_final(prepass, &tiles, &count, &capacity);
+    BT_HIP(hipSetDevice(t->ctx->device));
+    // a read of the atlas: level0 is passed on without marking any layer written
+    const Attachment& at = a->attachments[ai];
+    return launch_geometry(t->ctx->stream, v, G, t->d_entries, at.meta, at.level0, tiles, count, capacity, 0u, vertices_device, vertex_capacity, approximation);
+}
+
+bt_status tile_geometry(const char* who, bool hp, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    static_assert(sizeof(bt_terrain_vertex) == 48, "three 16-byte stores per vertex");
+    static_assert(sizeof(bt_model_approximation) == 448, "a by-value kernel argument, a multiple of 16 bytes");
+    GeometryParams G{};
+    bt_view_state v{};
+    if (bt_status s = geometry_check(who, t, a, ai, view, flags, &G, &v, hp, approximation)) return s;
+    if (!count) return BT_OK;
+    if (!tiles || !out) {
+        set_error("%s: NULL %s", who, tiles ? "out_host" : "tiles");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t slots = geometry_slots(G), tile_bytes = slots * sizeof(bt_terrain_vertex);
+    if (out_bytes < uint64_t(count) * tile_bytes) {
+        set_error("%s: out_bytes %llu < %u tiles x %llu vertices x 48", who, (unsigned long long)out_bytes, count, (unsigned long long)slots);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_tile_coordinate& c = tiles[i];
+        if (c.side >= t->sides || c.lod >= t->lod_count || c.x >= (1u << c.lod) || c.y >= (1u << c.lod)) {
+            set_error("%s: tile %u (%u, %u, %u, %u) is not a tile of this terrain", who, i, c.side, c.lod, c.x, c.y);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // one launch per 32 MiB of vertices (at least one tile); the scratch is the normals' (bt_ctx::normal), until bt_ctx_trim
+    const uint32_t chunk = uint32_t(std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / tile_bytes)));
+    const uint64_t in_bytes = (sizeof(bt_tile_coordinate) * uint64_t(chunk) + 15u) & ~15ull, need = in_bytes + uint64_t(chunk) * tile_bytes;
+    if (bt_status st = ctx->normal.reserve(ctx, need)) return st;
+    uint8_t* dev = (uint8_t*)ctx->normal.dev;
+    const Attachment& at = a->attachments[ai];
+    for (uint32_t first = 0; first < count; first += chunk) {
+        const uint32_t n = std::min(chunk, count - first);
+        BT_HIP(hipMemcpyAsync(dev, tiles + first, sizeof(bt_tile_coordinate) * size_t(n), hipMemcpyHostToDevice, s));
+        // a read of the atlas: level0 is passed on without marking any layer written
+        if (bt_status st = launch_geometry(s, v, G, t->d_entries, at.meta, at.level0, (const bt_tile_coordinate*)dev, nullptr, n, first, dev + in_bytes, uint64_t(n) * slots,
+                                           approximation))
+            return st;
+        BT_HIP(hipMemcpyAsync((uint8_t*)out + uint64_t(first) * tile_bytes, dev + in_bytes, uint64_t(n) * tile_bytes, hipMemcpyDeviceToHost, s));
+        BT_HIP(hipStreamSynchronize(s));  // (the next chunk reuses the scratch, and `tiles` / `out` are pageable)
+    }
+    synchronised(t);
+    return BT_OK;
+}
+}  // namespace
+
+bt_status bt_tile_tree_build_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tiling_prepass* prepass, uint32_t flags,
+                                      void* vertices_device, uint64_t vertex_capacity) {
+    return build_geometry("bt_tile_tree_build_geometry", false, t, a, ai, view, nullptr, prepass, flags, vertices_device, vertex_capacity);
+}
+
+bt_status bt_tile_tree_tile_geometry(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_tile_coordinate* tiles, uint32_t count,
+                                     uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    return tile_geometry("bt_tile_tree_tile_geometry", false, t, a, ai, view, nullptr, tiles, count, flags, out, out_bytes);
+}
+
+bt_status bt_tile_tree_build_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                                         const bt_tiling_prepass* prepass, uint32_t flags, void* vertices_device, uint64_t vertex_capacity) {
+    return build_geometry("bt_tile_tree_build_geometry_hp", true, t, a, ai, view, approximation, prepass, flags, vertices_device, vertex_capacity);
+}
+
+bt_status bt_tile_tree_tile_geometry_hp(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_view_state* view, const bt_model_approximation* approximation,
+                                        const bt_tile_coordinate* tiles, uint32_t count, uint32_t flags, bt_terrain_vertex* out, uint64_t out_bytes) {
+    return tile_geometry("bt_tile_tree_tile_geometry_hp", true, t, a, ai, view, approximation, tiles, count, flags, out, out_bytes);
+}
+
+}  // extern "C"
