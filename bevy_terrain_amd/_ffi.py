@@ -209,6 +209,15 @@ class PaintStampC(C.Structure):
                 ("radius", C.c_float), ("opacity", C.c_float), ("color", C.c_float * 4)]
 
 
+SPLAT_WEIGHTS, SPLAT_COLOUR = 0, 1
+SPLAT_MAX_RULES, SPLAT_MAX_WEIGHT_RULES = 8, 4
+
+
+class SplatRuleC(C.Structure):
+    _fields_ = [("height_lo", C.c_float), ("height_hi", C.c_float), ("height_fade", C.c_float), ("steep_lo", C.c_float), ("steep_hi", C.c_float),
+                ("steep_fade", C.c_float), ("weight", C.c_float), ("colour", C.c_float * 3), ("_padding", C.c_uint32 * 2)]
+
+
 class EditStatsC(C.Structure):
     _fields_ = [("tiles_edited", C.c_uint32), ("tiles_missing", C.c_uint32), ("tiles_with_children", C.c_uint32),
                 ("tiles_downsampled", C.c_uint32), ("tiles_stitched", C.c_uint32), ("layers_mipped", C.c_uint32), ("launches", C.c_uint32),
@@ -284,6 +293,8 @@ PROTOTYPES = {
     "bt_atlas_edit_height": (_i32, [_vp, _u32, _u32, _P(EditStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_smooth_height": (_i32, [_vp, _u32, _u32, _u32, _P(SmoothStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_paint": (_i32, [_vp, _u32, _u32, _P(PaintStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_splat_from_height": (_i32, [_vp, _u32, _u32, _P(TerrainModelC), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(SplatRuleC), _u32, _P(C.c_uint8),
+                                          _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_read_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(_u32)]),
     "bt_atlas_write_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),

@@ -1,5 +1,5 @@
-// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_write_region / bt_atlas_read_region / bt_atlas_save_tiles: the
-// host half of in-place editing.
+// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_splat_from_height / bt_atlas_write_region / bt_atlas_read_region /
+// bt_atlas_save_tiles: the host half of in-place editing.
 //
 // An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
 // include/bevy_terrain_amd.h): the ancestors' centres, the aprons of every written tile and of its existing neighbours, the mips.  The plan
@@ -264,11 +264,13 @@ namespace {
 // (bt_ctx::edit_region is the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height)
 
 // The first step of a plan, the one that writes the rectangles of the edited tiles (the steps after it are the same for every call): the
-// brush or the paint brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps.  prepare() runs once the plan is known
+// brush or the paint brush on its stamps, the copy from a rectangle of host texels, the smoothing pair on its stamps, the rules of
+// bt_atlas_splat_from_height on the heights of another attachment.  prepare() runs once the plan is known
 // to write something: it adds what the step wants in the ring and readies its device buffer; launch() follows the ring's commit.
 struct FirstStep {
-    enum Kind { kBrush, kRegion, kSmooth, kPaint } kind;
-    // brush: bt_edit_stamp[count]; paint: bt_paint_stamp[count]; smooth: bt_smooth_stamp[count] and the box's kernel_radius
+    enum Kind { kBrush, kRegion, kSmooth, kPaint, kSplat } kind;
+    // brush: bt_edit_stamp[count]; paint: bt_paint_stamp[count]; smooth: bt_smooth_stamp[count] and the box's kernel_radius; splat:
+    // bt_splat_rule[count] (== splat.count)
     const void* stamps = nullptr;
     uint32_t count = 0, kernel_radius = 0;
     // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart; copied: the events of the staging
@@ -277,6 +279,8 @@ struct FirstStep {
     uint64_t row_pitch = 0;
     uint32_t x0 = 0, y0 = 0, width = 0, height = 0;
     hipEvent_t copied[bt_ctx::kStagingBuffers] = {};
+    // splat: the heights the rules read (their attachment's meta and level 0, the model, the LOD), the mode and the fallback texel
+    SplatSource splat{};
     // prepare() -> launch()
     std::vector<uint64_t> offsets;  // smooth: where each item's rectangle starts in the scratch, in dwords
     uint64_t stamps_at = 0, offsets_at = 0;
@@ -291,6 +295,7 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
     switch (kind) {
         case kBrush: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_edit_stamp)); return BT_OK;
         case kPaint: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_paint_stamp)); return BT_OK;
+        case kSplat: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_splat_rule)); return BT_OK;
         case kRegion: return stage_region(ctx, uint64_t(width) * m.pixel_size);
         case kSmooth: {
             uint64_t scratch_dwords = 0;
@@ -331,6 +336,7 @@ bt_status FirstStep::launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ri
     switch (kind) {
         case kBrush: return launch_edit_brush(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_edit_stamp*)(ring + stamps_at), count);
         case kPaint: return launch_edit_paint(ctx->stream, at.meta, at.level0, items, n, max_rows, (const bt_paint_stamp*)(ring + stamps_at), count);
+        case kSplat: return launch_edit_splat(ctx->stream, at.meta, at.level0, items, n, max_rows, splat, (const bt_splat_rule*)(ring + stamps_at));
         case kRegion: return launch_edit_region(ctx->stream, at.meta, at.level0, items, n, max_rows, ctx->edit_region.dev, x0, y0, width);
         case kSmooth:
             return launch_edit_smooth(ctx->stream, at.meta, at.level0, items, (const uint64_t*)(ring + offsets_at), n, max_rows, (const bt_smooth_stamp*)(ring + stamps_at), count,
@@ -421,6 +427,22 @@ bt_status check_target(const bt_atlas* a, uint32_t ai, uint32_t lod, Target targ
     return BT_OK;
 }
 
+// what bt_atlas_write_region, bt_atlas_read_region and bt_atlas_splat_from_height (`what`) check of their rectangle of mosaic texels: the
+// target, the side, the rectangle inside the mosaic of `lod`
+bt_status check_region(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, Target target, const char* what) {
+    if (bt_status s = check_target(a, ai, lod, target, what)) return s;
+    if (side >= (a->config.spherical ? 6u : 1u)) {
+        set_error("%s: side %u", what, side);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t size = uint64_t(a->attachments[ai].meta.center_size) << lod;
+    if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
+        set_error("%s: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", what, x0, x0 + width, y0, y0 + height, (unsigned long long)size);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    return BT_OK;
+}
+
 // the fields of a stamp that only its own call has, in the place the call reports them: before_falloff or after the radius
 const char* bad_own(const bt_edit_stamp& s, bool before_falloff) {
     if (before_falloff) return s.mode != BT_EDIT_ADD && s.mode != BT_EDIT_FLATTEN ? "mode" : nullptr;
@@ -504,9 +526,82 @@ std::vector<Box> stamp_boxes(const bt_atlas* a, uint32_t ai, uint32_t lod, const
     return boxes;
 }
 
+// the first defect of a rule of bt_atlas_splat_from_height, or NULL
+const char* bad_rule(const bt_splat_rule& r, uint32_t mode) {
+    const float bounds[2][3] = {{r.height_lo, r.height_hi, r.height_fade}, {r.steep_lo, r.steep_hi, r.steep_fade}};
+    for (const float* v : {bounds[0], bounds[1]}) {
+        if (std::isnan(v[0]) || std::isnan(v[1])) return "a NaN bound";
+        if (v[0] > v[1]) return "lo > hi";
+        if (!std::isfinite(v[2]) || v[2] < 0.0f) return "fade (finite and >= 0)";
+    }
+    if (!std::isfinite(r.weight) || r.weight < 0.0f) return "weight (finite and >= 0)";
+    for (float v : r.colour)
+        if (mode == BT_SPLAT_COLOUR ? !std::isfinite(v) : std::isnan(v)) return "colour (not finite)";
+    return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
+
+bt_status bt_atlas_splat_from_height(bt_atlas* a, uint32_t hi, uint32_t gi, const bt_terrain_model* model, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                     uint32_t width, uint32_t height, uint32_t mode, const bt_splat_rule* rules, uint32_t count, const uint8_t fallback[4],
+                                     bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats) {
+    const char* who = "bt_atlas_splat_from_height";
+    if (stats) *stats = bt_edit_stats{};
+    // what can be refused without the atlas is refused without it (as the stamps of the brushes are)
+    if (!model || !rules || !fallback || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", who, !model ? "model" : !rules ? "rules" : !fallback ? "fallback" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (mode != BT_SPLAT_WEIGHTS && mode != BT_SPLAT_COLOUR) {
+        set_error("%s: mode %u", who, mode);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint32_t most = mode == BT_SPLAT_WEIGHTS ? BT_SPLAT_MAX_WEIGHT_RULES : BT_SPLAT_MAX_RULES;
+    if (count == 0u || count > most) {
+        set_error("%s: %u rules (1 .. %u in this mode)", who, count, most);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++)
+        if (const char* bad = bad_rule(rules[i], mode)) {
+            set_error("%s: rule %u: %s", who, i, bad);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (bt_status s = check_model(model, who)) return s;
+    if (!a) {
+        set_error("%s: NULL atlas", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (hi == gi || hi >= a->attachments.size() || gi >= a->attachments.size()) {
+        set_error("%s: height attachment %u and target attachment %u of %zu", who, hi, gi, a->attachments.size());
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, gi, side, lod, x0, y0, width, height, kColours, who)) return s;
+    const Attachment& heights = a->attachments[hi];
+    const AttachmentMeta& hm = heights.meta;
+    const AttachmentMeta& gm = a->attachments[gi].meta;
+    if (hm.format != BT_FORMAT_R16) {
+        set_error("%s: height attachment format %u (the rules read R16 heights)", who, hm.format);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (hm.texture_size != gm.texture_size || hm.border_size != gm.border_size) {
+        set_error("%s: heights of texture_size %u, border_size %u and a target of %u, %u: a target texel is derived from the height texel in its place", who,
+                  hm.texture_size, hm.border_size, gm.texture_size, gm.border_size);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (hm.border_size == 0) {
+        set_error("%s: attachment %u has no border (the taps of an edge texel need the neighbour's texels)", who, hi);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!width || !height) return BT_OK;
+    FirstStep first{FirstStep::kSplat};
+    first.stamps = rules, first.count = count;
+    first.splat.meta = hm, first.splat.level0 = heights.level0, first.splat.model = model;  // a read of the heights: no layer of theirs is marked written
+    first.splat.lod = lod, first.splat.mode = mode, first.splat.count = count;
+    memcpy(&first.splat.fallback, fallback, 4);
+    return edit_boxes(a, gi, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, stats);
+}
 
 bt_status bt_atlas_edit_height(bt_atlas* a, uint32_t ai, uint32_t lod, const bt_edit_stamp* stamps, uint32_t count, bt_tile_coordinate* changed,
                                uint32_t changed_cap, bt_edit_stats* stats) {
@@ -560,17 +655,8 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
         set_error("bt_atlas_write_region: NULL changed with changed_cap > 0");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_target(a, ai, lod, kTexels, "bt_atlas_write_region")) return s;
-    if (side >= (a->config.spherical ? 6u : 1u)) {
-        set_error("bt_atlas_write_region: side %u", side);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, "bt_atlas_write_region")) return s;
     const Attachment& at = a->attachments[ai];
-    const uint64_t size = uint64_t(at.meta.center_size) << lod;
-    if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
-        set_error("bt_atlas_write_region: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", x0, x0 + width, y0, y0 + height, (unsigned long long)size);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
     if (!width || !height) return BT_OK;
     const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
     if (!row_pitch) row_pitch = row_bytes;
@@ -598,17 +684,8 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
         set_error("bt_atlas_read_region: NULL atlas");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = check_target(a, ai, lod, kTexels, "bt_atlas_read_region")) return s;
-    if (side >= (a->config.spherical ? 6u : 1u)) {
-        set_error("bt_atlas_read_region: side %u", side);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, "bt_atlas_read_region")) return s;
     const Attachment& at = a->attachments[ai];
-    const uint64_t size = uint64_t(at.meta.center_size) << lod;
-    if (uint64_t(x0) + width > size || uint64_t(y0) + height > size) {
-        set_error("bt_atlas_read_region: [%u, %u) x [%u, %u) outside the mosaic of %llu texels", x0, x0 + width, y0, y0 + height, (unsigned long long)size);
-        return BT_ERR_INVALID_ARGUMENT;
-    }
     if (!width || !height) return BT_OK;
     const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
     if (!row_pitch) row_pitch = row_bytes;

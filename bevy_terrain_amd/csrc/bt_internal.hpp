@@ -319,6 +319,19 @@ inline uint64_t smooth_item_dwords(const EditItem& it, uint32_t border_size) {
 }
 bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, const uint64_t* offsets, uint32_t n, uint32_t max_rows,
                              const bt_smooth_stamp* stamps, uint32_t stamp_count, uint32_t kernel_radius, void* scratch);
+// bt_splat.hip, the first step of bt_atlas_splat_from_height: the items are rectangles of the Rgba8 attachment (`m`, `atlas`) and every texel
+// of them is derived from the R16 attachment `src` of the same atlas (same texture_size and border_size; a tile has one layer index in
+// both).  rules: src.count records on the device.  splat_reach: how far, in texels, the height texels a target texel reads lie from it
+struct SplatSource {
+    AttachmentMeta meta;  // of the heights
+    const void* level0;
+    const bt_terrain_model* model;
+    uint32_t lod, mode, count;
+    uint32_t fallback;  // the four bytes as the texel's dword
+};
+uint32_t splat_reach(const AttachmentMeta& m);
+bt_status launch_edit_splat(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows, const SplatSource& src,
+                            const bt_splat_rule* rules);
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 

@@ -149,6 +149,12 @@ __device__ __forceinline__ uint32_t normal_enc(float v) {
     return uint32_t(floorf(0.5f + 255.0f * cl));
 }
 
+// enc8 of the render section: [0, 1] -> a byte, round half up (bt_render.hip's colour plane, bt_splat.hip's channels)
+__device__ __forceinline__ uint32_t enc8(float v) {
+    const float c = v > 0.0f ? (v > 1.0f ? 1.0f : v) : 0.0f;  // (a NaN encodes as 0)
+    return uint32_t(floorf(0.5f + 255.0f * c));
+}
+
 #endif  // __HIPCC__
 
 }  // namespace bt

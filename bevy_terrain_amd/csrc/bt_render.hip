@@ -19,10 +19,7 @@ using namespace bt::model;
 
 namespace {
 
-__device__ __forceinline__ uint32_t enc8(float v) {
-    const float c = v > 0.0f ? (v > 1.0f ? 1.0f : v) : 0.0f;  // (a NaN encodes as 0)
-    return uint32_t(floorf(0.5f + 255.0f * c));
-}
+// (enc8 of the colour plane: bt_normal_device.hpp, shared with the splat kernel of bt_splat.hip)
 
 __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                 const void* __restrict__ atlas, AttachmentMeta albedo_meta, const void* __restrict__ albedo,

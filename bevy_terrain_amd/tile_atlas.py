@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -168,6 +169,33 @@ class PaintStamp:
                                 {"smooth": _ffi.EDIT_FALLOFF_SMOOTH, "hard": _ffi.EDIT_FALLOFF_HARD}[self.falloff], self.channel_mask(),
                                 (C.c_float * 2)(float(self.center[0]), float(self.center[1])), float(self.radius), float(self.opacity),
                                 (C.c_float * 4)(*[float(v) for v in self.color]))
+
+
+@dataclass
+class SplatRule:
+    """bt_splat_rule: one rule of TileAtlas.splat_from_height.  A texel's weight under the rule is weight * band(height) * band(steep), each band 1
+    between its limits and falling to 0 (smoothstep) over `fade` outside them; fade 0 is a hard edge.  height: (lo, hi) in world height units
+    (the model's min_height .. max_height), -inf / +inf allowed.  slope: (lo, hi) in DEGREES from flat, converted here to the library's
+    steep = 1 - cos(slope); a lower limit <= 0 degrees becomes -inf and an upper limit >= 90 degrees +inf (no limit).  slope_fade is in units
+    of steep (1 - cos), not in degrees.  colour (r, g, b), normalised, is what "colour" mode blends; "weights" mode ignores it."""
+    height: Tuple[float, float] = (-math.inf, math.inf)
+    slope: Tuple[float, float] = (0.0, 90.0)
+    height_fade: float = 0.0
+    slope_fade: float = 0.0
+    weight: float = 1.0
+    colour: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+
+    def steep(self) -> Tuple[float, float]:
+        """the slope limits as the C struct carries them: 1 - cos, in binary32"""
+        lo, hi = float(self.slope[0]), float(self.slope[1])
+        lo = -math.inf if lo <= 0.0 else 1.0 - math.cos(math.radians(lo))
+        hi = math.inf if hi >= 90.0 else 1.0 - math.cos(math.radians(hi))
+        return float(np.float32(lo)), float(np.float32(hi))
+
+    def _c(self):
+        lo, hi = self.steep()
+        return _ffi.SplatRuleC(float(self.height[0]), float(self.height[1]), float(self.height_fade), lo, hi, float(self.slope_fade), float(self.weight),
+                               (C.c_float * 3)(*[float(v) for v in self.colour]), (C.c_uint32 * 2)(0, 0))
 
 
 def mosaic_position(uv, lod: int, center_size: int) -> Tuple[float, float]:
@@ -401,6 +429,30 @@ class TileAtlas:
         stamps = list(stamps)
         arr = (_ffi.PaintStampC * max(len(stamps), 1))(*[s._c() for s in stamps])
         return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_paint(self._h, attachment_index, lod, arr, len(stamps), changed, cap, stats))
+
+    def splat_from_height(self, height_attachment: int, target_attachment: int, rules, mode: str = "colour", fallback=(0, 0, 0, 255), rect=None,
+                          lod: Optional[int] = None, side: int = 0) -> Tuple[List[TileCoordinate], dict]:
+        """bt_atlas_splat_from_height: procedural texturing.  Evaluates the SplatRules (at most 8; 4 in "weights" mode) on the height and the
+        slope of every centre texel of the R16 attachment `height_attachment` inside rect = (x0, y0, w, h) (mosaic texels of `lod` on `side`;
+        default: the whole face) and writes the same texels of the Rgba8 attachment `target_attachment` (same texture and border size):
+        "colour": the rules' colours blended by their weights, alpha 255; "weights": byte k = rule k's share of the weight (a splat map).
+        A texel no rule reaches gets the four `fallback` bytes, a texel without height data becomes (0, 0, 0, 0).  Then the target's
+        ancestors, aprons and mips are restored as by write_region; on the device, without synchronising.  The terrain model is the
+        config's.  Returns (changed, stats) of the target."""
+        from .tile_tree import model_c
+        lod = self.lod_count - 1 if lod is None else lod
+        if rect is None:
+            a = self.config.attachments[target_attachment]
+            n = (a.texture_size - 2 * a.border_size) << lod
+            rect = (0, 0, n, n)
+        x0, y0, w, h = rect
+        rules = list(rules)
+        arr = (_ffi.SplatRuleC * max(len(rules), 1))(*[r._c() for r in rules])
+        bytes4 = (C.c_uint8 * 4)(*[int(v) for v in fallback])
+        mode_c = {"weights": _ffi.SPLAT_WEIGHTS, "colour": _ffi.SPLAT_COLOUR}[mode]
+        model = model_c(self.config.model)
+        return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_splat_from_height(
+            self._h, height_attachment, target_attachment, C.byref(model), side, lod, x0, y0, w, h, mode_c, arr, len(rules), bytes4, changed, cap, stats))
 
     def read_region(self, attachment_index: int, x0: int, y0: int, w: int, h: int, lod: Optional[int] = None, side: int = 0) -> Tuple[np.ndarray, int]:
         """bt_atlas_read_region: the w x h rectangle of centre texels at mosaic position (x0, y0) of `lod` on `side`, the inverse of

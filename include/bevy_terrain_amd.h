@@ -1049,6 +1049,61 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* tree, bt_atlas* atlas, uint32
 bt_status bt_atlas_tile_normals(bt_atlas* atlas, uint32_t attachment_index, const bt_terrain_model* model, const bt_tile_coordinate* coords,
                                 uint32_t count, uint8_t* out_host, uint64_t out_bytes);
 
+/* SPLAT (bt_atlas_splat_from_height): procedural texturing, the "splat maps or something similar" the reference's roadmap
+ * (docs/development.md) names as missing.  For a width x height rectangle of centre texels, mosaic coordinates of `lod` on `side`, the call
+ * evaluates up to BT_SPLAT_MAX_RULES height-and-slope rules per texel of the R16 attachment H = height_attachment and writes the result
+ * into the same texels of the Rgba8 attachment G = target_attachment of the same atlas (same texture_size and border_size), on the device;
+ * then it restores F for G exactly as bt_atlas_write_region does: the same plan, the same `changed` order, the same stats fields.  After the
+ * call G is byte-identical to F of the derived centre texels.  IEEE binary32, one rounding per written operation, no contraction.
+ * T, b, c are those of H; S_H is the level-0 layer L of H that holds the existing tile (side, lod, X, Y) (a tile has one layer index in all
+ * attachments of its atlas).  Centre texel (i, j) of that tile, whose mosaic texel (X * c + i, Y * c + j) lies in the rectangle:
+ *   1. raw = S_H[b + j][b + i].  raw == 0 (no data): the target texel becomes (0, 0, 0, 0) and nothing else is evaluated: the derived
+ *      map's hole mask is the heights'.
+ *   2. v = f32(raw) / 65535.0f (the exact unorm conversion);  h = min_height + (max_height - min_height) * v
+ *   3. uv = ((f32(i) + 0.5f) / f32(c), (f32(j) + 0.5f) / f32(c));  s = TILE NORMAL s(L, lod, uv) of H for `model` (the definition of the
+ *      surface-normal section above, the value bt_atlas_tile_normals encodes for this texel);  steep = 1.0f - s.z   (0 flat, 1 vertical)
+ *   4. clamp01(t) = t > 0 ? (t > 1 ? 1 : t) : 0   (a NaN gives 0);  sm(t) = (t * t) * (3.0f - 2.0f * t)
+ *      band(x; lo, hi, fade):  fade > 0:  r = clamp01((x - (lo - fade)) / fade);  q = clamp01(((hi + fade) - x) / fade)
+ *                              fade == 0: r = x >= lo ? 1 : 0;  q = x <= hi ? 1 : 0
+ *                              band = sm(r) * sm(q)
+ *   5. w_k = (weight_k * band(h; height_lo_k, height_hi_k, height_fade_k)) * band(steep; steep_lo_k, steep_hi_k, steep_fade_k) for k < count;
+ *      sum = ((w_0 + w_1) + ...) in index order
+ *   6. sum > 0:  BT_SPLAT_WEIGHTS (count <= BT_SPLAT_MAX_WEIGHT_RULES): byte k = enc8(w_k / sum) for k < count, 0 above
+ *                BT_SPLAT_COLOUR: byte ch (0 r, 1 g, 2 b) = enc8((((w_0 * colour_0[ch]) + w_1 * colour_1[ch]) + ...) / sum), byte 3 = 255
+ *                enc8 is the render section's: enc8(v) = u8(floorf(0.5f + 255.0f * clamp01(v)))
+ *                (the kernel starts both sums at 0.0f: 0 + x is x up to the sign of a zero, which the comparison sum > 0 and enc8 do not see)
+ *      otherwise (no rule reaches the texel): the four `fallback` bytes, verbatim
+ *   7. the zero rule, as in PAINT (in-place editing): a data texel never becomes a no-data texel: if bytes 0, 1, 2 are all 0, byte 0 is set to 1
+ * Tiles finer than `lod` are not touched (tiles_with_children), and the parents of G are downsample of its children, NOT the rules applied
+ * to coarser heights: that is what F says of any attachment.
+ * PRECONDITION: F holds for H (its aprons are its neighbours' centres; the taps of an edge texel read them), as for SMOOTHING.
+ * REACH: the height texels a target texel reads lie at most R = T / (2c) + 2 (integer division) texels from it on either axis: the tap
+ * offset of T / (2c) texels, the bilinear pair, one for the rounding of a tap position.  The call is a read of H (no layer of H is marked
+ * written) and a write of G, ordered behind everything queued on the context's stream and not synchronising, so called straight after
+ * bt_atlas_edit_height on H with the stamp's box widened by R on every side (and cut to the face) it re-derives what the edit invalidated.
+ * `changed` and `stats` describe G; texels of tiles the atlas does not hold are skipped (tiles_missing).  Launches: one splat launch, then
+ * as bt_atlas_write_region.  The rules travel in the plan scratch of the context (kept until bt_ctx_trim).
+ * All refusals come before anything is queued, with G untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: NULL atlas, model, rules or
+ * fallback, NULL changed with changed_cap > 0; an unknown mode; count == 0 or above the mode's limit; in any rule a NaN, lo > hi, a fade
+ * that is negative or not finite, a weight that is negative or not finite, a non-finite colour in BT_SPLAT_COLOUR; height_attachment ==
+ * target_attachment or either out of range; a malformed model; side, lod or the rectangle as refused by bt_atlas_write_region.
+ * BT_ERR_UNSUPPORTED: H not R16 or G not Rgba8; texture_size or border_size differing between the two; border_size 0 (the taps of an edge
+ * texel need the neighbour's texels); an odd centre size; a mosaic beyond 2^32 texels.  width == 0 or height == 0 (with valid arguments
+ * otherwise): BT_OK, nothing touched, as bt_atlas_write_region. */
+enum { BT_SPLAT_WEIGHTS = 0, BT_SPLAT_COLOUR = 1 };                      /* mode */
+enum { BT_SPLAT_MAX_RULES = 8, BT_SPLAT_MAX_WEIGHT_RULES = 4 };
+typedef struct bt_splat_rule {
+    float height_lo, height_hi, height_fade;  /* world height units (the model's min_height .. max_height); lo / hi may be -inf / +inf */
+    float steep_lo, steep_hi, steep_fade;     /* steep = 1 - cos(slope): 0 flat, 1 vertical */
+    float weight;                             /* finite, >= 0 */
+    float colour[3];                          /* BT_SPLAT_COLOUR only: normalised (1 = 255), finite */
+    uint32_t _padding[2];
+} bt_splat_rule;                              /* 48 bytes */
+bt_status bt_atlas_splat_from_height(bt_atlas* atlas, uint32_t height_attachment, uint32_t target_attachment, const bt_terrain_model* model,
+                                     uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t mode,
+                                     const bt_splat_rule* rules, uint32_t count, const uint8_t fallback[4],
+                                     bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+
 /* Rendering ("what does the terrain look like from here": preview thumbnails of a preprocessed dataset, headless visual checks of an
  * edit, a depth or normal image for a tool that is not wgpu, top-down maps).  The reference's renderer is Bevy / wgpu and stays out of
  * scope; this call casts one ray per pixel on the device and evaluates the fragment stage at the hit, so every plane is defined by the

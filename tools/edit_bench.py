@@ -28,6 +28,13 @@ it, for a radius-32 and a radius-2048 stamp at the same corner: bt_atlas_paint p
 of the stamp's box with the texels bt_atlas_read_region returned (rows `write_region_r{radius}`; the same plan; a tenth of the calls for the
 large box), their ratio, and bt_atlas_read_region of a 4096^2 rectangle beside bt_atlas_download_tiles of the layers it covers (wall time,
 both are synchronous; row `read_region_4096`).
+
+--splat: instead of the above, the 16k height job with a second, Rgba8 attachment of the same tiling and on it bt_atlas_splat_from_height: a
+whole-face derive in both modes (rows `splat_face_colour`, eight rules, and `splat_face_weights`, four; a tenth of the calls per window; with
+the bytes of heights read plus target texels written over the call's time, `GB_per_s`) and a box of the radius-32 stamp's footprint (row
+`splat_box`); beside them, in the same process, bt_atlas_paint with a stamp of the same footprint (`paint_face`, `paint_box`: the same plan
+behind another first step) and the host loop the call replaces: bt_atlas_read_region of the heights, bt_atlas_tile_normals of the tiles, the
+rules in numpy, bt_atlas_write_region of the result (wall time with its legs, `host_loop_box` and `host_loop_2048` for a 2048^2 box).
 """
 import argparse
 import json
@@ -196,14 +203,125 @@ def paint_mode(device, args, result):
     pre.close()
 
 
+def splat_mode(device, args, result):
+    import math
+
+    import numpy as np
+
+    F = np.float32
+    cfg = bt.TerrainConfig(lod_count=LOD_COUNT, atlas_size=ATLAS_SIZE, path="terrains/bench16k_splat",
+                           model=bt.TerrainModel.planar((0.0, 0.0, 0.0), 1000.0, -50.0, 450.0))
+    cfg.add_attachment(bt.AttachmentConfig(name="height", texture_size=TEXTURE_SIZE, border_size=BORDER, format=bt.AttachmentFormat.R16))
+    cfg.add_attachment(bt.AttachmentConfig(name="albedo", texture_size=TEXTURE_SIZE, border_size=BORDER, format=bt.AttachmentFormat.Rgba8))
+    atlas = bt.TileAtlas.new(cfg, device)
+    src = device.synth_fbm_r16(SIZE, SIZE, SEED)
+    pre = bt.Preprocessor.new().clear_attachment(0, atlas).preprocess_tile(
+        bt.PreprocessDataset(attachment_index=0, path="synthetic/fbm16k", lod_range=range(0, LOD_COUNT)),
+        bt.AssetServer().insert("synthetic/fbm16k", (src, SIZE, SIZE)), atlas)
+    pre.run(atlas)
+    index = {c: i for c, i in atlas.tiles()}
+    assert len(index) == 1365, len(index)
+    result["tiles"] = len(index)
+    R, inf = bt.SplatRule, math.inf
+    colour = [R(height=(-inf, 110.0), height_fade=20.0, colour=(0.1, 0.3, 0.7)), R(height=(110.0, 140.0), height_fade=15.0, colour=(0.8, 0.75, 0.5)),
+              R(height=(140.0, 230.0), height_fade=30.0, slope=(0.0, 30.0), slope_fade=0.05, colour=(0.3, 0.6, 0.2)),
+              R(height=(180.0, 260.0), height_fade=30.0, slope=(10.0, 40.0), slope_fade=0.05, colour=(0.1, 0.4, 0.15), weight=0.75),
+              R(height=(230.0, 330.0), height_fade=30.0, colour=(0.5, 0.45, 0.4)), R(slope=(40.0, 90.0), slope_fade=0.1, colour=(0.35, 0.3, 0.3), weight=4.0),
+              R(height=(300.0, inf), height_fade=25.0, slope=(0.0, 50.0), slope_fade=0.1, colour=(1.0, 1.0, 1.0), weight=2.0),
+              R(height=(200.0, 210.0), height_fade=5.0, colour=(0.6, 0.5, 0.3), weight=0.25)]
+    weights = colour[:4]
+    size = CENTER << (LOD_COUNT - 1)
+    corner = (16 * CENTER + 0.25, 16 * CENTER - 0.5)
+    lo = [max(0, int(np.floor(corner[i] - 32.0))) for i in range(2)]
+    hi = [min(size - 1, int(np.ceil(corner[i] + 32.0))) for i in range(2)]
+    box = (lo[0], lo[1], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1)
+    few = max(args.calls // 10, 5)
+
+    def row(call, calls, stats, **more):
+        device_ms, host_ms, windows = window(device, call, calls, args.repeats)
+        return dict({"device_ms_per_call": round(device_ms, 4), "host_ms_per_call": round(host_ms, 4), "device_ms_windows": windows, "calls_per_window": calls,
+                     "launches": stats["launches"], "changed_count": stats["changed_count"], "tiles_edited": stats["tiles_edited"]}, **more)
+
+    for name, mode, rules in (("splat_face_colour", "colour", colour), ("splat_face_weights", "weights", weights)):
+        changed, stats = atlas.splat_from_height(0, 1, rules, mode=mode)
+        r = row(lambda: atlas.splat_from_height(0, 1, rules, mode=mode), few, stats, rules=len(rules))
+        r["bytes_heights_read_plus_target_written"] = size * size * 6
+        r["GB_per_s"] = round(size * size * 6 / r["device_ms_per_call"] / 1e6, 1)
+        result[name] = r
+    changed, stats = atlas.splat_from_height(0, 1, colour, mode="colour", rect=box)
+    result["splat_box"] = row(lambda: atlas.splat_from_height(0, 1, colour, mode="colour", rect=box), args.calls, stats, box=list(box[2:]), rules=len(colour))
+    # the paint brush on the same footprints: the same plan behind another first step
+    for name, stamp, calls in (("paint_face", bt.PaintStamp((size / 2.0, size / 2.0), 2.0 * size, (0.8, 0.3, 0.2, 1.0), opacity=0.05, falloff="hard"), few),
+                               ("paint_box", bt.PaintStamp(corner, 32.0, (0.8, 0.3, 0.2, 1.0), opacity=0.05), args.calls)):
+        changed, stats = atlas.paint(1, [stamp])
+        result[name] = row(lambda: atlas.paint(1, [stamp]), calls, stats)
+    result["splat_over_paint_face"] = round(result["splat_face_colour"]["device_ms_per_call"] / result["paint_face"]["device_ms_per_call"], 3)
+    result["splat_over_paint_box"] = round(result["splat_box"]["device_ms_per_call"] / result["paint_box"]["device_ms_per_call"], 3)
+
+    # the host loop the call replaces
+    def band(x, lo_, hi_, fade):
+        if fade > 0:
+            r_, q_ = np.clip((x - F(lo_ - fade)) / F(fade), 0, 1), np.clip((F(hi_ + fade) - x) / F(fade), 0, 1)
+        else:
+            r_, q_ = (x >= lo_).astype(F), (x <= hi_).astype(F)
+        return (r_ * r_ * (F(3) - F(2) * r_)) * (q_ * q_ * (F(3) - F(2) * q_))
+
+    def host_loop(x0, y0, w, h):
+        t0 = time.perf_counter()
+        heights, missing = atlas.read_region(0, x0, y0, w, h)
+        t1 = time.perf_counter()
+        tiles = [c for c in index if c.lod == LOD_COUNT - 1 and x0 // CENTER <= c.x <= (x0 + w - 1) // CENTER and y0 // CENTER <= c.y <= (y0 + h - 1) // CENTER]
+        normals = atlas.tile_normals(0, tiles)
+        t2 = time.perf_counter()
+        steep = np.zeros((h, w), F)
+        for c, n in zip(tiles, normals):
+            ox, oy = c.x * CENTER, c.y * CENTER
+            xa, xb, ya, yb = max(x0, ox), min(x0 + w, ox + CENTER), max(y0, oy), min(y0 + h, oy + CENTER)
+            steep[ya - y0:yb - y0, xa - x0:xb - x0] = F(1) - (n[ya - oy:yb - oy, xa - ox:xb - ox, 2].astype(F) * F(2.0 / 255.0) - F(1))
+        world = F(-50.0) + F(500.0) * (heights.astype(F) / F(65535.0))
+        total, acc = np.zeros((h, w), F), np.zeros((h, w, 3), F)
+        for rule in colour:
+            s_lo, s_hi = rule.steep()
+            wk = F(rule.weight) * band(world, rule.height[0], rule.height[1], rule.height_fade) * band(steep, s_lo, s_hi, rule.slope_fade)
+            total += wk
+            acc += wk[..., None] * np.array(rule.colour, F)
+        out = np.zeros((h, w, 4), np.uint8)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[..., :3] = np.floor(F(0.5) + F(255) * np.clip(acc / total[..., None], 0, 1))
+        out[..., 3] = 255
+        out[total <= 0] = (0, 0, 0, 255)
+        out[..., 0] |= (out[..., :3] == 0).all(axis=-1).astype(np.uint8)
+        out[heights == 0] = 0
+        t3 = time.perf_counter()
+        atlas.write_region(1, out, x0, y0)
+        device.synchronize()
+        t4 = time.perf_counter()
+        return [(t4 - t0) * 1e3, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3]
+
+    for name, rect, repeats in (("host_loop_box", box, args.repeats), ("host_loop_2048", (int(corner[0]) - 1024, int(corner[1]) - 1024, 2048, 2048), 2)):
+        host_loop(*rect)
+        legs = [host_loop(*rect) for _ in range(repeats)]
+        total, read, normals, rules_ms, write = (round(median([leg[i] for leg in legs]), 3) for i in range(5))
+        result[name] = {"wall_ms": total, "read_region_ms": read, "tile_normals_ms": normals, "numpy_rules_ms": rules_ms, "write_region_ms": write, "box": list(rect[2:])}
+    pre.close()
+    device.free(src)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--bounds", action="store_true", help="time stamp + bt_height_bounds_update and stamp + bt_height_bounds_build")
     ap.add_argument("--paint", action="store_true", help="time bt_atlas_paint beside bt_atlas_write_region, and bt_atlas_read_region, on an Rgba8 job")
+    ap.add_argument("--splat", action="store_true", help="time bt_atlas_splat_from_height beside bt_atlas_paint and the host loop it replaces")
     args = ap.parse_args()
     device = bt.Device(0)
+    if args.splat:
+        result = {"tool": "edit_bench --splat", "texture_size": TEXTURE_SIZE, "lod_count": LOD_COUNT, "calls_per_window": args.calls, "windows": args.repeats,
+                  "note": "device ms per call: event pair around back-to-back calls, median of the windows; host loops: wall time"}
+        splat_mode(device, args, result)
+        print(json.dumps(result), flush=True)
+        return
     if args.paint:
         result = {"tool": "edit_bench --paint", "texture_size": TEXTURE_SIZE, "lod_count": LOD_COUNT, "calls_per_window": args.calls, "windows": args.repeats,
                   "note": "device ms per call: event pair around back-to-back calls, median of the windows"}
