@@ -10,7 +10,6 @@
 #include <cmath>
 #include <cstring>
 #include <map>
-#include <tuple>
 
 #include "bt_tile_io.hpp"
 
@@ -24,11 +23,6 @@ struct Rect {
 struct Box {  // a rectangle of mosaic texels of one side
     uint32_t side;
     Rect r;
-};
-struct CoordLess {
-    bool operator()(const bt_tile_coordinate& l, const bt_tile_coordinate& r) const {
-        return std::tie(l.side, l.lod, l.x, l.y) < std::tie(r.side, r.lod, r.x, r.y);
-    }
 };
 struct Dirty {
     uint32_t layer;
@@ -374,13 +368,12 @@ bt_status run_plan(bt_atlas* a, uint32_t ai, Plan& plan, FirstStep& first) {
         for (const auto& [coord, layer] : plan.changed) layers.push_back(layer);
         std::sort(layers.begin(), layers.end());
         layers.erase(std::unique(layers.begin(), layers.end()), layers.end());
-        for (size_t i = 0; i < layers.size();) {
-            size_t run = 1;
-            while (i + run < layers.size() && layers[i + run] == layers[i] + run) run++;
+        const bt_status mips = for_each_layer_run(0, layers.size(), [&](size_t i) { return layers[i]; }, false, [&](size_t i, size_t run) -> bt_status {
             if (bt_status s = bt_atlas_generate_mipmaps(a, ai, layers[i], uint32_t(run))) return s;
             plan.stats.launches += uint32_t(at.mips.size() - 1);
-            i += run;
-        }
+            return BT_OK;
+        });
+        if (mips) return mips;
         plan.stats.layers_mipped = uint32_t(layers.size());
     }
     return BT_OK;

@@ -466,7 +466,7 @@ __device__ __forceinline__ void corner_pixels(const FusedArgs& A, uint32_t item_
 // 1-3 ran the generic rows over flagged chunks as a launch of their own, fused_todo; round 4 redid flagged chunks behind the loop — every one
 // staged a second time; both are gone.)  kGeneric == true with kStaged == false reads the source directly (window too large for LDS) and runs
 // the generic rows — per-pixel validity for every pixel — inside its loop.
-// kDma (fast staged variant, rasters 16-byte aligned — the library pads what it uploads, bt_host.cpp add_raster): the source rows of the next
+// kDma (fast staged variant, rasters 16-byte aligned — the library pads what it uploads, bt_preprocess.cpp add_raster): the source rows of the next
 // chunk travel global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers, no commit pass).
 template <bool kStaged, bool kGeneric, uint32_t kT, uint32_t kP, bool kDma = false>
 __device__ __forceinline__ void fused_main_chunks(const FusedArgs& A, uint32_t item_index, uint32_t k_begin, uint32_t k_end, uint8_t* smem) {
@@ -590,7 +590,7 @@ __device__ __forceinline__ void fused_main_chunks(const FusedArgs& A, uint32_t i
     const uint32_t chunks_per_row = P / 8u;
     const uint32_t row_texels = uint32_t(raster.pitch / 2u);  // addressable texels per source row
     // (16-byte pieces: base and pitch 16-byte aligned — a row then ends on a piece boundary and no piece straddles it.  The library pads the
-    // rasters it uploads and copies a borrowed unaligned device raster once, bt_host.cpp add_raster: the texel-by-texel staging below is left
+    // rasters it uploads and copies a borrowed unaligned device raster once, bt_preprocess.cpp add_raster: the texel-by-texel staging below is left
     // for deferred host rasters of odd width)
     const bool wide = ((reinterpret_cast<uintptr_t>(raster.data) | raster.pitch) & 15u) == 0;
     constexpr uint32_t kBatch = 4;  // 16-byte loads per thread and chunk (host guarantees slots * pitch / 8 <= 256 * kBatch)
@@ -2639,7 +2639,7 @@ static uint32_t size_main_window(const bt_preprocessor* p, const JobPlan& j, Fus
     // LDS window of a workgroup: T consecutive mosaic columns x (kMainRows + 2b) mosaic rows of the source
     double ratio_x = 0.0, ratio_y = 0.0;
     uint64_t max_pitch = 0;
-    // every raster of the job 16-byte aligned in base and pitch, as LDS-DMA needs: add_raster (bt_host.cpp) gives every R16 raster such a
+    // every raster of the job 16-byte aligned in base and pitch, as LDS-DMA needs: add_raster (bt_preprocess.cpp) gives every R16 raster such a
     // base and pitch, so this only checks that invariant; a job that breaks it takes the run-time-pitch register staging
     bool aligned = true;
     const double mosaic = double(1u << lod_hi) * double(m.center_size);

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <deque>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -22,7 +23,7 @@ namespace bt {
 
 void set_error(const char* fmt, ...);
 bt_status hip_fail(hipError_t e, const char* what);
-// kind and axes of a caller's terrain model (bt_tile_tree.hip); `who`: the entry point the refusal names
+// kind and axes of a caller's terrain model (bt_view.cpp); `who`: the entry point the refusal names
 bt_status check_model(const bt_terrain_model* m, const char* who);
 
 #define BT_HIP(expr)                                          \
@@ -49,6 +50,25 @@ struct CoordHash {
 struct CoordEq {
     bool operator()(const bt_tile_coordinate& a, const bt_tile_coordinate& b) const { return operator_eq(a, b); }
 };
+struct CoordLess {  // the (side, lod, x, y) order of every sorted tile list
+    bool operator()(const bt_tile_coordinate& l, const bt_tile_coordinate& r) const {
+        return std::tie(l.side, l.lod, l.x, l.y) < std::tie(r.side, r.lod, r.x, r.y);
+    }
+};
+
+// The runs of consecutive atlas layers among elements [begin, end) of a list, `layer(i)` being the layer of element i: fn(first, count) per
+// run, in order, until one fails.  An element continues a run when its layer is the previous element's + 1 or, with merge_duplicates (a
+// sorted list that may name a layer twice: the mip passes), the previous element's again.
+template <typename Layer, typename Fn>
+bt_status for_each_layer_run(size_t begin, size_t end, Layer layer, bool merge_duplicates, Fn fn) {
+    for (size_t i = begin; i < end;) {
+        size_t j = i + 1;
+        while (j < end && (uint64_t(layer(j)) == uint64_t(layer(j - 1)) + 1u || (merge_duplicates && layer(j) == layer(j - 1)))) j++;
+        if (bt_status s = fn(i, j - i)) return s;
+        i = j;
+    }
+    return BT_OK;
+}
 
 // ---- device-visible descriptors -------------------------------------------------------------
 
@@ -154,7 +174,7 @@ struct Raster {
 };
 
 // A device buffer, optionally with a pinned twin of the same size, that only grows and is kept until bt_ctx_trim: a per-frame caller pays
-// no allocation (bt_host.cpp)
+// no allocation (bt_ctx.cpp)
 struct Scratch {
     void* dev = nullptr;
     void* host = nullptr;
@@ -237,7 +257,6 @@ namespace bt {
 bt_status ctx_staging(bt_ctx* ctx, size_t bytes_per_buffer);  // ensures ctx->staging[*] hold at least that much
 uint32_t usable_cpus();                  // CPUs this process may use: affinity mask capped by the cgroup CPU quota
 uint32_t ctx_io_threads(const bt_ctx* ctx);  // the resolved thread count of the save / load paths
-bt_status make_dirs(const std::string& dir);  // mkdir -p
 }
 
 struct bt_atlas {
@@ -372,7 +391,7 @@ struct FusedTile {
 };
 void fused_launch_tiles(const struct ::bt_preprocessor* p, const Launch& l, uint32_t item_begin, uint32_t item_count, std::vector<FusedTile>* out);
 
-// coordinate math (bt_host.cpp)
+// coordinate math (bt_coordinate.cpp)
 // neighbour k of a tile is at (x, y) + kNeighbourOffsets[k]: N, E, S, W, NW, NE, SE, SW (coordinate.rs:209-218) == the region order of stitch.wgsl:57-66
 inline constexpr int kNeighbourOffsets[8][2] = {{0, -1}, {1, 0}, {0, 1}, {-1, 0}, {-1, -1}, {1, -1}, {1, 1}, {-1, 1}};
 void tile_children(bt_tile_coordinate c, bt_tile_coordinate out[4]);
@@ -433,24 +452,7 @@ inline uint32_t shard_holder(const ::bt_preprocessor* p, uint32_t attachment, ui
                 return piece.owner_rank;
     return atlas_index % p->shard_world;
 }
-}  // namespace bt
 
-// bt_height_bounds (the min/max height table of the culling test, declared in the header): level l starts at height_bounds_offset(sides, l)
-namespace bt {
-inline uint64_t height_bounds_offset(uint32_t sides, uint32_t level) { return uint64_t(sides) * (((1ull << (2u * level)) - 1u) / 3u); }
-constexpr uint32_t kBoundsNotHeld = 0x0000FFFFu;  // min > max: the shadow's (and bt_height_bounds_build's) word of a tile the atlas does not hold
-// What bt_height_bounds_create really allocates: the public struct first (the handle points at it), then what bt_height_bounds_update
-// needs.  shadow has the table's shape and holds own(tile) of every held tile, kBoundsNotHeld elsewhere: an entry is own united with the
-// children, so the table alone does not say what own was.  current: table and shadow describe `atlas` / `attachment` as of the last build
-// or update (bt_height_bounds_write clears it).
-struct HeightBoundsImpl {
-    bt_height_bounds pub{};
-    uint32_t* shadow = nullptr;
-    uint64_t atlas_uid = 0;  // bt_atlas::uid
-    uint32_t attachment = 0;
-    bool current = false;
-};
-inline HeightBoundsImpl* bounds_impl(bt_height_bounds* b) { return reinterpret_cast<HeightBoundsImpl*>(b); }
 // bt_edit.cpp: the records of one call (an edit's plan, a bounds update's) on their way through the context's plan ring (bt_ctx::edit_*).
 // add() the host records, each 16-byte aligned; then, optionally, device_only() bytes behind them; every offset returned is relative to
 // the device base commit() hands back.  commit(), once: reserves pinned and device bytes of the ring, copies the records (they must still
@@ -472,9 +474,7 @@ private:
     std::vector<Record> records;
     uint64_t size = 0, upload = 0;  // of all records; of those up to the last host record: what the copy moves
 };
-}  // namespace bt
 
-namespace bt {
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain
 bt_status tiling_prepass_enqueue(bt_tiling_prepass* t, const bt_view_state* view, const float* device_height, uint32_t form);

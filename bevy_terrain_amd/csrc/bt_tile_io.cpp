@@ -1,5 +1,8 @@
-// Tile files: the writer / reader threads, the download-and-write pipeline of the save path, and the time stamps of the profiling build.
+// Tile files: the writer / reader threads, the download-and-write pipeline of the save path, the two load paths (bt_atlas_load_tiles,
+// bt_atlas_update), the small file-system helpers, and the time stamps of the profiling build.
+#include <dirent.h>
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -23,6 +26,51 @@ void trace_stamp(const char* what, size_t k) {
     if (g_trace) fprintf(stderr, "[stream] %7.3f ms %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g_trace_start).count(), what, k);
 }
 #endif
+
+bt_status write_file(const std::string& path, const void* data, size_t bytes) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) {
+        set_error("cannot open %s: %s", path.c_str(), strerror(errno));
+        return BT_ERR_IO;
+    }
+    const size_t wr = fwrite(data, 1, bytes, f);
+    fclose(f);
+    if (wr != bytes) {
+        set_error("short write to %s", path.c_str());
+        return BT_ERR_IO;
+    }
+    return BT_OK;
+}
+
+void remove_tree(const std::string& dir) {
+    DIR* d = opendir(dir.c_str());
+    if (!d) return;
+    while (dirent* e = readdir(d)) {
+        if (!strcmp(e->d_name, ".") || !strcmp(e->d_name, "..")) continue;
+        const std::string p = dir + "/" + e->d_name;
+        struct stat st;
+        if (lstat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode))
+            remove_tree(p);
+        else
+            unlink(p.c_str());
+    }
+    closedir(d);
+    rmdir(dir.c_str());
+}
+
+bt_status make_dirs(const std::string& dir) {
+    std::string cur;
+    for (size_t i = 0; i <= dir.size(); i++) {
+        if (i == dir.size() || dir[i] == '/') {
+            if (!cur.empty() && mkdir(cur.c_str(), 0777) != 0 && errno != EEXIST) {
+                set_error("mkdir %s: %s", cur.c_str(), strerror(errno));
+                return BT_ERR_IO;
+            }
+        }
+        if (i < dir.size()) cur.push_back(dir[i]);
+    }
+    return BT_OK;
+}
 
 void FileWriters::run() {
     for (;;) {
@@ -140,12 +188,10 @@ bt_status TileSaver::add(uint32_t ai, const std::string& dir, Tiles tiles, bool 
         // runs of consecutive layers; equally long runs at a constant layer stride (a band of tile rows in the x-major
         // atlas order: 4 layers every 32) travel as ONE pitched copy instead of one call per run
         std::vector<std::pair<size_t, size_t>> runs;  // (first tile of the chunk, length)
-        for (size_t i = lo; i < hi;) {
-            size_t run = 1;
-            while (i + run < hi && tiles[i + run].first == tiles[i].first + run) run++;
+        for_each_layer_run(lo, hi, [&](size_t i) { return tiles[i].first; }, false, [&](size_t i, size_t run) -> bt_status {
             runs.push_back({i, run});
-            i += run;
-        }
+            return BT_OK;
+        });
         bool regular = runs.size() >= 2;
         const uint64_t stride = regular ? uint64_t(tiles[runs[1].first].first) - tiles[runs[0].first].first : 0;
         for (size_t q = 1; regular && q < runs.size(); q++)
@@ -214,3 +260,175 @@ bt_status save_tiles(bt_atlas* a, uint32_t ai, const char* directory, std::vecto
 }
 
 }  // namespace bt
+
+using namespace bt;
+
+// The tail of both load paths: these layers of attachment `ai` have been filled, in any order and possibly one of them twice; ONE batched
+// mip-chain pass per run of consecutive layers
+static bt_status mip_filled_layers(bt_atlas* a, uint32_t ai, std::vector<uint32_t>& layers) {
+    if (a->attachments[ai].mips.size() <= 1) return BT_OK;
+    std::sort(layers.begin(), layers.end());
+    return for_each_layer_run(0, layers.size(), [&](size_t i) { return layers[i]; }, true, [&](size_t i, size_t n) {
+        return bt_atlas_generate_mipmaps(a, ai, layers[i], layers[i + n - 1] - layers[i] + 1);
+    });
+}
+
+extern "C" {
+
+// AtlasTileAttachmentWithData::start_loading (tile_atlas.rs:118-149) + GpuAtlasAttachment::upload_tiles
+// (gpu_tile_atlas.rs:309-336) for a batch of tiles: "{directory}/{coord}.bin" -> atlas layer of the tile (allocated
+// on demand, like request_tile does), then ONE batched mip-chain pass per run of consecutive layers instead of the
+// reference's per-tile CPU loop.  coords == NULL: every existing tile (load_tile_config) of the atlas.
+bt_status bt_atlas_load_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {
+    if (!a || ai >= a->attachments.size() || !directory || (count && !coords)) return BT_ERR_INVALID_ARGUMENT;
+    Attachment& at = a->attachments[ai];
+    std::vector<bt_tile_coordinate> all;
+    if (!coords) {
+        for (const bt_tile_coordinate& c : a->existing_tiles) all.push_back(c);
+        std::sort(all.begin(), all.end(), CoordLess());
+        coords = all.data();
+        count = uint32_t(all.size());
+    }
+    if (!count) return BT_OK;
+    BT_HIP(hipSetDevice(a->ctx->device));
+    // files -> three pinned buffers (reader threads) -> H2D on the context's stream: chunk c + 1 is read while chunk c uploads
+    constexpr uint32_t kBuffers = bt_ctx::kStagingBuffers;
+    const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (32ull << 20) / at.tile_bytes)));
+    if (bt_status s = ctx_staging(a->ctx, std::max<size_t>(32ull << 20, at.tile_bytes))) return s;
+    void** pinned = a->ctx->staging;
+    std::vector<uint32_t> layers;
+    hipEvent_t uploaded[kBuffers] = {};
+    bool in_flight[kBuffers] = {};
+    bt_status rc = BT_OK;
+    for (uint32_t k = 0; k < kBuffers && rc == BT_OK; k++) {
+        hipError_t e = hipEventCreateWithFlags(&uploaded[k], hipEventDisableTiming);
+        if (e != hipSuccess) rc = hip_fail(e, "load events");
+    }
+    if (rc == BT_OK) {
+        FileWriters readers(ctx_io_threads(a->ctx), kBuffers);
+        const uint32_t chunks = (count + chunk - 1) / chunk;
+        std::vector<std::vector<uint32_t>> index(kBuffers);
+        auto upload = [&](uint32_t c) -> bt_status {  // chunk c has been queued for reading: wait for its files, enqueue its copies
+            const uint32_t k = c % kBuffers;
+            readers.wait_buffer(k);
+            if (bt_status s = readers.status()) return s;
+            const bt_status copies = for_each_layer_run(0, index[k].size(), [&](size_t t) { return index[k][t]; }, false, [&](size_t t, size_t run) -> bt_status {
+                a->attachments[ai].mark_written(index[k][t], uint32_t(run));  // runs of consecutive layers are one copy
+                hipError_t e = hipMemcpyAsync((uint8_t*)at.level0 + at.tile_bytes * index[k][t], (const uint8_t*)pinned[k] + at.tile_bytes * t,
+                                              at.tile_bytes * run, hipMemcpyHostToDevice, a->ctx->stream);
+                return e != hipSuccess ? hip_fail(e, "tile upload") : BT_OK;
+            });
+            if (copies) return copies;
+            hipError_t e = hipEventRecord(uploaded[k], a->ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "tile upload");
+            in_flight[k] = true;
+            return BT_OK;
+        };
+        for (uint32_t c = 0; c < chunks && rc == BT_OK; c++) {
+            const uint32_t k = c % kBuffers, first = c * chunk, n = std::min(chunk, count - first);
+            if (in_flight[k]) {  // the buffer's previous upload must have left it
+                hipError_t e = hipEventSynchronize(uploaded[k]);
+                if (e != hipSuccess) rc = hip_fail(e, "tile upload");
+                in_flight[k] = false;
+            }
+            std::vector<FileWriters::Job> jobs;
+            index[k].clear();
+            for (uint32_t t = 0; t < n && rc == BT_OK; t++) {
+                bt_atlas_tile tile;
+                rc = bt_atlas_get_or_allocate_tile(a, coords[first + t], &tile);
+                if (rc) break;
+                index[k].push_back(tile.atlas_index);
+                layers.push_back(tile.atlas_index);
+                char name[64];
+                bt_tile_name(coords[first + t], name, sizeof name);
+                FileWriters::Job job{std::string(directory) + "/" + name + ".bin", (const uint8_t*)pinned[k] + at.tile_bytes * t, size_t(at.tile_bytes), k};
+                job.read = true;
+                jobs.push_back(std::move(job));
+            }
+            if (rc == BT_OK) readers.push(std::move(jobs));
+            if (rc == BT_OK && c > 0) rc = upload(c - 1);
+        }
+        if (rc == BT_OK) rc = upload(chunks - 1);
+        for (uint32_t k = 0; k < kBuffers; k++) readers.wait_buffer(k);  // (error paths: nobody may still write into the buffers)
+        hipError_t e = hipStreamSynchronize(a->ctx->stream);  // the staging buffers belong to the context: free for the next call
+        if (rc == BT_OK && e != hipSuccess) rc = hip_fail(e, "tile upload");
+    }
+    for (uint32_t k = 0; k < kBuffers; k++)
+        if (uploaded[k]) hipEventDestroy(uploaded[k]);
+    return rc ? rc : mip_filled_layers(a, ai, layers);
+}
+
+uint32_t bt_atlas_pending_loads(const bt_atlas* a) { return a ? uint32_t(a->to_load.size()) : 0u; }
+
+// TileAtlasState::update (tile_atlas.rs:327-345: start up to load_slots loads) + AtlasAttachment::update (:195-224:
+// finished loads -> loaded_tile_attachment, data into the atlas) + GpuAtlasAttachment::upload_tiles
+// (gpu_tile_atlas.rs:309-336), done synchronously for up to `max_loads` queued entries.
+bt_status bt_atlas_update(bt_atlas* a, const char* assets_root, uint32_t max_loads, uint32_t* loaded, uint32_t* failed) {
+    if (!a || !assets_root) return BT_ERR_INVALID_ARGUMENT;
+    if (loaded) *loaded = 0;
+    if (failed) *failed = 0;
+    if (a->to_load.empty()) return BT_OK;
+    BT_HIP(hipSetDevice(a->ctx->device));
+    uint64_t largest = 0;
+    for (const Attachment& at : a->attachments) largest = std::max(largest, at.tile_bytes);
+    const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (32ull << 20) / std::max<uint64_t>(largest, 1))));
+    if (bt_status s = ctx_staging(a->ctx, std::max<size_t>(32ull << 20, largest))) return s;
+    void* pinned = a->ctx->staging[0];
+    std::vector<std::vector<uint32_t>> mip_layers(a->attachments.size());
+    uint32_t budget = max_loads ? max_loads : 0xFFFFFFFFu, done = 0, bad = 0;
+    bt_status rc = BT_OK;
+    while (!a->to_load.empty() && budget && rc == BT_OK) {
+        std::vector<AtlasTileAttachment> batch;
+        while (!a->to_load.empty() && budget && batch.size() < chunk) {
+            batch.push_back(a->to_load.front());
+            a->to_load.pop_front();
+            budget--;
+        }
+        std::vector<bool> ok(batch.size(), false);
+        for (size_t k = 0; k < batch.size(); k++) {
+            const AtlasTileAttachment& t = batch[k];
+            const Attachment& at = a->attachments[t.attachment_index];
+            char name[64];
+            bt_tile_name(t.coordinate, name, sizeof name);
+            const std::string path = std::string(assets_root) + "/" + a->config.path + "/data/" + at.cfg.name + "/" + name + ".bin";
+            FILE* f = fopen(path.c_str(), "rb");
+            if (!f) continue;  // the reference returns the load slot and leaves the tile Loading (:202-204)
+            const size_t got = fread((uint8_t*)pinned + largest * k, 1, at.tile_bytes, f);
+            const bool longer = got == at.tile_bytes && fgetc(f) != EOF;
+            fclose(f);
+            ok[k] = got == at.tile_bytes && !longer;
+        }
+        for (size_t k = 0; k < batch.size() && rc == BT_OK; k++) {
+            if (!ok[k]) {
+                bad++;
+                continue;
+            }
+            const AtlasTileAttachment& t = batch[k];
+            Attachment& at = a->attachments[t.attachment_index];
+            at.mark_written(t.atlas_index, 1);
+            hipError_t e = hipMemcpyAsync((uint8_t*)at.level0 + at.tile_bytes * t.atlas_index, (const uint8_t*)pinned + largest * k, at.tile_bytes,
+                                          hipMemcpyHostToDevice, a->ctx->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "tile upload");
+        }
+        if (rc == BT_OK) {
+            hipError_t e = hipStreamSynchronize(a->ctx->stream);  // the pinned buffer is refilled next
+            if (e != hipSuccess) rc = hip_fail(e, "tile upload");
+        }
+        for (size_t k = 0; k < batch.size() && rc == BT_OK; k++) {
+            if (!ok[k]) continue;
+            const AtlasTileAttachment& t = batch[k];
+            // loaded_tile_attachment (:347-359); a slot that was reused for another tile meanwhile is ignored
+            auto it = a->tile_states.find(t.coordinate);
+            if (it == a->tile_states.end() || it->second.atlas_index != t.atlas_index || it->second.loading == 0) continue;
+            if (--it->second.loading == 0) a->state_version++;
+            mip_layers[t.attachment_index].push_back(t.atlas_index);
+            done++;
+        }
+    }
+    for (uint32_t ai = 0; ai < a->attachments.size() && rc == BT_OK; ai++) rc = mip_filled_layers(a, ai, mip_layers[ai]);
+    if (loaded) *loaded = done;
+    if (failed) *failed = bad;
+    return rc;
+}
+
+}  // extern "C"

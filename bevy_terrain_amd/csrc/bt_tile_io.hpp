@@ -1,4 +1,5 @@
-// Tile files (bt_tile_io.cpp): shared by the save path, the load path (bt_host.cpp) and the streamed run (bt_stream.cpp).
+// Tile files (bt_tile_io.cpp, which also holds the load paths): the writer / reader threads and the saver, shared by the save path, the
+// load paths and the streamed run (bt_stream.cpp), and the file-system helpers of whoever writes beside the tiles.
 #pragma once
 
 #include <condition_variable>
@@ -104,5 +105,9 @@ class TileSaver {
 };
 
 bt_status save_tiles(bt_atlas* a, uint32_t ai, const char* directory, TileSaver::Tiles tiles);
+
+bt_status make_dirs(const std::string& dir);  // mkdir -p
+bt_status write_file(const std::string& path, const void* data, size_t bytes);
+void remove_tree(const std::string& dir);  // rm -r; a directory that does not exist is fine
 
 }  // namespace bt

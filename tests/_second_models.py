@@ -1,5 +1,5 @@
 """Second, independent models of the parts of the contract the reference expresses in RUST (no executable counterpart here):
-written from the reference text a second time, in another shape than bt_host.cpp / bt_oracle*.c — closed forms and whole-table
+written from the reference text a second time, in another shape than the library's host code / bt_oracle*.c — closed forms and whole-table
 numpy array operations instead of replayed pushes and per-node loops — so that a misreading shared by the product and the oracle
 (same author, same reading) does not pass unnoticed.  Nothing here imports the oracle or the product.
 

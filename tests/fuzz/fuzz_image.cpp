@@ -13,7 +13,7 @@
 
 #include "bevy_terrain_amd.h"
 
-// the two library-internal symbols bt_image.cpp needs (defined in bt_host.cpp in the product)
+// the two library-internal symbols bt_image.cpp needs (defined in bt_ctx.cpp in the product)
 #include <hip/hip_runtime_api.h>
 namespace bt {
 void set_error(const char*, ...) {}

@@ -277,6 +277,56 @@ def test_tile_load_path_round_trip(device, tmp_path, fmt):
         assert "does not hold" in str(e.value), str(e.value)
 
 
+@pytest.mark.parametrize("path", ["load_tiles", "request_update"])
+def test_loaded_layers_in_several_runs_get_their_mips(device, tmp_path, path):
+    """Both load paths end in one mip pass per run of consecutive layers.  Five tiles on layers 0, 2, 3, 5 and 7 of an 8-layer atlas (the
+    layers between belong to tiles without a file), listed or queued out of layer order and one of them twice: four runs.  Every mip
+    level of every loaded layer equals the one on a second atlas that got the same bytes through upload_tile and ONE generate_mipmaps
+    over the whole range."""
+    T, b, mips = 16, 2, 3
+    cfg = bt.TerrainConfig(lod_count=3, atlas_size=8, path="terrains/runs", model=bt.TerrainModel.planar((0, 0, 0), 1000.0, 0.0, 1.0))
+    cfg.add_attachment(bt.AttachmentConfig(name="h", texture_size=T, border_size=b, format=bt.AttachmentFormat.R16, mip_level_count=mips))
+    tile = lambda lod, x, y: bt.TileCoordinate(0, lod, x, y)
+    slots = [tile(2, 0, 0), tile(2, 3, 3), tile(1, 1, 0), tile(2, 1, 2), tile(1, 0, 1), tile(0, 0, 0), tile(2, 2, 2), tile(2, 0, 3)]  # layer = position
+    filled = [0, 2, 3, 5, 7]
+    listed = [slots[i] for i in (5, 0, 7, 2, 0, 3)]  # neither layer nor coordinate order; layer 0's tile twice
+    rng = np.random.default_rng(5)
+    data = {i: rng.integers(1, 65536, size=(T, T), dtype=np.uint16) for i in filled}
+    root = str(tmp_path / "assets")
+    expected = bt.TileAtlas.new(cfg, device)
+    assert [expected.get_or_allocate_tile(c)[1] for c in slots] == list(range(8))
+    directory = expected.attachment_directory(root, 0)
+    os.makedirs(directory)
+    for i in filled:
+        expected.upload_tile(0, i, data[i])
+        data[i].tofile(os.path.join(directory, "%d_%d_%d_%d.bin" % (slots[i].side, slots[i].lod, slots[i].x, slots[i].y)))
+    expected.generate_mipmaps(0)
+    expected.save_tile_config(root)
+    atlas = bt.TileAtlas.new(cfg, device)
+    if path == "load_tiles":
+        assert [atlas.get_or_allocate_tile(c)[1] for c in slots] == list(range(8))
+        atlas.load_tiles(0, root, listed)
+    else:
+        # request_tile takes the slot at the front of the LRU: eight placeholder tiles, released in the order the requests below need,
+        # leave the free slots as 5, 0, 7, 2, 3, 1, 4, 6, so the load queue names the layers out of order too
+        order = [5, 0, 7, 2, 3, 1, 4, 6]
+        held = [tile(3, k, 7) for k in range(8)]
+        assert [atlas.get_or_allocate_tile(c)[1] for c in held] == list(range(8))
+        for i in order:
+            atlas.release_tile(held[i])
+        atlas.load_tile_config(root)  # the tiles exist, without a layer
+        for i in (5, 0, 7, 2, 0, 3, 1, 4, 6):  # `listed` (a second request queues nothing), then the three tiles without a file
+            atlas.request_tile(slots[i])
+        assert atlas.pending_loads() == 8
+        assert atlas.update(root) == (5, 3)  # the three tiles without a file stay Loading
+    assert {(c.side, c.lod, c.x, c.y): i for c, i in atlas.tiles() if c.lod < 3} == {(c.side, c.lod, c.x, c.y): i for i, c in enumerate(slots)}
+    for i in filled:
+        assert np.array_equal(atlas.download_tile(0, i), data[i]), i
+        for mip in range(1, mips):
+            want = expected.download_mip(0, mip, i)
+            assert want.any() and np.array_equal(atlas.download_mip(0, mip, i), want), (i, mip)
+
+
 @pytest.mark.parametrize("T,b,W", [(512, 4, 2100), (512, 8, 1900), (256, 2, 1100), (384, 6, 1500)])
 def test_fused_path_other_borders_and_sizes(device, T, b, W):
     # wider aprons / other texture sizes through the fused kernels (runtime-shape template instance for T != 512 or b != 2)

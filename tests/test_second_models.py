@@ -1,5 +1,5 @@
 """The second models of the Rust-side contract (tests/_second_models.py: closed forms / whole-table numpy, written from the reference
-text independently of bt_host.cpp and the oracle) against the ORACLE, on the CPU.  tests/test_gpu_second_models.py holds the same
+text independently of the library's host code and the oracle) against the ORACLE, on the CPU.  tests/test_gpu_second_models.py holds the same
 comparisons against the product."""
 import numpy as np
 import pytest
