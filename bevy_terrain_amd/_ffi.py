@@ -158,6 +158,17 @@ class RenderStatsC(C.Structure):
     _fields_ = [("launches", C.c_uint32), ("hit_pixels", C.c_uint32), ("inside_pixels", C.c_uint32), ("miss_pixels", C.c_uint32)]
 
 
+OCCLUSION_MAX_RAYS, SHADOW_NONE = 1 << 24, 255
+
+
+class OcclusionStatsC(C.Structure):
+    _fields_ = [("launches", C.c_uint32), ("lit", C.c_uint32), ("occluded", C.c_uint32), ("invalid", C.c_uint32)]
+
+
+class SunShadowC(C.Structure):
+    _fields_ = [("lift", C.c_double), ("distance", C.c_double), ("steps", C.c_uint32), ("_padding", C.c_uint32)]
+
+
 GEOMETRY_GRID, GEOMETRY_NO_MORPH, GEOMETRY_NO_BLEND = 1, 2, 4
 GEOMETRY_MAX_GRID = 32
 GEOMETRY_VIEW_RELATIVE = 8  # the _hp calls only
@@ -362,6 +373,10 @@ PROTOTYPES = {
     "bt_tile_tree_view_state": (_i32, [_vp, _P(ViewStateC)]),
     "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
     "bt_tile_tree_render": (_i32, [_vp, _vp, _u32, _P(RenderCameraC), _u32, _u32, _P(C.c_double), _P(C.c_uint8), _P(C.c_float), _P(C.c_uint8), _P(RenderStatsC)]),
+    "bt_tile_tree_sun_occlusion": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_double), _u32, C.c_double, C.c_double, _u32, _P(C.c_uint8),
+                                          _P(OcclusionStatsC)]),
+    "bt_tile_tree_render_shadowed": (_i32, [_vp, _vp, _u32, _P(RenderCameraC), _u32, _u32, _P(SunShadowC), _P(C.c_double), _P(C.c_uint8), _P(C.c_float),
+                                            _P(C.c_uint8), _P(C.c_uint8), _P(RenderStatsC)]),
     "bt_tile_tree_sample_normal": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_float), _P(C.c_float)]),
     "bt_atlas_tile_normals": (_i32, [_vp, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(C.c_uint8), _u64]),
     "bt_tile_tree_build_geometry": (_i32, [_vp, _vp, _u32, _P(ViewStateC), _vp, _u32, _vp, _u64]),

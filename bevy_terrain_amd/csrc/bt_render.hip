@@ -10,6 +10,11 @@
 // nothing crosses lanes until the pixel counters at the very end, which every lane of the wave reaches: lanes of pixels outside the
 // image, of finished rays and of INVALID rays skip the work, never the ballots.  The hit's value and height come from the evaluation that
 // found it.  Shading and the stores of the planes the caller asked for happen in the same launch.
+//
+// kShadow (bt_tile_tree_render_shadowed): a pixel that met the ground also marches its shadow ray, SUN OCCLUSION at p(t) towards the
+// camera's sun (occlusion_status of bt_raycast_device.hpp, the function bt_tile_tree_sun_occlusion runs), in the same lane and before the
+// colour is made; the march is left out where nothing could show its result (no shadow plane, and no colour plane, no lighting or a
+// surface that faces away from the sun).  The false instance is bt_tile_tree_render's kernel as it was: it reads no shadow field.
 #include "bt_normal_device.hpp"
 #include "bt_raycast_device.hpp"
 
@@ -21,6 +26,7 @@ namespace {
 
 // (enc8 of the colour plane: bt_normal_device.hpp, shared with the splat kernel of bt_splat.hip)
 
+template <bool kShadow>
 __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                 const void* __restrict__ atlas, AttachmentMeta albedo_meta, const void* __restrict__ albedo,
                                                                 NormalModel nm, RenderArgs a, const float* __restrict__ height) {
@@ -108,6 +114,17 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
             float cosine;
             n = world_normal(P, entries, m, (const uint16_t*)atlas, nm, p, approximate_height, cosine);
         }
+        // SHADOW PLANE
+        bool occluded = false;
+        if constexpr (kShadow) {
+            uint32_t shadow = BT_SHADOW_NONE;
+            if (hit && (a.shadow_plane || (a.rgba && lighting && dot3f(n, {cam.sun[0], cam.sun[1], cam.sun[2]}) > 0.0f))) {
+                shadow = occlusion_status(P, entries, m, atlas, p, {double(cam.sun[0]), double(cam.sun[1]), double(cam.sun[2])}, a.shadow.lift, a.shadow.distance,
+                                          a.shadow.steps, double(approximate_height), skip_above, ceiling);
+                occluded = shadow == BT_RAY_HIT || shadow == BT_RAY_INSIDE;
+            }
+            if (a.shadow_plane) a.shadow_plane[pixel] = uint8_t(shadow);
+        }
         if (a.t) a.t[pixel] = t;
         if (a.status) a.status[pixel] = uint8_t(status);
         if (a.normal) {
@@ -129,7 +146,13 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
                 if (lighting) {  // a plain Lambert term
                     const float d = dot3f(n, {cam.sun[0], cam.sun[1], cam.sun[2]});
                     const float l = d > 0.0f ? d : 0.0f;
-                    const float k = cam.ambient + (1.0f - cam.ambient) * l;
+                    float k;
+                    if constexpr (kShadow) {
+                        const float sh = occluded ? 0.0f : 1.0f;
+                        k = cam.ambient + (1.0f - cam.ambient) * (l * sh);
+                    } else {
+                        k = cam.ambient + (1.0f - cam.ambient) * l;
+                    }
                     for (int c = 0; c < 3; c++) base[c] = base[c] * k;
                 }
                 texel = enc8(base[0]) | (enc8(base[1]) << 8) | (enc8(base[2]) << 16) | (enc8(base[3]) << 24);
@@ -152,10 +175,14 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
 }  // namespace
 
 bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height) {
+                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height, bool shadowed) {
     if (!a.block_count) return BT_OK;
     const NormalModel nm = {P.model.min_height, P.model.max_height, normal_side_length(P.model)};
-    render_kernel<<<(a.block_count + kRenderBlocksPerGroup - 1u) / kRenderBlocksPerGroup, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
+    const uint32_t groups = (a.block_count + kRenderBlocksPerGroup - 1u) / kRenderBlocksPerGroup;
+    if (shadowed)
+        render_kernel<true><<<groups, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
+    else
+        render_kernel<false><<<groups, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "render_kernel");
 }

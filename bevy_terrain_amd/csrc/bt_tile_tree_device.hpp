@@ -1,6 +1,7 @@
 // Device half of sample_attachment / sample_height (terrain_data/mod.rs:265-307) shared by the kernels that sample the
-// terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip), raycast_kernel (bt_raycast.hip), render_kernel (bt_render.hip).  One
-// definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there, bit for bit.
+// terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip), raycast_kernel (bt_raycast.hip), render_kernel (bt_render.hip),
+// occlusion_kernel (bt_shadow.hip).  One definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there,
+// bit for bit.
 //
 // Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
 // where the reference defers to glam / libm.  compute_blend's log2 is the platform's (OCML here, libm in the oracle).
@@ -43,10 +44,30 @@ struct RenderArgs {
     float* normal;
     uint32_t* rgba;
     uint32_t* counters;
+    // bt_tile_tree_render_shadowed only (read by the kernel's shadowed instance alone): the SHADOW PLANE (device, may be NULL) and its march
+    uint8_t* shadow_plane;
+    bt_sun_shadow shadow;
 };
-// albedo == NULL: the grey of the height attachment (BT_RENDER_NO_ALBEDO); height as above
+// albedo == NULL: the grey of the height attachment (BT_RENDER_NO_ALBEDO); height as above.  shadowed: the kernel instance that casts a
+// shadow ray from every pixel that met the ground (bt_tile_tree_render_shadowed); false: bt_tile_tree_render's, which reads no shadow field
 bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height);
+                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height, bool shadowed);
+
+// bt_shadow.hip: one launch of bt_tile_tree_sun_occlusion.  Ray g = first_ray + r of the batch is point g % count, direction g / count; its
+// status goes to status[point * direction_count + direction].  A lane marches one ray, a workgroup kOcclusionThreads of them.
+constexpr uint32_t kOcclusionThreads = 256;
+struct OcclusionArgs {
+    const double* positions;   // count x 3 (device)
+    const double* directions;  // direction_count x 3 (device)
+    uint32_t count, direction_count;
+    uint32_t first_ray, ray_count;
+    double lift, distance;
+    uint32_t steps;
+    uint8_t* status;     // count * direction_count (device), point-major
+    uint32_t* counters;  // lit, occluded, invalid
+};
+bt_status launch_occlusion(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                           const OcclusionArgs& a, const float* height);
 
 // bt_geometry.hip: what TERRAIN GEOMETRY (include/bevy_terrain_amd.h) takes from the tree besides its entries
 struct GeometryParams {

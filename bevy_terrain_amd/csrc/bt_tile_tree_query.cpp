@@ -1,6 +1,7 @@
-// The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_render, bt_tile_tree_sample_normal and the
-// geometry calls.  Each validates, stages its inputs in scratch of the context (bt::Scratch: grown on demand, kept until bt_ctx_trim),
-// calls the launcher of its kernel file (bt_raycast.hip, bt_render.hip, bt_normal.hip, bt_geometry.hip) and copies the results back.
+// The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_sun_occlusion, bt_tile_tree_render(_shadowed),
+// bt_tile_tree_sample_normal and the geometry calls.  Each validates, stages its inputs in scratch of the context (bt::Scratch: grown on
+// demand, kept until bt_ctx_trim), calls the launcher of its kernel file (bt_raycast.hip, bt_shadow.hip, bt_render.hip, bt_normal.hip,
+// bt_geometry.hip) and copies the results back.
 #include <cmath>
 
 #include "bt_tile_tree_host.hpp"
@@ -82,15 +83,16 @@ bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const 
     return BT_OK;
 }
 
-bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
-                              uint8_t* out_status, float* out_normal, uint8_t* out_rgba, bt_render_stats* stats) {
-    const char* who = "bt_tile_tree_render";
-    if (t && a && !camera) {  // (refused before two contexts are)
-        set_error("%s: NULL camera", who);
+namespace {
+// bt_tile_tree_render (shadowed false: shadow and out_shadow NULL) and bt_tile_tree_render_shadowed
+bt_status render(const char* who, bool shadowed, bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds,
+                 const bt_sun_shadow* shadow, double* out_t, uint8_t* out_status, float* out_normal, uint8_t* out_rgba, uint8_t* out_shadow, bt_render_stats* stats) {
+    if (t && a && (!camera || (shadowed && !shadow))) {  // (refused before two contexts are)
+        set_error("%s: NULL %s", who, camera ? "shadow" : "camera");
         return BT_ERR_INVALID_ARGUMENT;
     }
     if (bt_status st = query_handles(who, t, a)) return st;
-    if (!out_t && !out_status && !out_normal && !out_rgba) {
+    if (!out_t && !out_status && !out_normal && !out_rgba && !out_shadow) {
         set_error("%s: every plane is NULL", who);
         return BT_ERR_INVALID_ARGUMENT;
     }
@@ -102,6 +104,11 @@ bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const b
     }
     if (steps < 1u || steps > uint32_t(BT_RENDER_MAX_STEPS) || refine_rounds > uint32_t(BT_RAYCAST_MAX_REFINE_ROUNDS)) {
         set_error("%s: steps %u (1 .. %u) / refine_rounds %u (at most %u)", who, steps, unsigned(BT_RENDER_MAX_STEPS), refine_rounds, unsigned(BT_RAYCAST_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (shadowed && (shadow->steps < 1u || shadow->steps > uint32_t(BT_RENDER_MAX_STEPS) || !std::isfinite(shadow->lift))) {
+        // (a non-finite or negative distance is no error: those shadow rays are BT_RAY_INVALID)
+        set_error("%s: shadow steps %u (1 .. %u) / lift %g (finite)", who, shadow->steps, unsigned(BT_RENDER_MAX_STEPS), shadow->lift);
         return BT_ERR_INVALID_ARGUMENT;
     }
     const bool has_albedo = cam.albedo_attachment != BT_RENDER_NO_ALBEDO;
@@ -129,10 +136,10 @@ bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const b
     bt_ctx* ctx = t->ctx;
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary
+    // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary (the shadow plane last)
     auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
     const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad(12u * pixels) : 0u),
-                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), need = s_off + (out_status ? pad(pixels) : 0u);
+                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), o_off = s_off + (out_status ? pad(pixels) : 0u), need = o_off + (out_shadow ? pad(pixels) : 0u);
     if (bt_status st = ctx->render.reserve(ctx, need)) return st;
     uint8_t* dev = (uint8_t*)ctx->render.dev;
     RenderArgs args{};
@@ -145,10 +152,12 @@ bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const b
     args.normal = out_normal ? (float*)(dev + n_off) : nullptr;
     args.rgba = out_rgba ? (uint32_t*)(dev + c_off) : nullptr;
     args.status = out_status ? dev + s_off : nullptr;
-    // a launch: whole 8 x 8 blocks whose worst case stays within BT_RAYCAST_MAX_SAMPLES (at least one fits: 64 * 4349 samples at most), cut to
-    // whole 8-row bands when it holds one
+    args.shadow_plane = out_shadow ? dev + o_off : nullptr;
+    if (shadowed) args.shadow = *shadow;
+    // a launch: whole 8 x 8 blocks whose worst case (with the shadow ray's steps + 1 samples in the shadowed form) stays within
+    // BT_RAYCAST_MAX_SAMPLES (at least one fits: 64 * (4349 + 4097) samples at most), cut to whole 8-row bands when it holds one
     const uint32_t blocks = args.blocks_x * ((cam.height + 7u) / 8u);
-    const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds);
+    const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds + (shadowed ? uint64_t(shadow->steps) + 1u : 0u));
     uint32_t per_launch = uint32_t(std::min<uint64_t>(blocks, uint64_t(BT_RAYCAST_MAX_SAMPLES) / block_samples));
     if (per_launch >= args.blocks_x) per_launch -= per_launch % args.blocks_x;
     BT_HIP(hipMemsetAsync(dev, 0, 16, s));
@@ -158,7 +167,7 @@ bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const b
         args.first_block = first;
         args.block_count = std::min(per_launch, blocks - first);
         // a read of the atlas: level0 is passed on without marking any layer written
-        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height)) {
+        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height, shadowed)) {
             (void)hipStreamSynchronize(s);
             return st;
         }
@@ -170,11 +179,93 @@ bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const b
     if (e == hipSuccess && out_status) e = hipMemcpyAsync(out_status, args.status, pixels, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, args.normal, 12u * pixels, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && out_rgba) e = hipMemcpyAsync(out_rgba, args.rgba, 4u * pixels, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_shadow) e = hipMemcpyAsync(out_shadow, args.shadow_plane, pixels, hipMemcpyDeviceToHost, s);
     const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
     if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
     synchronised(t);
     if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
     return BT_OK;
+}
+}  // namespace
+
+bt_status bt_tile_tree_sun_occlusion(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const double* positions, uint32_t count, const double* directions,
+                                     uint32_t direction_count, double lift, double distance, uint32_t steps, uint8_t* out_status, bt_occlusion_stats* stats) {
+    const char* who = "bt_tile_tree_sun_occlusion";
+    const Attachment* height;
+    if (bt_status s = query_check(who, t, a, ai, &height)) return s;
+    const Attachment& at = *height;
+    if (steps < 1u || steps > uint32_t(BT_RENDER_MAX_STEPS) || !std::isfinite(lift)) {
+        // (a non-finite or negative distance is no error: those rays are BT_RAY_INVALID)
+        set_error("%s: steps %u (1 .. %u) / lift %g (finite)", who, steps, unsigned(BT_RENDER_MAX_STEPS), lift);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t rays = uint64_t(count) * direction_count;
+    if (rays > uint64_t(BT_OCCLUSION_MAX_RAYS)) {
+        set_error("%s: %u points x %u directions exceed BT_OCCLUSION_MAX_RAYS (%u): split the batch", who, count, direction_count, unsigned(BT_OCCLUSION_MAX_RAYS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!rays) {
+        if (stats) *stats = {};
+        return BT_OK;
+    }
+    if (!positions || !directions || !out_status) {
+        set_error("%s: NULL %s", who, !positions ? "world_positions_xyz" : (directions ? "out_status" : "directions_xyz"));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the scratch (the ray queries': bt_ctx::raycast): the counters, the points, the directions, the statuses, each from a 256-byte boundary
+    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
+    const uint64_t p_bytes = 24ull * count, d_bytes = 24ull * direction_count, p_off = 256u, d_off = p_off + pad(p_bytes), s_off = d_off + pad(d_bytes);
+    if (bt_status st = ctx->raycast.reserve(ctx, s_off + pad(rays))) return st;
+    uint8_t* dev = (uint8_t*)ctx->raycast.dev;
+    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
+    BT_HIP(hipMemcpyAsync(dev + p_off, positions, p_bytes, hipMemcpyHostToDevice, s));
+    BT_HIP(hipMemcpyAsync(dev + d_off, directions, d_bytes, hipMemcpyHostToDevice, s));
+    OcclusionArgs args{};
+    args.positions = (const double*)(dev + p_off);
+    args.directions = (const double*)(dev + d_off);
+    args.count = count;
+    args.direction_count = direction_count;
+    args.lift = lift;
+    args.distance = distance;
+    args.steps = steps;
+    args.status = dev + s_off;
+    args.counters = (uint32_t*)dev;
+    // a launch: whole waves whose worst case, 64 * (steps + 1) samples each, stays within BT_RAYCAST_MAX_SAMPLES (63 waves at 4096 steps)
+    const uint32_t per_launch = 64u * uint32_t(uint64_t(BT_RAYCAST_MAX_SAMPLES) / (64ull * (uint64_t(steps) + 1u)));
+    const TreeParams P = make_params(t);
+    uint32_t launches = 0;
+    for (uint64_t first = 0; first < rays; first += per_launch, launches++) {
+        args.first_ray = uint32_t(first);
+        args.ray_count = uint32_t(std::min<uint64_t>(per_launch, rays - first));
+        // a read of the atlas: at.level0 is passed on without marking any layer written
+        if (bt_status st = launch_occlusion(s, P, t->d_entries, at.meta, at.level0, args, t->d_height)) {
+            (void)hipStreamSynchronize(s);
+            return st;
+        }
+    }
+    // nothing is copied back before the last launch has been queued
+    uint32_t counters[4] = {};
+    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_status, args.status, rays, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
+    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
+    synchronised(t);
+    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
+    return BT_OK;
+}
+
+bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
+                              uint8_t* out_status, float* out_normal, uint8_t* out_rgba, bt_render_stats* stats) {
+    return render("bt_tile_tree_render", false, t, a, ai, camera, steps, refine_rounds, nullptr, out_t, out_status, out_normal, out_rgba, nullptr, stats);
+}
+
+bt_status bt_tile_tree_render_shadowed(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds,
+                                       const bt_sun_shadow* shadow, double* out_t, uint8_t* out_status, float* out_normal, uint8_t* out_rgba, uint8_t* out_shadow,
+                                       bt_render_stats* stats) {
+    return render("bt_tile_tree_render_shadowed", true, t, a, ai, camera, steps, refine_rounds, shadow, out_t, out_status, out_normal, out_rgba, out_shadow, stats);
 }
 
 bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const double* positions, uint32_t count, float* normals, float* up_dot) {

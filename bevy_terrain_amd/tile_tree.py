@@ -257,6 +257,44 @@ class TileTree:
         out["stats"] = {name: getattr(stats, name) for name, _ in _ffi.RenderStatsC._fields_}
         return out
 
+    def sun_occlusion(self, attachment_index: int, positions, directions, lift: float, distance: float, steps: int = 64):
+        """bt_tile_tree_sun_occlusion: "is this point in the sun, for this direction towards it?" for every pair of positions (n, 3) and
+        directions (k, 3) or (3,), the directions used as given (distance is in units of their length).  A point's shadow ray starts
+        `lift` above it along the terrain's up direction there and is marched like raycast()'s at `steps` steps, no refinement.  Returns
+        ((n, k) uint8 statuses, stats): _ffi.RAY_MISS is lit, RAY_HIT and RAY_INSIDE are occluded, RAY_INVALID a point or direction that
+        cannot be marched; stats holds launches, lit, occluded, invalid.  A point raycast() or render() reported lies at or under the
+        ground: give it a lift larger than that march's residual."""
+        positions = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        directions = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        n, k = len(positions), len(directions)
+        status = np.zeros((n, k), np.uint8)
+        stats = _ffi.OcclusionStatsC()
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _ffi.check(_ffi.lib().bt_tile_tree_sun_occlusion(self._h, self.atlas._h, attachment_index, as_doubles(positions), n, as_doubles(directions), k, lift,
+                                                         distance, steps, status.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(stats)))
+        return status, {name: getattr(stats, name) for name, _ in _ffi.OcclusionStatsC._fields_}
+
+    def render_shadowed(self, camera: RenderCamera, lift: float, distance: float, shadow_steps: int = 64, steps: int = 256, refine_rounds: int = 2,
+                        planes=("t", "status", "normal", "rgba", "shadow"), attachment_index: int = 0):
+        """bt_tile_tree_render_shadowed: render() with cast shadows.  A pixel that met the ground casts a shadow ray towards camera.sun
+        (sun_occlusion's, with this lift, distance and shadow_steps); with camera.lighting an occluded pixel keeps only the ambient
+        light.  The extra plane "shadow" (height, width) uint8 holds the shadow ray's status (_ffi.RAY_*), _ffi.SHADOW_NONE where the
+        pixel met nothing; the other planes and "stats" are render()'s."""
+        unknown = set(planes) - {"t", "status", "normal", "rgba", "shadow"}
+        if unknown:
+            raise ValueError(f"unknown planes {sorted(unknown)}")
+        w, h = camera.width, camera.height
+        shapes = {"t": ((h, w), np.float64, C.c_double), "status": ((h, w), np.uint8, C.c_uint8), "normal": ((h, w, 3), np.float32, C.c_float),
+                  "rgba": ((h, w, 4), np.uint8, C.c_uint8), "shadow": ((h, w), np.uint8, C.c_uint8)}
+        out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in shapes if name in planes}
+        ptr = lambda name: out[name].ctypes.data_as(C.POINTER(shapes[name][2])) if name in out else None
+        stats = _ffi.RenderStatsC()
+        shadow = _ffi.SunShadowC(lift, distance, shadow_steps, 0)
+        _ffi.check(_ffi.lib().bt_tile_tree_render_shadowed(self._h, self.atlas._h, attachment_index, C.byref(camera.c()), steps, refine_rounds, C.byref(shadow),
+                                                           ptr("t"), ptr("status"), ptr("normal"), ptr("rgba"), ptr("shadow"), C.byref(stats)))
+        out["stats"] = {name: getattr(stats, name) for name, _ in _ffi.RenderStatsC._fields_}
+        return out
+
     def vertices_per_tile(self, grid: bool = False) -> int:
         """slots a tile takes in either geometry layout: the strip's 2 g (g + 2) (bt_view_state.vertices_per_tile) or the grid's (g + 1)^2"""
         g = self.view_config.grid_size

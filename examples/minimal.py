@@ -5,9 +5,11 @@ atlas streams the requested tiles from `data/height/*.bin` (mip chains built on 
 the tiling prepass (refine_tiles) that leaves the final tile list and the indirect draw arguments in HBM for whatever draws the terrain.
 The debug camera of the reference is replaced by a scripted fly-over.
 
-    python examples/preprocess_planar.py && python examples/minimal.py [--assets DIR] [--frames 120] [--render FILE.ppm]
+    python examples/preprocess_planar.py && python examples/minimal.py [--assets DIR] [--frames 120] [--render FILE.ppm [--shadows] [--sun X Y Z]]
 
---render writes what the last frame's camera sees, ray-cast on the GPU (TileTree.render), as a binary PPM.
+--render writes what the last frame's camera sees, ray-cast on the GPU (TileTree.render), as a binary PPM; with --shadows the picture has
+cast shadows (TileTree.render_shadowed: a pixel whose shadow ray towards the sun meets the terrain keeps only the ambient light); a
+low sun (--sun 0.75 0.3 0.6) makes them long.
 """
 import argparse
 import math
@@ -17,6 +19,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bevy_terrain_amd as bt  # noqa: E402
+from bevy_terrain_amd import _ffi  # noqa: E402
 from bevy_terrain_amd import (AttachmentConfig, AttachmentFormat, TerrainConfig, TerrainModel, TerrainViewConfig, TileAtlas, TileTree,  # noqa: E402
                               TilingPrepass, sample_height)
 
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--assets", default="assets")
     ap.add_argument("--frames", type=int, default=120)
     ap.add_argument("--render", metavar="FILE.ppm", help="write the last frame's view, ray-cast on the GPU, as a binary PPM")
+    ap.add_argument("--shadows", action="store_true", help="with --render: cast sun shadows (off by default)")
+    ap.add_argument("--sun", type=float, nargs=3, default=(0.4, 0.8, 0.45), metavar=("X", "Y", "Z"), help="with --render: the direction towards the sun")
     args = ap.parse_args()
     if not os.path.exists(os.path.join(args.assets, PATH, "config.tc")):
         sys.exit(f"{args.assets}/{PATH}/config.tc not found: run examples/preprocess_planar.py first")
@@ -75,8 +80,15 @@ def main():
     if args.render:
         # the picture of the last frame: from the view position towards the middle of the terrain, lit by a plain Lambert term
         camera = bt.RenderCamera.perspective(view_position, (-math.cos(phi), -0.35, -math.sin(phi)), (0.0, 1.0, 0.0), math.radians(60.0), 640, 360, 0.0, 2.0 * TERRAIN_SIZE,
-                                             lighting=True, sun=(0.4, 0.8, 0.45), ambient=0.3, background=(120, 170, 230, 255))
-        image = tile_tree.render(camera, steps=512, refine_rounds=2, planes=("rgba",))
+                                             lighting=True, sun=tuple(args.sun), ambient=0.3, background=(120, 170, 230, 255))
+        if args.shadows:
+            # a shadow ray from every pixel that met the ground: lifted 0.5 (the march above leaves a hit within 2000 / 512 / 64^2 of the
+            # ground), marched 192 steps towards the sun over the terrain's width
+            image = tile_tree.render_shadowed(camera, 0.5, TERRAIN_SIZE, 192, steps=512, refine_rounds=2, planes=("rgba", "shadow"))
+            occluded = int(((image["shadow"] == _ffi.RAY_HIT) | (image["shadow"] == _ffi.RAY_INSIDE)).sum())
+            print(f"sun shadows: {occluded} of {image['stats']['hit_pixels'] + image['stats']['inside_pixels']} ground pixels are in shadow")
+        else:
+            image = tile_tree.render(camera, steps=512, refine_rounds=2, planes=("rgba",))
         bt.write_ppm(args.render, image["rgba"])
         print(f"rendered {camera.width} x {camera.height} to {args.render}: {image['stats']}")
     print(f"{args.frames} frames, {requested_total} tile requests, {loaded_total} tile loads ({failed_total} failed), pending {tile_atlas.pending_loads()}, "

@@ -1177,6 +1177,75 @@ bt_status bt_tile_tree_render(bt_tile_tree* tree, bt_atlas* atlas, uint32_t heig
                               uint32_t steps, uint32_t refine_rounds, double* out_t, uint8_t* out_status,
                               float* out_normal_xyz /* 3 per pixel */, uint8_t* out_rgba /* 4 per pixel */, bt_render_stats* stats);
 
+/* Sun shadows ("is this point in the sun, for this sun direction": cast shadows in the pictures of bt_tile_tree_render, and the same
+ * question for placement and analysis: where vegetation goes, where snow stays, solar exposure over a day's arc of directions, a
+ * sky-view factor from a fan of them).  The reference's roadmap lists shadow rendering as missing; it has nothing to compare with, so
+ * the answer is defined by the ray query above.
+ *
+ * SUN OCCLUSION.  For a world point q, a direction s TOWARDS the light (f64, used as given, not normalised), a lift (f64, world units), a
+ * distance (f64, in units of |s|) and N = steps, against the tree's current state and one R16 attachment:
+ *     n(q)  = the altitude direction of the ray section at q: local = position_world_to_local(m, q),
+ *             n = normalize3(transform_vector(m, spherical ? local : (0, 1, 0)))
+ *     ray   = {origin_a = q_a + lift * n_a (one multiply, one add per component), direction = s, t_min = 0.0, t_max = distance}
+ *     result = the status bt_tile_tree_raycast returns for that ray with steps = N and refine_rounds = 0 (the definition is that one, not
+ *             restated; the ceiling skip applies unchanged).
+ *   BT_RAY_MISS: lit.  BT_RAY_HIT and BT_RAY_INSIDE: occluded.  BT_RAY_INVALID: a non-finite q (or a lifted origin that is not finite), a
+ *   zero or non-finite s, a non-finite or negative distance; none of these is an error.
+ *   What the lift is for: a point a ray query reported (bt_ray_hit.position, a pixel's p(t)) lies at or under the ground, f(q) <= 0, so
+ *   with lift = 0 its shadow ray is BT_RAY_INSIDE whatever the sun: the ground shadows itself.  The lift must exceed the residual of the
+ *   march that found the point (about |d| * (t_max - t_min) / (steps * 64^refine_rounds) along the ray, less in altitude for a grazing
+ *   ray), and on slopes also the height the ground gains over one shadow step.  The lift is along n, not along the surface normal.
+ *   The march is dt = distance / N long per step: an occluder thinner than |s| * dt along the ray can be stepped over, as by any ray here.
+ *   Out of scope: soft shadows and penumbrae (the sun is a direction, the answer is binary), and baking the result into an atlas
+ *   attachment.
+ *
+ * bt_tile_tree_sun_occlusion: SUN OCCLUSION of `count` points for each of `direction_count` directions shared by all points, one status
+ * byte per pair: out_status[point * direction_count + d].  The kernel gives a ray to a lane, which marches it sample by sample and stops
+ * at the first sample at or under the ground (bt_tile_tree_raycast spends a wave and whole rounds of 64 samples per ray).  A launch is a run of
+ * whole waves (64 rays each; ray g of the batch is point g % count, direction g / count) whose worst case, 64 * (steps + 1)
+ * samples per wave, stays within BT_RAYCAST_MAX_SAMPLES; a larger batch is several launches (stats->launches), and nothing is copied back
+ * before the last one has been queued.  stats (may be NULL): launches and the number of lit (MISS), occluded (HIT or INSIDE) and invalid rays.
+ * Refused before anything is queued, out_status untouched.  BT_ERR_INVALID_ARGUMENT: NULL handles, handles of different contexts, an
+ * attachment index out of range, steps outside 1 .. BT_RENDER_MAX_STEPS, a non-finite lift, count * direction_count >
+ * BT_OCCLUSION_MAX_RAYS, a NULL array when count * direction_count > 0.  BT_ERR_UNSUPPORTED: an attachment that is not R16.
+ * count == 0 or direction_count == 0: BT_OK, nothing touched but a non-NULL stats, which is zeroed.  Ordered behind the work queued on the
+ * context's stream; synchronous (host arrays in and out); a read (no layer is marked written).  Scratch (the ray queries': 24 bytes
+ * per point and per direction and one per ray of the largest batch so far) stays in the context until bt_ctx_trim. */
+enum { BT_OCCLUSION_MAX_RAYS = 16777216 };
+typedef struct bt_occlusion_stats {
+    uint32_t launches, lit, occluded, invalid;
+} bt_occlusion_stats;
+bt_status bt_tile_tree_sun_occlusion(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const double* world_positions_xyz, uint32_t count,
+                                     const double* directions_xyz, uint32_t direction_count, double lift, double distance, uint32_t steps,
+                                     uint8_t* out_status /* count * direction_count, point-major */, bt_occlusion_stats* stats);
+
+/* bt_tile_tree_render_shadowed: bt_tile_tree_render with cast shadows.  Every plane of bt_tile_tree_render is defined as it is there, and:
+ *
+ * SHADOW PLANE, 1 byte per pixel: for a BT_RAY_HIT or BT_RAY_INSIDE pixel, SUN OCCLUSION at q = p(t) with s_a = double(camera.sun[a]) (the
+ *   exact widening) and shadow->lift, shadow->distance, shadow->steps; for any other pixel BT_SHADOW_NONE.
+ * COLOUR PLANE with BT_RENDER_LIGHTING: sh = (the shadow plane's value is BT_RAY_HIT or BT_RAY_INSIDE) ? 0.0f : 1.0f and
+ *   k = ambient + (1.0f - ambient) * (l * sh).  l * 1.0f is l, and for a finite l, l * 0.0f is 0: a lit pixel has the bytes
+ *   bt_tile_tree_render gives it, an occluded pixel the bytes bt_tile_tree_render gives with sun = (0, 0, 0).  Without BT_RENDER_LIGHTING the
+ *   colour is bt_tile_tree_render's and the shadow plane is defined all the same.
+ * When out_shadow is NULL and the colour cannot show the result (no out_rgba, no BT_RENDER_LIGHTING, or l == 0) the kernel leaves the
+ * shadow march out; that cannot be observed.
+ *
+ * A launch is a run of whole 8 x 8 blocks whose worst case, 64 * ((steps + 1 + 63 * refine_rounds) + (shadow->steps + 1)) samples per
+ * block, stays within BT_RAYCAST_MAX_SAMPLES, cut to whole bands as in bt_tile_tree_render.  Refusals: those of bt_tile_tree_render, and
+ * BT_ERR_INVALID_ARGUMENT for a NULL shadow, shadow->steps outside 1 .. BT_RENDER_MAX_STEPS, a non-finite shadow->lift, and all FIVE planes
+ * NULL.  A non-finite or negative shadow->distance is no error (BT_RAY_INVALID in the shadow plane, lit in the colour).  Synchronous, a
+ * read; the scratch is bt_tile_tree_render's, one byte per pixel more with a shadow plane. */
+typedef struct bt_sun_shadow {
+    double lift, distance; /* SUN OCCLUSION's, world units / units of |sun| */
+    uint32_t steps;        /* 1 .. BT_RENDER_MAX_STEPS */
+    uint32_t _padding;
+} bt_sun_shadow;
+#define BT_SHADOW_NONE 255u
+bt_status bt_tile_tree_render_shadowed(bt_tile_tree* tree, bt_atlas* atlas, uint32_t height_attachment, const bt_render_camera* camera,
+                                       uint32_t steps, uint32_t refine_rounds, const bt_sun_shadow* shadow, double* out_t, uint8_t* out_status,
+                                       float* out_normal_xyz /* 3 per pixel */, uint8_t* out_rgba /* 4 per pixel */,
+                                       uint8_t* out_shadow /* 1 per pixel */, bt_render_stats* stats);
+
 /* Terrain geometry ("where are the vertices of the tiles the prepass selected": colliders for the visible tiles, mesh export, a renderer
  * that is not wgpu).  bt_frame_update ends with final_tiles and indirect arguments whose vertex_count counts vertices of the reference's
  * vertex stage (src/shaders/render/vertex.wgsl: compute_tile_uv, compute_local_position, compute_morph, compute_blend, lookup_tile through
