@@ -122,8 +122,8 @@ def assert_hits_equal(got, exp):
 class Streamed:
     """a terrain streamed into a device tree and the oracle's tree in lock step (the loop of test_streaming_loop_entries_and_heights)"""
 
-    def __init__(self, device, tmp_path, kind, frames=12, texture_size=T, border_size=B):
-        self.model, self.omodel = MODELS[kind]
+    def __init__(self, device, tmp_path, kind, frames=12, texture_size=T, border_size=B, model=None):
+        self.model, self.omodel = model or MODELS[kind]  # model: a (TerrainModel, oracle model) pair of `kind` other than MODELS'
         root, cfg, tiles = build_terrain(device, tmp_path, self.model, LODS, texture_size, border_size)
         atlas_size = 256 if kind == "planar" else 512
         scfg = bt.TerrainConfig(lod_count=LODS, atlas_size=atlas_size, path=cfg.path, model=self.model)

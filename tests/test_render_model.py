@@ -173,12 +173,12 @@ def test_enc8_and_launches():
     assert R.launches(8 * 100, 8, 4096, 4) == (-(-100 // ((1 << 24) // per_block)), (1 << 24) // per_block)
 
 
-def cpu_scene(kind, omodel, frames=12):
+def cpu_scene(kind, omodel, frames=12, texture_size=R.T, border_size=R.B):
     """test_gpu_raycast.Streamed without a device: the oracle preprocesses the same rasters, its tree streams the tiles along the same camera
     path, and the approximate height of each frame is the oracle's sample_height at the view position"""
-    W = 2 ** (R.LODS - 1) * (R.T - 2 * R.B) + 13
+    W = 2 ** (R.LODS - 1) * (texture_size - 2 * border_size) + 13
     spherical = kind != "planar"
-    atlas = O.OracleAtlas(R.LODS, 6 * 400 if spherical else 400, spherical, [(R.T, R.B, 1, O.FORMAT_R16)])
+    atlas = O.OracleAtlas(R.LODS, 6 * 400 if spherical else 400, spherical, [(texture_size, border_size, 1, O.FORMAT_R16)])
     atlas.clear_attachment(0)
     if spherical:
         atlas.preprocess_spherical(0, [K.smooth_raster(W, W, seed=3 + s) for s in range(6)], (0, R.LODS))
@@ -186,7 +186,7 @@ def cpu_scene(kind, omodel, frames=12):
         atlas.preprocess_tile(0, K.smooth_raster(W, W, seed=3), (0, R.LODS))
     atlas.run(4)
     tiles = {coord: atlas.tile(0, i) for coord, i in atlas.tiles()}
-    s = types.SimpleNamespace(omodel=omodel, T=R.T, B=R.B, layers={}, approximate_height=0.0)
+    s = types.SimpleNamespace(omodel=omodel, T=texture_size, B=border_size, layers={}, approximate_height=0.0)
     s.otree = O.TileTree(omodel, R.LODS, O.make_view_config(tree_size=4, load_distance=1.2, blend_distance=1.0))
     stream = O.Stream(256 if kind == "planar" else 512, 1, existing=list(tiles))
     for pos in camera_path(kind, frames, seed=5):
@@ -195,7 +195,7 @@ def cpu_scene(kind, omodel, frames=12):
             s.layers[index] = tiles[coord]
         s.otree.apply_requests(stream)
         s.otree.adjust_to_tile_atlas(stream)
-        s.approximate_height = float(s.otree.sample_attachment(O.FORMAT_R16, R.T, R.B, s.layers, [pos])[1][0])
+        s.approximate_height = float(s.otree.sample_attachment(O.FORMAT_R16, texture_size, border_size, s.layers, [pos])[1][0])
         s.otree.set_approximate_height(s.approximate_height)
         s.view = pos
     return s
