@@ -229,6 +229,25 @@ class SplatRuleC(C.Structure):
                 ("steep_fade", C.c_float), ("weight", C.c_float), ("colour", C.c_float * 3), ("_padding", C.c_uint32 * 2)]
 
 
+PATH_MAX_CELLS, PATH_MAX_GOALS = 1 << 22, 4096
+PATH_GOAL, PATH_UNREACHABLE, PATH_BLOCKED = 8, 254, 255
+PATH_TRACE_OK, PATH_TRACE_BLOCKED, PATH_TRACE_UNREACHABLE, PATH_TRACE_LOOP = 0, 1, 2, 3
+
+
+class PathCostC(C.Structure):
+    _fields_ = [("min_height", C.c_float), ("max_height", C.c_float), ("cell_size", C.c_float), ("max_grade", C.c_float),
+                ("grade_weight", C.c_float), ("climb_weight", C.c_float), ("descend_weight", C.c_float), ("_padding", C.c_uint32)]
+
+
+class PathGoalC(C.Structure):
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("cost0", C.c_float)]
+
+
+class PathStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("blocked", C.c_uint32), ("reachable", C.c_uint32), ("goals_used", C.c_uint32),
+                ("goals_blocked", C.c_uint32), ("tiles_missing", C.c_uint32), ("sweeps", C.c_uint32), ("launches", C.c_uint32)]
+
+
 class EditStatsC(C.Structure):
     _fields_ = [("tiles_edited", C.c_uint32), ("tiles_missing", C.c_uint32), ("tiles_with_children", C.c_uint32),
                 ("tiles_downsampled", C.c_uint32), ("tiles_stitched", C.c_uint32), ("layers_mipped", C.c_uint32), ("launches", C.c_uint32),
@@ -309,6 +328,9 @@ PROTOTYPES = {
     "bt_atlas_read_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(_u32)]),
     "bt_atlas_write_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
+    "bt_atlas_path_field": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(PathCostC), _P(PathGoalC), _u32, _P(C.c_uint8), _P(C.c_float),
+                                   _P(C.c_uint8), _P(PathStatsC)]),
+    "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),
     "bt_generate_mipmaps": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _u64]),

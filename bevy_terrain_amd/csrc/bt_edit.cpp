@@ -670,24 +670,15 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
     return rc;
 }
 
-bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* texels,
-                               uint64_t row_pitch, uint32_t* tiles_missing) {
-    if (tiles_missing) *tiles_missing = 0;
-    if (!a) {
-        set_error("bt_atlas_read_region: NULL atlas");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, "bt_atlas_read_region")) return s;
+}  // extern "C"
+
+bt_status bt::region_check(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, const char* what) {
+    return check_region(a, ai, side, lod, x0, y0, width, height, kTexels, what);
+}
+
+bt_status bt::region_gather(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* dst, uint32_t* tiles_missing) {
     const Attachment& at = a->attachments[ai];
-    if (!width || !height) return BT_OK;
-    const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
-    if (!row_pitch) row_pitch = row_bytes;
-    if (!texels || row_pitch < row_bytes) {
-        set_error("bt_atlas_read_region: %s", !texels ? "NULL texels_host" : "row_pitch smaller than a row");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
     bt_ctx* ctx = a->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
     // the items: the rectangle's part of every tile the atlas holds, as a write's first level
     DirtyTiles tiles;
     const uint64_t met = meet_tiles(a, at.meta.center_size, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, tiles);
@@ -699,19 +690,19 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
         items.push_back(make_item(coord, d, at.meta.center_size));
         max_rows = std::max(max_rows, d.r.y1 - d.r.y0 + 1u);
     }
-    // layers -> the staged rectangle on the device (what no tile covers: zeros, from a memset queued before the launch)
+    // layers -> the rectangle on the device (what no tile covers: zeros, from a memset queued before the launch)
+    if (missing) BT_HIP(hipMemsetAsync(dst, 0, uint64_t(width) * height * at.meta.pixel_size, ctx->stream));
+    if (items.empty()) return BT_OK;
+    PlanRing ring;
+    const uint64_t items_at = ring.add(items);
+    uint8_t* dev = nullptr;
+    if (bt_status s = ring.commit(ctx, &dev)) return s;
+    return launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, dst, x0, y0, width);
+}
+
+bt_status bt::region_stage_out(bt_ctx* ctx, const void* src, void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height, const char* what) {
+    // the rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
     const uint64_t total = row_bytes * height;
-    if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
-    if (missing) BT_HIP(hipMemsetAsync(ctx->edit_region.dev, 0, total, ctx->stream));
-    if (!items.empty()) {
-        PlanRing ring;
-        const uint64_t items_at = ring.add(items);
-        uint8_t* dev = nullptr;
-        if (bt_status s = ring.commit(ctx, &dev)) return s;
-        if (bt_status s = launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, ctx->edit_region.dev, x0, y0, width))
-            return s;
-    }
-    // the staged rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
     if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
         if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
     const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
@@ -733,7 +724,7 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
         const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
         empty(k);
         if (e == hipSuccess && !landing[k].copied) e = hipEventCreateWithFlags(&landing[k].copied, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)ctx->edit_region.dev + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)src + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(landing[k].copied, ctx->stream);
         if (e == hipSuccess) landing[k].row = row, landing[k].rows = rows;
     }
@@ -741,7 +732,33 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
     if (e != hipSuccess) hipStreamSynchronize(ctx->stream);  // nothing may still be landing in the context's buffers when the call returns
     for (Landing& l : landing)
         if (l.copied) hipEventDestroy(l.copied);
-    return e == hipSuccess ? BT_OK : hip_fail(e, "bt_atlas_read_region staging");
+    return e == hipSuccess ? BT_OK : hip_fail(e, what);
+}
+
+extern "C" {
+
+bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* texels,
+                               uint64_t row_pitch, uint32_t* tiles_missing) {
+    if (tiles_missing) *tiles_missing = 0;
+    if (!a) {
+        set_error("bt_atlas_read_region: NULL atlas");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, "bt_atlas_read_region")) return s;
+    const Attachment& at = a->attachments[ai];
+    if (!width || !height) return BT_OK;
+    const uint64_t row_bytes = uint64_t(width) * at.meta.pixel_size;
+    if (!row_pitch) row_pitch = row_bytes;
+    if (!texels || row_pitch < row_bytes) {
+        set_error("bt_atlas_read_region: %s", !texels ? "NULL texels_host" : "row_pitch smaller than a row");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    const uint64_t total = row_bytes * height;
+    if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
+    if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, ctx->edit_region.dev, tiles_missing)) return s;
+    return region_stage_out(ctx, ctx->edit_region.dev, texels, row_bytes, row_pitch, height, "bt_atlas_read_region staging");
 }
 
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {

@@ -244,7 +244,10 @@ struct bt_ctx {
     bt::Scratch render;
     // the staged rectangle of write_region and read_region / the new texels of smooth_height on the device
     bt::Scratch edit_region;
-    std::array<bt::Scratch*, 5> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_path_field: the planes of one call on the device (raw texels, mask, heights, D, next, the block flags); and its
+    // words with a pinned twin (the per-sweep counters of a batch, the counts of bt_path_stats)
+    bt::Scratch path, path_words;
+    std::array<bt::Scratch*, 7> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
     // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out (kept until bt_ctx_trim)
@@ -475,6 +478,39 @@ private:
     std::vector<Record> records;
     uint64_t size = 0, upload = 0;  // of all records; of those up to the last host record: what the copy moves
 };
+
+// bt_edit.cpp, the halves of bt_atlas_read_region that bt_atlas_path_field shares.  region_check: what the read refuses of attachment,
+// side, lod and rectangle (`what` names the entry point).  region_gather: the rectangle's texels of the layers -> `dst` on the device
+// (tightly packed rows; tiles the atlas does not hold: zeros, counted in *tiles_missing), enqueued on the context's stream.
+// region_stage_out: `height` rows of row_bytes from `src` on the device through the context's pinned staging buffers into host rows
+// row_pitch apart; synchronous
+bt_status region_check(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, const char* what);
+bt_status region_gather(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* dst, uint32_t* tiles_missing);
+bt_status region_stage_out(bt_ctx* ctx, const void* src, void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height, const char* what);
+
+// bt_path.hip: the kernels of bt_atlas_path_field.  Planes are width x height, row-major; D holds the bits of non-negative floats
+struct PathPlanes {
+    const uint16_t* raw;   // the gathered texels
+    const uint8_t* mask;   // the caller's mask on the device, or nullptr
+    float* h;              // heights; NaN = blocked (raw 0, a missing tile or the mask)
+    uint32_t* D;           // the field, as bits
+    uint8_t* next;         // between prepare and next: 1 marks a cell that some goal entry names
+    uint32_t width, height;
+    uint32_t blocks_x, blocks_y;  // of kPathBlock x kPathBlock cells
+};
+struct PathCounts {  // the device words of bt_path_stats
+    uint32_t blocked, reachable, goals_blocked, _padding;
+};
+constexpr uint32_t kPathBlock = 32;
+constexpr uint32_t kPathRounds = 64;  // rounds of one block in one sweep, at most
+// prepare: h and the count of blocked cells; the goals (device list) into D (memset to +inf before) by atomicMin, their cells
+// marked in `next` (memset to 0 before) and the 3 x 3 blocks around each in `flags` (memset to 0 before); blocked goals counted
+bt_status launch_path_prepare(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, const bt_path_goal* goals, uint32_t goal_count, uint32_t* flags, PathCounts* counts);
+// one sweep: every block whose flag in `active` is set clears it, relaxes its cells in LDS (at most `rounds` rounds) and sets the flags of the blocks that have to
+// look again in `activate`; *marked counts the blocks that set a flag
+bt_status launch_path_relax(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked);
+// the next plane by the header's rule, and the count of reachable cells
+bt_status launch_path_next(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, const bt_path_goal* goals, uint32_t goal_count, PathCounts* counts);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

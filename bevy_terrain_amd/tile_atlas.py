@@ -198,6 +198,41 @@ class SplatRule:
                                (C.c_float * 3)(*[float(v) for v in self.colour]), (C.c_uint32 * 2)(0, 0))
 
 
+@dataclass
+class PathCost:
+    """bt_path_cost: how TileAtlas.path_field turns heights into edge weights.  A raw texel becomes the height min_height + (max_height -
+    min_height) * raw / 65535; cell_size is the world length of one texel (on a cube face, where texels are not uniform, the caller's
+    approximation).  A step of length run (cell_size, or cell_size * sqrt 2) that rises by `rise` has the grade g = |rise| / run, exists only
+    if g <= max_grade, and costs run * (1 + grade_weight * g) + climb_weight * max(rise, 0) + descend_weight * max(-rise, 0)."""
+    min_height: float = 0.0
+    max_height: float = 1.0
+    cell_size: float = 1.0
+    max_grade: float = math.inf
+    grade_weight: float = 0.0
+    climb_weight: float = 0.0
+    descend_weight: float = 0.0
+
+    def _c(self):
+        return _ffi.PathCostC(float(self.min_height), float(self.max_height), float(self.cell_size), float(self.max_grade), float(self.grade_weight),
+                              float(self.climb_weight), float(self.descend_weight), 0)
+
+
+PATH_TRACE_STATUS = {_ffi.PATH_TRACE_OK: "ok", _ffi.PATH_TRACE_BLOCKED: "blocked", _ffi.PATH_TRACE_UNREACHABLE: "unreachable", _ffi.PATH_TRACE_LOOP: "loop"}
+
+
+def trace_path(next_plane: np.ndarray, start: Tuple[int, int]) -> Tuple[np.ndarray, str]:
+    """bt_path_trace: follows the (h, w) uint8 next plane of TileAtlas.path_field from start = (x, y) to a goal -> ((n, 2) uint32 array of
+    the cells (x, y) on the way, start and goal included; "ok", "blocked", "unreachable" or "loop").  Host code: no device."""
+    next_plane = np.ascontiguousarray(next_plane, dtype=np.uint8)
+    h, w = next_plane.shape
+    count, status = C.c_uint32(), C.c_uint32()
+    ptr = next_plane.ctypes.data_as(C.POINTER(C.c_uint8))
+    _ffi.check(_ffi.lib().bt_path_trace(ptr, w, h, int(start[0]), int(start[1]), None, 0, C.byref(count), C.byref(status)))
+    cells = np.zeros((count.value, 2), dtype=np.uint32)
+    _ffi.check(_ffi.lib().bt_path_trace(ptr, w, h, int(start[0]), int(start[1]), cells.ctypes.data_as(C.POINTER(C.c_uint32)), count.value, C.byref(count), C.byref(status)))
+    return cells, PATH_TRACE_STATUS[status.value]
+
+
 def mosaic_position(uv, lod: int, center_size: int) -> Tuple[float, float]:
     """The mosaic position (EditStamp.center units) of face coordinate uv in [0, 1]^2 at `lod`: the face is 2^lod * center_size texels
     wide and texel g covers [g / n, (g + 1) / n) with its position at the integer g, so the middle of texel g maps to g."""
@@ -464,6 +499,35 @@ class TileAtlas:
         missing = C.c_uint32()
         _ffi.check(_ffi.lib().bt_atlas_read_region(self._h, attachment_index, side, lod, x0, y0, w, h, out.ctypes.data_as(C.c_void_p), 0, C.byref(missing)))
         return out, missing.value
+
+    def path_field(self, attachment_index: int, x0: int, y0: int, w: int, h: int, cost: "PathCost", goals, blocked: Optional[np.ndarray] = None,
+                   lod: Optional[int] = None, side: int = 0, want_cost: bool = True, want_next: bool = True):
+        """bt_atlas_path_field: the shortest-path field of the w x h window of centre texels at mosaic position (x0, y0) of `lod` on `side`
+        of an R16 attachment towards `goals` (up to 4096 of (x, y) or (x, y, cost0), in cells of the window), over the 8-connected grid
+        without corner cutting, with the edge weights of `cost` (PathCost).  Texels without data, tiles the atlas does not hold and cells
+        where the optional (h, w) mask `blocked` is non-zero are blocked.  Returns (cost, next, stats): cost (h, w) float32, the cost of
+        travelling from each cell to its best goal (+inf: none, or blocked); next (h, w) uint8: 0..7 the neighbour to step to ((1,0),
+        (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1)), 8 a goal, 254 unreachable, 255 blocked (trace_path follows it); stats:
+        bt_path_stats as a dict.  want_cost / want_next False: that plane is not copied out and None comes back in its place.  Both planes
+        are exact: bit for bit what Dijkstra's algorithm gives in binary32.  Ordered behind the queued work; synchronous; a read."""
+        lod = self.lod_count - 1 if lod is None else lod
+        goals = [tuple(g) for g in goals]
+        arr = (_ffi.PathGoalC * max(len(goals), 1))(*[_ffi.PathGoalC(int(g[0]), int(g[1]), float(g[2]) if len(g) > 2 else 0.0) for g in goals])
+        mask = None
+        if blocked is not None:
+            mask = np.ascontiguousarray(blocked, dtype=np.uint8)
+            if mask.shape != (h, w):
+                raise ValueError(f"path_field: a mask of shape {mask.shape} for a window of {(h, w)}")
+        cost_out = np.zeros((h, w), dtype=np.float32) if want_cost else None
+        next_out = np.zeros((h, w), dtype=np.uint8) if want_next else None
+        stats = _ffi.PathStatsC()
+        cost_c = cost._c()
+        _ffi.check(_ffi.lib().bt_atlas_path_field(
+            self._h, attachment_index, side, lod, x0, y0, w, h, C.byref(cost_c), arr, len(goals),
+            mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None,
+            cost_out.ctypes.data_as(C.POINTER(C.c_float)) if want_cost else None,
+            next_out.ctypes.data_as(C.POINTER(C.c_uint8)) if want_next else None, C.byref(stats)))
+        return cost_out, next_out, {name: getattr(stats, name) for name, _ in _ffi.PathStatsC._fields_}
 
     def write_region(self, attachment_index: int, texels: np.ndarray, x0: int, y0: int, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_write_region: copy `texels` ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros allowed) verbatim over the centre

@@ -57,6 +57,7 @@ enum {
     BT_ERR_UNSUPPORTED = -5, /* e.g. AttachmentFormat::Rgb8 / Rg16: silently unprocessed upstream */
     BT_ERR_OUT_OF_MEMORY = -6,
     BT_ERR_OVERFLOW = -7, /* tile buffer of the tiling prepass too small */
+    BT_ERR_INTERNAL = -8, /* a bound the library proves was passed (bt_atlas_path_field: more sweeps than cells): a defect, text in bt_last_error() */
 };
 
 #define BT_INVALID_ATLAS_INDEX 0xFFFFFFFFu /* terrain_data/mod.rs:34 */
@@ -1422,6 +1423,83 @@ typedef struct bt_frame_info {
 } bt_frame_info;
 bt_status bt_frame_update(bt_tile_tree* tree, bt_atlas* atlas, bt_tiling_prepass* prepass /* may be NULL */,
                           const double view_world_position[3], uint32_t flags, bt_frame_info* out /* may be NULL */);
+
+/* ---------------- path-finding: a shortest-path field over a rectangle of heights, and the route it holds
+ * PATH FIELD (bt_atlas_path_field; R16 only).  IEEE binary32, one rounding per written operation, no contraction.
+ * Input: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of an R16 attachment (the rectangle of
+ * bt_atlas_read_region).  It lies inside one face: a path does not cross a cube edge.  Cell (x, y), 0 <= x < width, 0 <= y < height, is
+ * mosaic texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index y * width + x.
+ * Cells.  raw = the centre texel.  The cell is BLOCKED when raw == 0 (no data), when its tile is one the atlas does not hold (such texels
+ * read as 0), or when blocked_host[y * width + x] != 0 (the optional host mask).  Otherwise
+ *     h = min_height + (max_height - min_height) * (f32(raw) / 65535.0f)                       the correctly rounded division
+ * Neighbours.  k = 0..7 with (dx, dy) = (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1).  The edge a -> b_k exists only if
+ *     both cells are inside the window and not blocked,
+ *     for odd k (a diagonal) both (a.x + dx, a.y) and (a.x, a.y + dy) are inside and not blocked (no corner cutting),
+ *     and the grade test below passes.
+ * Edge weight w(a -> b), with cell_diag = cell_size * 1.41421356f formed once on the host:
+ *     run  = k odd ? cell_diag : cell_size
+ *     rise = h_b - h_a
+ *     g    = fabsf(rise) / run                      the edge exists only if g <= max_grade (a NaN fails)
+ *     up   = rise > 0 ? rise : 0
+ *     down = rise < 0 ? -rise : 0
+ *     w    = ((run * (1.0f + grade_weight * g)) + climb_weight * up) + descend_weight * down
+ * All weights are >= 0, so w >= run > 0.
+ * Goals: up to BT_PATH_MAX_GOALS entries {x, y, cost0}, cost0 finite and >= 0.  A goal on a blocked cell is skipped and counted.
+ * Field.  D(c) = the minimum over all paths c = c_n, ..., c_0 with c_0 a goal of the left fold v_0 = cost0, v_(i+1) = v_i + w(c_(i+1) -> c_i);
+ * D(c) = +inf when no path exists or c is blocked.  D is the cost of travelling FROM the cell TO a goal: climb_weight and descend_weight
+ * make it direction-dependent.  fl(v + w) is monotone in v and never below v, so Dijkstra with these rounded adds computes D, every fixed
+ * point of X(c) = min(goal cost0 at c, min_k (X(b_k) + w(c -> b_k))) whose values are costs of real paths equals D, and relaxation from
+ * +inf reaches D in any order: both planes are functions of the input alone, bit for bit.
+ * Next plane (u8): BT_PATH_BLOCKED for a blocked cell; BT_PATH_UNREACHABLE for D = +inf; BT_PATH_GOAL where a usable goal at the cell has
+ * cost0 == D(c) (checked first); otherwise the smallest k with D(b_k) + w(c -> b_k) == D(c).
+ * cell_size is the caller's world length of one texel.  On a cube face the texels are not uniform: one cell_size is the caller's
+ * approximation of them.
+ * The call: synchronous, host arrays in and out, ordered behind the work queued on the context's stream; a read: no layer is marked
+ * written.  cost_out (width * height floats), next_out (width * height bytes) and stats may each be NULL.  Launches: the gather of
+ * bt_atlas_read_region, one prepare launch, sweeps of the relaxation kernel in batches of 4, 8, 16, then 32 (after each batch the last
+ * sweep's count of blocks that still had work is read back; 0 ends the loop; more than width * height sweeps: BT_ERR_INTERNAL), one launch
+ * for the next plane.  The scratch stays in the context until bt_ctx_trim.  stats->sweeps and stats->launches describe that schedule and may differ
+ * from run to run; everything else in bt_path_stats, and both planes, are functions of the input.
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL cost or goals; goal_count 0 or above BT_PATH_MAX_GOALS;
+ * width * height above BT_PATH_MAX_CELLS; a goal outside the window or with a cost0 that is not finite or negative; a cell_size that is
+ * not finite or <= 0; a weight that is negative or not finite; a max_grade that is NaN or negative (+inf is allowed); a min_height,
+ * max_height or max_height - min_height that is not finite.  BT_ERR_UNSUPPORTED: a non-R16 attachment, an odd centre size.  width == 0 or
+ * height == 0 (with valid arguments otherwise; the goals, which cannot lie inside, are not looked at): BT_OK, nothing touched. */
+#define BT_PATH_MAX_CELLS (1u << 22)
+#define BT_PATH_MAX_GOALS 4096u
+enum { BT_PATH_GOAL = 8, BT_PATH_UNREACHABLE = 254, BT_PATH_BLOCKED = 255 }; /* values of the next plane besides k = 0..7 */
+typedef struct bt_path_cost {
+    float min_height, max_height; /* finite, with a finite difference */
+    float cell_size;              /* finite, > 0 */
+    float max_grade;              /* >= 0, +inf allowed */
+    float grade_weight, climb_weight, descend_weight; /* finite, >= 0 */
+    uint32_t _padding;
+} bt_path_cost; /* 32 bytes */
+typedef struct bt_path_goal {
+    uint32_t x, y; /* cell of the window */
+    float cost0;   /* finite, >= 0 */
+} bt_path_goal;    /* 12 bytes */
+typedef struct bt_path_stats {
+    uint32_t cells, blocked, reachable;  /* width * height; blocked cells; cells with a finite D */
+    uint32_t goals_used, goals_blocked;  /* goal entries on free / on blocked cells */
+    uint32_t tiles_missing;              /* tiles of the rectangle the atlas does not hold */
+    uint32_t sweeps, launches;           /* relaxation launches; all kernel launches of the call, the gather counted as one */
+} bt_path_stats;
+bt_status bt_atlas_path_field(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                              uint32_t width, uint32_t height, const bt_path_cost* cost, const bt_path_goal* goals, uint32_t goal_count,
+                              const uint8_t* blocked_host /* may be NULL */, float* cost_out /* may be NULL */,
+                              uint8_t* next_out /* may be NULL */, bt_path_stats* stats /* may be NULL */);
+/* bt_path_trace: follows a next plane from (start_x, start_y) to a goal.  Host code, no device.  Writes up to `cap` cells as (x, y)
+ * pairs into out_xy (may be NULL with cap 0), start and goal included, and *count_out (may be NULL) gets the full count of cells visited.
+ * *status_out: BT_PATH_TRACE_OK (ended on BT_PATH_GOAL), _BLOCKED / _UNREACHABLE (the start is such a cell; count 1), _LOOP: no goal within
+ * width * height steps, a step that leaves the window, or a byte on the way that is none of k = 0..7 and BT_PATH_GOAL.  On the planes of
+ * bt_atlas_path_field a _LOOP can only arise where an add was absorbed: D >= 2^24 * w makes two cells tie and point at each other.
+ * Never reads outside the plane.  BT_ERR_INVALID_ARGUMENT: NULL next or status_out, NULL out_xy with cap > 0, width or height 0, a start
+ * outside the window. */
+enum { BT_PATH_TRACE_OK = 0, BT_PATH_TRACE_BLOCKED = 1, BT_PATH_TRACE_UNREACHABLE = 2, BT_PATH_TRACE_LOOP = 3 };
+bt_status bt_path_trace(const uint8_t* next, uint32_t width, uint32_t height, uint32_t start_x, uint32_t start_y, uint32_t* out_xy,
+                        uint32_t cap, uint32_t* count_out, uint32_t* status_out);
 
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
