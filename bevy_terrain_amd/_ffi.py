@@ -144,6 +144,27 @@ class RayHitC(C.Structure):
                 ("height", C.c_float), ("_padding", C.c_uint32)]
 
 
+CONTACT_NONE, CONTACT_TOUCHING, CONTACT_BELOW, CONTACT_INVALID, CONTACT_FAR = 0, 1, 2, 3, 4
+COLLIDE_MAX_REFINE_ROUNDS, COLLIDE_MAX_SAMPLES, SWEEP_MAX_STEPS, SWEEP_MAX_BISECTIONS = 6, 1 << 24, 4096, 32
+
+
+class SphereC(C.Structure):
+    _fields_ = [("center", C.c_double * 3), ("radius", C.c_double)]
+
+
+class SphereContactC(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("candidate", C.c_uint32), ("distance", C.c_double), ("depth", C.c_double), ("point", C.c_double * 3),
+                ("normal", C.c_double * 3), ("height", C.c_float), ("_padding", C.c_uint32)]
+
+
+class SphereSweepC(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("radius", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
+class SweepHitC(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("step", C.c_uint32), ("t", C.c_double), ("t_above", C.c_double), ("contact", SphereContactC)]
+
+
 RENDER_ORTHOGRAPHIC, RENDER_LIGHTING = 1, 2
 RENDER_MAX_STEPS, RENDER_MAX_PIXELS, RENDER_NO_ALBEDO = 4096, 1 << 24, 0xFFFFFFFF
 
@@ -395,6 +416,8 @@ PROTOTYPES = {
     "bt_tile_tree_view_state": (_i32, [_vp, _P(ViewStateC)]),
     "bt_tile_tree_raycast": (_i32, [_vp, _vp, _u32, _P(RayC), _u32, _u32, _u32, _P(RayHitC)]),
     "bt_tile_tree_render": (_i32, [_vp, _vp, _u32, _P(RenderCameraC), _u32, _u32, _P(C.c_double), _P(C.c_uint8), _P(C.c_float), _P(C.c_uint8), _P(RenderStatsC)]),
+    "bt_tile_tree_collide_spheres": (_i32, [_vp, _vp, _u32, _P(SphereC), _u32, _u32, _P(SphereContactC)]),
+    "bt_tile_tree_sweep_spheres": (_i32, [_vp, _vp, _u32, _P(SphereSweepC), _u32, _u32, _u32, _u32, _P(SweepHitC)]),
     "bt_tile_tree_sun_occlusion": (_i32, [_vp, _vp, _u32, _P(C.c_double), _u32, _P(C.c_double), _u32, C.c_double, C.c_double, _u32, _P(C.c_uint8),
                                           _P(OcclusionStatsC)]),
     "bt_tile_tree_render_shadowed": (_i32, [_vp, _vp, _u32, _P(RenderCameraC), _u32, _u32, _P(SunShadowC), _P(C.c_double), _P(C.c_uint8), _P(C.c_float),

@@ -235,7 +235,7 @@ struct bt_ctx {
     // bt_atlas_tile_bounds: the layer list and the pyramids of one chunk of layers, on the device and pinned
     bt::Scratch bounds;
     // bt_tile_tree_raycast: the rays and the hits of one call on the device; bt_tile_tree_sun_occlusion: the counters, points, directions
-    // and statuses of one call
+    // and statuses of one call; bt_tile_tree_collide_spheres / bt_tile_tree_sweep_spheres: the spheres (sweeps) and the contacts (hits) of one call
     bt::Scratch raycast;
     // bt_tile_tree_sample_normal: the positions, normals and cosines of one call; bt_atlas_tile_normals: the tile list and up to three
     // chunks of normal maps on their way to the pinned staging buffers; bt_tile_tree_tile_geometry(_hp): the tile list and the vertices of one chunk

@@ -1,6 +1,6 @@
 // Device half of sample_attachment / sample_height (terrain_data/mod.rs:265-307) shared by the kernels that sample the
 // terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip), raycast_kernel (bt_raycast.hip), render_kernel (bt_render.hip),
-// occlusion_kernel (bt_shadow.hip).  One definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there,
+// occlusion_kernel (bt_shadow.hip), collide_kernel and sweep_kernel (bt_collide.hip).  One definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there,
 // bit for bit.
 //
 // Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
@@ -68,6 +68,16 @@ struct OcclusionArgs {
 };
 bt_status launch_occlusion(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
                            const OcclusionArgs& a, const float* height);
+
+// bt_collide.hip: SPHERE CONTACT of `count` spheres / SPHERE SWEEP of `count` sweeps (device) against the tree's entries and one R16
+// attachment -> contacts / hits (device); one wave each, kCollideWavesPerGroup of them per workgroup; height as above
+constexpr uint32_t kCollideThreads = 256;
+constexpr uint32_t kCollideWavesPerGroup = kCollideThreads / 64u;
+bt_status launch_collide(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                         const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds, bt_sphere_contact* contacts, const float* height);
+bt_status launch_sweep(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
+                       const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections, uint32_t refine_rounds, bt_sweep_hit* hits,
+                       const float* height);
 
 // bt_geometry.hip: what TERRAIN GEOMETRY (include/bevy_terrain_amd.h) takes from the tree besides its entries
 struct GeometryParams {

@@ -1,7 +1,7 @@
-// The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_sun_occlusion, bt_tile_tree_render(_shadowed),
-// bt_tile_tree_sample_normal and the geometry calls.  Each validates, stages its inputs in scratch of the context (bt::Scratch: grown on
-// demand, kept until bt_ctx_trim), calls the launcher of its kernel file (bt_raycast.hip, bt_shadow.hip, bt_render.hip, bt_normal.hip,
-// bt_geometry.hip) and copies the results back.
+// The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_collide_spheres, bt_tile_tree_sweep_spheres,
+// bt_tile_tree_sun_occlusion, bt_tile_tree_render(_shadowed), bt_tile_tree_sample_normal and the geometry calls.  Each validates, stages its
+// inputs in scratch of the context (bt::Scratch: grown on demand, kept until bt_ctx_trim), calls the launcher of its kernel file
+// (bt_raycast.hip, bt_collide.hip, bt_shadow.hip, bt_render.hip, bt_normal.hip, bt_geometry.hip) and copies the results back.
 #include <cmath>
 
 #include "bt_tile_tree_host.hpp"
@@ -42,6 +42,31 @@ bt_status query_check(const char* who, const bt_tile_tree* t, const bt_atlas* a,
 
 }  // namespace bt
 
+namespace {
+// what bt_tile_tree_collide_spheres and bt_tile_tree_sweep_spheres share once their limits hold: the batch goes to the ray queries'
+// scratch, `launch` runs on it (in, out on the device), the results come back
+template <class In, class Out, class Launch>
+bt_status collide_batch(const char* who, bt_tile_tree* t, const In* in, uint32_t count, Out* out, Launch launch) {
+    if (!count) return BT_OK;
+    if (!in || !out) {
+        set_error("%s: NULL %s", who, in ? "output array" : "input array");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    bt_ctx* ctx = t->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t in_bytes = sizeof(In) * uint64_t(count), out_bytes = sizeof(Out) * uint64_t(count);
+    if (bt_status st = ctx->raycast.reserve(ctx, in_bytes + out_bytes)) return st;
+    uint8_t* dev = (uint8_t*)ctx->raycast.dev;
+    BT_HIP(hipMemcpyAsync(dev, in, in_bytes, hipMemcpyHostToDevice, s));
+    if (bt_status st = launch(s, (const In*)dev, (Out*)(dev + in_bytes))) return st;
+    BT_HIP(hipMemcpyAsync(out, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
+    BT_HIP(hipStreamSynchronize(s));
+    synchronised(t);
+    return BT_OK;
+}
+}  // namespace
+
 extern "C" {
 
 bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds,
@@ -81,6 +106,54 @@ bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const 
     BT_HIP(hipStreamSynchronize(s));
     synchronised(t);
     return BT_OK;
+}
+
+bt_status bt_tile_tree_collide_spheres(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds,
+                                       bt_sphere_contact* contacts) {
+    static_assert(sizeof(bt_sphere) == 32 && sizeof(bt_sphere_contact) == 80, "the layouts the header states");
+    const char* who = "bt_tile_tree_collide_spheres";
+    const Attachment* height;
+    if (bt_status s = query_check(who, t, a, ai, &height)) return s;
+    const Attachment& at = *height;
+    if (refine_rounds > uint32_t(BT_COLLIDE_MAX_REFINE_ROUNDS)) {
+        set_error("%s: refine_rounds %u (at most %u)", who, refine_rounds, unsigned(BT_COLLIDE_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a sphere costs R + 1 rounds of 64 samples (one wave per sphere)
+    if (uint64_t(count) * 64u * (uint64_t(refine_rounds) + 1u) > uint64_t(BT_COLLIDE_MAX_SAMPLES)) {
+        set_error("%s: %u spheres x %u rounds of 64 samples exceed BT_COLLIDE_MAX_SAMPLES (%u): split the batch", who, count, refine_rounds + 1u,
+                  unsigned(BT_COLLIDE_MAX_SAMPLES));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    return collide_batch(who, t, spheres, count, contacts, [&](hipStream_t s, const bt_sphere* in, bt_sphere_contact* out) {
+        return launch_collide(s, make_params(t), t->d_entries, at.meta, at.level0, in, count, refine_rounds, out, t->d_height);
+    });
+}
+
+bt_status bt_tile_tree_sweep_spheres(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections,
+                                     uint32_t refine_rounds, bt_sweep_hit* hits) {
+    static_assert(sizeof(bt_sphere_sweep) == 72 && sizeof(bt_sweep_hit) == 104, "the layouts the header states");
+    const char* who = "bt_tile_tree_sweep_spheres";
+    const Attachment* height;
+    if (bt_status s = query_check(who, t, a, ai, &height)) return s;
+    const Attachment& at = *height;
+    if (steps < 1u || steps > uint32_t(BT_SWEEP_MAX_STEPS) || bisections > uint32_t(BT_SWEEP_MAX_BISECTIONS) || refine_rounds > uint32_t(BT_COLLIDE_MAX_REFINE_ROUNDS)) {
+        set_error("%s: steps %u (1 .. %u) / bisections %u (at most %u) / refine_rounds %u (at most %u)", who, steps, unsigned(BT_SWEEP_MAX_STEPS), bisections,
+                  unsigned(BT_SWEEP_MAX_BISECTIONS), refine_rounds, unsigned(BT_COLLIDE_MAX_REFINE_ROUNDS));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a sweep costs at most steps + 1 + bisections + 1 contacts of R + 1 rounds of 64 samples each
+    const uint64_t contacts = uint64_t(steps) + bisections + 2u;
+    if (uint64_t(count) * 64u * (uint64_t(refine_rounds) + 1u) * contacts > uint64_t(BT_COLLIDE_MAX_SAMPLES)) {
+        set_error("%s: %u sweeps x %u contacts x %u rounds of 64 samples exceed BT_COLLIDE_MAX_SAMPLES (%u): split the batch", who, count, unsigned(contacts),
+                  refine_rounds + 1u, unsigned(BT_COLLIDE_MAX_SAMPLES));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    // a read of the atlas: at.level0 is passed on without marking any layer written
+    return collide_batch(who, t, sweeps, count, hits, [&](hipStream_t s, const bt_sphere_sweep* in, bt_sweep_hit* out) {
+        return launch_sweep(s, make_params(t), t->d_entries, at.meta, at.level0, in, count, steps, bisections, refine_rounds, out, t->d_height);
+    });
 }
 
 namespace {

@@ -62,6 +62,13 @@ RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("direction", np.float64, 3), (
 RAY_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.float64), ("t_above", np.float64), ("position", np.float64, 3),
                           ("height", np.float32), ("_padding", np.uint32)])
 
+# numpy mirrors of bt_sphere / bt_sphere_contact / bt_sphere_sweep / bt_sweep_hit
+SPHERE_DTYPE = np.dtype([("center", np.float64, 3), ("radius", np.float64)])
+SPHERE_CONTACT_DTYPE = np.dtype([("status", np.uint32), ("candidate", np.uint32), ("distance", np.float64), ("depth", np.float64), ("point", np.float64, 3),
+                                 ("normal", np.float64, 3), ("height", np.float32), ("_padding", np.uint32)])
+SPHERE_SWEEP_DTYPE = np.dtype([("origin", np.float64, 3), ("direction", np.float64, 3), ("radius", np.float64), ("t_min", np.float64), ("t_max", np.float64)])
+SWEEP_HIT_DTYPE = np.dtype([("status", np.uint32), ("step", np.uint32), ("t", np.float64), ("t_above", np.float64), ("contact", SPHERE_CONTACT_DTYPE)])
+
 
 class RenderCamera:
     """bt_render_camera (include/bevy_terrain_amd.h): the camera of TileTree.render.  origin, forward, right and up are used as given (f64):
@@ -236,6 +243,37 @@ class TileTree:
                                                    refine_rounds, hits.ctypes.data_as(C.POINTER(_ffi.RayHitC))))
         if normals:
             return hits, self.sample_normal(attachment_index, hits["position"])[0]
+        return hits
+
+    def collide_spheres(self, attachment_index: int, centers, radii, refine_rounds: int = 2):
+        """bt_tile_tree_collide_spheres: "does this sphere touch the ground: where, how deep, along which normal" for a batch, one launch.
+        centers (n, 3), radii a scalar or (n,); returns a structured array (SPHERE_CONTACT_DTYPE): status (_ffi.CONTACT_*), candidate,
+        distance (to the closest ground point found; the altitude over the foot when BELOW), depth = radius - distance, point, normal
+        (from the point towards the centre), height.  CONTACT_NONE reports the clearance; CONTACT_FAR and CONTACT_INVALID nothing."""
+        centers = np.asarray(centers, dtype=np.float64).reshape(-1, 3)
+        n = len(centers)
+        spheres = np.zeros(n, SPHERE_DTYPE)
+        spheres["center"] = centers
+        spheres["radius"] = radii
+        contacts = np.zeros(n, SPHERE_CONTACT_DTYPE)
+        _ffi.check(_ffi.lib().bt_tile_tree_collide_spheres(self._h, self.atlas._h, attachment_index, spheres.ctypes.data_as(C.POINTER(_ffi.SphereC)), n,
+                                                           refine_rounds, contacts.ctypes.data_as(C.POINTER(_ffi.SphereContactC))))
+        return contacts
+
+    def sweep_spheres(self, attachment_index: int, origins, directions, radii, t_min, t_max, steps: int = 64, bisections: int = 16, refine_rounds: int = 2):
+        """bt_tile_tree_sweep_spheres: continuous collision of spheres moving as origin + t * direction for t in [t_min, t_max], one launch.
+        The march stops at the first of steps + 1 positions where the sphere touches the ground (or its centre is under it) and bisects
+        the bracket.  Returns a structured array (SWEEP_HIT_DTYPE): status (_ffi.RAY_*), step, t (blocked), t_above (free) and the
+        contact at t (collide_spheres' record)."""
+        origins = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+        n = len(origins)
+        sweeps = np.zeros(n, SPHERE_SWEEP_DTYPE)
+        sweeps["origin"] = origins
+        sweeps["direction"] = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+        sweeps["radius"], sweeps["t_min"], sweeps["t_max"] = radii, t_min, t_max
+        hits = np.zeros(n, SWEEP_HIT_DTYPE)
+        _ffi.check(_ffi.lib().bt_tile_tree_sweep_spheres(self._h, self.atlas._h, attachment_index, sweeps.ctypes.data_as(C.POINTER(_ffi.SphereSweepC)), n, steps,
+                                                         bisections, refine_rounds, hits.ctypes.data_as(C.POINTER(_ffi.SweepHitC))))
         return hits
 
     def render(self, camera: RenderCamera, steps: int = 256, refine_rounds: int = 2, planes=("t", "status", "normal", "rgba"), attachment_index: int = 0):

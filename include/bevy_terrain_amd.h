@@ -1247,6 +1247,83 @@ bt_status bt_tile_tree_render_shadowed(bt_tile_tree* tree, bt_atlas* atlas, uint
                                        float* out_normal_xyz /* 3 per pixel */, uint8_t* out_rgba /* 4 per pixel */,
                                        uint8_t* out_shadow /* 1 per pixel */, bt_render_stats* stats);
 
+/* Terrain collision ("does this body touch the ground: where, how deep, along which normal": a physics step, a character controller).
+ * The reference's roadmap lists collision as missing.  A ray has no radius; these two calls answer for a sphere, against the ground every
+ * other query here uses (sample_height with LOD blend and best-loaded-tile fallback), so a contact agrees with
+ * bt_tile_tree_sample_attachment and bt_tile_tree_raycast bit for bit.  IEEE binary64 unless a value is marked f32, one rounding per
+ * written operation, no contraction; dot3, normalize3, position_world_to_local, position_local_to_world, transform_vector as in the ray
+ * section; cross as in the normals' section, in f64.  ray_frame(m, p) = (local, n, ground0) of the ray section at p.
+ *
+ * SPHERE CONTACT of a centre c, a radius r and R = refine_rounds, against the tree's current state and the model m:
+ *   1. A non-finite component of c, a non-finite r or r < 0: BT_CONTACT_INVALID, every other field 0, nothing is sampled.
+ *   2. local, n, ground0 = ray_frame(m, c); a = dot3(c - ground0, n).
+ *   3. When border_size >= 1 and max_height >= min_height (the ray section's ceiling skip) and a - r > double(lerp(min_height, max_height,
+ *      1.0f)): BT_CONTACT_FAR, every other field 0, nothing is fetched.  This broad phase is part of the definition.  On a plane and on a
+ *      sphere the altitude line is the geometric normal and no ground is above the ceiling, so FAR implies no contact.  On an ellipsoid
+ *      the altitude line is not the geometric normal (the reference's choice): the ellipsoid's FAR is that of the altitude line.
+ *   4. The ground point G(q) of a world point q: local_q = position_world_to_local(m, q); h_q = the `heights` value (f32)
+ *      bt_tile_tree_sample_attachment returns for q (its surface point is position_local_to_world(m, local_q, approximate_height); an
+ *      unloaded tile samples as 0); G(q) = position_local_to_world(m, local_q, double(h_q)).
+ *   5. g0 = G(c), f = a - double(h0).  f <= 0: BT_CONTACT_BELOW with point = g0, normal = n, distance = f, depth = r - f, candidate = 0,
+ *      height = h0.  A NaN f compares false and the definition goes on.
+ *   6. Tangent basis.  Planar: e1 = (1, 0, 0), e2 = (0, 0, 1).  Otherwise k = the index of the smallest |n_k| (ties: the lowest index), u =
+ *      the unit vector of axis k, e1 = normalize3(cross(u, n)), e2 = cross(n, e1).
+ *   7. best = {D2 = dot3(g0 - c, g0 - c), candidate 0, point g0, height h0}, (ox, oy) = (0, 0), w = r.  For round k = 0 .. R, lane
+ *      l = 0 .. 63, i = l & 7, j = l >> 3:
+ *          x = ox + w * ((2.0 * double(i) - 7.0) / 7.0);  y = oy + w * ((2.0 * double(j) - 7.0) / 7.0)
+ *          q_a = c_a + (x * e1_a + y * e2_a);  g = G(q);  d2 = dot3(g - c, g - c)
+ *      the round's winner is the smallest d2 (ties: the lowest l; a NaN d2 never wins).  If its d2 < best.D2 (strictly) best becomes the
+ *      winner with candidate = 64 k + l + 1 and (ox, oy) its (x, y); otherwise both stay.  After each round w = w * (2.0 / 7.0).
+ *   8. distance = sqrt(best.D2); status = distance < r ? BT_CONTACT_TOUCHING : BT_CONTACT_NONE (NONE reports every field: the clearance);
+ *      depth = r - distance; point and height are best's; normal_a = (c_a - point_a) * (1.0 / distance) when distance > 0, otherwise n.
+ *   The foot is a candidate, so flat ground gives the exact distance.  On a plane of gradient g (g * g <= 2) whose nearest point lies
+ *   within the first window, the reported distance exceeds the true one, d, by at most (2 + g * g) * s * s / (8 d), s = r * (2/7)^(R+1)
+ *   the last round's stencil spacing.  The distance never grows with R.
+ *
+ * SPHERE SWEEP (continuous collision, the "move" of move-and-slide): the centre moves as c(t) = origin + t * direction (the ray
+ * section's p(t)).  blocked(t) = SPHERE CONTACT of (c(t), r, R) is TOUCHING or BELOW.  Coarse march: dt and t_i exactly as in the ray
+ * section for i = 0 .. steps; the hit step is the smallest i with blocked(t_i).  None: BT_RAY_MISS.  i == 0: BT_RAY_INSIDE, t = t_above =
+ * t_min.  Otherwise BT_RAY_HIT, lo = t_(i-1), hi = t_i, and for each of `bisections` rounds mid = lo + (hi - lo) * 0.5; blocked(mid) ? hi
+ * = mid : lo = mid.  t = hi, t_above = lo, contact = SPHERE CONTACT at c(t).  BT_RAY_MISS and BT_RAY_INVALID leave every other field 0.
+ * BT_RAY_INVALID: the ray section's rules, and r not finite or < 0.  Ground thinner than a step is passed through, as by any ray here.
+ *
+ * Limits, checked before anything is queued (BT_ERR_INVALID_ARGUMENT): NULL handles or two contexts (before the count == 0 shortcut),
+ * refine_rounds <= BT_COLLIDE_MAX_REFINE_ROUNDS, 1 <= steps <= BT_SWEEP_MAX_STEPS, bisections <= BT_SWEEP_MAX_BISECTIONS, count * 64 *
+ * (R + 1) <= BT_COLLIDE_MAX_SAMPLES for contacts and count * 64 * (R + 1) * (steps + bisections + 2) <= BT_COLLIDE_MAX_SAMPLES for sweeps
+ * (64-bit products), a NULL array with count > 0.  Non-R16 attachments: BT_ERR_UNSUPPORTED.  count == 0: BT_OK, nothing touched.  Each call
+ * is one launch (one wave per sphere or sweep, a round is one G(q) per lane), ordered behind the work queued on the context's stream;
+ * synchronous (host arrays in and out); a read (no layer is marked written).  Scratch (the ray queries': 112 bytes per sphere, 176 per
+ * sweep of the largest batch so far) stays in the context until bt_ctx_trim.
+ * Out of scope: capsules and boxes, a contact manifold of more than one point, restitution and friction, bodies against bodies. */
+enum { BT_CONTACT_NONE = 0, BT_CONTACT_TOUCHING = 1, BT_CONTACT_BELOW = 2, BT_CONTACT_INVALID = 3, BT_CONTACT_FAR = 4 };
+enum { BT_COLLIDE_MAX_REFINE_ROUNDS = 6, BT_COLLIDE_MAX_SAMPLES = 16777216, BT_SWEEP_MAX_STEPS = 4096, BT_SWEEP_MAX_BISECTIONS = 32 };
+typedef struct bt_sphere {
+    double center[3];
+    double radius;
+} bt_sphere;
+typedef struct bt_sphere_contact {
+    uint32_t status;    /* BT_CONTACT_* */
+    uint32_t candidate; /* 0: the foot; 64 k + l + 1: lane l of round k */
+    double distance, depth;
+    double point[3], normal[3];
+    float height; /* h sampled for `point` */
+    uint32_t _padding;
+} bt_sphere_contact;
+bt_status bt_tile_tree_collide_spheres(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_sphere* spheres, uint32_t count,
+                                       uint32_t refine_rounds, bt_sphere_contact* contacts_out);
+typedef struct bt_sphere_sweep {
+    double origin[3], direction[3];
+    double radius, t_min, t_max;
+} bt_sphere_sweep;
+typedef struct bt_sweep_hit {
+    uint32_t status; /* BT_RAY_* */
+    uint32_t step;   /* the hit step i of the coarse march */
+    double t, t_above;
+    bt_sphere_contact contact; /* SPHERE CONTACT at c(t) */
+} bt_sweep_hit;
+bt_status bt_tile_tree_sweep_spheres(bt_tile_tree* tree, bt_atlas* atlas, uint32_t attachment_index, const bt_sphere_sweep* sweeps, uint32_t count,
+                                     uint32_t steps, uint32_t bisections, uint32_t refine_rounds, bt_sweep_hit* hits_out);
+
 /* Terrain geometry ("where are the vertices of the tiles the prepass selected": colliders for the visible tiles, mesh export, a renderer
  * that is not wgpu).  bt_frame_update ends with final_tiles and indirect arguments whose vertex_count counts vertices of the reference's
  * vertex stage (src/shaders/render/vertex.wgsl: compute_tile_uv, compute_local_position, compute_morph, compute_blend, lookup_tile through
