@@ -18,56 +18,38 @@ using namespace bt::model;
 
 namespace {
 
-struct WaveSetup {
-    uint32_t lane, index;
-    double approximate_height, ceiling;
-    bool skip_above;
-};
-
-__device__ __forceinline__ WaveSetup wave_setup(const TreeParams& P, const AttachmentMeta& m, const float* __restrict__ height) {
-    WaveSetup s;
-    s.lane = threadIdx.x & 63u;
-    s.index = blockIdx.x * kCollideWavesPerGroup + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
-    s.approximate_height = double(height ? *height : P.approximate_height);
-    s.skip_above = m.border_size >= 1u && P.model.max_height >= P.model.min_height;
-    s.ceiling = double(height_of_value(P.model, 1.0f));
-    return s;
-}
+// the wave's sphere or sweep of the batch (wave-uniform)
+__device__ __forceinline__ uint32_t wave_index() { return blockIdx.x * kCollideWavesPerGroup + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))); }
 
 __global__ __launch_bounds__(kCollideThreads) void collide_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                   const void* __restrict__ atlas, const bt_sphere* __restrict__ spheres, uint32_t count,
                                                                   uint32_t refine_rounds, bt_sphere_contact* __restrict__ contacts,
                                                                   const float* __restrict__ height) {
-    const WaveSetup s = wave_setup(P, m, height);
-    if (s.index >= count) return;  // the whole wave
-    const bt_sphere sphere = spheres[s.index];
-    const bt_sphere_contact contact = sphere_contact(P, entries, m, atlas, {sphere.center[0], sphere.center[1], sphere.center[2]}, sphere.radius, refine_rounds,
-                                                     s.lane, s.approximate_height, s.skip_above, s.ceiling);
-    if (s.lane == 0) contacts[s.index] = contact;
+    const uint32_t lane = threadIdx.x & 63u, index = wave_index();
+    if (index >= count) return;  // the whole wave
+    const Ground G = ground_view(P, entries, m, atlas, height);
+    const bt_sphere sphere = spheres[index];
+    const bt_sphere_contact contact = sphere_contact(G, {sphere.center[0], sphere.center[1], sphere.center[2]}, sphere.radius, refine_rounds, lane);
+    if (lane == 0) contacts[index] = contact;
 }
 
 __global__ __launch_bounds__(kCollideThreads) void sweep_kernel(TreeParams P, const bt_tile_tree_entry* __restrict__ entries, AttachmentMeta m,
                                                                 const void* __restrict__ atlas, const bt_sphere_sweep* __restrict__ sweeps, uint32_t count,
                                                                 uint32_t steps, uint32_t bisections, uint32_t refine_rounds, bt_sweep_hit* __restrict__ hits,
                                                                 const float* __restrict__ height) {
-    const WaveSetup s = wave_setup(P, m, height);
-    if (s.index >= count) return;  // the whole wave
-    const bt_sphere_sweep sweep = sweeps[s.index];
+    const uint32_t lane = threadIdx.x & 63u, index = wave_index();
+    if (index >= count) return;  // the whole wave
+    const Ground G = ground_view(P, entries, m, atlas, height);
+    const bt_sphere_sweep sweep = sweeps[index];
     bt_ray ray;
     for (int a = 0; a < 3; a++) ray.origin[a] = sweep.origin[a], ray.direction[a] = sweep.direction[a];
     ray.t_min = sweep.t_min;
     ray.t_max = sweep.t_max;
 
     bt_sweep_hit hit{};
-    bool valid = finite(ray.t_min) && finite(ray.t_max) && ray.t_max >= ray.t_min && finite(sweep.radius) && sweep.radius >= 0.0;
-    bool nonzero = false;
-    for (int a = 0; a < 3; a++) {
-        valid = valid && finite(ray.origin[a]) && finite(ray.direction[a]);
-        nonzero = nonzero || ray.direction[a] != 0.0;
-    }
-    if (!(valid && nonzero)) {
+    if (!(ray_valid(ray) && finite(sweep.radius) && sweep.radius >= 0.0)) {
         hit.status = BT_RAY_INVALID;
-        if (s.lane == 0) hits[s.index] = hit;
+        if (lane == 0) hits[index] = hit;
         return;
     }
     // one loop over the sweep's contacts, so that sphere_contact is compiled once: the coarse march (phase 0: step i), the bisection
@@ -77,8 +59,7 @@ __global__ __launch_bounds__(kCollideThreads) void sweep_kernel(TreeParams P, co
     double lo = 0.0, hi = 0.0;
     for (;;) {
         const double t = phase == 0u ? ray.t_min + double(i) * dt : (phase == 1u ? lo + (hi - lo) * 0.5 : hi);
-        const bt_sphere_contact contact =
-            sphere_contact(P, entries, m, atlas, ray_point(ray, t), sweep.radius, refine_rounds, s.lane, s.approximate_height, s.skip_above, s.ceiling);
+        const bt_sphere_contact contact = sphere_contact(G, ray_point(ray, t), sweep.radius, refine_rounds, lane);
         if (phase == 2u) {
             hit.contact = contact;
             break;
@@ -100,7 +81,7 @@ __global__ __launch_bounds__(kCollideThreads) void sweep_kernel(TreeParams P, co
                 }
             } else if (++i > steps) {
                 hit.status = BT_RAY_MISS;
-                if (s.lane == 0) hits[s.index] = hit;
+                if (lane == 0) hits[index] = hit;
                 return;
             }
         } else {
@@ -111,26 +92,24 @@ __global__ __launch_bounds__(kCollideThreads) void sweep_kernel(TreeParams P, co
     }
     hit.t = hi;
     hit.t_above = lo;
-    if (s.lane == 0) hits[s.index] = hit;
+    if (lane == 0) hits[index] = hit;
 }
 
 }  // namespace
 
-bt_status launch_collide(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                         const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds, bt_sphere_contact* contacts, const float* height) {
+bt_status launch_collide(hipStream_t stream, const TerrainRef& g, const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds, bt_sphere_contact* contacts) {
     if (!count) return BT_OK;
-    collide_kernel<<<(count + kCollideWavesPerGroup - 1u) / kCollideWavesPerGroup, kCollideThreads, 0, stream>>>(P, entries, m, atlas, spheres, count, refine_rounds,
-                                                                                                             contacts, height);
+    collide_kernel<<<(count + kCollideWavesPerGroup - 1u) / kCollideWavesPerGroup, kCollideThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, spheres, count,
+                                                                                                             refine_rounds, contacts, g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "collide_kernel");
 }
 
-bt_status launch_sweep(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                       const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections, uint32_t refine_rounds, bt_sweep_hit* hits,
-                       const float* height) {
+bt_status launch_sweep(hipStream_t stream, const TerrainRef& g, const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections,
+                       uint32_t refine_rounds, bt_sweep_hit* hits) {
     if (!count) return BT_OK;
-    sweep_kernel<<<(count + kCollideWavesPerGroup - 1u) / kCollideWavesPerGroup, kCollideThreads, 0, stream>>>(P, entries, m, atlas, sweeps, count, steps, bisections,
-                                                                                                           refine_rounds, hits, height);
+    sweep_kernel<<<(count + kCollideWavesPerGroup - 1u) / kCollideWavesPerGroup, kCollideThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, sweeps, count, steps,
+                                                                                                           bisections, refine_rounds, hits, g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "sweep_kernel");
 }

@@ -20,13 +20,12 @@ struct GroundPoint {
 };
 
 // G(q) and h_q of step 4
-__device__ __forceinline__ GroundPoint ground_point(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
-                                                    const void* __restrict__ atlas, model::V3 local, double approximate_height) {
+__device__ __forceinline__ GroundPoint ground_point(const Ground& G, model::V3 local) {
     using namespace model;
     float value[4];
-    sample_surface(P, entries, m, atlas, position_local_to_world(P.model, local, approximate_height), value);
-    const float h = height_of_value(P.model, value[0]);
-    return {position_local_to_world(P.model, local, double(h)), h};
+    sample_ground(G, position_local_to_world(G.P.model, local, G.approximate_height), value);
+    const float h = height_of_value(G.P.model, value[0]);
+    return {position_local_to_world(G.P.model, local, double(h)), h};
 }
 
 __device__ __forceinline__ model::V3 cross3(model::V3 a, model::V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
@@ -45,24 +44,22 @@ __device__ __forceinline__ double wave_min_key(double d2, uint32_t& winner) {
     return __longlong_as_double((long long)key);
 }
 
-__device__ __forceinline__ bt_sphere_contact sphere_contact(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
-                                                            const void* __restrict__ atlas, model::V3 c, double r, uint32_t refine_rounds, uint32_t lane,
-                                                            double approximate_height, bool skip_above, double ceiling) {
+__device__ __forceinline__ bt_sphere_contact sphere_contact(const Ground& G, model::V3 c, double r, uint32_t refine_rounds, uint32_t lane) {
     using namespace model;
     bt_sphere_contact out{};
     if (!(finite(c.x) && finite(c.y) && finite(c.z) && finite(r)) || r < 0.0) {
         out.status = BT_CONTACT_INVALID;
         return out;
     }
-    const Model& model = P.model;
+    const Model& model = G.P.model;
     const RayFrame frame = ray_frame(model, c);
     const V3& n = frame.n;
     const double a = dot3(sub3(c, frame.ground0), n);
-    if (skip_above && a - r > ceiling) {
+    if (G.skip_above && a - r > G.ceiling) {
         out.status = BT_CONTACT_FAR;
         return out;
     }
-    const GroundPoint foot = ground_point(P, entries, m, atlas, frame.local, approximate_height);
+    const GroundPoint foot = ground_point(G, frame.local);
     const double f = a - double(foot.h);
     if (f <= 0.0) {
         out.status = BT_CONTACT_BELOW;
@@ -93,7 +90,7 @@ __device__ __forceinline__ bt_sphere_contact sphere_contact(const TreeParams& P,
     for (uint32_t round = 0; round <= refine_rounds; round++) {
         const double x = ox + w * sx, y = oy + w * sy;
         const V3 q = {c.x + (x * e1.x + y * e2.x), c.y + (x * e1.y + y * e2.y), c.z + (x * e1.z + y * e2.z)};
-        const GroundPoint s = ground_point(P, entries, m, atlas, ray_frame(model, q).local, approximate_height);
+        const GroundPoint s = ground_point(G, ray_frame(model, q).local);
         const V3 d = sub3(s.g, c);
         uint32_t winner;
         const double least = wave_min_key(dot3(d, d), winner);

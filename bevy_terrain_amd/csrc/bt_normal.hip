@@ -32,9 +32,8 @@ __global__ __launch_bounds__(128) void tile_tree_normal_kernel(TreeParams P, con
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const V3 p = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
-    const float approximate_height = height ? *height : P.approximate_height;
     float cosine;
-    const F3 out = world_normal(P, entries, m, atlas, nm, p, approximate_height, cosine);
+    const F3 out = world_normal(ground_view(P, entries, m, atlas, height), nm, p, cosine);
     normals[3 * uint64_t(i)] = out.x;
     normals[3 * uint64_t(i) + 1] = out.y;
     normals[3 * uint64_t(i) + 2] = out.z;
@@ -122,11 +121,10 @@ uint32_t bake_halo(const AttachmentMeta& m) { return m.texture_size / (2u * m.ce
 
 namespace bt {
 
-bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                               const double* positions, uint32_t count, float* normals, float* up_dot, const float* height) {
+bt_status launch_sample_normal(hipStream_t stream, const TerrainRef& g, const double* positions, uint32_t count, float* normals, float* up_dot) {
     if (!count) return BT_OK;
-    const NormalModel nm = {P.model.min_height, P.model.max_height, normal_side_length(P.model)};
-    tile_tree_normal_kernel<<<(count + 127u) / 128u, 128, 0, stream>>>(P, entries, m, (const uint16_t*)atlas, nm, positions, count, normals, up_dot, height);
+    const NormalModel nm = {g.P.model.min_height, g.P.model.max_height, normal_side_length(g.P.model)};
+    tile_tree_normal_kernel<<<(count + 127u) / 128u, 128, 0, stream>>>(g.P, g.entries, g.m, (const uint16_t*)g.atlas, nm, positions, count, normals, up_dot, g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "tile_tree_normal_kernel");
 }

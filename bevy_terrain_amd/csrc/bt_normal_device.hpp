@@ -104,15 +104,16 @@ __device__ __forceinline__ F3 lookup_normal(const AttachmentMeta& m, const uint1
 
 // WORLD NORMAL at world position p (steps 1 - 10): the normal and, in `cosine`, up_dot.  One definition for tile_tree_normal_kernel
 // (bt_normal.hip) and render_kernel (bt_render.hip).
-__device__ __forceinline__ F3 world_normal(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
-                                           const uint16_t* __restrict__ atlas, const NormalModel& nm, model::V3 p, float approximate_height, float& cosine) {
+__device__ __forceinline__ F3 world_normal(const Ground& G, const NormalModel& nm, model::V3 p, float& cosine) {
     using namespace model;
+    const TreeParams& P = G.P;
+    const uint16_t* atlas = (const uint16_t*)G.atlas;
     F3 out = {0.0f, 0.0f, 0.0f};
     cosine = 0.0f;
     if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
         const bool spherical = is_spherical(P.model);
         const V3 local = position_world_to_local(P.model, p);
-        const V3 surface = position_local_to_world(P.model, local, double(approximate_height));
+        const V3 surface = position_local_to_world(P.model, local, G.approximate_height);
         // normal_local_to_world: local_from_world_transpose * local, identity rotation
         F3 VN = {0.0f, 1.0f, 0.0f};
         if (spherical) {
@@ -131,9 +132,9 @@ __device__ __forceinline__ F3 world_normal(const TreeParams& P, const bt_tile_tr
         uint32_t lod;
         float ratio;
         compute_blend(P, surface, lod, ratio);
-        F3 n = lookup_normal(m, atlas, nm, lookup_tile_at(P, entries, c, lod), spherical, tan, bit, N);
+        F3 n = lookup_normal(G.m, atlas, nm, lookup_tile_at(P, G.entries, c, lod), spherical, tan, bit, N);
         if (ratio > 0.0f) {
-            const F3 n2 = lookup_normal(m, atlas, nm, lookup_tile_at(P, entries, c, lod - 1u), spherical, tan, bit, N);
+            const F3 n2 = lookup_normal(G.m, atlas, nm, lookup_tile_at(P, G.entries, c, lod - 1u), spherical, tan, bit, N);
             n = {n.x + (n2.x - n.x) * ratio, n.y + (n2.y - n.y) * ratio, n.z + (n2.z - n.z) * ratio};
         }
         out = dot3f(n, n) > 0.0f ? norm3f(n) : N;

@@ -13,7 +13,9 @@
 // texels and the blend of two of them stay within [0, 1] (rounding is monotone and every weight is in [0, 1] once the tile has a border,
 // border_size >= 1) and the f32 lerp is monotone in its weight for max_height >= min_height.  Such a sample fetches nothing.
 //
-// The per-sample evaluation (ray_eval) lives in bt_raycast_device.hpp, shared with the render kernel (bt_render.hip).
+// That skip (Ground::skip_above / ceiling, built by ground_view of bt_tile_tree_device.hpp) and the per-sample evaluation (ray_eval), the
+// validity of a ray (ray_valid) and the refinement's bracket (refine_bracket) live in bt_raycast_device.hpp, shared with the render kernel
+// (bt_render.hip), the occlusion kernel (bt_shadow.hip) and the sweep kernel (bt_collide.hip).
 #include "bt_raycast_device.hpp"
 
 namespace bt {
@@ -32,19 +34,11 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t index = blockIdx.x * kRaysPerGroup + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
     if (index >= count) return;  // the whole wave
-    const double approximate_height = double(height ? *height : P.approximate_height);
+    const Ground G = ground_view(P, entries, m, atlas, height);
     const bt_ray ray = rays[index];
-    const bool skip_above = m.border_size >= 1u && P.model.max_height >= P.model.min_height;
-    const double ceiling = double(height_of_value(P.model, 1.0f));
 
     bt_ray_hit hit{};
-    bool valid = finite(ray.t_min) && finite(ray.t_max) && ray.t_max >= ray.t_min;
-    bool nonzero = false;
-    for (int a = 0; a < 3; a++) {
-        valid = valid && finite(ray.origin[a]) && finite(ray.direction[a]);
-        nonzero = nonzero || ray.direction[a] != 0.0;
-    }
-    if (!(valid && nonzero)) {
+    if (!ray_valid(ray)) {
         hit.status = BT_RAY_INVALID;
         if (lane == 0) hits[index] = hit;
         return;
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
     for (uint32_t base = 0; base <= steps && !found; base += 64u) {
         const uint32_t i = base + lane;
         RayEval e = {false, 0.0f, 0.0f};
-        if (i <= steps) e = ray_eval(P, entries, m, atlas, ray_point(ray, ray.t_min + double(i) * dt), approximate_height, skip_above, ceiling);
+        if (i <= steps) e = ray_eval(G, ray_point(ray, ray.t_min + double(i) * dt));
         const unsigned long long bits = __ballot(e.below);
         if (bits) {
             const uint32_t first = uint32_t(__ffsll(bits)) - 1u;
@@ -84,14 +78,13 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
         for (uint32_t round = 0; round < refine_rounds; round++) {
             const double width = hi - lo;
             RayEval e = {false, 0.0f, 0.0f};
-            if (lane != 0) e = ray_eval(P, entries, m, atlas, ray_point(ray, lo + width * (double(lane) / 64.0)), approximate_height, skip_above, ceiling);
+            if (lane != 0) e = ray_eval(G, ray_point(ray, lo + width * (double(lane) / 64.0)));
             const unsigned long long bits = __ballot(e.below);
             const uint32_t k = bits ? uint32_t(__ffsll(bits)) - 1u : 64u;
             if (k != 64u) h_hit = __shfl(e.height, int(k));
-            const double new_hi = k == 64u ? hi : lo + width * (double(k) / 64.0);
-            const double new_lo = k == 1u ? lo : lo + width * (double(k - 1u) / 64.0);
-            hi = new_hi;
-            lo = new_lo;
+            const Bracket b = refine_bracket(lo, hi, k);
+            hi = b.hi;
+            lo = b.lo;
         }
     }
     hit.step = step;
@@ -107,10 +100,10 @@ __global__ __launch_bounds__(kRaycastThreads) void raycast_kernel(TreeParams P, 
 
 }  // namespace
 
-bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                         const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits, const float* height) {
+bt_status launch_raycast(hipStream_t stream, const TerrainRef& g, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits) {
     if (!count) return BT_OK;
-    raycast_kernel<<<(count + kRaysPerGroup - 1u) / kRaysPerGroup, kRaycastThreads, 0, stream>>>(P, entries, m, atlas, rays, count, steps, refine_rounds, hits, height);
+    raycast_kernel<<<(count + kRaysPerGroup - 1u) / kRaysPerGroup, kRaycastThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, rays, count, steps, refine_rounds, hits,
+                                                                                             g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "raycast_kernel");
 }

@@ -1,7 +1,7 @@
 // A camera's view of the terrain, ray-cast image-order (bt_tile_tree_render; the definition is in include/bevy_terrain_amd.h).
 //
-// Every plane is made of the library's existing definitions: a pixel's ray is marched as bt_tile_tree_raycast marches it (ray_eval of
-// bt_raycast_device.hpp, ceiling skip included), the normal at the hit is WORLD NORMAL (world_normal of bt_normal_device.hpp), the colour
+// Every plane is made of the library's existing definitions: a pixel's ray is marched as bt_tile_tree_raycast marches it (ray_eval,
+// lane_march and refine_bracket of bt_raycast_device.hpp, ceiling skip included), the normal at the hit is WORLD NORMAL (world_normal of bt_normal_device.hpp), the colour
 // is the attachment value sample_surface returns there (bt_tile_tree_device.hpp).  So the image agrees with the point queries bit for bit.
 //
 // One lane per pixel, one wave per 8 x 8 block of pixels, four blocks per workgroup; no LDS, no barrier.  Neighbouring pixels visit the
@@ -41,9 +41,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
     uint32_t status = BT_RAY_INVALID;
 
     if (active) {
-        const float approximate_height = height ? *height : P.approximate_height;
-        const bool skip_above = m.border_size >= 1u && P.model.max_height >= P.model.min_height;
-        const double ceiling = double(height_of_value(P.model, 1.0f));
+        const Ground G = ground_view(P, entries, m, atlas, height);
         // PIXEL RAY
         const double sx = (2.0 * (double(x) + 0.5)) / double(cam.width) - 1.0;
         const double sy = 1.0 - (2.0 * (double(y) + 0.5)) / double(cam.height);
@@ -59,46 +57,31 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
         }
         ray.t_min = cam.t_min;
         ray.t_max = cam.t_max;
-        bool valid = finite(ray.t_min) && finite(ray.t_max) && ray.t_max >= ray.t_min;
-        bool nonzero = false;
-        for (int k = 0; k < 3; k++) {
-            valid = valid && finite(ray.origin[k]) && finite(ray.direction[k]);
-            nonzero = nonzero || ray.direction[k] != 0.0;
-        }
 
         double t = 0.0;
         float value = 0.0f;
-        if (valid && nonzero) {
+        if (ray_valid(ray)) {
             // MARCH, the lane's own: coarse steps 0 .. steps until the first at or under the ground
             const double dt = (ray.t_max - ray.t_min) / double(a.steps);
-            status = BT_RAY_MISS;
-            uint32_t step = 0;
-            for (uint32_t i = 0; i <= a.steps; i++) {
-                const RayEval e = ray_eval(P, entries, m, atlas, ray_point(ray, ray.t_min + double(i) * dt), double(approximate_height), skip_above, ceiling);
-                if (e.below) {
-                    status = i == 0u ? BT_RAY_INSIDE : BT_RAY_HIT;
-                    step = i;
-                    value = e.value;
-                    break;
-                }
-            }
+            const LaneMarch march = lane_march(G, ray, dt, a.steps);
+            status = march.status;
+            value = march.e.value;
             if (status == BT_RAY_INSIDE) t = ray.t_min;
             if (status == BT_RAY_HIT) {
-                double lo = ray.t_min + double(step - 1u) * dt, hi = ray.t_min + double(step) * dt;
+                double lo = ray.t_min + double(march.step - 1u) * dt, hi = ray.t_min + double(march.step) * dt;
                 for (uint32_t round = 0; round < a.refine_rounds; round++) {
                     const double width = hi - lo;
                     uint32_t k = 1;
                     for (; k < 64u; k++) {
-                        const RayEval e = ray_eval(P, entries, m, atlas, ray_point(ray, lo + width * (double(k) / 64.0)), double(approximate_height), skip_above, ceiling);
+                        const RayEval e = ray_eval(G, ray_point(ray, lo + width * (double(k) / 64.0)));
                         if (e.below) {
                             value = e.value;
                             break;
                         }
                     }
-                    const double new_hi = k == 64u ? hi : lo + width * (double(k) / 64.0);
-                    const double new_lo = k == 1u ? lo : lo + width * (double(k - 1u) / 64.0);
-                    hi = new_hi;
-                    lo = new_lo;
+                    const Bracket b = refine_bracket(lo, hi, k);
+                    hi = b.hi;
+                    lo = b.lo;
                 }
                 t = hi;
             }
@@ -112,15 +95,14 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
         F3 n = {0.0f, 0.0f, 0.0f};
         if (hit && (a.normal || (a.rgba && lighting))) {
             float cosine;
-            n = world_normal(P, entries, m, (const uint16_t*)atlas, nm, p, approximate_height, cosine);
+            n = world_normal(G, nm, p, cosine);
         }
         // SHADOW PLANE
         bool occluded = false;
         if constexpr (kShadow) {
             uint32_t shadow = BT_SHADOW_NONE;
             if (hit && (a.shadow_plane || (a.rgba && lighting && dot3f(n, {cam.sun[0], cam.sun[1], cam.sun[2]}) > 0.0f))) {
-                shadow = occlusion_status(P, entries, m, atlas, p, {double(cam.sun[0]), double(cam.sun[1]), double(cam.sun[2])}, a.shadow.lift, a.shadow.distance,
-                                          a.shadow.steps, double(approximate_height), skip_above, ceiling);
+                shadow = occlusion_status(G, p, {double(cam.sun[0]), double(cam.sun[1]), double(cam.sun[2])}, a.shadow.lift, a.shadow.distance, a.shadow.steps);
                 occluded = shadow == BT_RAY_HIT || shadow == BT_RAY_INSIDE;
             }
             if (a.shadow_plane) a.shadow_plane[pixel] = uint8_t(shadow);
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
             if (hit) {
                 float base[4];
                 if (albedo) {
-                    sample_surface(P, entries, albedo_meta, albedo, surface_position(P.model, p, double(approximate_height)), base);
+                    sample_surface(P, entries, albedo_meta, albedo, surface_position(P.model, p, G.approximate_height), base);
                 } else {
                     const float g = 0.5f * value;  // sample_color (attachments.wgsl:109-113)
                     base[0] = base[1] = base[2] = g;
@@ -162,27 +144,19 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(TreeParams P, co
     }
 
     // the pixel counters: the whole wave is here, whatever its lanes did above
-    const unsigned long long hits = __ballot(active && status == BT_RAY_HIT);
-    const unsigned long long insides = __ballot(active && status == BT_RAY_INSIDE);
-    const unsigned long long misses = __ballot(active && status == BT_RAY_MISS);
-    if (lane == 0u) {
-        if (hits) atomicAdd(&a.counters[0], uint32_t(__popcll(hits)));
-        if (insides) atomicAdd(&a.counters[1], uint32_t(__popcll(insides)));
-        if (misses) atomicAdd(&a.counters[2], uint32_t(__popcll(misses)));
-    }
+    wave_count(a.counters, lane, active && status == BT_RAY_HIT, active && status == BT_RAY_INSIDE, active && status == BT_RAY_MISS);
 }
 
 }  // namespace
 
-bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height, bool shadowed) {
+bt_status launch_render(hipStream_t stream, const TerrainRef& g, const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, bool shadowed) {
     if (!a.block_count) return BT_OK;
-    const NormalModel nm = {P.model.min_height, P.model.max_height, normal_side_length(P.model)};
+    const NormalModel nm = {g.P.model.min_height, g.P.model.max_height, normal_side_length(g.P.model)};
     const uint32_t groups = (a.block_count + kRenderBlocksPerGroup - 1u) / kRenderBlocksPerGroup;
     if (shadowed)
-        render_kernel<true><<<groups, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
+        render_kernel<true><<<groups, kRenderThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, albedo_meta, albedo, nm, a, g.height);
     else
-        render_kernel<false><<<groups, kRenderThreads, 0, stream>>>(P, entries, m, atlas, albedo_meta, albedo, nm, a, height);
+        render_kernel<false><<<groups, kRenderThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, albedo_meta, albedo, nm, a, g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "render_kernel");
 }

@@ -31,33 +31,23 @@ __global__ __launch_bounds__(kOcclusionThreads) void occlusion_kernel(TreeParams
     if (active) {
         const uint32_t ray = a.first_ray + in_launch;  // (< count * direction_count <= BT_OCCLUSION_MAX_RAYS)
         const uint32_t direction = ray / a.count, point = ray - direction * a.count;
-        const float approximate_height = height ? *height : P.approximate_height;
-        const bool skip_above = m.border_size >= 1u && P.model.max_height >= P.model.min_height;
-        const double ceiling = double(height_of_value(P.model, 1.0f));
+        const Ground G = ground_view(P, entries, m, atlas, height);
         const double* q = a.positions + 3ull * point;
         const double* s = a.directions + 3ull * direction;
-        status = occlusion_status(P, entries, m, atlas, {q[0], q[1], q[2]}, {s[0], s[1], s[2]}, a.lift, a.distance, a.steps, double(approximate_height), skip_above,
-                                  ceiling);
+        status = occlusion_status(G, {q[0], q[1], q[2]}, {s[0], s[1], s[2]}, a.lift, a.distance, a.steps);
         a.status[uint64_t(point) * a.direction_count + direction] = uint8_t(status);
     }
 
     // the ray counters: the whole wave is here, whatever its lanes did above
-    const unsigned long long lit = __ballot(active && status == BT_RAY_MISS);
-    const unsigned long long occluded = __ballot(active && (status == BT_RAY_HIT || status == BT_RAY_INSIDE));
-    const unsigned long long invalid = __ballot(active && status == BT_RAY_INVALID);
-    if (lane == 0u) {
-        if (lit) atomicAdd(&a.counters[0], uint32_t(__popcll(lit)));
-        if (occluded) atomicAdd(&a.counters[1], uint32_t(__popcll(occluded)));
-        if (invalid) atomicAdd(&a.counters[2], uint32_t(__popcll(invalid)));
-    }
+    // (lit, occluded, invalid)
+    wave_count(a.counters, lane, active && status == BT_RAY_MISS, active && (status == BT_RAY_HIT || status == BT_RAY_INSIDE), active && status == BT_RAY_INVALID);
 }
 
 }  // namespace
 
-bt_status launch_occlusion(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                           const OcclusionArgs& a, const float* height) {
+bt_status launch_occlusion(hipStream_t stream, const TerrainRef& g, const OcclusionArgs& a) {
     if (!a.ray_count) return BT_OK;
-    occlusion_kernel<<<(a.ray_count + kOcclusionThreads - 1u) / kOcclusionThreads, kOcclusionThreads, 0, stream>>>(P, entries, m, atlas, a, height);
+    occlusion_kernel<<<(a.ray_count + kOcclusionThreads - 1u) / kOcclusionThreads, kOcclusionThreads, 0, stream>>>(g.P, g.entries, g.m, g.atlas, a, g.height);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BT_OK : hip_fail(e, "occlusion_kernel");
 }

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kThreads) void tile_tree_update_kernel(TreeParams P
     __shared__ uint32_t s_rel[2][kWaves], s_req[2][kWaves];
     // the tree's height lives on the device (bt_frame_update: the host's copy may lag a frame).  Kept beside P: writing into the
     // by-value kernel argument makes the compiler copy the struct to scratch
-    const float approximate_height = height ? *height : P.approximate_height;
+    const float approximate_height = tree_height(P.approximate_height, height);
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t ts = P.tree_size, per_layer = ts * ts, total = P.sides * P.lod_count * per_layer;
     uint32_t rel_base = 0, req_base = 0, sweep = 0;
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(128) void tile_tree_sample_kernel(TreeParams P, con
                                                                float4* __restrict__ out, float* heights, const float* height) {  // (heights / height may be ONE buffer — enqueue_height reads the old height, then overwrites it: no __restrict__)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    const float approximate_height = height ? *height : P.approximate_height;
+    const float approximate_height = tree_height(P.approximate_height, height);
     const V3 p = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
     const V3 surface = surface_position(P.model, p, double(approximate_height));
     float value[4];
@@ -193,6 +193,9 @@ TreeParams make_params(const bt_tile_tree* t) {
     for (uint32_t s = 0; s < 6; s++) P.view_coordinate[s] = s < t->sides ? coordinate_project_to_side(vc, s, t->model) : Coordinate{s, {0.0, 0.0}};
     return P;
 }
+
+// a read of the atlas: at.level0 is passed on without marking any layer written
+TerrainRef make_ground(const bt_tile_tree* t, const Attachment& at) { return {make_params(t), t->d_entries, at.meta, at.level0, t->d_height}; }
 
 // the host's mirror of the tree's height: refreshed whenever the stream has just been synchronised
 static void adopt_height(bt_tile_tree* t) {

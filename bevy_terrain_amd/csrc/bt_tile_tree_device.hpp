@@ -1,7 +1,10 @@
 // Device half of sample_attachment / sample_height (terrain_data/mod.rs:265-307) shared by the kernels that sample the
 // terrain through a tile tree: tile_tree_sample_kernel (bt_tile_tree.hip), raycast_kernel (bt_raycast.hip), render_kernel (bt_render.hip),
-// occlusion_kernel (bt_shadow.hip), collide_kernel and sweep_kernel (bt_collide.hip).  One definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there,
-// bit for bit.
+// occlusion_kernel (bt_shadow.hip), collide_kernel and sweep_kernel (bt_collide.hip), tile_tree_normal_kernel (bt_normal.hip).  One
+// definition, so a height a ray meets is the height bt_tile_tree_sample_attachment reports there, bit for bit.
+//
+// What such a kernel is handed is one thing on either side of the launch: TerrainRef on the host (make_ground of bt_tile_tree_host.hpp
+// builds it, every launch_* takes it), Ground on the device (ground_view builds it at kernel entry from the kernel's own parameters).
 //
 // Arithmetic: IEEE binary64 / binary32, one rounding per written operation, see bt_model.hpp for the definitions
 // where the reference defers to glam / libm.  compute_blend's log2 is the platform's (OCML here, libm in the oracle).
@@ -21,14 +24,21 @@ struct TreeParams {
     model::Coordinate view_coordinate[6];  // the view coordinate projected to every side
 };
 
-// bt_raycast.hip: `count` rays (device) against the tree's entries and one R16 attachment -> hits (device); height: the tree's device copy
-// of approximate_height (may be NULL: P.approximate_height)
-bt_status launch_raycast(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                         const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits, const float* height);
+// The terrain a query kernel samples, as the host hands it to a launcher: the tree's parameters and entries (device), one R16 attachment
+// (its meta and level 0, device) and the tree's device copy of approximate_height (may be NULL: P.approximate_height)
+struct TerrainRef {
+    TreeParams P;
+    const bt_tile_tree_entry* entries;
+    AttachmentMeta m;
+    const void* atlas;
+    const float* height;
+};
+
+// bt_raycast.hip: `count` rays (device) against the terrain -> hits (device)
+bt_status launch_raycast(hipStream_t stream, const TerrainRef& g, const bt_ray* rays, uint32_t count, uint32_t steps, uint32_t refine_rounds, bt_ray_hit* hits);
 // bt_normal.hip: the world normals (3 floats each) and, when up_dot is not NULL, their cosine against the mesh normal, of `count` world
-// positions (device) against the tree's entries and one R16 attachment; height as above
-bt_status launch_sample_normal(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                               const double* positions, uint32_t count, float* normals, float* up_dot, const float* height);
+// positions (device)
+bt_status launch_sample_normal(hipStream_t stream, const TerrainRef& g, const double* positions, uint32_t count, float* normals, float* up_dot);
 
 // bt_render.hip: one launch of bt_tile_tree_render.  A wave renders one 8 x 8 block of pixels, a workgroup kRenderBlocksPerGroup of them;
 // the launch covers blocks first_block .. first_block + block_count - 1 of the image's blocks_x x ceil(height / 8) blocks, row-major.
@@ -48,10 +58,9 @@ struct RenderArgs {
     uint8_t* shadow_plane;
     bt_sun_shadow shadow;
 };
-// albedo == NULL: the grey of the height attachment (BT_RENDER_NO_ALBEDO); height as above.  shadowed: the kernel instance that casts a
-// shadow ray from every pixel that met the ground (bt_tile_tree_render_shadowed); false: bt_tile_tree_render's, which reads no shadow field
-bt_status launch_render(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                        const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, const float* height, bool shadowed);
+// albedo == NULL: the grey of the height attachment (BT_RENDER_NO_ALBEDO).  shadowed: the kernel instance that casts a shadow ray from
+// every pixel that met the ground (bt_tile_tree_render_shadowed); false: bt_tile_tree_render's, which reads no shadow field
+bt_status launch_render(hipStream_t stream, const TerrainRef& g, const AttachmentMeta& albedo_meta, const void* albedo, const RenderArgs& a, bool shadowed);
 
 // bt_shadow.hip: one launch of bt_tile_tree_sun_occlusion.  Ray g = first_ray + r of the batch is point g % count, direction g / count; its
 // status goes to status[point * direction_count + direction].  A lane marches one ray, a workgroup kOcclusionThreads of them.
@@ -66,18 +75,15 @@ struct OcclusionArgs {
     uint8_t* status;     // count * direction_count (device), point-major
     uint32_t* counters;  // lit, occluded, invalid
 };
-bt_status launch_occlusion(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                           const OcclusionArgs& a, const float* height);
+bt_status launch_occlusion(hipStream_t stream, const TerrainRef& g, const OcclusionArgs& a);
 
-// bt_collide.hip: SPHERE CONTACT of `count` spheres / SPHERE SWEEP of `count` sweeps (device) against the tree's entries and one R16
-// attachment -> contacts / hits (device); one wave each, kCollideWavesPerGroup of them per workgroup; height as above
+// bt_collide.hip: SPHERE CONTACT of `count` spheres / SPHERE SWEEP of `count` sweeps (device) against the terrain -> contacts / hits
+// (device); one wave each, kCollideWavesPerGroup of them per workgroup
 constexpr uint32_t kCollideThreads = 256;
 constexpr uint32_t kCollideWavesPerGroup = kCollideThreads / 64u;
-bt_status launch_collide(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                         const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds, bt_sphere_contact* contacts, const float* height);
-bt_status launch_sweep(hipStream_t stream, const TreeParams& P, const bt_tile_tree_entry* entries, const AttachmentMeta& m, const void* atlas,
-                       const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections, uint32_t refine_rounds, bt_sweep_hit* hits,
-                       const float* height);
+bt_status launch_collide(hipStream_t stream, const TerrainRef& g, const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds, bt_sphere_contact* contacts);
+bt_status launch_sweep(hipStream_t stream, const TerrainRef& g, const bt_sphere_sweep* sweeps, uint32_t count, uint32_t steps, uint32_t bisections,
+                       uint32_t refine_rounds, bt_sweep_hit* hits);
 
 // bt_geometry.hip: what TERRAIN GEOMETRY (include/bevy_terrain_amd.h) takes from the tree besides its entries
 struct GeometryParams {
@@ -209,6 +215,34 @@ __device__ __forceinline__ void sample_surface(const TreeParams& P, const bt_til
 
 // sample_height's last step (terrain_data/mod.rs:297-307): f32::lerp(min_height, max_height, value.x)
 __device__ __forceinline__ float height_of_value(const model::Model& model, float value) { return model.min_height + (model.max_height - model.min_height) * value; }
+
+// the tree's approximate_height as a kernel reads it: the device copy the frame chain writes on the stream (bt_frame_update: the host's
+// copy in P may lag a frame), the host's where the caller has none
+__device__ __forceinline__ float tree_height(float host_height, const float* height) { return height ? *height : host_height; }
+
+// The terrain as a device function samples it: the kernel's own parameters and the three values every sample of a query derives from them.
+// P and m are held by value: the copy dissolves into the kernel's argument loads, where a reference to the argument turned the height
+// into a load through a generic pointer held in vector registers (ten more VGPRs in occlusion_kernel and render_kernel<true>).
+// skip_above / ceiling, the ceiling skip of ray_eval and sphere_contact (bt_raycast.hip's header has the argument): a sample whose altitude
+// is above `ceiling` = lerp(min_height, max_height, 1.0f) is above the ground whatever the atlas holds, provided the tiles have a border
+// and the height range is not inverted.
+struct Ground {
+    TreeParams P;
+    const bt_tile_tree_entry* entries;
+    AttachmentMeta m;
+    const void* atlas;
+    double approximate_height;
+    bool skip_above;
+    double ceiling;
+};
+// at kernel entry, from the kernel's __restrict__ parameters: the ONE place these three expressions are written
+__device__ __forceinline__ Ground ground_view(const TreeParams& P, const bt_tile_tree_entry* __restrict__ entries, const AttachmentMeta& m,
+                                              const void* __restrict__ atlas, const float* __restrict__ height) {
+    return {P, entries, m, atlas, double(tree_height(P.approximate_height, height)), m.border_size >= 1u && P.model.max_height >= P.model.min_height,
+            double(height_of_value(P.model, 1.0f))};
+}
+// sample_surface of the ground's own attachment
+__device__ __forceinline__ void sample_ground(const Ground& G, model::V3 surface, float value[4]) { sample_surface(G.P, G.entries, G.m, G.atlas, surface, value); }
 
 #endif  // __HIPCC__
 

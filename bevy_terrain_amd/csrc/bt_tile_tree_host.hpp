@@ -58,6 +58,7 @@ struct bt_tile_tree {
 namespace bt {
 
 TreeParams make_params(const bt_tile_tree* t);  // what the kernels read of the tree, the host's copy of the height included
+TerrainRef make_ground(const bt_tile_tree* t, const Attachment& at);  // what a query's launcher takes: the tree and one attachment's level 0
 // after every synchronisation of the context's stream on the tree's behalf: the height a frame left in pinned memory becomes the host's
 // copy, and the staging table may be rewritten
 void synchronised(bt_tile_tree* t);

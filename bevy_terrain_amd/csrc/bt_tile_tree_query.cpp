@@ -1,8 +1,11 @@
 // The queries that read the terrain through a tile tree: bt_tile_tree_raycast, bt_tile_tree_collide_spheres, bt_tile_tree_sweep_spheres,
 // bt_tile_tree_sun_occlusion, bt_tile_tree_render(_shadowed), bt_tile_tree_sample_normal and the geometry calls.  Each validates, stages its
 // inputs in scratch of the context (bt::Scratch: grown on demand, kept until bt_ctx_trim), calls the launcher of its kernel file
-// (bt_raycast.hip, bt_collide.hip, bt_shadow.hip, bt_render.hip, bt_normal.hip, bt_geometry.hip) and copies the results back.
+// (bt_raycast.hip, bt_collide.hip, bt_shadow.hip, bt_render.hip, bt_normal.hip, bt_geometry.hip) and copies the results back.  The two
+// shapes that sequence takes are here once: staged_batch (one array in, one launch, one array out: ray casting, contacts, sweeps) and
+// counted_run (counters and planes in scratch, the launches in pieces: rendering, sun occlusion).
 #include <cmath>
+#include <initializer_list>
 
 #include "bt_tile_tree_host.hpp"
 
@@ -43,13 +46,14 @@ bt_status query_check(const char* who, const bt_tile_tree* t, const bt_atlas* a,
 }  // namespace bt
 
 namespace {
-// what bt_tile_tree_collide_spheres and bt_tile_tree_sweep_spheres share once their limits hold: the batch goes to the ray queries'
-// scratch, `launch` runs on it (in, out on the device), the results come back
+// what bt_tile_tree_raycast, bt_tile_tree_collide_spheres and bt_tile_tree_sweep_spheres share once their limits hold: the batch goes to
+// the ray queries' scratch, `launch` runs on it (in, out on the device), the results come back.  in_name / out_name: what the call's
+// message calls a NULL array
 template <class In, class Out, class Launch>
-bt_status collide_batch(const char* who, bt_tile_tree* t, const In* in, uint32_t count, Out* out, Launch launch) {
+bt_status staged_batch(const char* who, bt_tile_tree* t, const char* in_name, const In* in, uint32_t count, const char* out_name, Out* out, Launch launch) {
     if (!count) return BT_OK;
     if (!in || !out) {
-        set_error("%s: NULL %s", who, in ? "output array" : "input array");
+        set_error("%s: NULL %s", who, in ? out_name : in_name);
         return BT_ERR_INVALID_ARGUMENT;
     }
     bt_ctx* ctx = t->ctx;
@@ -63,6 +67,42 @@ bt_status collide_batch(const char* who, bt_tile_tree* t, const In* in, uint32_t
     BT_HIP(hipMemcpyAsync(out, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
     BT_HIP(hipStreamSynchronize(s));
     synchronised(t);
+    return BT_OK;
+}
+
+uint64_t pad256(uint64_t v) { return (v + 255u) & ~255ull; }
+
+// a plane of results in scratch and where the caller wants it (host NULL: not wanted)
+struct Plane {
+    void* host;
+    const void* dev;
+    uint64_t bytes;
+};
+
+// What render() and bt_tile_tree_sun_occlusion share once their scratch is laid out: three counters in the first 16 bytes of the scratch
+// `dev` (the planes start at byte 256), cleared here; `total` units of work issued as launch(first, n) in pieces of per_launch; then the
+// counters and the planes come back, the stream is synchronised once, and *stats = {launches, the three counters}.
+template <class Stats, class Launch>
+bt_status counted_run(const char* who, bt_tile_tree* t, uint8_t* dev, uint64_t total, uint32_t per_launch, std::initializer_list<Plane> planes, Stats* stats,
+                      Launch launch) {
+    hipStream_t s = t->ctx->stream;
+    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
+    uint32_t launches = 0;
+    for (uint64_t first = 0; first < total; first += per_launch, launches++) {
+        if (bt_status st = launch(uint32_t(first), uint32_t(std::min<uint64_t>(per_launch, total - first)))) {
+            (void)hipStreamSynchronize(s);
+            return st;
+        }
+    }
+    // nothing is copied back before the last launch has been queued
+    uint32_t counters[4] = {};
+    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
+    for (const Plane& p : planes)
+        if (e == hipSuccess && p.host) e = hipMemcpyAsync(p.host, p.dev, p.bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
+    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
+    synchronised(t);
+    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
     return BT_OK;
 }
 }  // namespace
@@ -86,26 +126,9 @@ bt_status bt_tile_tree_raycast(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const 
                   unsigned(BT_RAYCAST_MAX_SAMPLES));
         return BT_ERR_INVALID_ARGUMENT;
     }
-    if (!count) return BT_OK;
-    if (!rays || !hits) {
-        set_error("bt_tile_tree_raycast: NULL %s", rays ? "hits_out" : "rays");
-        return BT_ERR_INVALID_ARGUMENT;
-    }
-    bt_ctx* ctx = t->ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const uint64_t in_bytes = sizeof(bt_ray) * uint64_t(count), out_bytes = sizeof(bt_ray_hit) * uint64_t(count);
-    if (bt_status st = ctx->raycast.reserve(ctx, in_bytes + out_bytes)) return st;
-    uint8_t* dev = (uint8_t*)ctx->raycast.dev;
-    BT_HIP(hipMemcpyAsync(dev, rays, in_bytes, hipMemcpyHostToDevice, s));
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    if (bt_status st = launch_raycast(s, make_params(t), t->d_entries, at.meta, at.level0, (const bt_ray*)dev, count, steps, refine_rounds,
-                                      (bt_ray_hit*)(dev + in_bytes), t->d_height))
-        return st;
-    BT_HIP(hipMemcpyAsync(hits, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, s));
-    BT_HIP(hipStreamSynchronize(s));
-    synchronised(t);
-    return BT_OK;
+    return staged_batch("bt_tile_tree_raycast", t, "rays", rays, count, "hits_out", hits, [&](hipStream_t s, const bt_ray* in, bt_ray_hit* out) {
+        return launch_raycast(s, make_ground(t, at), in, count, steps, refine_rounds, out);
+    });
 }
 
 bt_status bt_tile_tree_collide_spheres(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_sphere* spheres, uint32_t count, uint32_t refine_rounds,
@@ -125,9 +148,8 @@ bt_status bt_tile_tree_collide_spheres(bt_tile_tree* t, bt_atlas* a, uint32_t ai
                   unsigned(BT_COLLIDE_MAX_SAMPLES));
         return BT_ERR_INVALID_ARGUMENT;
     }
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    return collide_batch(who, t, spheres, count, contacts, [&](hipStream_t s, const bt_sphere* in, bt_sphere_contact* out) {
-        return launch_collide(s, make_params(t), t->d_entries, at.meta, at.level0, in, count, refine_rounds, out, t->d_height);
+    return staged_batch(who, t, "input array", spheres, count, "output array", contacts, [&](hipStream_t s, const bt_sphere* in, bt_sphere_contact* out) {
+        return launch_collide(s, make_ground(t, at), in, count, refine_rounds, out);
     });
 }
 
@@ -150,9 +172,8 @@ bt_status bt_tile_tree_sweep_spheres(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
                   refine_rounds + 1u, unsigned(BT_COLLIDE_MAX_SAMPLES));
         return BT_ERR_INVALID_ARGUMENT;
     }
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    return collide_batch(who, t, sweeps, count, hits, [&](hipStream_t s, const bt_sphere_sweep* in, bt_sweep_hit* out) {
-        return launch_sweep(s, make_params(t), t->d_entries, at.meta, at.level0, in, count, steps, bisections, refine_rounds, out, t->d_height);
+    return staged_batch(who, t, "input array", sweeps, count, "output array", hits, [&](hipStream_t s, const bt_sphere_sweep* in, bt_sweep_hit* out) {
+        return launch_sweep(s, make_ground(t, at), in, count, steps, bisections, refine_rounds, out);
     });
 }
 
@@ -208,11 +229,10 @@ bt_status render(const char* who, bool shadowed, bt_tile_tree* t, bt_atlas* a, u
     }
     bt_ctx* ctx = t->ctx;
     BT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary (the shadow plane last)
-    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
-    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad(12u * pixels) : 0u),
-                   s_off = c_off + (out_rgba ? pad(4u * pixels) : 0u), o_off = s_off + (out_status ? pad(pixels) : 0u), need = o_off + (out_shadow ? pad(pixels) : 0u);
+    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad256(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad256(12u * pixels) : 0u),
+                   s_off = c_off + (out_rgba ? pad256(4u * pixels) : 0u), o_off = s_off + (out_status ? pad256(pixels) : 0u),
+                   need = o_off + (out_shadow ? pad256(pixels) : 0u);
     if (bt_status st = ctx->render.reserve(ctx, need)) return st;
     uint8_t* dev = (uint8_t*)ctx->render.dev;
     RenderArgs args{};
@@ -233,31 +253,15 @@ bt_status render(const char* who, bool shadowed, bt_tile_tree* t, bt_atlas* a, u
     const uint64_t block_samples = 64ull * (uint64_t(steps) + 1u + 63ull * refine_rounds + (shadowed ? uint64_t(shadow->steps) + 1u : 0u));
     uint32_t per_launch = uint32_t(std::min<uint64_t>(blocks, uint64_t(BT_RAYCAST_MAX_SAMPLES) / block_samples));
     if (per_launch >= args.blocks_x) per_launch -= per_launch % args.blocks_x;
-    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
-    const TreeParams P = make_params(t);
-    uint32_t launches = 0;
-    for (uint32_t first = 0; first < blocks; first += per_launch, launches++) {
-        args.first_block = first;
-        args.block_count = std::min(per_launch, blocks - first);
-        // a read of the atlas: level0 is passed on without marking any layer written
-        if (bt_status st = launch_render(s, P, t->d_entries, at.meta, at.level0, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, t->d_height, shadowed)) {
-            (void)hipStreamSynchronize(s);
-            return st;
-        }
-    }
-    // nothing is copied back before the last launch has been queued
-    uint32_t counters[4] = {};
-    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_t) e = hipMemcpyAsync(out_t, args.t, 8u * pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_status) e = hipMemcpyAsync(out_status, args.status, pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, args.normal, 12u * pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_rgba) e = hipMemcpyAsync(out_rgba, args.rgba, 4u * pixels, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_shadow) e = hipMemcpyAsync(out_shadow, args.shadow_plane, pixels, hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
-    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
-    synchronised(t);
-    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
-    return BT_OK;
+    const TerrainRef ground = make_ground(t, at);
+    return counted_run(who, t, dev, blocks, per_launch,
+                       {{out_t, args.t, 8u * pixels}, {out_status, args.status, pixels}, {out_normal, args.normal, 12u * pixels}, {out_rgba, args.rgba, 4u * pixels},
+                        {out_shadow, args.shadow_plane, pixels}},
+                       stats, [&](uint32_t first, uint32_t n) {
+                           args.first_block = first;
+                           args.block_count = n;
+                           return launch_render(ctx->stream, ground, albedo.meta, has_albedo ? albedo.level0 : nullptr, args, shadowed);
+                       });
 }
 }  // namespace
 
@@ -289,11 +293,9 @@ bt_status bt_tile_tree_sun_occlusion(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // the scratch (the ray queries': bt_ctx::raycast): the counters, the points, the directions, the statuses, each from a 256-byte boundary
-    auto pad = [](uint64_t v) { return (v + 255u) & ~255ull; };
-    const uint64_t p_bytes = 24ull * count, d_bytes = 24ull * direction_count, p_off = 256u, d_off = p_off + pad(p_bytes), s_off = d_off + pad(d_bytes);
-    if (bt_status st = ctx->raycast.reserve(ctx, s_off + pad(rays))) return st;
+    const uint64_t p_bytes = 24ull * count, d_bytes = 24ull * direction_count, p_off = 256u, d_off = p_off + pad256(p_bytes), s_off = d_off + pad256(d_bytes);
+    if (bt_status st = ctx->raycast.reserve(ctx, s_off + pad256(rays))) return st;
     uint8_t* dev = (uint8_t*)ctx->raycast.dev;
-    BT_HIP(hipMemsetAsync(dev, 0, 16, s));
     BT_HIP(hipMemcpyAsync(dev + p_off, positions, p_bytes, hipMemcpyHostToDevice, s));
     BT_HIP(hipMemcpyAsync(dev + d_off, directions, d_bytes, hipMemcpyHostToDevice, s));
     OcclusionArgs args{};
@@ -308,26 +310,12 @@ bt_status bt_tile_tree_sun_occlusion(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
     args.counters = (uint32_t*)dev;
     // a launch: whole waves whose worst case, 64 * (steps + 1) samples each, stays within BT_RAYCAST_MAX_SAMPLES (63 waves at 4096 steps)
     const uint32_t per_launch = 64u * uint32_t(uint64_t(BT_RAYCAST_MAX_SAMPLES) / (64ull * (uint64_t(steps) + 1u)));
-    const TreeParams P = make_params(t);
-    uint32_t launches = 0;
-    for (uint64_t first = 0; first < rays; first += per_launch, launches++) {
-        args.first_ray = uint32_t(first);
-        args.ray_count = uint32_t(std::min<uint64_t>(per_launch, rays - first));
-        // a read of the atlas: at.level0 is passed on without marking any layer written
-        if (bt_status st = launch_occlusion(s, P, t->d_entries, at.meta, at.level0, args, t->d_height)) {
-            (void)hipStreamSynchronize(s);
-            return st;
-        }
-    }
-    // nothing is copied back before the last launch has been queued
-    uint32_t counters[4] = {};
-    hipError_t e = hipMemcpyAsync(counters, dev, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_status, args.status, rays, hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);  // (also when a copy was refused: `counters` must not be written after the return)
-    if (e != hipSuccess || w != hipSuccess) return hip_fail(e != hipSuccess ? e : w, who);
-    synchronised(t);
-    if (stats) *stats = {launches, counters[0], counters[1], counters[2]};
-    return BT_OK;
+    const TerrainRef ground = make_ground(t, at);
+    return counted_run(who, t, dev, rays, per_launch, {{out_status, args.status, rays}}, stats, [&](uint32_t first, uint32_t n) {
+        args.first_ray = first;
+        args.ray_count = n;
+        return launch_occlusion(s, ground, args);
+    });
 }
 
 bt_status bt_tile_tree_render(bt_tile_tree* t, bt_atlas* a, uint32_t ai, const bt_render_camera* camera, uint32_t steps, uint32_t refine_rounds, double* out_t,
@@ -357,9 +345,8 @@ bt_status bt_tile_tree_sample_normal(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
     if (bt_status st = ctx->normal.reserve(ctx, in_bytes + n_bytes + d_bytes)) return st;
     uint8_t* dev = (uint8_t*)ctx->normal.dev;
     BT_HIP(hipMemcpyAsync(dev, positions, in_bytes, hipMemcpyHostToDevice, s));
-    // a read of the atlas: at.level0 is passed on without marking any layer written
-    if (bt_status st = launch_sample_normal(s, make_params(t), t->d_entries, at.meta, at.level0, (const double*)dev, count, (float*)(dev + in_bytes),
-                                            up_dot ? (float*)(dev + in_bytes + n_bytes) : nullptr, t->d_height))
+    if (bt_status st = launch_sample_normal(s, make_ground(t, at), (const double*)dev, count, (float*)(dev + in_bytes),
+                                            up_dot ? (float*)(dev + in_bytes + n_bytes) : nullptr))
         return st;
     BT_HIP(hipMemcpyAsync(normals, dev + in_bytes, n_bytes, hipMemcpyDeviceToHost, s));
     if (up_dot) BT_HIP(hipMemcpyAsync(up_dot, dev + in_bytes + n_bytes, d_bytes, hipMemcpyDeviceToHost, s));
