@@ -26,28 +26,32 @@
 // liberty: t / 65535.0f is evaluated as q0 = t*r, e = fma(-q0, 65535, t), q = fma(e, r, q0) with
 // r = RN(1/65535) (Markstein's correctly rounded division); equality with `/` for all 65536 inputs is
 // checked on the device by bt_selftest() and on the CPU by tests/test_oracle_preprocess.py.
+//
+// Where things are.  This file is the ONE device translation unit of the fused path: the shared device vocabulary, fused_main, fused_tail and
+// fused_direct reach the compiler in that order (the kernels are hand-scheduled against what it makes of the unit as a whole), then
+// selftest_kernel and, on the host, fused_launch_range — the only host code that names a kernel instance — and bt_selftest.  The headers
+// included inside the namespace below are this file's text, not units of their own.
+//   bt_fused_args.hpp   : what kernels, launcher and planner share: the constants, MainItem, FusedArgs, split_axis, MainShared, FusedJobDev, FusedState
+//   bt_fused_common.hpp : the device vocabulary of all three families
+//   here                : fused_main (fused_main_chunks, fused_main_kernel, fused_corner_kernel, the sites of bt_fused_debug.inc)
+//   bt_fused_tail.hpp   : the apron rows, the R16 / Rgba8 reductions, the pulled seam regions, fused_tail_kernel
+//   here                : fused_direct (the Rgba8 row helpers, fused_direct_rgba8_kernel)
+//   bt_fused_plan.cpp   : the planner (fused_plan and its stages) and what a run asks of the plan afterwards; host code only
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
-#include "bt_internal.hpp"
+#include "bt_fused_args.hpp"
 
 namespace bt {
 
 namespace {
 
-constexpr uint32_t kInvalid = 0xFFFFFFFFu;
-
 #include "bt_stitch.hpp"  // project_to_side, stitch_source, stitch_region_body (the cube's cross-face seam regions)
 
-// Ablation switches of the profiling build (tools/, -DBT_DEBUG_HOOKS): compiled out of the product library, where
-// the branches they guard fold away and no environment variable is read.
-#ifdef BT_DEBUG_HOOKS
-#define BT_ABLATE(A, bits) ((A).ablate & (bits))
-#else
-#define BT_ABLATE(A, bits) 0u
-#endif
-constexpr uint32_t kMainRows = 8;                // centre rows per fused_main workgroup (multiple of 4)
+#include "bt_fused_common.hpp"
+
 #ifndef BT_DMA_POS
 #define BT_DMA_POS 0
 #endif
@@ -57,370 +61,6 @@ constexpr uint32_t kMainRows = 8;                // centre rows per fused_main w
 // first quad the clean 16k job is 0 .. 1.8 % faster (bimodal from run to run), behind rows 2 / 3 ~1 % faster with the masked job 2 % slower,
 // behind the second quad 3 % slower — inside the noise that matters, so the issue stays at the top.
 constexpr uint32_t kDmaPos = BT_DMA_POS;
-constexpr uint32_t kMaxBorder = 8;
-
-struct MainItem {  // one finest-LOD tile
-    uint32_t side, x, y, atlas_index, raster;
-};
-
-struct FusedArgs {
-    AttachmentMeta m;
-    uint16_t* atlas;
-    const RasterDev* rasters;
-    const MainItem* items;
-    const uint32_t* grids;         // per (side, lod): n x n atlas indices, x-major (x * n + y), INVALID = absent
-    uint32_t grid_lod_lo, grid_lod_hi, grid_sides;  // the grids of (side, lod), lod_lo <= lod <= lod_hi, follow each other side-major, LODs ascending
-    // A job queued onto a fresh atlas holds its tiles in the reference's allocation order (preprocessor.rs:234-343: per side the finest
-    // LOD first, x-major, then each coarser LOD), i.e. atlas index = arithmetic on the coordinate.  regular != 0: the host checked every
-    // grid entry against that closed form, and a lookup is a handful of scalar operations instead of a dependent load from the grids
-    // (fused_tail was a chain of five dependent round trips, three of them lookups).
-    uint32_t regular, reg_first;
-    // fused_tail on a cube (round 5): the cross-face apron regions of the LODs fused_main produced — their sources, the neighbour faces'
-    // centres, are complete when the tail starts — ride in the tail launch as extra workgroups, one region each (stitch.wgsl:12-51, 79-118),
-    // instead of waiting for a launch of their own behind it.  seam_skip: the tail's own apron-row workgroups leave those regions alone.
-    const TaskDev* seam_tasks;
-    uint32_t seam_count, seam_skip;
-    // round 6: the cross-face regions of the LODs the tail ITSELF produces ride in it too — not as copies of the neighbour face's centre (another
-    // workgroup of this launch is still writing it) but PULLED: evaluated from the tail's input LOD on the neighbour face with the tail's own
-    // reduction (TaskDev::raster = LODs below the input, rel_index[region] = the neighbour tile's x << 16 | y).  seam_pull: the tail's pushes then
-    // leave a region beyond exactly one face edge alone instead of clamping into it (a pull workgroup writes it) — and no stitch launch follows.
-    uint32_t seam_pull;
-    uint32_t tail_extras;  // fused_tail: apron blocks per side (the top / bottom apron rows — Rgba8: and columns — of the LODs above)
-    float tlx, tly, brx, bry;
-    uint32_t lod;         // finest LOD of this launch (fused_main) / input LOD (fused_tail)
-    uint32_t levels;      // LODs produced by this launch: main 1..3 (lod, lod-1, lod-2); tail 1..3 below lod
-    uint32_t item_count;  // fused_main: tiles
-    uint32_t groups;      // fused_main: row groups per tile
-    uint32_t sides;       // fused_tail: 1 or 6
-    uint32_t lds_pitch;   // fused_main: texels per staged source row (multiple of 8)
-    uint32_t lds_rows;    // fused_main: staged source rows that fit
-    uint32_t apron_lods;  // fused_tail: LODs lod, lod+1, ... (this many) get their top / bottom apron rows from extra workgroups
-    uint32_t rotate_priority;  // fused_main: wave priority rotates with the chunk index (see fused_main_chunks)
-    uint32_t apron_cols;  // fused_tail (Rgba8 after fused_direct, which writes centres only): ... and their left / right apron columns
-    // fused_main / fused_direct: every finest tile of the job still holds bt_atlas_create's zeros (Attachment::written, decided by the host per
-    // run): "the previous value" of a pixel without data (split.wgsl:34-42) IS 0 — taken as a constant instead of fetched from the atlas.  Both
-    // reference examples are this case (clear_attachment, then one dataset per attachment: preprocess_planar.rs:16-60).
-    uint32_t prev_zero;
-    // fused_main: the tile's 2b apron rows (first / last chunk only) read their source rows from global memory instead of the staged window, which
-    // then holds the centre rows alone — set by the host when that is what lets four workgroups share a CU's LDS (source-to-tile ratios from ~1.25)
-    uint32_t apron_global;
-    // fused_main, run-time-pitch DMA variant: ONE staging buffer — the next chunk's rows are requested when every wave has read this chunk's (no overlap inside the
-    // workgroup; the CU's other workgroups cover) — set by the host when two buffers would keep a fourth workgroup off the CU's LDS (ratios from ~1.36 at T = 512)
-    uint32_t single_buffer;
-    uint32_t ablate;      // debug only (env BT_FUSED_ABLATE): 1 no pyramid, 2 no finest stores, 4 no parent stores, 64 no grand-parent stores (static path), 8 no staging loads, 16 prologue only, 256 / 512 finest / parent stores without arithmetic (use with 16); skeleton shapes: 65536 parent rows in bursts of four chunks, 262144 parent rows as 16-byte stores, 1048576 finest rows as 16-byte stores
-};
-
-// t / 65535.0f, correctly rounded, in 3 VALU ops (see header)
-__device__ __forceinline__ float unorm16_to_float(uint32_t t) {
-    const float x = float(t);
-    const float r = 1.0f / 65535.0f;
-    const float q0 = x * r;
-    const float e = __builtin_fmaf(-q0, 65535.0f, x);
-    return __builtin_fmaf(e, r, q0);
-}
-// floor(0.5 + 65535 * clamp(e, 0, 1)): med3 clamps (no NaN reaches here); the u32 conversion truncates,
-// which is floor for the non-negative argument
-__device__ __forceinline__ uint32_t float_to_unorm16(float e) {
-    const float cl = __builtin_amdgcn_fmed3f(e, 0.0f, 1.0f);
-    return uint32_t(0.5f + 65535.0f * cl);
-}
-__device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
-
-struct Axis {
-    int i0, i1;
-    float fr;
-};
-
-// split.wgsl:25-32 for centre coordinate r (0..c-1) of tile index `tile` (see bt_kernels.hip split_axis)
-// (also evaluated on the host, bit for bit the same IEEE operations, to size the LDS window exactly)
-__host__ __device__ __forceinline__ Axis split_axis(uint32_t r, uint32_t c, uint32_t tile, float scale, float lo, float hi, uint32_t dim) {
-    const float tc = float(r) / float(c);
-    const float s = (float(tile) + tc) / scale;
-    const float u = (s - lo) / (hi - lo);
-    const float q = u * float(dim) - 0.5f;
-    const float fl = floorf(q);
-    Axis a;
-    a.fr = q - fl;
-    const int i = int(fl);
-    const int last = int(dim) - 1;
-    const int j = i + 1;
-    a.i0 = i < 0 ? 0 : (i > last ? last : i);
-    a.i1 = j < 0 ? 0 : (j > last ? last : j);
-    return a;
-}
-
-__device__ __forceinline__ uint32_t grid_lookup(const FusedArgs& A, uint32_t side, uint32_t lod, int x, int y) {
-    const int n = int(1u << lod);
-    if (x < 0 || y < 0 || x >= n || y >= n) return kInvalid;
-    if (lod < A.grid_lod_lo || lod > A.grid_lod_hi || side >= A.grid_sides) return kInvalid;
-    if (A.regular) {  // sum of 4^l for lod < l <= lod_hi tiles precede the LOD's on its side, lod_lo .. lod_hi make a side
-        const uint32_t hi4 = 4u << (2u * A.grid_lod_hi);
-        return A.reg_first + side * ((hi4 - (1u << (2u * A.grid_lod_lo))) / 3u) + (hi4 - (4u << (2u * lod))) / 3u + uint32_t(x) * uint32_t(n) + uint32_t(y);
-    }
-    // offset of the (side, lod) grid: computed, not looked up (one dependent load less in every lookup chain):
-    // sum of 4^l for lod_lo <= l < lod = (4^lod - 4^lod_lo) / 3
-    const uint32_t lo4 = 1u << (2u * A.grid_lod_lo), per_side = ((4u << (2u * A.grid_lod_hi)) - lo4) / 3u;
-    const uint32_t off = side * per_side + ((1u << (2u * lod)) - lo4) / 3u;
-    return A.grids[off + uint32_t(x) * uint32_t(n) + uint32_t(y)];
-}
-
-// A tile of some LOD together with its 8 same-face neighbours (stitch.wgsl:57-66 regions N, E, S, W, NW,
-// NE, SE, SW).  Out-of-face neighbours count as absent here; on a cube the face-edge tiles are re-stitched
-// afterwards by the generic kernel.  Named members: indexed arrays would be demoted to scratch / LDS.
-struct TileNb {
-    uint32_t self, n, e, s, w;
-};
-
-__device__ __forceinline__ TileNb load_tile_nb(const FusedArgs& A, uint32_t side, uint32_t lod, uint32_t x, uint32_t y) {
-    const int ix = int(x), iy = int(y);
-    TileNb t;
-    t.self = grid_lookup(A, side, lod, ix, iy);
-    t.n = grid_lookup(A, side, lod, ix, iy - 1);
-    t.e = grid_lookup(A, side, lod, ix + 1, iy);
-    t.s = grid_lookup(A, side, lod, ix, iy + 1);
-    t.w = grid_lookup(A, side, lod, ix - 1, iy);
-    return t;
-}
-
-// Write centre pixel (cx, cy) of tile (side, lod, tx, ty) — atlas layer `self_index` — and every apron
-// texel that copies it (stitch.wgsl:53-118 inverted):
-//  - the tile's own apron where the neighbour on that side is absent (repeat_data clamps into the centre),
-//  - the facing apron of each existing neighbour whose b-wide strip contains the pixel.
-// Neighbours are looked up only for the few pixels within b of a tile edge.
-template <bool kCentre = true, typename TT = uint16_t>
-__device__ __forceinline__ void push_pixel(const FusedArgs& A, uint32_t side, uint32_t lod, uint32_t tx, uint32_t ty,
-                                           uint32_t self_index, uint32_t cx, uint32_t cy, TT v) {
-    const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size;
-    const uint64_t tile_texels = uint64_t(T) * T;
-    TT* atlas = reinterpret_cast<TT*>(A.atlas);
-    TT* self = atlas + uint64_t(self_index) * tile_texels;
-    if (kCentre) self[uint64_t(b + cy) * T + b + cx] = v;  // (false: the caller stored the centre texel, e.g. as half of a pair)
-    const int ex = cx < b ? -1 : (cx >= c - b ? 1 : 0);
-    const int ey = cy < b ? -1 : (cy >= c - b ? 1 : 0);
-    if (ex == 0 && ey == 0) return;
-    const uint32_t o = b + c;
-    const int ix = int(tx), iy = int(ty);
-    // a neighbour at offset (dx, dy) sees our centre (cx, cy) at texture (b + cx - dx*c, b + cy - dy*c)
-    const uint32_t ax = uint32_t(int(b + cx) - ex * int(c)), ay = uint32_t(int(b + cy) - ey * int(c));
-    // (cube, A.seam_pull: a neighbour beyond exactly ONE face edge lives on another face and a pull workgroup of this launch writes that region)
-    const int nn = int(1u << lod);
-    auto cross_face = [&](int x, int y) { return A.seam_pull != 0 && ((x < 0 || x >= nn) != (y < 0 || y >= nn)); };
-    if (ex != 0) {
-        const uint32_t n = grid_lookup(A, side, lod, ix + ex, iy);
-        if (n != kInvalid) {
-            atlas[uint64_t(n) * tile_texels + uint64_t(b + cy) * T + ax] = v;
-        } else if (cross_face(ix + ex, iy)) {
-        } else if (cx == 0 || cx == c - 1) {  // absent: our outermost column is replicated into our own apron
-            const uint32_t x0 = ex < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++) self[uint64_t(b + cy) * T + x0 + j] = v;
-        }
-    }
-    if (ey != 0) {
-        const uint32_t n = grid_lookup(A, side, lod, ix, iy + ey);
-        if (n != kInvalid) {
-            atlas[uint64_t(n) * tile_texels + uint64_t(ay) * T + b + cx] = v;
-        } else if (cross_face(ix, iy + ey)) {
-        } else if (cy == 0 || cy == c - 1) {
-            const uint32_t y0 = ey < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++) self[uint64_t(y0 + j) * T + b + cx] = v;
-        }
-    }
-    if (ex != 0 && ey != 0) {
-        const uint32_t n = grid_lookup(A, side, lod, ix + ex, iy + ey);
-        if (n != kInvalid) {
-            atlas[uint64_t(n) * tile_texels + uint64_t(ay) * T + ax] = v;
-        } else if (cross_face(ix + ex, iy + ey)) {
-        } else if ((cx == 0 || cx == c - 1) && (cy == 0 || cy == c - 1)) {  // corner region clamps both axes
-            const uint32_t x0 = ex < 0 ? 0u : o, y0 = ey < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++)
-                for (uint32_t i = 0; i < b; i++) self[uint64_t(y0 + j) * T + x0 + i] = v;
-        }
-    }
-}
-
-// push_pixel in two halves for fused_tail, which is a latency chain: push_targets does the neighbour LOOKUPS of a centre pixel —
-// coordinates only, no data — so that they are in flight together with the thread's other loads; push_store does the stores.
-// (One memory counter covers loads and stores on this ISA: a lookup issued after a store waits for that store, so four
-// push_pixel calls in a row cost an edge thread four round trips.)  A 2 x 2 pixel block with even coordinates shares its
-// targets when b is even.
-struct PushNb {
-    int ex, ey;
-    uint32_t nx, ny, nxy;
-    uint32_t skip;  // bit 0 / 1 / 2: the x / y / diagonal neighbour lies beyond exactly one face edge of a cube and a pull workgroup writes that region (A.seam_pull)
-};
-__device__ __forceinline__ PushNb push_targets(const FusedArgs& A, uint32_t side, uint32_t lod, uint32_t tx, uint32_t ty, uint32_t cx, uint32_t cy, bool active) {
-    const uint32_t b = A.m.border_size, c = A.m.center_size;
-    PushNb t{0, 0, kInvalid, kInvalid, kInvalid, 0u};
-    if (!active) return t;
-    t.ex = cx < b ? -1 : (cx >= c - b ? 1 : 0);
-    t.ey = cy < b ? -1 : (cy >= c - b ? 1 : 0);
-    if (t.ex != 0) t.nx = grid_lookup(A, side, lod, int(tx) + t.ex, int(ty));
-    if (t.ey != 0) t.ny = grid_lookup(A, side, lod, int(tx), int(ty) + t.ey);
-    if (t.ex != 0 && t.ey != 0) t.nxy = grid_lookup(A, side, lod, int(tx) + t.ex, int(ty) + t.ey);
-    if (A.seam_pull) {
-        const int nn = int(1u << lod), x = int(tx) + t.ex, y = int(ty) + t.ey;
-        const bool out_x = x < 0 || x >= nn, out_y = y < 0 || y >= nn;
-        t.skip = (t.ex != 0 && out_x ? 1u : 0u) | (t.ey != 0 && out_y ? 2u : 0u) | (t.ex != 0 && t.ey != 0 && out_x != out_y ? 4u : 0u);
-    }
-    return t;
-}
-template <typename TT = uint16_t>
-__device__ __forceinline__ void push_store(const FusedArgs& A, const PushNb& t, uint32_t self_index, uint32_t cx, uint32_t cy, TT v) {
-    if (t.ex == 0 && t.ey == 0) return;
-    const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size, o = b + c;
-    const uint64_t tile_texels = uint64_t(T) * T;
-    TT* atlas = reinterpret_cast<TT*>(A.atlas);
-    TT* self = atlas + uint64_t(self_index) * tile_texels;
-    const uint32_t ax = uint32_t(int(b + cx) - t.ex * int(c)), ay = uint32_t(int(b + cy) - t.ey * int(c));
-    if (t.ex != 0) {
-        if (t.nx != kInvalid) {
-            atlas[uint64_t(t.nx) * tile_texels + uint64_t(b + cy) * T + ax] = v;
-        } else if (t.skip & 1u) {
-        } else if (cx == 0 || cx == c - 1) {
-            const uint32_t x0 = t.ex < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++) self[uint64_t(b + cy) * T + x0 + j] = v;
-        }
-    }
-    if (t.ey != 0) {
-        if (t.ny != kInvalid) {
-            atlas[uint64_t(t.ny) * tile_texels + uint64_t(ay) * T + b + cx] = v;
-        } else if (t.skip & 2u) {
-        } else if (cy == 0 || cy == c - 1) {
-            const uint32_t y0 = t.ey < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++) self[uint64_t(y0 + j) * T + b + cx] = v;
-        }
-    }
-    if (t.ex != 0 && t.ey != 0) {
-        if (t.nxy != kInvalid) {
-            atlas[uint64_t(t.nxy) * tile_texels + uint64_t(ay) * T + ax] = v;
-        } else if (t.skip & 4u) {
-        } else if ((cx == 0 || cx == c - 1) && (cy == 0 || cy == c - 1)) {
-            const uint32_t x0 = t.ex < 0 ? 0u : o, y0 = t.ey < 0 ? 0u : o;
-            for (uint32_t j = 0; j < b; j++)
-                for (uint32_t i = 0; i < b; i++) self[uint64_t(y0 + j) * T + x0 + i] = v;
-        }
-    }
-}
-
-// downsample.wgsl:25-39 on four texels in OFFSETS order (0,0),(0,1),(1,0),(1,1) of (dx, dy)
-__device__ __forceinline__ uint32_t downsample4(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11) {
-    if (t00 != 0 && t01 != 0 && t10 != 0 && t11 != 0) {
-        // all four valid (the common case): ((((0 + a) + b) + c) + d) / 4, and x / 4 == x * 0.25 exactly
-        const float value = ((unorm16_to_float(t00) + unorm16_to_float(t01)) + unorm16_to_float(t10)) + unorm16_to_float(t11);
-        return float_to_unorm16(value * 0.25f);
-    }
-    float value = 0.0f, count = 0.0f;
-    if (t00 != 0) { value += unorm16_to_float(t00); count += 1.0f; }
-    if (t01 != 0) { value += unorm16_to_float(t01); count += 1.0f; }
-    if (t10 != 0) { value += unorm16_to_float(t10); count += 1.0f; }
-    if (t11 != 0) { value += unorm16_to_float(t11); count += 1.0f; }
-    if (count == 0.0f) return 0;
-    return float_to_unorm16(value / count);
-}
-
-// the same for packed Rgba8 texels: a texel counts when any of r, g, b is non-zero (downsample.wgsl:31), all four
-// channels are averaged; operation order of bt_kernels.hip downsample_texel<BT_FORMAT_RGBA8>
-__device__ __forceinline__ float unorm8_to_float(uint32_t t) {
-    const float x = float(t), r = 1.0f / 255.0f;
-    const float q0 = x * r;
-    return __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, x), r, q0);
-}
-__device__ __forceinline__ uint32_t downsample4_rgba8(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11) {
-    const uint32_t t[4] = {t00, t01, t10, t11};
-    if ((t00 & 0x00FFFFFFu) != 0 && (t01 & 0x00FFFFFFu) != 0 && (t10 & 0x00FFFFFFu) != 0 && (t11 & 0x00FFFFFFu) != 0) {
-        // all four count (the common case): ((((0 + a) + b) + c) + d) / 4, and x / 4 == x * 0.25 exactly; the sum of four
-        // values in [0, 1] stays in [0, 4], so the clamp of pack4x8unorm is a no-op.  Evaluated in the 2^8-scaled domain:
-        // F(t) = fma(x, RN(1 / 255), x) == 256 * RN(t / 255) for all 256 inputs (bt_selftest), additions and the exact
-        // factor 0.25 commute with the power-of-two scale, and 255 * v == (255 / 256) * (256 v) as real numbers, so every
-        // rounding sees the value the unscaled expression sees — the same texel for a third of the conversion work.
-        uint32_t out = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t sh = 8 * k;
-            const float a = float((t00 >> sh) & 0xFFu), bq = float((t01 >> sh) & 0xFFu), cq = float((t10 >> sh) & 0xFFu), d = float((t11 >> sh) & 0xFFu);
-            const float r = 1.0f / 255.0f;
-            const float sum = ((__builtin_fmaf(a, r, a) + __builtin_fmaf(bq, r, bq)) + __builtin_fmaf(cq, r, cq)) + __builtin_fmaf(d, r, d);
-            out |= uint32_t(0.5f + (255.0f / 256.0f) * (sum * 0.25f)) << sh;
-        }
-        return out;
-    }
-    float value[4] = {0.0f, 0.0f, 0.0f, 0.0f}, count = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if ((t[i] & 0x00FFFFFFu) != 0) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) value[k] += unorm8_to_float((t[i] >> (8 * k)) & 0xFFu);
-            count += 1.0f;
-        }
-    if (count == 0.0f) return 0;
-    uint32_t out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float e = value[k] / count;
-        const float cl = e < 0.0f ? 0.0f : (e > 1.0f ? 1.0f : e);
-        out |= uint32_t(floorf(0.5f + 255.0f * cl)) << (8 * k);
-    }
-    return out;
-}
-
-// general (slow) evaluation of the finest-LOD mosaic pixel (tile, r) from the source; used for the
-// b x b corner aprons only.  `home` = atlas tile holding that pixel (for the keep-previous rule).
-__device__ __forceinline__ uint32_t split_value_slow(const FusedArgs& A, const RasterDev& r, uint32_t tx, uint32_t rx, uint32_t ty,
-                                                  uint32_t ry, uint32_t home_index) {
-    const float scale = float(1u << A.lod);
-    const uint32_t c = A.m.center_size, b = A.m.border_size, T = A.m.texture_size;
-    const Axis ax = split_axis(rx, c, tx, scale, A.tlx, A.brx, r.width);
-    const Axis ay = split_axis(ry, c, ty, scale, A.tly, A.bry, r.height);
-    typedef const uint8_t __attribute__((address_space(1))) * global_bytes;
-    typedef const uint16_t __attribute__((address_space(1))) * global_u16;
-    const global_u16 row0 = (global_u16)((global_bytes)r.data + uint64_t(ay.i0) * r.pitch);
-    const global_u16 row1 = (global_u16)((global_bytes)r.data + uint64_t(ay.i1) * r.pitch);
-    const uint32_t t00 = row0[ax.i0], t10 = row0[ax.i1], t01 = row1[ax.i0], t11 = row1[ax.i1];
-    if (t00 == 0 || t10 == 0 || t01 == 0 || t11 == 0) {
-        if (home_index == kInvalid || A.prev_zero) return 0;
-        return A.atlas[uint64_t(home_index) * T * T + uint64_t(b + ry) * T + b + rx];
-    }
-    const float top = mixf(unorm16_to_float(t00), unorm16_to_float(t10), ax.fr);
-    const float bot = mixf(unorm16_to_float(t01), unorm16_to_float(t11), ax.fr);
-    return float_to_unorm16(mixf(top, bot, ay.fr));
-}
-
-// blockIdx -> logical work id such that each XCD (blocks b, b+8, b+16, ... run on XCD b % 8) walks a
-// contiguous range of work: neighbouring row groups / tiles then share source halos through one L2.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t total) {
-    const uint32_t q = total / 8u, r = total % 8u, xcd = bid % 8u, i = bid / 8u;
-    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + i;
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
-
-struct RowParam {  // one centre row of the workgroup: LDS slots of its two source rows + the y weight
-    int y0, y1;
-    float fy;
-    uint32_t pad;
-};
-
-constexpr uint32_t kMaxChunks = 64;  // chunks one workgroup may run through (T <= 512: a whole tile)
-struct MainShared {  // fixed part of the dynamic LDS block (size is a multiple of 16 bytes)
-    // row tables of ALL chunks of the workgroup's run, written once in the prologue; index = (k - k_begin) * kMainRows + row
-    int row_y0[kMaxChunks * kMainRows];    // first source row; bit 31: the second source row is the same one (clamped)
-    float2 row_fy[kMaxChunks * kMainRows];  // y weights (fy, 1 - fy): read by every lane at one address (a broadcast), used as they arrive
-    int win_ymin[kMaxChunks];              // source window of a chunk: first row ...
-    uint32_t win_slots[kMaxChunks];        // ... and row count; bit 31: the chunk's rows use source rows y, y+1, ..., y+kMainRows
-    RowParam apron[2 * kMaxBorder];  // [0, b): top apron rows, [b, 2b): bottom apron rows (pad = mosaic row ry)
-    int xmin, xmax;
-    uint32_t pad_[2];  // (the dynamic LDS block behind this struct stays 16-byte aligned)
-};
-static_assert(sizeof(MainShared) % 16 == 0, "LDS carve must stay 16-byte aligned");
 
 struct Texel4 {  // the four source texels a column pair needs from one source row
     float a0, a1, b0, b1;  // converted
@@ -1279,394 +919,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
 __global__ __launch_bounds__(64) void fused_corner_kernel(FusedArgs A) { corner_pixels(A, blockIdx.x, threadIdx.x, blockDim.x); }
 
-// ---- fused_tail: up to three LODs below `A.lod`, read from the atlas ---------------------------------
-// Workgroup = 64 x 64 pixels of the LOD-`lod` mosaic, 16 x 16 threads, 4 x 4 input pixels per thread: a thread
-// owns 2 x 2 pixels of lod-1 and one pixel of lod-2 in registers; 2 x 2 neighbouring threads (lanes l, l+1,
-// l+16, l+17 of one wave) combine into one pixel of lod-3 with three shuffles.  No LDS, no barrier, one tile
-// lookup per thread and LOD (c % 4 == 0: a 4 x 4 block never straddles a tile).
-// Top / bottom apron rows (whole rows, corners included) of the tiles of the LODs fused_main produced below the
-// finest one: stitch.wgsl:53-118 for same-side neighbours — neighbour's centre rows, or the own centre clamped
-// when it is absent.  (Cube face edges are re-stitched afterwards by the generic kernel.)  One thread per pixel pair.
-constexpr uint32_t kApronPairsPerThread = 4;  // (a workgroup = 1024 pixel pairs: a T = 512, b = 2 tile's four apron rows — a quarter of the extra workgroups of one pair per thread)
-__device__ __forceinline__ void tail_apron_rows(const FusedArgs& A, uint32_t side, uint32_t e) {
-    const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size, o = b + c;
-    const uint32_t pairs = b * T, per_block = 256u * kApronPairsPerThread, blocks_per_tile = (pairs + per_block - 1u) / per_block;
-    for (uint32_t k = 0; k < A.apron_lods; k++) {
-        const uint32_t lod = A.lod + k, n = 1u << lod, blocks = n * n * blocks_per_tile;
-        if (e >= blocks) {
-            e -= blocks;
-            continue;
-        }
-        const uint32_t tile = e / blocks_per_tile, i0 = (e % blocks_per_tile) * per_block + threadIdx.x;
-        const uint32_t tx = tile / n, ty = tile % n;
-        const uint32_t self = grid_lookup(A, side, lod, int(tx), int(ty));
-        if (self == kInvalid) return;
-        // every load first (unconditional, from clamped addresses), then the stores: one round trip for the thread's four pairs
-        uint32_t v[kApronPairsPerThread][2], dst[kApronPairsPerThread];
-        bool live[kApronPairsPerThread];
-#pragma unroll
-        for (uint32_t q = 0; q < kApronPairsPerThread; q++) {
-            const uint32_t i = i0 + 256u * q;
-            live[q] = i < pairs;
-            const uint32_t ii = live[q] ? i : 0u;
-            const uint32_t r = ii / (T / 2u), px = 2u * (ii % (T / 2u)), py = r < b ? r : c + r;
-            const int rx = px < b ? -1 : (px >= o ? 1 : 0), ry = r < b ? -1 : 1;
-            if (A.seam_skip) {
-                // cube: a neighbour beyond ONE edge of the face lives on another face and a seam workgroup of this launch writes the region
-                // (beyond two edges — the cube's corner — there is none: clamped below like any absent neighbour)
-                const bool out_x = int(tx) + rx < 0 || int(tx) + rx >= int(n), out_y = int(ty) + ry < 0 || int(ty) + ry >= int(n);
-                if (out_x != out_y) live[q] = false;
-            }
-            const uint32_t nb = grid_lookup(A, side, lod, int(tx) + rx, int(ty) + ry);
-#pragma unroll
-            for (uint32_t h = 0; h < 2; h++) {
-                const uint32_t x = px + h;
-                const uint32_t sx = nb != kInvalid ? uint32_t(int(x) - rx * int(c)) : min(max(x, b), o - 1u);
-                const uint32_t sy = nb != kInvalid ? uint32_t(int(py) - ry * int(c)) : min(max(py, b), o - 1u);
-                v[q][h] = A.atlas[uint64_t(nb != kInvalid ? nb : self) * T * T + sy * T + sx];
-            }
-            dst[q] = py * T + px;
-        }
-#pragma unroll
-        for (uint32_t q = 0; q < kApronPairsPerThread; q++)
-            if (live[q]) *reinterpret_cast<uint32_t*>(A.atlas + uint64_t(self) * T * T + dst[q]) = v[q][0] | (v[q][1] << 16);
-        return;
-    }
-}
-
-// Rgba8 twin (one 4-byte texel per thread) that also does the left / right apron columns: after fused_direct, which writes
-// the centres of the two parent LODs only, these workgroups are the whole stitch of those tiles (stitch.wgsl:53-118 for
-// same-face neighbours; cube seams are re-stitched by the batched kernel afterwards, like everywhere in the fused plans).
-__device__ __forceinline__ uint32_t tail_apron_texels_per_tile(const FusedArgs& A) {
-    return 2u * A.m.border_size * A.m.texture_size + (A.apron_cols ? 2u * A.m.border_size * A.m.center_size : 0u);
-}
-__device__ __forceinline__ void tail_aprons_rgba8(const FusedArgs& A, uint32_t side, uint32_t e) {
-    const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size, o = b + c;
-    const uint32_t per_tile = tail_apron_texels_per_tile(A), blocks_per_tile = (per_tile + 255u) / 256u;
-    uint32_t* atlas = reinterpret_cast<uint32_t*>(A.atlas);
-    for (uint32_t k = 0; k < A.apron_lods; k++) {
-        const uint32_t lod = A.lod + k, n = 1u << lod, blocks = n * n * blocks_per_tile;
-        if (e >= blocks) {
-            e -= blocks;
-            continue;
-        }
-        const uint32_t tile = e / blocks_per_tile, i = (e % blocks_per_tile) * 256u + threadIdx.x;
-        if (i >= per_tile) return;
-        const uint32_t tx = tile / n, ty = tile % n;
-        const uint32_t self = grid_lookup(A, side, lod, int(tx), int(ty));
-        if (self == kInvalid) return;
-        uint32_t px, py;
-        if (i < 2u * b * T) {  // whole apron rows (with the corners)
-            const uint32_t r = i / T;
-            px = i % T;
-            py = r < b ? r : c + r;
-        } else {  // apron columns of the centre rows
-            const uint32_t j = i - 2u * b * T, kk = j % (2u * b);
-            px = kk < b ? kk : c + kk;
-            py = b + j / (2u * b);
-        }
-        const int rx = px < b ? -1 : (px >= o ? 1 : 0), ry = py < b ? -1 : (py >= o ? 1 : 0);
-        if (A.seam_skip) {  // cube: a region beyond exactly ONE face edge belongs to a seam workgroup of this launch (see tail_apron_rows)
-            const bool out_x = int(tx) + rx < 0 || int(tx) + rx >= int(n), out_y = int(ty) + ry < 0 || int(ty) + ry >= int(n);
-            if (out_x != out_y) return;
-        }
-        const uint32_t nb = grid_lookup(A, side, lod, int(tx) + rx, int(ty) + ry);
-        const uint32_t sx = nb != kInvalid ? uint32_t(int(px) - rx * int(c)) : min(max(px, b), o - 1u);
-        const uint32_t sy = nb != kInvalid ? uint32_t(int(py) - ry * int(c)) : min(max(py, b), o - 1u);
-        atlas[uint64_t(self) * T * T + py * T + px] = atlas[uint64_t(nb != kInvalid ? nb : self) * T * T + sy * T + sx];
-        return;
-    }
-}
-
-// kRegular: the atlas indices follow the closed form (FusedArgs::regular) — as a compile-time fact the table lookups and their
-// registers fall away (64 VGPRs: eight waves per SIMD)
-// downsample.wgsl:25-39 for R16 in the 2^16-scaled domain of fused_main's fast loop (round 5; downsample4 above is the plain form).
-// F(t) = fma(x, r, x) = 65536 * RN(t / 65535) and F(0) = 0: a no-data texel adds an exact 0 to the running sum, so ((F00 + F01) + F10) + F11
-// IS the sum over the valid texels in OFFSETS order, rounding for rounding; what differs is the divisor.  All four valid (the common case):
-// 0.5 + (0.25 * k) * sum with k = 65535 / 65536 (sum * 0.25 is exact).  Otherwise ONE IEEE division by the count — scaling by a power of two
-// commutes with it, and an average of values <= 1 needs no clamp — and count 0 gives 0.5 + k * (0 / 1) -> 0, the defined "no data".
-typedef float tail_f2 __attribute__((ext_vector_type(2)));
-typedef uint16_t tail_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ tail_f2 tail_conv2(uint32_t a, uint32_t bq) {
-    const tail_f2 x = {float(a), float(bq)}, kr = {1.0f / 65535.0f, 1.0f / 65535.0f};
-    return __builtin_elementwise_fma(x, kr, x);
-}
-// two 2 x 2 averages at once: block A = a_top over a_bot, packed texel pairs (low half = x0), block B likewise
-__device__ __forceinline__ void down_pair_r16(uint32_t a_top, uint32_t a_bot, uint32_t b_top, uint32_t b_bot, uint32_t& qa, uint32_t& qb) {
-    const tail_f2 khalf = {0.5f, 0.5f}, kn = {65535.0f / 65536.0f, 65535.0f / 65536.0f}, knq = {0.25f * (65535.0f / 65536.0f), 0.25f * (65535.0f / 65536.0f)};
-    const tail_u16x2 one = {1, 1};
-    const tail_u16x2 at = __builtin_bit_cast(tail_u16x2, a_top), ab = __builtin_bit_cast(tail_u16x2, a_bot), bt2 = __builtin_bit_cast(tail_u16x2, b_top), bb = __builtin_bit_cast(tail_u16x2, b_bot);
-    const tail_u16x2 m = __builtin_elementwise_min(__builtin_elementwise_min(at, ab), __builtin_elementwise_min(bt2, bb));
-    // OFFSETS order (0,0),(0,1),(1,0),(1,1) of (dx, dy): ((x0y0 + x0y1) + x1y0) + x1y1
-    const tail_f2 sum = ((tail_conv2(a_top & 0xFFFFu, b_top & 0xFFFFu) + tail_conv2(a_bot & 0xFFFFu, b_bot & 0xFFFFu)) + tail_conv2(a_top >> 16, b_top >> 16)) + tail_conv2(a_bot >> 16, b_bot >> 16);
-    tail_f2 w = khalf + knq * sum;
-    if (__builtin_expect(m.x == 0 || m.y == 0, 0)) {  // (rare) some texel has no data: the valid-average
-        const tail_u16x2 ca = __builtin_elementwise_min(at, one) + __builtin_elementwise_min(ab, one), cb = __builtin_elementwise_min(bt2, one) + __builtin_elementwise_min(bb, one);
-        const tail_f2 d = {sum.x / float(max(uint32_t(ca.x) + uint32_t(ca.y), 1u)), sum.y / float(max(uint32_t(cb.x) + uint32_t(cb.y), 1u))};
-        w = khalf + kn * d;
-    }
-    qa = uint32_t(w.x);
-    qb = uint32_t(w.y);
-}
-__device__ __forceinline__ uint32_t down_one_r16(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11) {
-    const float r = 1.0f / 65535.0f;
-    const float x00 = float(t00), x01 = float(t01), x10 = float(t10), x11 = float(t11);
-    const float sum = ((__builtin_fmaf(x00, r, x00) + __builtin_fmaf(x01, r, x01)) + __builtin_fmaf(x10, r, x10)) + __builtin_fmaf(x11, r, x11);
-    float w = 0.5f + (0.25f * (65535.0f / 65536.0f)) * sum;
-    if (__builtin_expect(min(min(t00, t01), min(t10, t11)) == 0, 0)) {
-        const uint32_t count = min(t00, 1u) + min(t01, 1u) + min(t10, 1u) + min(t11, 1u);
-        w = 0.5f + (65535.0f / 65536.0f) * (sum / float(max(count, 1u)));
-    }
-    return uint32_t(w);
-}
-
-// Pixel (mx, my) of the LOD-`lod` mosaic of face `side`, evaluated from the tail's INPUT LOD (lod + K, complete when the launch starts) with the
-// tail's own reduction in its own order — (x, y), (x, y + 1), (x + 1, y), (x + 1, y + 1), downsample.wgsl:25-39 per level, every level quantised —
-// i.e. bit for bit what the mosaic workgroups of this launch write into that tile's centre (R16).
-template <typename TT>
-__device__ __forceinline__ uint32_t tail_down(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11) {  // the tail's reduction of one level, per format
-    if constexpr (std::is_same<TT, uint16_t>::value) return down_one_r16(t00, t01, t10, t11);
-    else return downsample4_rgba8(t00, t01, t10, t11);
-}
-template <int K, typename TT>
-__device__ __forceinline__ uint32_t pull_value(const FusedArgs& A, uint32_t side, uint32_t lod, uint32_t mx, uint32_t my) {
-    if constexpr (K == 0) {
-        const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size;
-        const uint32_t tx = mx / c, ty = my / c;
-        const uint32_t idx = grid_lookup(A, side, lod, int(tx), int(ty));
-        if (idx == kInvalid) return 0u;  // an absent tile reads as no data, like the mosaic workgroups' loads
-        return reinterpret_cast<const TT*>(A.atlas)[uint64_t(idx) * T * T + uint64_t(b + my - ty * c) * T + b + mx - tx * c];
-    } else {
-        const uint32_t t00 = pull_value<K - 1, TT>(A, side, lod + 1u, 2u * mx, 2u * my), t01 = pull_value<K - 1, TT>(A, side, lod + 1u, 2u * mx, 2u * my + 1u);
-        const uint32_t t10 = pull_value<K - 1, TT>(A, side, lod + 1u, 2u * mx + 1u, 2u * my), t11 = pull_value<K - 1, TT>(A, side, lod + 1u, 2u * mx + 1u, 2u * my + 1u);
-        return tail_down<TT>(t00, t01, t10, t11);
-    }
-}
-
-// ONE cross-face apron region of a tile the tail itself produces (stitch.wgsl:12-51, 79-118), pulled: the texel the reference copies out of
-// the neighbour face's centre is evaluated from the tail's input instead (task.raster = LODs between the tile and the input; the neighbour
-// tile's coordinate rides in rel_index[region] as x << 16 | y).  One workgroup of 256 threads; kPack = 2: two adjacent pixels per dword store.
-template <typename TT, uint32_t kPack>
-__device__ __forceinline__ void stitch_region_pull(const FusedArgs& A, const TaskDev& task) {
-    const uint32_t Tsz = A.m.texture_size, b = A.m.border_size, c = A.m.center_size, o = b + c;
-    const uint32_t region = uint32_t(__ffs(int(task.regions))) - 1u;  // 0 top, 1 right, 2 bottom, 3 left, 4 TL, 5 TR, 6 BR, 7 BL
-    const uint32_t x0 = (region == 0u || region == 2u) ? b : ((region == 1u || region == 5u || region == 6u) ? o : 0u);
-    const uint32_t y0 = (region == 1u || region == 3u) ? b : ((region == 2u || region == 6u || region == 7u) ? o : 0u);
-    const uint32_t w = (region == 0u || region == 2u) ? c : b, h = (region == 1u || region == 3u) ? c : b;
-    const int rx = (region == 1u || region == 5u || region == 6u) ? 1 : ((region == 3u || region == 4u || region == 7u) ? -1 : 0);
-    const int ry = (region == 2u || region == 6u || region == 7u) ? 1 : ((region == 0u || region == 4u || region == 5u) ? -1 : 0);
-    const uint32_t other = task.rel_side[region], nx = task.rel_index[region] >> 16, ny = task.rel_index[region] & 0xFFFFu;
-    // task.raster = levels | part << 8 | parts << 16: a region is shared out over `parts` workgroups (a thread then evaluates one pixel pair:
-    // the pull workgroups are the longest of the launch — 4^levels dependent-free loads per pixel — and must not outlast the mosaic's)
-    const uint32_t levels = task.raster & 0xFFu, part = (task.raster >> 8) & 0xFFu, parts = max(1u, task.raster >> 16);
-    const uint32_t count = (w / kPack) * h, share = (count + parts - 1u) / parts, i_end = min(count, (part + 1u) * share);
-    // levels <= 2: the 2^levels x 2^levels input block of a pixel lies in ONE input tile (c is a multiple of 4): one tile lookup, one division per axis
-    const uint32_t in_lod = task.lod + levels, cn = c >> levels;  // cn: pixels of this LOD one input tile's centre covers
-    for (uint32_t i = part * share + threadIdx.x; i < i_end; i += 256u) {
-        const uint32_t px = x0 + kPack * (i % (w / kPack)), py = y0 + i / (w / kPack);
-        if (py >= A.m.row_limit) continue;
-        uint32_t v[kPack];
-#pragma unroll
-        for (uint32_t e = 0; e < kPack; e++) {
-            // neighbour_data of stitch.wgsl: the apron texel as a texel of the neighbour tile (its centre: [b, b + c) on both axes), then as a pixel of its face's mosaic
-            const uint2 q = project_to_side(uint32_t(int(px + e) - rx * int(c)), uint32_t(int(py) - ry * int(c)), Tsz, task.side, other);
-            const uint32_t mx = nx * c + (q.x - b), my = ny * c + (q.y - b);
-            if (BT_ABLATE(A, 2147483648u)) {  // (2147483648: pull workgroups store zeros without evaluating anything — timing experiment)
-                v[e] = 0;
-            } else if (levels <= 2u && (c & 3u) == 0) {
-                const uint32_t tx = mx / cn, ty = my / cn;  // the input tile, and the block's first pixel in it
-                const uint32_t idx = grid_lookup(A, other, in_lod, int(tx), int(ty));
-                const TT* src = reinterpret_cast<const TT*>(A.atlas) + uint64_t(idx == kInvalid ? 0u : idx) * Tsz * Tsz + uint64_t(b + ((my - ty * cn) << levels)) * Tsz + b + ((mx - tx * cn) << levels);
-                // every load unconditional and issued before the first use (a conditional load becomes its own divergent block with a wait behind it:
-                // sixteen dependent round trips per pixel made these the longest workgroups of the launch); an absent tile reads as no data
-                const uint32_t keep = idx == kInvalid ? 0u : 0xFFFFFFFFu;
-                if (levels == 1u) {
-                    const uint32_t t00 = src[0], t01 = src[Tsz], t10 = src[1], t11 = src[Tsz + 1u];
-                    v[e] = tail_down<TT>(t00 & keep, t01 & keep, t10 & keep, t11 & keep);
-                } else {
-                    uint32_t t[4][4];  // [dy][dx]
-#pragma unroll
-                    for (uint32_t dy = 0; dy < 4; dy++)
-#pragma unroll
-                        for (uint32_t dx = 0; dx < 4; dx++) t[dy][dx] = uint32_t(src[dy * Tsz + dx]) & keep;
-                    auto two = [&](uint32_t dx, uint32_t dy) -> uint32_t { return tail_down<TT>(t[dy][dx], t[dy + 1][dx], t[dy][dx + 1], t[dy + 1][dx + 1]); };
-                    v[e] = tail_down<TT>(two(0u, 0u), two(0u, 2u), two(2u, 0u), two(2u, 2u));
-                }
-            } else {
-                v[e] = levels == 1u ? pull_value<1, TT>(A, other, task.lod, mx, my) : levels == 2u ? pull_value<2, TT>(A, other, task.lod, mx, my) : pull_value<3, TT>(A, other, task.lod, mx, my);
-            }
-        }
-        TT* dst = reinterpret_cast<TT*>(A.atlas) + uint64_t(task.atlas_index) * Tsz * Tsz + uint64_t(py) * Tsz + px;
-        if (BT_ABLATE(A, 4194304u) && (v[0] | v[kPack - 1]) != 0x12345u) continue;  // (4194304: evaluated, not stored — timing experiment)
-        if constexpr (kPack == 2) *reinterpret_cast<uint32_t*>(dst) = v[0] | (v[1] << 16);
-        else *dst = TT(v[0]);
-    }
-}
-
-template <uint32_t kFormat, bool kRegular>
-__global__ __launch_bounds__(256) void fused_tail_kernel(FusedArgs A_in) {
-    FusedArgs A = A_in;
-    A.regular = kRegular ? 1u : 0u;
-    constexpr bool kR16 = kFormat == BT_FORMAT_R16;
-    using TT = typename std::conditional<kR16, uint16_t, uint32_t>::type;  // texel
-    // Workgroup -> work, XCD-aware (round 5).  Workgroups go to the XCDs round robin (blockIdx.x % 8) and every XCD has its own L2; a
-    // 64-pixel-wide mosaic column starts b texels into a tile row, i.e. it shares its first and last 128-byte line with the workgroup
-    // beside it — dispatched in mosaic order the two sit on different XCDs and every line is fetched from HBM twice
-    // (profiles/r05_pmc_summary.json: the tail read 67.7 MB for 33.5 MB of texels).  So: XCD k takes the k-th eighth of the mosaic
-    // workgroups (whole rows of them, neighbours in x back to back on one L2), and in front of those its eighth of the extra workgroups —
-    // apron rows (Rgba8: and columns) of the LODs above, on a cube the cross-face seam regions first: short dependent chains that run
-    // beside the mosaic work instead of behind the last of it.
-    // The extras of an XCD, in dispatch order: its share of the cross-face seam regions (task f = j * 8 + xcd: the list's head — the pulled
-    // regions, the launch's longest workgroups — spreads over all eight XCDs; round 6: with all of them on XCD 0 the launch ended 4 us late),
-    // then its eighth of the apron blocks (side-major), then its eighth of the mosaic.
-    const uint32_t nx = ((1u << A.lod) * A.m.center_size + 63u) / 64u, per_side_m = nx * nx, per_side_a = A.tail_extras;
-    const uint32_t total_m = A.sides * per_side_m, total_a = A.sides * per_side_a, chunk_m = (total_m + 7u) / 8u, chunk_a = (total_a + 7u) / 8u;
-    const uint32_t chunk_s = (A.seam_count + 7u) / 8u, chunk_e = chunk_s + chunk_a;
-    uint32_t side, block_x, block_y;
-    {
-        const uint32_t xcd = blockIdx.x % 8u, j = blockIdx.x / 8u;
-        if (j < chunk_e) {
-            if (BT_ABLATE(A, 268435456u)) return;  // (268435456: no extra workgroups — timing experiment)
-            if (j < chunk_s) {  // one cross-face region
-                const uint32_t f = j * 8u + xcd;
-                if (f < A.seam_count) {
-                    const bool pulled = A.seam_tasks[f].raster != 0u;  // a region of a tile this launch produces: pulled from the input LOD
-                    if constexpr (kR16) {
-                        const bool pairs = (A.m.border_size & 1u) == 0 && (A.m.texture_size & 1u) == 0;
-                        if (pulled) {
-                            if (pairs) stitch_region_pull<uint16_t, 2>(A, A.seam_tasks[f]);
-                            else stitch_region_pull<uint16_t, 1>(A, A.seam_tasks[f]);
-                        } else if (pairs) stitch_region_body<uint16_t, 2>(A.m, A.atlas, A.seam_tasks[f]);
-                        else stitch_region_body<uint16_t, 1>(A.m, A.atlas, A.seam_tasks[f]);
-                    } else {
-                        if (pulled) stitch_region_pull<uint32_t, 1>(A, A.seam_tasks[f]);
-                        else stitch_region_body<uint32_t, 1>(A.m, A.atlas, A.seam_tasks[f]);
-                    }
-                }
-                return;
-            }
-            const uint32_t id = xcd * chunk_a + (j - chunk_s);
-            if (id >= total_a) return;
-            side = id / per_side_a;
-            const uint32_t e = id - side * per_side_a;
-            if constexpr (kR16) tail_apron_rows(A, side, e);
-            else tail_aprons_rgba8(A, side, e);
-            return;
-        }
-        const uint32_t id = xcd * chunk_m + (j - chunk_e);
-        if (id >= total_m) return;
-        side = id / per_side_m;
-        const uint32_t r = id - side * per_side_m;
-        block_y = r / nx;
-        block_x = r - block_y * nx;
-    }
-    const uint32_t T = A.m.texture_size, b = A.m.border_size, c = A.m.center_size;
-    const uint32_t tile_texels = T * T;
-    const uint32_t size = (1u << A.lod) * c;  // mosaic extent of the input LOD (a multiple of 4)
-    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
-    const uint32_t gx = block_x * 64u + 4u * tx, gy = block_y * 64u + 4u * ty;  // first input pixel
-    const bool active = gx < size && gy < size;
-    // ONE division per axis: c is a multiple of 4, so the 4 x 4 block lies in one tile, and the tile / in-tile coordinates
-    // of its pixel at LOD-k follow by shifts: tile >> k, ((tile & (2^k - 1)) * c + rem) >> k
-    const uint32_t tile_x = gx / c, tile_y = gy / c, rem_x = gx - tile_x * c, rem_y = gy - tile_y * c;
-    const uint32_t rx1 = ((tile_x & 1u) * c + rem_x) >> 1, ry1 = ((tile_y & 1u) * c + rem_y) >> 1;
-    TT* atlas = reinterpret_cast<TT*>(A.atlas);
-    auto down = [](uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11) -> uint32_t {
-        if constexpr (kR16) return down_one_r16(t00, t01, t10, t11);
-        else return downsample4_rgba8(t00, t01, t10, t11);
-    };
-
-    uint32_t t[4][4];  // [row][col]  (R16: t[r][0], t[r][1] hold the row's two DWORDS — pixels 0 | 1 and 2 | 3 — as loaded)
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) t[r][k] = 0;
-    // all tile lookups up front (independent of the data): one round of memory latency instead of four
-    uint32_t idx = kInvalid, self1 = kInvalid, self2 = kInvalid, self3 = kInvalid;
-    if (active) {
-        idx = grid_lookup(A, side, A.lod, int(tile_x), int(tile_y));
-        self1 = grid_lookup(A, side, A.lod - 1, int(tile_x >> 1), int(tile_y >> 1));
-        if (A.levels >= 2) self2 = grid_lookup(A, side, A.lod - 2, int(tile_x >> 2), int(tile_y >> 2));
-        if (A.levels >= 3) self3 = grid_lookup(A, side, A.lod - 3, int(tile_x >> 3), int(tile_y >> 3));
-    }
-    // ... and the neighbour tiles the four lod-1 pixels will be pushed into (edge pixels only), while nothing has been stored yet.
-    // b even: the 2 x 2 block (even coordinates) lies in one edge region and shares its targets; b odd: per pixel, push_pixel
-    const bool pre = (b & 1u) == 0;
-    const PushNb nb1 = push_targets(A, side, A.lod - 1, tile_x >> 1, tile_y >> 1, rx1, ry1, active && pre);
-    if (active) {
-        if (idx != kInvalid && !BT_ABLATE(A, 33554432u)) {  // an absent tile reads as no data  (33554432: no texel loads — timing experiment)
-            const TT* p = atlas + uint64_t(idx) * tile_texels + (b + rem_y) * T + b + rem_x;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                if constexpr (kR16) {  // 4-byte aligned (b even)
-                    const uint2 w = *reinterpret_cast<const uint2 __attribute__((aligned(4)))*>(p + r * T);  // one 8-byte load from a dword-aligned address
-                    t[r][0] = w.x;
-                    t[r][1] = w.y;
-                } else {  // 8-byte aligned (b even or not: (b + 4k) texels of 4 bytes; pairs need b even) — two texels per load
-                    if ((b & 1u) == 0) {
-                        const uint2 lo = *reinterpret_cast<const uint2*>(p + r * T), hi = *reinterpret_cast<const uint2*>(p + r * T + 2);
-                        t[r][0] = lo.x;
-                        t[r][1] = lo.y;
-                        t[r][2] = hi.x;
-                        t[r][3] = hi.y;
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; k++) t[r][k] = p[r * T + k];
-                    }
-                }
-            }
-        }
-    }
-    // lod-1: 2 x 2 pixels, each from a 2 x 2 block in OFFSETS order (0,0),(0,1),(1,0),(1,1) of (dx, dy)
-    uint32_t q[2][2];  // [row][col]
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        if constexpr (kR16) {  // the row pair's two pixels at once, from the packed dwords
-            down_pair_r16(t[2 * r][0], t[2 * r + 1][0], t[2 * r][1], t[2 * r + 1][1], q[r][0], q[r][1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 2; k++) q[r][k] = down(t[2 * r][2 * k], t[2 * r + 1][2 * k], t[2 * r][2 * k + 1], t[2 * r + 1][2 * k + 1]);
-        }
-    }
-    if (active) {
-        const uint32_t self = self1;
-        if (self != kInvalid && !BT_ABLATE(A, 1073741824u)) {  // (1073741824: no lod-1 stores — timing experiment)
-            // R16: the two pixels of a row are one aligned dword of the tile (x1, b, c even); aprons per pixel, edge pixels only
-            TT* centre = atlas + uint64_t(self) * tile_texels + (b + ry1) * T + b + rx1;
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                if constexpr (kR16) {
-                    *reinterpret_cast<uint32_t*>(centre + r * T) = q[r][0] | (q[r][1] << 16);
-                } else {
-                    centre[r * T] = q[r][0];
-                    centre[r * T + 1] = q[r][1];
-                }
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (BT_ABLATE(A, 536870912u)) continue;  // (536870912: no apron pushes of lod-1 — timing experiment)
-                    if (pre) push_store<TT>(A, nb1, self, rx1 + k, ry1 + r, TT(q[r][k]));
-                    else push_pixel<false, TT>(A, side, A.lod - 1, tile_x >> 1, tile_y >> 1, self, rx1 + k, ry1 + r, TT(q[r][k]));
-                }
-            }
-        }
-    }
-    if (A.levels < 2 || BT_ABLATE(A, 67108864u)) return;  // (67108864: lod-1 only — timing experiment)
-    const uint32_t v2 = down(q[0][0], q[1][0], q[0][1], q[1][1]);
-    if (active) {
-        const uint32_t self = self2;
-        if (self != kInvalid)
-            push_pixel<true, TT>(A, side, A.lod - 2, tile_x >> 2, tile_y >> 2, self, ((tile_x & 3u) * c + rem_x) >> 2, ((tile_y & 3u) * c + rem_y) >> 2, TT(v2));
-    }
-    if (A.levels < 3) return;
-    // lod-3: threads (tx, ty) with both even own the pixel; partners are lanes +1 (dx), +16 (dy), +17
-    const uint32_t right = __shfl_down(v2, 1), below = __shfl_down(v2, 16), diag = __shfl_down(v2, 17);
-    if (active && ((tx | ty) & 1u) == 0) {
-        const uint32_t v3 = down(v2, below, right, diag);
-        const uint32_t self = self3;
-        if (self != kInvalid)
-            push_pixel<true, TT>(A, side, A.lod - 3, tile_x >> 3, tile_y >> 3, self, ((tile_x & 7u) * c + rem_x) >> 3, ((tile_y & 7u) * c + rem_y) >> 3, TT(v3));
-    }
-}
+#include "bt_fused_tail.hpp"
 
 
 
@@ -1807,8 +1060,6 @@ template <int kCtrl>
 __device__ __forceinline__ uint32_t quad_dpp(uint32_t v) {
     return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), kCtrl, 0xf, 0xf, true));
 }
-
-constexpr uint32_t kDirectRows = 4, kDirectMaxBlocks = 16;
 
 // kRep: a source coarser than the tile grid in y (ratios below 1: the host decides per job) — the chain of a block may stand still (BlockInfo::rep).  The BASELINE
 // shapes (4096 over 4064, 8192 over 8128) run the kernel without it: the select it needs costs config 2's albedo job 2 % (same-lease A/B, round 6)
@@ -2269,832 +1520,6 @@ __global__ void selftest_kernel(uint32_t* failures) {
 }
 
 }  // namespace
-
-// =============================================================================== host side: planning
-
-struct FusedJobDev {  // one fused launch of a compiled queue
-    FusedArgs args;
-    uint32_t attachment;
-    uint32_t queue_job = 0;  // the preprocess job whose item list and grids args.items / args.grids point to (fused_upload)
-    uint32_t lds_pad = 0;    // profiling build only (BT_FUSED_LDS_PAD at plan time): extra dynamic LDS per workgroup
-    std::vector<MainItem> host_items;  // fused_main's / fused_direct's items as uploaded (tile-row order): streamed runs cut fused_main's into bands, fused_source_window reads both
-    uint32_t seam_first = 0;  // fused_tail with seam workgroups: its tasks are p->tasks_dev[seam_first ...] (args.seam_count of them)
-    // fused_main / fused_direct: the atlas layers of the job's finest tiles (a no-data pixel's "previous value" is read from one of them) and of
-    // all its tiles (written by this job's launches); fused_begin_run decides args.prev_zero from Attachment::written before every run
-    std::vector<uint32_t> finest_layers, all_layers;
-};
-
-// the fused path's per-queue state, owned by the bt_preprocessor that compiled it (bt_preprocessor::fused)
-struct FusedState {
-    std::vector<FusedJobDev> jobs;
-    void* arrays = nullptr;  // device copy of every job's item list and grids (one allocation per queue: fused_upload)
-    std::vector<uint8_t> whole_raster;  // [raster]: a launch without an item list (the hybrid plan's batched split) reads it: no window is known
-};
-
-}  // namespace bt
-
-#include <algorithm>
-namespace bt {
-
-static FusedState& state_of(bt_preprocessor* p) {
-    if (!p->fused) p->fused = new FusedState();
-    return *p->fused;
-}
-
-void fused_release(bt_preprocessor* p) {
-    if (!p->fused) return;
-    hipFree(p->fused->arrays);
-    delete p->fused;
-    p->fused = nullptr;
-}
-
-// The dense grids of atlas indices of a job, one per (side, LOD): sides [0, sides) x LODs [lod_lo, lod_hi], kInvalid where no tile is queued
-struct JobGrid {
-    uint32_t sides = 1, lod_lo = 0, lod_hi = 0;
-    std::vector<uint32_t> offsets, cells;  // offsets[side * 32 + lod]: where that grid starts in cells (x-major: x * n + y)
-    JobGrid() = default;
-    JobGrid(uint32_t sides_, uint32_t lo, uint32_t hi) : sides(sides_), lod_lo(lo), lod_hi(hi), offsets(6 * 32, kInvalid) {
-        for (uint32_t side = 0; side < sides; side++)
-            for (uint32_t lod = lod_lo; lod <= lod_hi; lod++) {
-                offsets[side * 32 + lod] = uint32_t(cells.size());
-                cells.resize(cells.size() + (size_t(1) << (2 * lod)), kInvalid);
-            }
-    }
-    bool holds(const bt_tile_coordinate& c) const { return c.side < sides && c.lod >= lod_lo && c.lod <= lod_hi && c.x < (1u << c.lod) && c.y < (1u << c.lod); }
-    uint32_t& cell(const bt_tile_coordinate& c) { return cells[offsets[c.side * 32 + c.lod] + (size_t(c.x) << c.lod) + c.y]; }
-    uint32_t cell(const bt_tile_coordinate& c) const { return cells[offsets[c.side * 32 + c.lod] + (size_t(c.x) << c.lod) + c.y]; }
-    // f(side, lod, x, y, atlas index) for every cell of the LODs [lo, end) of every side (side, LOD, x, y ascending); false from f stops the
-    // walk, and for_each returns false then
-    template <typename F>
-    bool for_each(uint32_t lo, uint32_t end, F&& f) const {
-        for (uint32_t side = 0; side < sides; side++)
-            for (uint32_t lod = lo; lod < end; lod++) {
-                const uint32_t* g = cells.data() + offsets[side * 32 + lod];
-                for (uint32_t x = 0; x < (1u << lod); x++)
-                    for (uint32_t y = 0; y < (1u << lod); y++)
-                        if (!f(side, lod, x, y, g[(size_t(x) << lod) + y])) return false;
-            }
-        return true;
-    }
-    uint64_t tiles_at(uint32_t lod) const {
-        uint64_t n = 0;
-        for_each(lod, lod + 1, [&](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t v) {
-            n += v != kInvalid;
-            return true;
-        });
-        return n;
-    }
-};
-
-// One job (one preprocess_tile / preprocess_spherical call) while fused_plan plans it
-struct JobPlan {
-    uint32_t job = 0;
-    std::vector<const Task*> splits, downs, stitches;
-    uint32_t ai = 0;  // attachment
-    AttachmentMeta m{};
-    bool direct = false, hybrid = false;  // the plan of the finest LOD: fused_direct, the batched kernels, or (neither) fused_main
-    bool spherical = false;
-    uint32_t main_levels = 1;  // LODs the main / direct launch produces (the hybrid plan: 1, the batched kernels')
-    JobGrid grid;
-    bool shard = false;  // sharded: this rank's column strips (plan_shards)
-    uint32_t strip_shift = 0, strips = 0, units_per_rank = 0;
-    std::vector<MainItem> items;  // this rank's finest tiles in launch order
-    FusedArgs args{};  // what the job's fused launches share
-    uint64_t source_bytes = 0;
-    std::vector<uint32_t> finest_layers, all_layers;  // (Attachment::written bookkeeping: fused_begin_run)
-
-    uint32_t main_lo() const { return grid.lod_hi - (main_levels - 1); }  // LODs main_lo .. lod_hi come out of the main launch
-    // the first tail launch also fills the top / bottom apron rows of the LODs fused_main produced (no stitch launch for them)
-    // (after fused_direct, which writes centres only, the tail's extra workgroups do all four sides: no stitch launch)
-    bool rows_in_tail() const { return !shard && main_lo() > grid.lod_lo && main_levels > 1 && (direct || m.border_size % 2u == 0); }
-    uint64_t tile_bytes() const { return uint64_t(m.texture_size) * m.texture_size * m.pixel_size; }
-    uint64_t apron_bytes() const { return 2 * (2 * uint64_t(m.border_size) * (m.texture_size + m.center_size)) * m.pixel_size; }  // a whole stitch: read + written
-    FusedJobDev fused_job() const {
-        FusedJobDev d{args, ai};
-        d.queue_job = job;
-        return d;
-    }
-};
-
-// What the stages append to: the queue's task records and launches, and the fused jobs the launches point to (Launch::aux0)
-struct PlanOut {
-    std::vector<TaskDev>& tasks;
-    std::vector<Launch>& plan;
-    FusedState& state;
-};
-
-static Launch job_launch(const JobPlan& j, LaunchKind kind, uint32_t variant) {
-    Launch l{};
-    l.kind = kind;
-    l.variant = variant;
-    l.attachment = j.ai;
-    return l;
-}
-
-// A job qualifies for the fused path when
-//  - the attachment is R16 with T <= 512, even b, c % 4 == 0, c >= 2b;
-//  - at every LOD but the finest, each queued tile has all four children queued (full quadtree below it).
-// Otherwise the whole queue runs on the generic kernels.  collect_job, fill_grid and qualifies return false where it does not.
-static bool collect_job(const bt_preprocessor* p, const bt_atlas* a, uint32_t job, JobPlan& j) {
-    j.job = job;
-    for (const Task& t : p->queue) {
-        if (t.job != job) continue;
-        if (t.type == kSplit) j.splits.push_back(&t);
-        else if (t.type == kDownsample) j.downs.push_back(&t);
-        else if (t.type == kStitch) j.stitches.push_back(&t);
-    }
-    if (j.splits.empty()) return false;
-    j.ai = j.splits[0]->attachment_index;
-    const AttachmentMeta& m = j.m = a->attachments[j.ai].meta;
-    // fused_main: R16, T <= 512, even b <= 8.  Otherwise (Rgba8, large tiles, odd borders) the HYBRID plan: the batched
-    // split + stitch kernels produce the finest LOD, fused_tail (format-generic) everything below it, three LODs per
-    // launch, aprons pushed — instead of one downsample launch per LOD and a stitch over every tile.
-    const bool tail_ok = (m.format == BT_FORMAT_R16 || m.format == BT_FORMAT_RGBA8) && (m.center_size & 3u) == 0 &&
-                         m.center_size >= 2 * m.border_size && m.border_size != 0 && (m.format != BT_FORMAT_R16 || (m.border_size & 1u) == 0);
-    const bool main_ok = tail_ok && m.format == BT_FORMAT_R16 && m.texture_size <= 512 && m.border_size <= 8;
-    if (!tail_ok) return false;
-    // Rgba8: fused_direct (no LDS staging) produces the finest LOD with its aprons and the two parent LODs
-    j.direct = !main_ok && m.format == BT_FORMAT_RGBA8;
-    j.hybrid = !main_ok && !j.direct;
-    // (layer x tile texels is formed in 64 bits everywhere: an attachment of 2^32 texels or more — 16384 tiles of 512^2 — takes the fused plans
-    // like any other; rounds 2 - 6 sent such atlases to the batched kernels, found with a GEBCO-sized job at the end of round 6)
-    const uint32_t lod_hi = j.splits[0]->coord.lod;
-    uint32_t lod_lo = lod_hi;
-    for (const Task* t : j.downs) lod_lo = std::min(lod_lo, t->coord.lod);
-    if (lod_hi > 13) return false;  // dense per-LOD grids (4^lod entries) and 32-bit grid offsets
-    j.spherical = a->config.spherical != 0;
-    j.grid = JobGrid(j.spherical ? 6u : 1u, lod_lo, lod_hi);
-    // main launch: finest LOD + up to two more
-    j.main_levels = j.hybrid ? 1u : std::min(3u, lod_hi - lod_lo + 1);
-    return true;
-}
-
-static bool fill_grid(JobPlan& j) {
-    JobGrid& g = j.grid;
-    for (const Task* t : j.splits) {
-        if (!g.holds(t->coord) || t->coord.lod != g.lod_hi) return false;
-        g.cell(t->coord) = t->atlas_index;
-    }
-    for (const Task* t : j.downs) {
-        if (!g.holds(t->coord)) return false;
-        g.cell(t->coord) = t->atlas_index;
-    }
-    return true;
-}
-
-static bool qualifies(const JobPlan& j) {
-    const JobGrid& g = j.grid;
-    // completeness: every downsample tile has its four children in the grids
-    for (const Task* t : j.downs) {
-        bt_tile_coordinate ch[4];
-        tile_children(t->coord, ch);
-        for (int k = 0; k < 4; k++)
-            if (g.cell(ch[k]) == kInvalid) return false;
-    }
-    // every tile that is stitched must be in the grids and vice versa (same tile set)
-    size_t present = 0;
-    for (uint32_t v : g.cells) present += v != kInvalid;
-    if (present != j.stitches.size()) return false;
-    // The fused kernels take a tile's apron from the job's own grid; the queue recorded the neighbours the ATLAS holds
-    // (stitch_and_save_layer -> get_tile).  They differ when tiles of an earlier job or dataset border this one: then
-    // only the generic path stitches across that seam, so the job does not qualify.
-    for (const Task* t : j.stitches) {
-        const bt_tile_coordinate& c = t->coord;
-        if (!g.holds(c) || g.cell(c) != t->atlas_index) return false;
-        bt_tile_coordinate nb[8];
-        tile_neighbours(c, false, nb);  // same-face neighbours (cube seams are re-stitched by the generic kernel)
-        for (int i = 0; i < 8; i++) {
-            const bool same_face = !is_invalid(nb[i]);
-            const uint32_t in_grid = same_face ? g.cell(nb[i]) : kInvalid;
-            const bool recorded_same_face = t->rel[i].atlas_index != BT_INVALID_ATLAS_INDEX && t->rel[i].coordinate.side == c.side && same_face;
-            if (same_face && in_grid != (recorded_same_face ? t->rel[i].atlas_index : kInvalid)) return false;
-        }
-    }
-    // all split tasks share the dataset rectangle
-    const Task* s0 = j.splits[0];
-    for (const Task* t : j.splits)
-        if (t->tl[0] != s0->tl[0] || t->tl[1] != s0->tl[1] || t->br[0] != s0->br[0] || t->br[1] != s0->br[1]) return false;
-    return true;
-}
-
-// ---- sharding (multi-GPU).  Unit = one column strip of one side at the granularity of the coarsest LOD the main
-// kernel produces (a strip = 2^(levels-1) finest columns = one column of that LOD), units numbered side-major;
-// rank r owns the units [r * U / world, (r + 1) * U / world).  A unit's tiles of a LOD are contiguous atlas layers
-// (x-major allocation order), so the exchange is a list of contiguous layer runs, each with its owning rank.
-static void plan_shards(bt_preprocessor* p, JobPlan& j) {
-    const JobGrid& g = j.grid;
-    const uint32_t world = p->shard_world, levels = std::min(3u, g.lod_hi - g.lod_lo + 1);
-    j.strip_shift = levels - 1;
-    j.strips = 1u << (g.lod_hi - j.strip_shift);
-    const uint32_t units = g.sides * j.strips;
-    // (fused_direct shards like fused_main: finest tiles complete from the source, parent centres inside a strip, everything else after the exchange)
-    j.shard = world > 1 && units % world == 0 && !j.hybrid;
-    if (!j.shard) return;
-    j.units_per_rank = units / world;
-    auto base_of = [&](uint32_t side, uint32_t lod) { return g.cells[g.offsets[side * 32 + lod]]; };
-    j.shard = g.for_each(g.lod_hi + 1 - levels, g.lod_hi + 1, [&](uint32_t side, uint32_t lod, uint32_t x, uint32_t y, uint32_t v) {
-        const uint32_t base = base_of(side, lod);
-        return base != kInvalid && v == base + ((x << lod) + y);  // the fresh x-major layout
-    });
-    if (!j.shard) return;
-    for (uint32_t side = 0; side < g.sides; side++)
-        for (uint32_t k = 0; k < levels; k++) {
-            const uint32_t lod = g.lod_hi - k, n = 1u << lod, base = base_of(side, lod), cols_per_strip = n / j.strips;
-            // maximal runs of strips with one owner
-            for (uint32_t strip = 0; strip < j.strips;) {
-                const uint32_t owner = (side * j.strips + strip) / j.units_per_rank;
-                uint32_t end = strip + 1;
-                while (end < j.strips && (side * j.strips + end) / j.units_per_rank == owner) end++;
-                p->shard_pieces.push_back({j.ai, side, lod, base + strip * cols_per_strip * n, (end - strip) * cols_per_strip * n, owner});
-                strip = end;
-            }
-            // the regular case (one side, every rank an equal run): also expressible as ONE in-place all-gather
-            if (g.sides == 1) p->shard_ranges.push_back({j.ai, side, lod, base, n / world * n});
-        }
-}
-
-static void order_items(const bt_preprocessor* p, JobPlan& j) {
-    for (const Task* t : j.splits) {
-        if (j.shard && (t->coord.side * j.strips + (t->coord.x >> j.strip_shift)) / j.units_per_rank != p->shard_rank) continue;
-        j.items.push_back({t->coord.side, t->coord.x, t->coord.y, t->atlas_index, uint32_t(t->raster)});
-    }
-    // Workgroup order = tile rows (y outer, x inner) instead of the queue's x-major order: an XCD then streams whole
-    // source rows (its 128 concurrent workgroups cover 4 tile rows x all columns), and x neighbours run on the same XCD
-    // at the same time, so the apron bytes one pushes into the other's parent rows merge in one L2.  16k job: 333 -> 285 us.
-    std::stable_sort(j.items.begin(), j.items.end(), [](const MainItem& a, const MainItem& b2) {
-        return a.side != b2.side ? a.side < b2.side : (a.y != b2.y ? a.y < b2.y : a.x < b2.x);
-    });
-}
-
-// the closed form of grid_lookup: does every entry follow it?  (*first: FusedArgs::reg_first)
-static bool regular_layout(const JobGrid& g, uint32_t* first) {
-    const uint32_t hi4 = 4u << (2u * g.lod_hi), per_side = (hi4 - (1u << (2u * g.lod_lo))) / 3u, f = g.cells.empty() ? 0u : g.cells[g.offsets[g.lod_hi]];
-    *first = f;
-    return f != kInvalid && g.for_each(g.lod_lo, g.lod_hi + 1, [&](uint32_t side, uint32_t lod, uint32_t x, uint32_t y, uint32_t v) {
-        return v == f + side * per_side + (hi4 - (4u << (2u * lod))) / 3u + ((x << lod) + y);
-    });
-}
-
-// what the job's fused launches share, the source bytes it reads and the atlas layers it writes
-static void describe_job(const bt_preprocessor* p, const bt_atlas* a, JobPlan& j) {
-    FusedArgs& args = j.args;
-    args.m = j.m;
-#ifdef BT_DEBUG_HOOKS
-    if (const char* e = getenv("BT_FUSED_ABLATE")) args.ablate = uint32_t(strtoul(e, nullptr, 0));
-#endif
-    args.atlas = (uint16_t*)a->attachments[j.ai].level0;
-    args.rasters = p->rasters_dev;  // (re)allocated by bt_preprocessor_run before the first launch
-    args.tlx = j.splits[0]->tl[0];
-    args.tly = j.splits[0]->tl[1];
-    args.brx = j.splits[0]->br[0];
-    args.bry = j.splits[0]->br[1];
-    args.sides = j.grid.sides;
-    args.grid_lod_lo = j.grid.lod_lo;
-    args.grid_lod_hi = j.grid.lod_hi;
-    args.grid_sides = j.grid.sides;
-    args.regular = regular_layout(j.grid, &args.reg_first) ? 1u : 0u;
-    std::vector<bool> seen(p->rasters.size(), false);
-    for (const Task* t : j.splits)
-        if (!seen[t->raster]) {
-            seen[t->raster] = true;
-            j.source_bytes += uint64_t(p->rasters[t->raster].dev.width) * p->rasters[t->raster].dev.height * j.m.pixel_size;
-        }
-    j.grid.for_each(j.grid.lod_lo, j.grid.lod_hi + 1, [&](uint32_t, uint32_t lod, uint32_t, uint32_t, uint32_t v) {
-        if (v != kInvalid) {
-            j.all_layers.push_back(v);
-            if (lod == j.grid.lod_hi) j.finest_layers.push_back(v);
-        }
-        return true;
-    });
-}
-
-// the source once + every tile of the LODs the main / direct launch produces
-static uint64_t main_bytes(const JobPlan& j) {
-    uint64_t bytes = j.source_bytes;
-    for (uint32_t k = 0; k < j.main_levels; k++) bytes += j.grid.tiles_at(j.grid.lod_hi - k) * j.tile_bytes();
-    return bytes;
-}
-
-static FusedJobDev main_job(const JobPlan& j) {  // a fused_main / fused_direct launch over the job's items
-    FusedJobDev job = j.fused_job();
-    job.args.lod = j.grid.lod_hi;
-    job.args.levels = j.main_levels;
-    job.args.item_count = uint32_t(j.items.size());
-    job.host_items = j.items;
-    job.finest_layers = j.finest_layers;
-    job.all_layers = j.all_layers;
-    return job;
-}
-
-static void plan_hybrid(const JobPlan& j, PlanOut& out) {
-    Launch ls = job_launch(j, kLaunchSplit, BT_VARIANT_HYBRID);
-    ls.first_task = uint32_t(out.tasks.size());
-    for (const Task* t : j.splits) {
-        out.tasks.push_back(to_device_task(*t));
-        if (t->raster >= 0 && size_t(t->raster) < out.state.whole_raster.size()) out.state.whole_raster[size_t(t->raster)] = 1;  // (every rank splits every tile)
-    }
-    ls.task_count = uint32_t(j.splits.size());
-    ls.algorithmic_bytes = j.source_bytes + uint64_t(j.splits.size()) * j.tile_bytes();
-    out.plan.push_back(ls);
-    Launch lt = job_launch(j, kLaunchStitch, BT_VARIANT_HYBRID);
-    lt.first_task = uint32_t(out.tasks.size());
-    for (const Task* t : j.stitches)
-        if (t->coord.lod == j.grid.lod_hi) out.tasks.push_back(to_device_task(*t));
-    lt.task_count = uint32_t(out.tasks.size()) - lt.first_task;
-    lt.algorithmic_bytes = uint64_t(lt.task_count) * j.apron_bytes();
-    if (lt.task_count) out.plan.push_back(lt);
-}
-
-static void plan_direct(const bt_preprocessor* p, const JobPlan& j, PlanOut& out) {
-    FusedJobDev job = main_job(j);
-    bool rep = false, skips = false;
-    {   // source rows per tile row: below 1 output rows repeat source-row pairs
-        const double mosaic = double(j.m.center_size) * double(1u << j.grid.lod_hi);
-        for (const Task* t : j.splits) {
-            const RasterDev& r = p->rasters[t->raster].dev;
-            const double ratio = double(r.height) / (double(j.args.bry - j.args.tly) * mosaic);
-            if (ratio < 0.9999) rep = true;
-            if (ratio > 1.02) skips = true;  // (the BASELINE shapes, 1.008, pass over a row in one block of 32: they stay on the plain kernel)
-        }
-    }
-    {   // row blocks per workgroup: as many as keep at least one resident generation (1024 workgroups) busy
-        const uint64_t blocks = uint64_t(j.items.size()) * ((j.m.center_size + kDirectRows - 1) / kDirectRows);
-        job.args.groups = uint32_t(std::min<uint64_t>(kDirectMaxBlocks, std::max<uint64_t>(1, (blocks + 1023) / 1024)));
-#ifdef BT_DEBUG_HOOKS
-        if (const char* e = getenv("BT_FUSED_PARTS")) job.args.groups = std::max(1u, std::min(kDirectMaxBlocks, uint32_t(atoi(e))));
-#endif
-    }
-    Launch ld = job_launch(j, kLaunchFusedDirect, rep ? BT_VARIANT_DIRECT_REP : skips ? BT_VARIANT_DIRECT_SKIPS : BT_VARIANT_DIRECT);
-    ld.task_count = uint32_t(j.items.size());
-    ld.aux0 = uint32_t(out.state.jobs.size());
-    ld.algorithmic_bytes = main_bytes(j);
-    out.state.jobs.push_back(job);
-    out.plan.push_back(ld);
-}
-
-// fused_main's LDS window (FusedArgs::lds_pitch, lds_rows, apron_global, single_buffer) and the instance that runs it: its BT_VARIANT_* bit
-static uint32_t size_main_window(const bt_preprocessor* p, const JobPlan& j, FusedArgs& A) {
-    const AttachmentMeta& m = j.m;
-    const uint32_t lod_hi = j.grid.lod_hi;
-    // LDS window of a workgroup: T consecutive mosaic columns x (kMainRows + 2b) mosaic rows of the source
-    double ratio_x = 0.0, ratio_y = 0.0;
-    uint64_t max_pitch = 0;
-    // every raster of the job 16-byte aligned in base and pitch, as LDS-DMA needs: add_raster (bt_preprocess.cpp) gives every R16 raster such a
-    // base and pitch, so this only checks that invariant; a job that breaks it takes the run-time-pitch register staging
-    bool aligned = true;
-    const double mosaic = double(1u << lod_hi) * double(m.center_size);
-    for (const Task* t : j.splits) {
-        const RasterDev& r = p->rasters[t->raster].dev;
-        max_pitch = std::max<uint64_t>(max_pitch, r.pitch);
-        ratio_x = std::max(ratio_x, double(r.width) / (double(A.brx - A.tlx) * mosaic));
-        ratio_y = std::max(ratio_y, double(r.height) / (double(A.bry - A.tly) * mosaic));
-        if (((reinterpret_cast<uintptr_t>(r.data) | r.pitch) & 15u) != 0) aligned = false;
-    }
-    const uint32_t rows = std::min(kMainRows, m.center_size) + 2 * m.border_size;
-    const uint64_t cols_needed = uint64_t(double(m.texture_size - 1) * ratio_x) + 4 + 7;
-    uint64_t rows_needed = uint64_t(double(rows - 1) * ratio_y) + 4;  // contiguous source-row range (safe bound)
-    uint64_t exact_core = rows_needed;  // ... of the centre rows alone (without the first / last chunk's apron rows)
-    {   // exact: replay the kernel's own window computation for every tile row and chunk (same f32 operations)
-        const uint32_t c = m.center_size, b = m.border_size, chunks = (c + kMainRows - 1) / kMainRows;
-        const float scale = float(1u << lod_hi);
-        uint64_t exact = 1;
-        exact_core = 1;
-        std::vector<std::pair<uint32_t, int>> seen;  // (tile row, raster)
-        for (const Task* t : j.splits) {
-            const std::pair<uint32_t, int> key(t->coord.y, t->raster);
-            if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
-            seen.push_back(key);
-            const uint32_t H = p->rasters[t->raster].dev.height, n = 1u << lod_hi, ty = t->coord.y;
-            auto axis = [&](uint32_t tile, uint32_t r) { return split_axis(r, c, tile, scale, A.tly, A.bry, H); };
-            for (uint32_t k = 0; k < chunks; k++) {
-                const uint32_t r0 = k * kMainRows, r1 = std::min(c, r0 + kMainRows) - 1;
-                int lo = axis(ty, r0).i0, hi = axis(ty, r1).i1;
-                exact_core = std::max<uint64_t>(exact_core, uint64_t(hi - lo + 1));
-                if (k == 0) lo = std::min(lo, ty > 0 ? axis(ty - 1, c - b).i0 : axis(ty, 0).i0);
-                if (k == chunks - 1) hi = std::max(hi, ty + 1 < n ? axis(ty + 1, b - 1).i1 : axis(ty, c - 1).i1);
-                exact = std::max<uint64_t>(exact, uint64_t(hi - lo + 1));
-            }
-        }
-        rows_needed = std::min(rows_needed, exact);
-    }
-    const uint64_t pitch = (cols_needed + 7) / 8 * 8;
-    const uint64_t budget = 65536 - sizeof(MainShared);
-    A.lds_pitch = uint32_t(std::min<uint64_t>(pitch, 1u << 20));
-    // the whole window must fit (the bounds above are conservative); otherwise lds_rows = 0 selects the
-    // kernel variant that reads the source directly
-    // the staging loop holds one batch of 8 x 16-byte loads per thread: the window must fit that too
-    // and its byte offsets from the first row are kept in 32 bits
-    // (the register staging holds one batch of 4 x 16-byte loads per thread: a window of more pieces than that — ratios from ~1.2 up at
-    // T = 512 — is staged by LDS-DMA alone, when every raster of the job is 16-byte aligned; rounds 2 - 6 sent such jobs to the unstaged kernel)
-    // Four workgroups per CU need <= 40 KB each (160 KB of LDS).  When the window with the apron rows is past that and the centre rows alone are
-    // not (ratios ~1.25 - 1.35 at T = 512; at 1.41 the same step takes the job from two workgroups to three), the apron rows — 2b of a tile's T —
-    // read global memory and the window shrinks: ratio 1.3, 553 -> 3xx us (round 6, profiles/r06_gebco_size.txt)
-    const uint64_t kQuarter = (160u << 10) / 4, kThird = (160u << 10) / 3, fixed = sizeof(MainShared);
-    const uint64_t core_rows = std::min(rows_needed, exact_core);
-    // (only the run-time-pitch DMA variant knows the mode: aligned rasters, T = 512 or a window past the register batch, not the 528 pitch)
-    const bool dma_variant = aligned && pitch <= 4096 && pitch != 528 && (m.texture_size == 512 || core_rows * (pitch / 8) > 256 * 4);
-    {
-        const uint64_t with_aprons = fixed + 2 * rows_needed * pitch * 2, core = fixed + 2 * core_rows * pitch * 2;
-        auto groups = [&](uint64_t bytes) { return bytes <= kQuarter ? 4 : bytes <= kThird ? 3 : bytes <= (80u << 10) ? 2 : 1; };
-        if (dma_variant && groups(core) > groups(with_aprons)) {
-            A.apron_global = 1;
-            rows_needed = core_rows;
-        }
-    }
-    uint64_t buffers = 2;
-    // ... and where even the centre rows alone, twice, leave room for three workgroups or fewer, ONE buffer of them may leave room for four (FusedArgs::single_buffer)
-    if (dma_variant && fixed + 2 * rows_needed * pitch * 2 > kQuarter && fixed + core_rows * pitch * 2 <= kQuarter) {
-        A.single_buffer = 1;
-        A.apron_global = 1;
-        rows_needed = core_rows;
-        buffers = 1;
-    }
-    const bool fits_lds = buffers * rows_needed * pitch * 2 <= budget && (rows_needed + 1) * max_pitch < (1ull << 31);
-    const bool fits_batch = rows_needed * (pitch / 8) <= 256 * 4;
-    // (and by choice at T = 512, where it measured 2 % faster than the register staging on a 86400 x 43200 job; at T = 256 — half-empty
-    // 1 KB pieces — the register staging is 6 % faster and stays)
-    const bool dma_only = fits_lds && aligned && pitch <= 4096 && (!fits_batch || m.texture_size == 512);
-    A.lds_rows = fits_lds && (fits_batch || dma_only) ? uint32_t(rows_needed) : 0u;
-    if ((A.apron_global || A.single_buffer) && A.lds_rows && !dma_only) {  // (cannot happen by the conditions above; a window without apron rows in a variant that stages them would overrun)
-        A.apron_global = 0;
-        A.single_buffer = 0;
-        A.lds_rows = 0;
-    }
-    if (!A.lds_rows) return BT_VARIANT_MAIN_UNSTAGED;
-    if (aligned && m.texture_size == 512 && A.lds_pitch == 528) return BT_VARIANT_MAIN_DMA_528;
-    // a window the register staging cannot batch (a source-to-tile ratio away from 1), or T = 512 at any other pitch: LDS-DMA with a run-time pitch (round 6)
-    if (dma_only) return A.single_buffer ? BT_VARIANT_MAIN_SINGLE_BUFFER : A.apron_global ? BT_VARIANT_MAIN_APRON_GLOBAL : BT_VARIANT_MAIN_DMA_PITCH;
-    return BT_VARIANT_MAIN_REG_PITCH;
-}
-
-static void plan_main(const bt_preprocessor* p, const JobPlan& j, PlanOut& out) {
-    FusedJobDev job = main_job(j);
-#ifdef BT_DEBUG_HOOKS
-    if (const char* e = getenv("BT_FUSED_LDS_PAD")) job.lds_pad = uint32_t(atoi(e));
-#endif
-    {
-        const uint32_t chunks = (j.m.center_size + kMainRows - 1) / kMainRows;
-        // 4 workgroups of 4 waves per CU (128 VGPRs each) = 1024 resident: pick the number of parts per tile so
-        // that the grid is a whole number of 1024-workgroup rounds where possible
-        uint32_t parts = 1;
-#ifdef BT_DEBUG_HOOKS
-        if (const char* e = getenv("BT_FUSED_PARTS")) parts = uint32_t(atoi(e));
-        else
-#endif
-        {
-            while (parts < chunks && uint64_t(j.items.size()) * parts < 1024) parts++;
-            for (uint32_t cand = parts; cand <= std::min(chunks, parts + 8); cand++)
-                if ((uint64_t(j.items.size()) * cand) % 1024 == 0) { parts = cand; break; }
-        }
-        parts = std::max(parts, (chunks + kMaxChunks - 1) / kMaxChunks);  // row tables of a workgroup hold kMaxChunks chunks
-        job.args.groups = std::max(1u, std::min(parts, chunks));
-    }
-    Launch lm = job_launch(j, kLaunchFusedMain, size_main_window(p, j, job.args));
-    job.args.rotate_priority = 1;
-    lm.kernels = lm.variant == BT_VARIANT_MAIN_UNSTAGED ? 2u : 1u;  // (without the LDS window: fused_corner + fused_main in one entry)
-    lm.task_count = uint32_t(j.items.size());
-    lm.aux0 = uint32_t(out.state.jobs.size());
-    lm.algorithmic_bytes = main_bytes(j);
-    out.state.jobs.push_back(job);
-    out.plan.push_back(lm);
-}
-
-static void plan_apron_stitch(const JobPlan& j, PlanOut& out) {
-    if (j.main_levels <= 1 || j.rows_in_tail()) return;
-    // fused_main writes the centres and the left / right apron columns of the parent / grand-parent tiles; their
-    // top / bottom apron rows (whole 1 KB rows) come from the batched stitch kernel — sharded: everything, after
-    // the all-gather, from the then complete centres
-    Launch ls = job_launch(j, kLaunchStitch, BT_VARIANT_STITCH_LAUNCH);
-    ls.first_task = uint32_t(out.tasks.size());
-    for (const Task* t : j.stitches)
-        if (t->coord.lod != j.grid.lod_hi && t->coord.lod + j.main_levels > j.grid.lod_hi) out.tasks.push_back(to_device_task(*t));
-    ls.task_count = uint32_t(out.tasks.size()) - ls.first_task;
-    ls.algorithmic_bytes = uint64_t(ls.task_count) * j.apron_bytes();
-    ls.phase = j.shard ? 2u : 0u;
-    // fused_main also writes the left / right apron columns of these tiles (from registers); sharded runs lose
-    // the ones that crossed a strip boundary in the all-gather and re-stitch everything
-    ls.aux0 = (j.shard || j.direct) ? 0u : 1u;  // (fused_direct writes centres only: all four sides)
-    if (!j.shard && !j.direct) ls.algorithmic_bytes = uint64_t(ls.task_count) * 2 * (2 * j.m.border_size * uint64_t(j.m.texture_size)) * j.m.pixel_size;
-    if (ls.task_count) out.plan.push_back(ls);
-}
-
-struct TailPlan {
-    int job = -1, plan = -1;  // the first tail launch: its fused job and plan entry (-1: none)
-    uint32_t launches = 0;
-};
-
-// tail launches: three LODs at a time below the last fused one
-static TailPlan plan_tails(const JobPlan& j, PlanOut& out) {
-    const uint64_t Tt = j.m.texture_size, cc = j.m.center_size, bpp = j.m.pixel_size;
-    TailPlan tails;
-    for (uint32_t in_lod = j.main_lo(); in_lod > j.grid.lod_lo;) {
-        tails.launches++;
-        const uint32_t levels = std::min(3u, in_lod - j.grid.lod_lo);
-        FusedJobDev tail = j.fused_job();
-        tail.all_layers = j.all_layers;
-        tail.args.lod = in_lod;
-        tail.args.levels = levels;
-        tail.args.apron_lods = (j.rows_in_tail() && in_lod == j.main_lo()) ? j.main_levels - 1 : 0u;
-        tail.args.apron_cols = j.direct ? 1u : 0u;
-        Launch lt = job_launch(j, kLaunchFusedTail, j.args.regular ? BT_VARIANT_TAIL_REGULAR : BT_VARIANT_TAIL_IRREGULAR);
-        lt.aux0 = uint32_t(out.state.jobs.size());
-        lt.phase = j.shard ? 2u : 0u;
-        lt.algorithmic_bytes = j.grid.tiles_at(in_lod) * cc * cc * bpp;
-        for (uint32_t k = 0; k < tail.args.apron_lods; k++) lt.algorithmic_bytes += j.grid.tiles_at(in_lod + k) * 2 * (2 * j.m.border_size * (Tt + (j.direct ? cc : 0))) * bpp;
-        for (uint32_t k = 1; k <= levels; k++) {
-            lt.algorithmic_bytes += j.grid.tiles_at(in_lod - k) * j.tile_bytes();
-            lt.task_count += uint32_t(j.grid.tiles_at(in_lod - k));
-        }
-        if (tails.job < 0) {
-            tails.job = int(out.state.jobs.size());
-            tails.plan = int(out.plan.size());
-        }
-        out.state.jobs.push_back(tail);
-        out.plan.push_back(lt);
-        in_lod -= levels;
-    }
-    return tails;
-}
-
-// Every region beyond exactly one face edge of the face-edge stitch tasks of the LODs [lo, end) has its neighbour on the other face (pulled:
-// of the same LOD, with 16-bit coordinates), and every face-edge tile of those LODs that the grids hold has a stitch task (seam_skip / seam_pull
-// make the tail leave the cross-face regions of every such grid tile alone: one without a task would keep stale apron texels there)
-static bool seams_covered(const JobPlan& j, uint32_t lo, uint32_t end, bool pulled) {
-    std::unordered_set<uint32_t> stitched;
-    for (const Task* t : j.stitches) {
-        if (!on_face_edge(t->coord) || t->coord.lod < lo || t->coord.lod >= end) continue;
-        stitched.insert(t->atlas_index);
-        const int n = int(1u << t->coord.lod);
-        for (int i = 0; i < 8; i++) {
-            const int nx = int(t->coord.x) + kNeighbourOffsets[i][0], ny = int(t->coord.y) + kNeighbourOffsets[i][1];
-            const bool out_x = nx < 0 || nx >= n, out_y = ny < 0 || ny >= n;
-            const bt_atlas_tile& r = t->rel[i];
-            const bool across = r.atlas_index != BT_INVALID_ATLAS_INDEX && r.coordinate.side != t->coord.side;
-            if (out_x != out_y && !(across && (!pulled || (r.coordinate.lod == t->coord.lod && r.coordinate.x < 65536u && r.coordinate.y < 65536u))))
-                return false;
-        }
-    }
-    return j.grid.for_each(lo, end, [&](uint32_t, uint32_t lod, uint32_t x, uint32_t y, uint32_t v) {
-        return !(on_face_edge({0, lod, x, y}) && v != kInvalid && !stitched.count(v));
-    });
-}
-
-// cube: aprons that cross a face edge (stitch.wgsl:12-51, 79-118), one task — one workgroup — per region: only the apron regions whose
-// neighbour lives on another face (the fused kernels wrote the rest).  The regions of the LODs fused_main produced read centres that are
-// complete when the tail launch starts: they ride in that launch as extra workgroups (round 5: the 16k-texel-wide job's seam launch was
-// 33 of 500 us), and the tail's own apron-row workgroups leave those regions alone (FusedArgs::seam_skip).  What the tail itself
-// produces (the few tiles of the top LODs) is stitched by the generic kernel behind it, as before.
-static void plan_cube_seams(const JobPlan& j, const TailPlan& tails, PlanOut& out) {
-    const AttachmentMeta& m = j.m;
-    const uint32_t main_lo = j.main_lo(), lod_hi = j.grid.lod_hi;
-    // in the tail launch: R16 main plan, unsharded, a tail launch with apron-row workgroups exists, and EVERY region beyond exactly one
-    // face edge of the tiles whose apron rows the tail writes has its neighbour (then "skip" and "a seam workgroup writes it" coincide)
-    const bool in_tail = !j.shard && !j.hybrid && tails.job >= 0 && out.state.jobs[size_t(tails.job)].args.apron_lods != 0 &&  // (round 6: Rgba8 after fused_direct too)
-                         seams_covered(j, main_lo, lod_hi, false);
-    // Round 6: the cross-face regions of the LODs the tail ITSELF produces ride in it as well, PULLED from the tail's input (FusedArgs::seam_pull) —
-    // when ONE tail launch produces every lower LOD (its input then lies at most three LODs above any of them), every region beyond exactly
-    // one face edge of those tiles has its cross-face neighbour, and every face-edge grid tile of those LODs has a stitch task (the tail's
-    // pushes leave those regions alone).  No stitch launch follows the tail then: the cube job is two launches.
-    const bool pull = in_tail && tails.launches == 1 && seams_covered(j, j.grid.lod_lo, main_lo, true);
-    uint64_t tail_pixels = 0, late_pixels = 0;
-    const uint32_t tail_first = uint32_t(out.tasks.size());
-    for (int pass = 0; pass < 2; pass++) {  // the tail launch's regions first, then the later launch's
-        if (pass == 1 && in_tail) {
-            FusedJobDev& tj = out.state.jobs[size_t(tails.job)];
-            tj.seam_first = tail_first;
-            tj.args.seam_count = uint32_t(out.tasks.size()) - tail_first;
-            tj.args.seam_skip = 1;
-            tj.args.seam_pull = pull ? 1u : 0u;
-            out.plan[size_t(tails.plan)].algorithmic_bytes += 2 * tail_pixels * m.pixel_size;
-        }
-        const uint32_t first = uint32_t(out.tasks.size());
-        // (pass 0 in two sweeps: the pulled regions FIRST — they are the launch's longest workgroups and the seam list's head is dispatched first)
-        for (int sweep = (pass == 0 && pull) ? 0 : 1; sweep < 2; sweep++)
-            for (const Task* t : j.stitches) {
-                if (!on_face_edge(t->coord)) continue;
-                if (j.hybrid && t->coord.lod == lod_hi) continue;  // stitched completely by the batched kernel above
-                const bool pulled = pull && t->coord.lod < main_lo;
-                const bool rides = in_tail && (t->coord.lod >= main_lo || pulled);
-                if (rides != (pass == 0)) continue;
-                if (pass == 0 && pull && pulled != (sweep == 0)) continue;
-                const TaskDev d = to_device_task(*t);
-                for (int i = 0; i < 8; i++)
-                    if (d.rel_index[i] != BT_INVALID_ATLAS_INDEX && d.rel_side[i] != d.side) {
-                        TaskDev e = d;
-                        e.regions = 1u << i;
-                        uint32_t parts = 1;
-                        if (pulled) {  // evaluated from the tail's input LOD (main_lo) on the neighbour face: how many LODs up, and where the neighbour tile lies
-                            // an edge region is shared out so that a thread evaluates one pixel pair (256 per workgroup); a corner region is one workgroup
-                            const uint32_t pixels = m.border_size * (i < 4 ? m.center_size : m.border_size);
-                            const uint32_t pairs = (m.format != BT_FORMAT_R16 || ((m.border_size | m.texture_size) & 1u)) ? pixels : pixels / 2u;  // what one thread stores
-                            parts = std::max(1u, std::min(255u, (pairs + 255u) / 256u));
-                            e.rel_index[i] = (t->rel[i].coordinate.x << 16) | t->rel[i].coordinate.y;
-                        }
-                        for (uint32_t part = 0; part < parts; part++) {
-                            if (pulled) e.raster = (main_lo - t->coord.lod) | (part << 8) | (parts << 16);
-                            out.tasks.push_back(e);
-                        }
-                        (pass == 0 ? tail_pixels : late_pixels) += uint64_t(m.border_size) * (i < 4 ? m.center_size : m.border_size);
-                    }
-            }
-        if (pass == 0) continue;
-        Launch ls = job_launch(j, kLaunchStitch, BT_VARIANT_STITCH_LAUNCH);
-        ls.aux0 = 2u;  // one region per task
-        ls.first_task = first;
-        ls.task_count = uint32_t(out.tasks.size()) - first;
-        ls.algorithmic_bytes = 2 * late_pixels * m.pixel_size;
-        ls.phase = j.shard ? 2u : 0u;
-        if (ls.task_count) out.plan.push_back(ls);
-    }
-}
-
-// Every job's item list and grids in ONE device allocation, each array 256-byte aligned (as an allocation of its own is): at[2k] is where
-// job k's items start, at[2k + 1] its grids.  The fused jobs' args.items / args.grids point into it
-static bt_status fused_upload(FusedState& state, const std::vector<std::vector<MainItem>>& items, const std::vector<std::vector<uint32_t>>& grids) {
-    std::vector<size_t> at(2 * items.size());
-    size_t bytes = 0;
-    for (size_t k = 0; k < at.size(); k++) {
-        at[k] = (bytes + 255) & ~size_t(255);
-        bytes = at[k] + (k % 2 ? grids[k / 2].size() * sizeof(uint32_t) : items[k / 2].size() * sizeof(MainItem));
-    }
-    BT_HIP(hipMalloc(&state.arrays, bytes ? bytes : 1));
-    uint8_t* base = (uint8_t*)state.arrays;
-    for (size_t k = 0; k < items.size(); k++) {
-        if (!items[k].empty()) BT_HIP(hipMemcpy(base + at[2 * k], items[k].data(), items[k].size() * sizeof(MainItem), hipMemcpyHostToDevice));
-        if (!grids[k].empty()) BT_HIP(hipMemcpy(base + at[2 * k + 1], grids[k].data(), grids[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    for (FusedJobDev& job : state.jobs) {
-        job.args.items = (const MainItem*)(base + at[2 * job.queue_job]);
-        job.args.grids = (const uint32_t*)(base + at[2 * job.queue_job + 1]);
-    }
-    return BT_OK;
-}
-
-bool fused_plan(bt_preprocessor* p, bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan) {
-    FusedState& state = state_of(p);
-    hipFree(state.arrays);
-    state.arrays = nullptr;
-    state.jobs.clear();
-    state.whole_raster.assign(p->rasters.size(), 0);
-    if (p->queue.empty()) return false;
-
-    PlanOut out{tasks, plan, state};
-    std::vector<std::vector<MainItem>> items;
-    std::vector<std::vector<uint32_t>> grids;
-    for (uint32_t job = 0; job < p->jobs; job++) {
-        JobPlan j;
-        if (!collect_job(p, a, job, j) || !fill_grid(j) || !qualifies(j)) return false;
-        plan_shards(p, j);
-        order_items(p, j);
-        describe_job(p, a, j);
-        if (j.hybrid) plan_hybrid(j, out);
-        else if (j.direct) plan_direct(p, j, out);
-        else plan_main(p, j, out);
-        plan_apron_stitch(j, out);
-        const TailPlan tails = plan_tails(j, out);
-        if (j.spherical) plan_cube_seams(j, tails, out);
-        items.push_back(std::move(j.items));
-        grids.push_back(std::move(j.grid.cells));
-    }
-    return fused_upload(state, items, grids) == BT_OK;
-}
-
-// Before the launches of a run, in plan order: a fused main / direct launch whose finest tiles are all still unwritten since bt_atlas_create
-// (Attachment::written) runs with FusedArgs::prev_zero — bit-identical by construction, the fetch would return the memset's 0 — and every
-// launch marks the layers it writes, so a later job of the same queue that overlays these tiles takes the fetching path.  Returns how many
-// launches got the flag (bt_run_stats::prev_zero_launches).
-uint32_t fused_begin_run(bt_preprocessor* p, bt_atlas* a) {
-    uint32_t flagged = 0;
-    for (const Launch& l : p->plan) {
-        Attachment& at = a->attachments[l.attachment];
-        if (l.kind == kLaunchSplit || l.kind == kLaunchDownsample || l.kind == kLaunchStitch) {
-            for (uint32_t i = l.first_task; i < l.first_task + l.task_count && i < p->tasks_host.size(); i++) at.mark_written(p->tasks_host[i].atlas_index, 1);
-            continue;
-        }
-        if (!p->fused || l.aux0 >= p->fused->jobs.size()) continue;
-        FusedJobDev& job = p->fused->jobs[l.aux0];
-        if (l.kind == kLaunchFusedMain || l.kind == kLaunchFusedDirect) {
-            bool fresh = !job.finest_layers.empty();
-            for (uint32_t layer : job.finest_layers) fresh = fresh && layer < at.written.size() && !at.written[layer];
-            job.args.prev_zero = fresh ? 1u : 0u;
-            flagged += fresh;
-        }
-        for (uint32_t layer : job.all_layers) at.mark_written(layer, 1);
-    }
-    return flagged;
-}
-
-// The source texels [x0, x1) x [y0, y1) of raster `raster` that the launches of the compiled plan read — for a sharded
-// preprocessor: this rank's column strips + their halo (finest aprons are evaluated from the source; fused_main's staged windows
-// start on an 8-texel boundary and are lds_pitch wide; fused_direct reads texel by texel).  Conservative (a missing neighbour tile
-// only shrinks what the kernel reads).  Decided PER RASTER: false — the caller assumes the whole raster — unless every launch that
-// reads it is a fused_main / fused_direct launch with an item list (a height raster read by fused_main and an albedo raster read by
-// fused_direct in one queue get a window each; a raster the hybrid plan's batched split reads has none).
-bool fused_source_window(const bt_preprocessor* p, uint32_t raster, uint32_t out[4]) {
-    if (!p->fused || raster >= p->rasters.size()) return false;
-    if (raster < p->fused->whole_raster.size() && p->fused->whole_raster[raster]) return false;
-    const RasterDev& r = p->rasters[raster].dev;
-    uint32_t x0 = r.width, y0 = r.height, x1 = 0, y1 = 0;
-    bool any = false, known = false;
-    for (const Launch& l : p->plan) {
-        if ((l.kind != kLaunchFusedMain && l.kind != kLaunchFusedDirect) || l.aux0 >= p->fused->jobs.size()) continue;
-        const FusedJobDev& job = p->fused->jobs[l.aux0];
-        if (job.host_items.empty()) continue;
-        known = true;
-        const bool direct = l.variant == BT_VARIANT_DIRECT || l.variant == BT_VARIANT_DIRECT_REP || l.variant == BT_VARIANT_DIRECT_SKIPS;
-        const FusedArgs& A = job.args;
-        const uint32_t c = A.m.center_size, b = A.m.border_size, n = 1u << A.lod;
-        const float scale = float(n);
-        auto ax = [&](uint32_t tile, uint32_t col) { return split_axis(col, c, tile, scale, A.tlx, A.brx, r.width); };
-        auto ay = [&](uint32_t tile, uint32_t row) { return split_axis(row, c, tile, scale, A.tly, A.bry, r.height); };
-        for (const MainItem& it : job.host_items) {
-            if (it.raster != raster) continue;
-            any = true;
-            const int lo_x = std::min(it.x > 0 ? ax(it.x - 1, c - b).i0 : ax(it.x, 0).i0, ax(it.x, 0).i0);
-            const int hi_x = std::max(it.x + 1 < n ? ax(it.x + 1, b - 1).i1 : ax(it.x, c - 1).i1, ax(it.x, c - 1).i1);
-            const int lo_y = std::min(it.y > 0 ? ay(it.y - 1, c - b).i0 : ay(it.y, 0).i0, ay(it.y, 0).i0);
-            const int hi_y = std::max(it.y + 1 < n ? ay(it.y + 1, b - 1).i1 : ay(it.y, c - 1).i1, ay(it.y, c - 1).i1);
-            uint32_t xa = uint32_t(std::max(lo_x, 0)), xe = uint32_t(hi_x) + 1u;
-            if (!direct) {
-                xa &= ~7u;
-                if (l.variant != BT_VARIANT_MAIN_UNSTAGED) xe = std::max(xe, xa + A.lds_pitch);  // the staged window: lds_pitch texels from the aligned start
-                if (xe + 8u > r.width) xe = r.width;                   // (pieces past the row's end re-read its last 16 bytes)
-            }
-            x0 = std::min(x0, xa);
-            x1 = std::max(x1, std::min(xe, r.width));
-            y0 = std::min(y0, uint32_t(std::max(lo_y, 0)));
-            y1 = std::max(y1, std::min(uint32_t(hi_y) + 1u, r.height));
-        }
-    }
-    if (!known) return false;
-    if (!any) x0 = y0 = x1 = y1 = 0;  // a cube face none of this rank's units lie on
-    out[0] = x0;
-    out[1] = y0;
-    out[2] = x1;
-    out[3] = y1;
-    return true;
-}
-
-// Bands of whole tile rows of a fused main / direct launch (streamed runs), with the raster each band reads and the last source row its
-// kernels touch (the bottom apron rows of its last tile row are evaluated with the next tile row's formula: same f32 operations as the
-// kernels' row tables).  The items are in (side, tile row, x) order; a band never crosses a side (a cube job: six rasters, one after the
-// other).  tile_rows_per_band == 0: a quarter of the face's tile rows, at most 4 (the 16k job: 8 bands of 4 rows; a 4k job: 4 bands of 2).
-bool fused_stream_bands(bt_preprocessor* p, const Launch& l, uint32_t tile_rows_per_band, std::vector<StreamBand>* bands) {
-    if ((l.kind != kLaunchFusedMain && l.kind != kLaunchFusedDirect) || !p->fused || l.aux0 >= p->fused->jobs.size()) return false;
-    const FusedJobDev& job = p->fused->jobs[l.aux0];
-    const std::vector<MainItem>& items = job.host_items;
-    if (items.empty() || l.variant == BT_VARIANT_MAIN_UNSTAGED) return false;  // (the unstaged fused_main is two kernels over the whole item list)
-    const uint32_t c = job.args.m.center_size, b = job.args.m.border_size, n = 1u << job.args.lod;
-    if (tile_rows_per_band == 0) tile_rows_per_band = std::max(1u, std::min(4u, n / 4u));
-    const float scale = float(n);
-    bands->clear();
-    size_t i = 0;
-    while (i < items.size()) {
-        const uint32_t side = items[i].side, raster = items[i].raster;
-        if (raster >= p->rasters.size()) return false;
-        const RasterDev& r = p->rasters[raster].dev;
-        auto axis = [&](uint32_t tile, uint32_t row) { return split_axis(row, c, tile, scale, job.args.tly, job.args.bry, r.height); };
-        StreamBand band{};
-        band.item_begin = uint32_t(i);
-        band.tile_y_begin = items[i].y;
-        band.side = side;
-        band.raster = raster;
-        uint32_t rows = 0, y = items[i].y;
-        while (i < items.size() && items[i].side == side && (items[i].y == y || rows + 1 < tile_rows_per_band)) {
-            if (items[i].raster != raster) return false;  // one source per side
-            if (items[i].y != y) {
-                if (items[i].y < y) return false;  // not in tile-row order
-                y = items[i].y;
-                rows++;
-            }
-            i++;
-        }
-        band.item_count = uint32_t(i) - band.item_begin;
-        band.tile_y_end = y + 1;
-        const int hi = y + 1 < n ? axis(y + 1, b - 1).i1 : axis(y, c - 1).i1;
-        band.source_row_end = uint32_t(std::min<int64_t>(int64_t(r.height), int64_t(hi) + 1));
-        // a raster's bands follow each other and its source rows never decrease from band to band (they do not for a dataset rectangle with
-        // top < bottom); a raster that comes back after another one's bands cannot be streamed
-        if (!bands->empty() && bands->back().raster == raster) {
-            if (bands->back().source_row_end > band.source_row_end) return false;
-        } else {
-            for (const StreamBand& earlier : *bands)
-                if (earlier.raster == raster) return false;
-        }
-        bands->push_back(band);
-    }
-    return true;
-}
-
-void fused_launch_tiles(const bt_preprocessor* p, const Launch& l, uint32_t item_begin, uint32_t item_count, std::vector<FusedTile>* out) {
-    out->clear();
-    if ((l.kind != kLaunchFusedMain && l.kind != kLaunchFusedDirect) || !p->fused || l.aux0 >= p->fused->jobs.size()) return;
-    const FusedJobDev& job = p->fused->jobs[l.aux0];
-    for (uint64_t i = item_begin; i < uint64_t(item_begin) + item_count && i < job.host_items.size(); i++) {
-        const MainItem& it = job.host_items[size_t(i)];
-        out->push_back({{it.side, job.args.lod, it.x, it.y}, it.atlas_index});
-    }
-}
 
 // one fused plan entry: the kernel instance of its variant (fused_plan chose it) over the items [item_begin, item_begin + item_count) of a
 // main / direct launch's list (a band of a streamed run; default: all)

@@ -358,7 +358,7 @@ bt_status launch_edit_splat(hipStream_t stream, const AttachmentMeta& m, void* a
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 
-// fused-path state of a preprocessor (bt_fused.hip): launch descriptors + device buffers of its compiled queue
+// fused-path state of a preprocessor (bt_fused_args.hpp; bt_fused_plan.cpp fills it): launch descriptors + device buffers of its compiled queue
 struct FusedState;
 void fused_release(struct ::bt_preprocessor* p);
 
@@ -366,11 +366,11 @@ bt_status release_queue(struct ::bt_preprocessor* p);  // bt_run.cpp
 bt_status ensure_compiled(struct ::bt_preprocessor* p, struct ::bt_atlas* a, uint32_t mode);  // bt_run.cpp: queue -> launch plan
 // bt_run.cpp: one launch of the plan; a fused main / direct launch runs the items [item_begin, item_begin + item_count) of its list (streamed runs' bands)
 bt_status run_plan_entry(struct ::bt_preprocessor* p, struct ::bt_atlas* a, const Launch& l, uint32_t item_begin = 0, uint32_t item_count = 0xFFFFFFFFu);
-uint32_t fused_begin_run(struct ::bt_preprocessor* p, struct ::bt_atlas* a);  // bt_fused.hip: per run, before its launches (FusedArgs::prev_zero, Attachment::written)
+uint32_t fused_begin_run(struct ::bt_preprocessor* p, struct ::bt_atlas* a);  // bt_fused_plan.cpp: per run, before its launches (FusedArgs::prev_zero, Attachment::written)
 bt_status check_distributed_one_sided(const struct ::bt_preprocessor* p);  // bt_run.cpp: BT_RUN_SHARD_DISTRIBUTED is refused for a cube job
 void record_saves(struct ::bt_preprocessor* p, struct ::bt_atlas* a);      // bt_run.cpp: the queue's Save tasks -> bt_atlas::to_save, once per queue and save
-bool fused_plan(struct ::bt_preprocessor* p, struct ::bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan);  // bt_fused.hip: queue -> fused launch plan; false: the generic plan
-bool fused_source_window(const struct ::bt_preprocessor* p, uint32_t raster, uint32_t out[4]);  // bt_fused.hip: the texels of a raster the plan's launches read; false: no window is known
+bool fused_plan(struct ::bt_preprocessor* p, struct ::bt_atlas* a, std::vector<TaskDev>& tasks, std::vector<Launch>& plan);  // bt_fused_plan.cpp: queue -> fused launch plan; false: the generic plan
+bool fused_source_window(const struct ::bt_preprocessor* p, uint32_t raster, uint32_t out[4]);  // bt_fused_plan.cpp: the texels of a raster the plan's launches read; false: no window is known
 // bt_stream.cpp: w = the fused source window of raster i when the caller asks for it and the plan has one, else the whole raster
 void raster_window(const struct ::bt_preprocessor* p, uint32_t i, bool use_fused_window, uint32_t w[4]);
 bt_status upload_pending_rasters(struct ::bt_preprocessor* p, const std::vector<uint8_t>* skip = nullptr);  // bt_stream.cpp: deferred host rasters, all at once (skip[i]: not raster i)

@@ -1,8 +1,8 @@
-"""Which kernel variant produced the tiles: every plan and kernel variant the launch planner (fused_plan, bt_fused.hip) can choose, pinned by a
+"""Which kernel variant produced the tiles: every plan and kernel variant the launch planner (fused_plan, bt_fused_plan.cpp) can choose, pinned by a
 small job that must report EXACTLY its variants (bt_run_stats.variants) and match the oracle tile for tile — on a fresh atlas, re-run onto the
 written atlas (no-data texels fetch their previous value), through the streamed pipeline and onto a fresh atlas primed with non-zero
 previous contents (the fetch must read the right texel of the right layer).  A planner change (a threshold, the size of
-MainShared) that moves a case to another variant fails here and has to be moved on purpose; a variant without a case fails on the CPU
+MainShared in bt_fused_args.hpp) that moves a case to another variant fails here and has to be moved on purpose; a variant without a case fails on the CPU
 (test_every_variant_has_a_case)."""
 
 import numpy as np

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Register / scratch / LDS use of every kernel of a source file (default bt_fused.hip) as compiled for gfx950 (the metadata the assembler emits):
+# Register / scratch / LDS use of every kernel of a source file (default bt_fused.hip, the translation unit of every fused kernel: bt_fused_common.hpp
+# and bt_fused_tail.hpp are its text and cannot be compiled on their own) as compiled for gfx950 (the metadata the assembler emits):
 #   tools/kernel_resources.sh [pattern] [source.hip]          e.g. tools/kernel_resources.sh raycast bt_raycast.hip
 #                                                               tools/kernel_resources.sh normal bt_normal.hip   (tile_tree_normal_kernel, tile_normals_kernel)
 #                                                               tools/kernel_resources.sh edit bt_edit.hip   (edit_brush / edit_paint / edit_region / edit_gather / edit_smooth / edit_downsample)
