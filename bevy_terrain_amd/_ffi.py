@@ -250,6 +250,25 @@ class SplatRuleC(C.Structure):
                 ("steep_fade", C.c_float), ("weight", C.c_float), ("colour", C.c_float * 3), ("_padding", C.c_uint32 * 2)]
 
 
+SCATTER_MAX_RULES, SCATTER_NO_MASK = 8, 0xFFFFFFFF
+
+
+class ScatterRuleC(C.Structure):
+    _fields_ = [("height_lo", C.c_float), ("height_hi", C.c_float), ("height_fade", C.c_float), ("steep_lo", C.c_float), ("steep_hi", C.c_float),
+                ("steep_fade", C.c_float), ("density", C.c_float), ("scale_lo", C.c_float), ("scale_hi", C.c_float), ("mask_channel", C.c_uint32),
+                ("_padding", C.c_uint32 * 2)]
+
+
+class ScatterInstanceC(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("normal", C.c_float * 3), ("scale", C.c_float), ("yaw", C.c_float), ("rule", C.c_uint32),
+                ("cell", C.c_uint32 * 2)]
+
+
+class ScatterStatsC(C.Structure):
+    _fields_ = [("total", C.c_uint64), ("written", C.c_uint64), ("cells", C.c_uint64), ("cells_no_data", C.c_uint64),
+                ("per_rule", C.c_uint64 * SCATTER_MAX_RULES), ("launches", C.c_uint32), ("_padding", C.c_uint32)]
+
+
 PATH_MAX_CELLS, PATH_MAX_GOALS = 1 << 22, 4096
 PATH_GOAL, PATH_UNREACHABLE, PATH_BLOCKED = 8, 254, 255
 PATH_TRACE_OK, PATH_TRACE_BLOCKED, PATH_TRACE_UNREACHABLE, PATH_TRACE_LOOP = 0, 1, 2, 3
@@ -346,6 +365,8 @@ PROTOTYPES = {
     "bt_atlas_paint": (_i32, [_vp, _u32, _u32, _P(PaintStampC), _u32, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_splat_from_height": (_i32, [_vp, _u32, _u32, _P(TerrainModelC), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(SplatRuleC), _u32, _P(C.c_uint8),
                                           _P(TileCoordinateC), _u32, _P(EditStatsC)]),
+    "bt_atlas_scatter_instances": (_i32, [_vp, _u32, _u32, _P(TerrainModelC), _P(TileCoordinateC), _u32, _P(ScatterRuleC), _u32, _u32, C.c_float,
+                                          _P(ScatterInstanceC), _u64, _P(_u64), _P(ScatterStatsC)]),
     "bt_atlas_read_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(_u32)]),
     "bt_atlas_write_region": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _P(TileCoordinateC), _u32, _P(EditStatsC)]),
     "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),

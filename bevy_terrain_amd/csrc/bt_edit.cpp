@@ -1,4 +1,4 @@
-// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_splat_from_height / bt_atlas_write_region / bt_atlas_read_region /
+// bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_splat_from_height / bt_atlas_scatter_instances (its checks) / bt_atlas_write_region / bt_atlas_read_region /
 // bt_atlas_save_tiles: the host half of in-place editing.
 //
 // An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
@@ -11,6 +11,7 @@
 #include <cstring>
 #include <map>
 
+#include "bt_model.hpp"
 #include "bt_tile_io.hpp"
 
 using namespace bt;
@@ -519,23 +520,126 @@ std::vector<Box> stamp_boxes(const bt_atlas* a, uint32_t ai, uint32_t lod, const
     return boxes;
 }
 
-// the first defect of a rule of bt_atlas_splat_from_height, or NULL
-const char* bad_rule(const bt_splat_rule& r, uint32_t mode) {
+// the first defect of the height and slope bands of a rule (bt_splat_rule and bt_scatter_rule begin with the same six bounds), or NULL
+template <typename Rule>
+const char* bad_bands(const Rule& r) {
     const float bounds[2][3] = {{r.height_lo, r.height_hi, r.height_fade}, {r.steep_lo, r.steep_hi, r.steep_fade}};
     for (const float* v : {bounds[0], bounds[1]}) {
         if (std::isnan(v[0]) || std::isnan(v[1])) return "a NaN bound";
         if (v[0] > v[1]) return "lo > hi";
         if (!std::isfinite(v[2]) || v[2] < 0.0f) return "fade (finite and >= 0)";
     }
+    return nullptr;
+}
+
+// the first defect of a rule of bt_atlas_splat_from_height, or NULL
+const char* bad_rule(const bt_splat_rule& r, uint32_t mode) {
+    if (const char* bad = bad_bands(r)) return bad;
     if (!std::isfinite(r.weight) || r.weight < 0.0f) return "weight (finite and >= 0)";
     for (float v : r.colour)
         if (mode == BT_SPLAT_COLOUR ? !std::isfinite(v) : std::isnan(v)) return "colour (not finite)";
     return nullptr;
 }
 
+// the first defect of a rule of bt_atlas_scatter_instances, or NULL; masked: the call has a mask attachment
+const char* bad_scatter_rule(const bt_scatter_rule& r, bool masked) {
+    if (const char* bad = bad_bands(r)) return bad;
+    if (!(r.density >= 0.0f && r.density <= 1.0f)) return "density (in [0, 1])";
+    if (!std::isfinite(r.scale_lo) || !std::isfinite(r.scale_hi) || r.scale_lo > r.scale_hi) return "scale (finite, scale_lo <= scale_hi)";
+    if (r.mask_channel != BT_SCATTER_NO_MASK && r.mask_channel > 3u) return "mask_channel (0 .. 3 or BT_SCATTER_NO_MASK)";
+    if (r.mask_channel != BT_SCATTER_NO_MASK && !masked) return "a mask_channel without a mask attachment";
+    return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
+
+bt_status bt_atlas_scatter_instances(bt_atlas* a, uint32_t hi, uint32_t mi, const bt_terrain_model* model, const bt_tile_coordinate* coords, uint32_t count,
+                                     const bt_scatter_rule* rules, uint32_t rule_count, uint32_t seed, float jitter, bt_scatter_instance* out, uint64_t cap,
+                                     uint64_t* out_first, bt_scatter_stats* stats) {
+    const char* who = "bt_atlas_scatter_instances";
+    if (stats) *stats = bt_scatter_stats{};
+    // what can be refused without the atlas is refused without it (as SPLAT's rules are)
+    if (!model || !rules || !stats || (count && !coords) || (cap && !out)) {
+        set_error("%s: NULL %s", who, !model ? "model" : !rules ? "rules" : !stats ? "stats" : count && !coords ? "coords with count > 0" : "out_host with cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (rule_count == 0u || rule_count > BT_SCATTER_MAX_RULES) {
+        set_error("%s: %u rules (1 .. %u)", who, rule_count, unsigned(BT_SCATTER_MAX_RULES));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool masked = mi != BT_SCATTER_NO_MASK;
+    for (uint32_t i = 0; i < rule_count; i++)
+        if (const char* bad = bad_scatter_rule(rules[i], masked)) {
+            set_error("%s: rule %u: %s", who, i, bad);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    if (!(jitter >= 0.0f && jitter <= 1.0f)) {
+        set_error("%s: jitter %g (in [0, 1])", who, double(jitter));
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_model(model, who)) return s;
+    if (!a) {
+        set_error("%s: NULL atlas", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (hi >= a->attachments.size() || (masked && (mi == hi || mi >= a->attachments.size()))) {
+        set_error("%s: height attachment %u and mask attachment %u of %zu", who, hi, mi, a->attachments.size());
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const Attachment& heights = a->attachments[hi];
+    const AttachmentMeta& hm = heights.meta;
+    if (hm.format != BT_FORMAT_R16) {
+        set_error("%s: height attachment format %u (the rules read R16 heights)", who, hm.format);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (masked) {
+        const AttachmentMeta& mm = a->attachments[mi].meta;
+        if (mm.format != BT_FORMAT_RGBA8) {
+            set_error("%s: mask attachment format %u (a mask channel is a byte of an Rgba8 texel)", who, mm.format);
+            return BT_ERR_UNSUPPORTED;
+        }
+        if (hm.texture_size != mm.texture_size || hm.border_size != mm.border_size) {
+            set_error("%s: heights of texture_size %u, border_size %u and a mask of %u, %u: a cell reads the mask texel in its place", who, hm.texture_size,
+                      hm.border_size, mm.texture_size, mm.border_size);
+            return BT_ERR_UNSUPPORTED;
+        }
+    }
+    if (hm.border_size == 0) {
+        set_error("%s: attachment %u has no border (the taps of an edge cell need the neighbour's texels)", who, hi);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (hm.center_size % 2u) {
+        set_error("%s: odd centre size %u (texture_size %u, border_size %u)", who, hm.center_size, hm.texture_size, hm.border_size);
+        return BT_ERR_UNSUPPORTED;
+    }
+    const model::Model md = model::make_model(*model);
+    const uint32_t layers = masked ? std::min(hm.atlas_size, a->attachments[mi].meta.atlas_size) : hm.atlas_size;
+    std::vector<ScatterTile> tiles(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const bt_tile_coordinate& co = coords[i];
+        if (co.side >= model::side_count(md) || co.lod >= a->config.lod_count || co.lod > 31u || (uint64_t(co.x) >> co.lod) || (uint64_t(co.y) >> co.lod)) {
+            set_error("%s: coords[%u] = (%u, %u, %u, %u): side / lod / x / y out of range", who, i, co.side, co.lod, co.x, co.y);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        if ((uint64_t(hm.center_size) << co.lod) > 0xFFFFFFFFull) {
+            set_error("%s: coords[%u]: a mosaic of %u x 2^%u texels", who, i, hm.center_size, co.lod);
+            return BT_ERR_UNSUPPORTED;
+        }
+        const auto it = a->tile_states.find(co);
+        if (it == a->tile_states.end() || it->second.atlas_index >= layers) {
+            set_error("%s: the atlas holds no layer for coords[%u] = (%u, %u, %u, %u)", who, i, co.side, co.lod, co.x, co.y);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        tiles[i] = {it->second.atlas_index, co.lod, co.side, co.x, co.y};
+    }
+    if (!count) return BT_OK;
+    ScatterJob job{};
+    job.meta = hm, job.heights = heights.level0, job.mask = masked ? a->attachments[mi].level0 : nullptr;  // reads: no layer is marked written
+    job.model = model, job.rules = rules, job.rule_count = rule_count, job.seed = seed, job.jitter = jitter;
+    return scatter_run(a->ctx, job, tiles, out, cap, out_first, stats);
+}
 
 bt_status bt_atlas_splat_from_height(bt_atlas* a, uint32_t hi, uint32_t gi, const bt_terrain_model* model, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
                                      uint32_t width, uint32_t height, uint32_t mode, const bt_splat_rule* rules, uint32_t count, const uint8_t fallback[4],

@@ -247,7 +247,10 @@ struct bt_ctx {
     // bt_atlas_path_field: the planes of one call on the device (raw texels, mask, heights, D, next, the block flags); and its
     // words with a pinned twin (the per-sweep counters of a batch, the counts of bt_path_stats)
     bt::Scratch path, path_words;
-    std::array<bt::Scratch*, 7> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_scatter_instances: the totals, the tile list and the firsts of one call, the block records, block offsets and cell bytes of
+    // one chunk of it, and the instance list on the device
+    bt::Scratch scatter;
+    std::array<bt::Scratch*, 8> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
     // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
     // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out (kept until bt_ctx_trim)
@@ -355,6 +358,23 @@ struct SplatSource {
 uint32_t splat_reach(const AttachmentMeta& m);
 bt_status launch_edit_splat(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows, const SplatSource& src,
                             const bt_splat_rule* rules);
+// bt_scatter.hip, bt_atlas_scatter_instances behind its argument checks (bt_edit.cpp): the listed tiles (each with the layer that holds it)
+// of the R16 attachment `meta` / `heights`, the optional Rgba8 mask attachment of the same texture_size and border_size (`mask`: its
+// level 0, or nullptr), the checked rules.  Synchronous: the list, the firsts and the stats are the caller's when it returns
+struct ScatterTile {
+    uint32_t layer, lod, side, x, y;
+};
+struct ScatterJob {
+    AttachmentMeta meta;  // of the heights
+    const void* heights;
+    const void* mask;
+    const bt_terrain_model* model;
+    const bt_scatter_rule* rules;
+    uint32_t rule_count, seed;
+    float jitter;
+};
+bt_status scatter_run(bt_ctx* ctx, const ScatterJob& job, const std::vector<ScatterTile>& tiles, bt_scatter_instance* out, uint64_t cap, uint64_t* out_first,
+                      bt_scatter_stats* stats);
 bt_status launch_synth_fbm(bt_ctx* ctx, void* dst, uint32_t w, uint32_t h, uint64_t pitch, uint32_t x0, uint32_t y0,
                            uint32_t base_cell, uint32_t octaves, uint32_t seed);
 

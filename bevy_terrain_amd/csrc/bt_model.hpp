@@ -226,8 +226,8 @@ BT_HD Coordinate coordinate_from_world_position(V3 world, const Model& m) {
     return {side, {0.5 * w.x + 0.5, 0.5 * w.y + 0.5}};
 }
 
-// coordinate.rs:115-135
-BT_HD V3 coordinate_world_position(Coordinate c, const Model& m, float height) {
+// coordinate.rs:115-133: the local position of a coordinate (unit on a spherical model), which coordinate_world_position displaces
+BT_HD V3 coordinate_local_position(Coordinate c, const Model& m) {
     V3 local;
     if (is_spherical(m)) {
         const V2 w = {(c.uv.x - 0.5) / 0.5, (c.uv.y - 0.5) / 0.5};
@@ -244,7 +244,11 @@ BT_HD V3 coordinate_world_position(Coordinate c, const Model& m, float height) {
     } else {
         local = {c.uv.x - 0.5, 0.0, c.uv.y - 0.5};
     }
-    return position_local_to_world(m, local, double(height));
+    return local;
+}
+// coordinate.rs:115-135
+BT_HD V3 coordinate_world_position(Coordinate c, const Model& m, float height) {
+    return position_local_to_world(m, coordinate_local_position(c, m), double(height));
 }
 
 // coordinate.rs:27-53, 137-151 (SideInfo: 0 = Fixed0, 1 = Fixed1, 2 = PositiveS, 3 = PositiveT)

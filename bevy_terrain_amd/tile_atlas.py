@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -196,6 +196,40 @@ class SplatRule:
         lo, hi = self.steep()
         return _ffi.SplatRuleC(float(self.height[0]), float(self.height[1]), float(self.height_fade), lo, hi, float(self.slope_fade), float(self.weight),
                                (C.c_float * 3)(*[float(v) for v in self.colour]), (C.c_uint32 * 2)(0, 0))
+
+
+@dataclass
+class ScatterRule:
+    """bt_scatter_rule: one rule of TileAtlas.scatter_instances.  A cell places an instance of the rule with the probability density *
+    band(height) * band(steep) * mask, the bands being SplatRule's (height in world height units, slope in DEGREES from flat, slope_fade in
+    units of steep = 1 - cos).  mask_channel: None, or the channel (0 .. 3 or "r", "g", "b", "a") of the mask attachment whose byte / 255
+    multiplies the probability.  scale: (lo, hi), the range an instance's scale is drawn from.  Rules exclude each other: a cell places at
+    most one instance, of the first rule (in list order) its random number falls to."""
+    height: Tuple[float, float] = (-math.inf, math.inf)
+    slope: Tuple[float, float] = (0.0, 90.0)
+    height_fade: float = 0.0
+    slope_fade: float = 0.0
+    density: float = 1.0
+    scale: Tuple[float, float] = (1.0, 1.0)
+    mask_channel: Optional[Union[int, str]] = None
+
+    def steep(self) -> Tuple[float, float]:
+        """the slope limits as the C struct carries them: 1 - cos, in binary32"""
+        return SplatRule.steep(self)
+
+    def channel(self) -> int:
+        if self.mask_channel is None:
+            return _ffi.SCATTER_NO_MASK
+        return "rgba".index(self.mask_channel) if isinstance(self.mask_channel, str) else int(self.mask_channel)
+
+    def _c(self):
+        lo, hi = self.steep()
+        return _ffi.ScatterRuleC(float(self.height[0]), float(self.height[1]), float(self.height_fade), lo, hi, float(self.slope_fade), float(self.density),
+                                 float(self.scale[0]), float(self.scale[1]), self.channel(), (C.c_uint32 * 2)(0, 0))
+
+
+# bt_scatter_instance as a numpy record: 56 bytes, no padding
+SCATTER_INSTANCE_DTYPE = np.dtype([("position", "<f8", 3), ("normal", "<f4", 3), ("scale", "<f4"), ("yaw", "<f4"), ("rule", "<u4"), ("cell", "<u4", 2)])
 
 
 @dataclass
@@ -488,6 +522,41 @@ class TileAtlas:
         model = model_c(self.config.model)
         return self._edit_result(lambda changed, cap, stats: _ffi.lib().bt_atlas_splat_from_height(
             self._h, height_attachment, target_attachment, C.byref(model), side, lod, x0, y0, w, h, mode_c, arr, len(rules), bytes4, changed, cap, stats))
+
+    def scatter_instances(self, height_attachment: int, rules, coords, mask_attachment: Optional[int] = None, seed: int = 0, jitter: float = 1.0,
+                          cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, dict]:
+        """bt_atlas_scatter_instances: vegetation placement.  Every centre texel (cell) of the listed tiles of the R16 attachment
+        `height_attachment` places at most one instance: of the first ScatterRule (at most 8) its random number falls to, a rule's
+        probability being density * band(height) * band(slope) * the byte of its mask_channel of the Rgba8 attachment `mask_attachment`
+        (same texture and border size; e.g. a weights splat map or a painted density) / 255.  The random numbers are a hash of `seed` and
+        the cell's mosaic position, so a tile's instances do not depend on what else is listed; `jitter` in [0, 1] moves an instance off its
+        texel's centre.  Returns (instances, first, stats): instances, a structured array (SCATTER_INSTANCE_DTYPE: position f64 x 3 and normal
+        f32 x 3 in world space, scale, yaw in [0, 2 pi), rule, cell = mosaic texel) in list order, j major then i within a tile; first
+        (len(coords) + 1) uint64: first[t] is the index of tile t's first instance, first[-1] the total; stats: bt_scatter_stats as a dict.
+        cap=None sizes the list with a first call that writes nothing; with a cap only the first min(total, cap) instances come back while
+        first and stats describe the whole list.  The terrain model is the config's.  Ordered behind the queued work; synchronous; a read."""
+        from .tile_tree import model_c
+        coords, rules = list(coords), list(rules)
+        arr = (_ffi.TileCoordinateC * max(len(coords), 1))(*[t._c() if hasattr(t, "_c") else _ffi.TileCoordinateC(*t) for t in coords])
+        rules_c = (_ffi.ScatterRuleC * max(len(rules), 1))(*[r._c() for r in rules])
+        model = model_c(self.config.model)
+        mask = _ffi.SCATTER_NO_MASK if mask_attachment is None else mask_attachment
+        first = np.zeros(len(coords) + 1, dtype=np.uint64)
+        stats = _ffi.ScatterStatsC()
+
+        def call(out, n):
+            _ffi.check(_ffi.lib().bt_atlas_scatter_instances(self._h, height_attachment, mask, C.byref(model), arr, len(coords), rules_c, len(rules), seed, float(jitter),
+                                                             out.ctypes.data_as(C.POINTER(_ffi.ScatterInstanceC)) if n else None, n,
+                                                             first.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(stats)))
+
+        if cap is None:
+            call(None, 0)
+            cap = stats.total
+        out = np.zeros(cap, dtype=SCATTER_INSTANCE_DTYPE)
+        call(out, cap)
+        result = {name: getattr(stats, name) for name, _ in _ffi.ScatterStatsC._fields_ if name != "_padding"}
+        result["per_rule"] = list(stats.per_rule)
+        return out[:stats.written], first, result
 
     def read_region(self, attachment_index: int, x0: int, y0: int, w: int, h: int, lod: Optional[int] = None, side: int = 0) -> Tuple[np.ndarray, int]:
         """bt_atlas_read_region: the w x h rectangle of centre texels at mosaic position (x0, y0) of `lod` on `side`, the inverse of

@@ -172,7 +172,7 @@ bt_status bt_ctx_synchronize(bt_ctx* ctx);
  * sources need not be allocated again: 0.5 GB for a 16k R16 raster, six of 128 MB for a cube job; at most 8 buffers and 4 GiB) and
  * the pinned staging buffers of the save / load paths and the device and pinned scratch of bt_atlas_tile_bounds,
  * the device scratch of bt_tile_tree_raycast, the device scratch of bt_tile_tree_sample_normal and bt_atlas_tile_normals (their pinned
- * half is the staging buffers above), the device planes of bt_tile_tree_render.
+ * half is the staging buffers above), the device planes of bt_tile_tree_render, the device scratch and list of bt_atlas_scatter_instances.
  * Synchronises the context's stream first.  `freed_bytes` (may be NULL): device + pinned bytes released. */
 bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes);
 /* Host threads that write (bt_preprocessor_save / _run_streamed) and read (bt_atlas_load_tiles) tile files for this context.
@@ -1104,6 +1104,79 @@ bt_status bt_atlas_splat_from_height(bt_atlas* atlas, uint32_t height_attachment
                                      uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t mode,
                                      const bt_splat_rule* rules, uint32_t count, const uint8_t fallback[4],
                                      bt_tile_coordinate* changed, uint32_t changed_cap, bt_edit_stats* stats);
+
+/* SCATTER (bt_atlas_scatter_instances): vegetation placement, the use of terrain data the reference's documents name and leave to the
+ * application ("texturing, vegetation placement, etc.", docs/development.md; "a vegetation map (for placing trees and bushes)",
+ * docs/implementation.md).  For every centre texel (a cell) of the listed tiles the call decides, from a hash of the cell's mosaic position
+ * and up to BT_SCATTER_MAX_RULES height-and-slope rules, whether the cell places an instance, and returns the instances as one ordered
+ * list on the host.  It works per tile, so a streaming view scatters a tile when it loads and again after an edit.
+ * IEEE binary32, one rounding per written operation, no contraction; f64 where stated.  H is the R16 attachment height_attachment
+ * (T = texture_size, b = border_size, c = T - 2b); L is the layer that holds the listed tile (side, lod, X, Y), S_H its texels
+ * [row][column]; M is the optional Rgba8 attachment mask_attachment of the same atlas, with the same T and b (a tile has one layer index
+ * in all attachments of its atlas).  Cell (i, j), 0 <= i, j < c, of a listed tile has the mosaic texel (gx, gy) = (X * c + i, Y * c + j):
+ *   1. mix(x): x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16   (uint32, wrapping)
+ *      k = mix(mix(mix(seed ^ (side << 8 | lod)) ^ gx) ^ gy);  r_n = mix(k + n * 0x9E3779B9u) for n = 0 .. 4
+ *      f(r) = f32(r >> 8) * 2^-24   (exact, in [0, 1)).  The key holds only the mosaic position: an instance does not depend on which
+ *      other tiles are listed, on their order, or on the atlas layer.
+ *   2. a_x = 0.5f + (f(r_1) - 0.5f) * jitter;  a_y = 0.5f + (f(r_2) - 0.5f) * jitter
+ *      uv = ((f32(i) + a_x) / f32(c), (f32(j) + a_y) / f32(c))
+ *   3. no data: the cell places nothing if S_H[b + j][b + i] == 0, or if any of the four texels of the centre tap is 0: the tap (u_x, u_y)
+ *      of TILE NORMAL at this uv (its t_a, rem_a, i_a and clamped texels).  Both count in cells_no_data; nothing else is evaluated.
+ *   4. v = the centre tap's bilinear value (TILE NORMAL's A, B, v);  h = min_height + (max_height - min_height) * v
+ *      s = TILE NORMAL s(L, lod, uv) of H for `model`;  steep = 1.0f - s.z
+ *   5. p_k = ((density_k * band(h; height_lo_k, height_hi_k, height_fade_k)) * band(steep; steep_lo_k, steep_hi_k, steep_fade_k)) * m_k for
+ *      k < rule_count, band() of SPLAT step 4;  m_k = 1.0f when mask_channel_k is BT_SCATTER_NO_MASK, otherwise
+ *      f32(byte mask_channel_k of M's texel [b + j][b + i] of layer L) / 255.0f
+ *   6. u = f(r_0);  A_0 = 0.0f;  A_(k+1) = A_k + p_k in index order.  The cell places ONE instance, of the first k with u < A_(k+1);
+ *      without such a k it places nothing.  So rules exclude each other, and a rule behind a sum that has reached 1 places nothing.
+ *   7. the instance: rule = k;  cell = (gx, gy);  scale = scale_lo_k + (scale_hi_k - scale_lo_k) * f(r_3);  yaw = 6.2831855f * f(r_4)
+ *      position (f64) = coordinate_world_position({side, ((f64(X) + f64(uv.x)) / 2^lod, (f64(Y) + f64(uv.y)) / 2^lod)}, model, h)
+ *      (coordinate.rs:115-135: the local position of the coordinate, unit on a spherical model, displaced by h along the model's normal)
+ *      normal = norm3f(W(s)) with W of WORLD NORMAL steps 2 - 4, VN taken from that local position ((0, 1, 0) on a plane) and the
+ *      tile's side as the face
+ *   8. order: tiles in list order, within a tile j major, then i.  out_first[t] is the index of the first instance of coords[t] and
+ *      out_first[count] = total.  A coordinate may be listed more than once: each entry gives its own, identical, segment.
+ *   9. capacity: the first min(total, cap) instances are written to out_host; what lies beyond them is untouched.  total, per_rule,
+ *      cells_no_data and out_first describe the whole list whatever cap is: cap == 0 with a NULL out_host asks for the size.
+ * The list's bytes are the same from run to run.  PRECONDITION: F holds for H (the taps of an edge cell read its aprons), as for SPLAT.
+ * Ordered behind the work queued on the context's stream; synchronous (host arrays in and out); a read (no layer of H or M is marked
+ * written); scratch stays in the context until bt_ctx_trim.  Three launches per chunk of at most 1024 listed tiles (two with cap == 0).
+ * count == 0 (with valid arguments otherwise): BT_OK, *stats zeroed, out_first untouched.
+ * All refusals come before anything is queued, with *stats zeroed and the outputs untouched.  BT_ERR_INVALID_ARGUMENT: NULL atlas, model,
+ * stats or rules; NULL coords with count > 0; NULL out_host with cap > 0; rule_count == 0 or above BT_SCATTER_MAX_RULES; in any rule a NaN,
+ * lo > hi, a fade that is negative or not finite, a density outside [0, 1], a scale that is not finite or scale_lo > scale_hi, a
+ * mask_channel that is neither 0 .. 3 nor BT_SCATTER_NO_MASK, a mask_channel while mask_attachment is BT_SCATTER_NO_MASK; jitter not in
+ * [0, 1]; height_attachment == mask_attachment or either out of range; a malformed model; a coordinate with a bad side, lod or x / y, or
+ * one the atlas holds no layer for.  BT_ERR_UNSUPPORTED: H not R16 or M not Rgba8; texture_size or border_size differing between the
+ * two; border_size 0 (the taps of an edge cell need the neighbour's texels); an odd centre size; a mosaic beyond 2^32 texels (as SPLAT). */
+enum { BT_SCATTER_MAX_RULES = 8 };
+#define BT_SCATTER_NO_MASK 0xFFFFFFFFu
+typedef struct bt_scatter_rule {
+    float height_lo, height_hi, height_fade;  /* as bt_splat_rule */
+    float steep_lo, steep_hi, steep_fade;     /* as bt_splat_rule */
+    float density;                            /* probability per cell, finite, in [0, 1] */
+    float scale_lo, scale_hi;                 /* finite, scale_lo <= scale_hi */
+    uint32_t mask_channel;                    /* 0 .. 3: byte of the mask attachment's texel; BT_SCATTER_NO_MASK: none */
+    uint32_t _padding[2];
+} bt_scatter_rule;                            /* 48 bytes */
+typedef struct bt_scatter_instance {
+    double position[3];                       /* world, f64 */
+    float normal[3];                          /* world, unit */
+    float scale, yaw;                         /* yaw in [0, 2 pi) */
+    uint32_t rule;                            /* index of the rule that placed it */
+    uint32_t cell[2];                         /* mosaic texel (gx, gy) of its LOD and side */
+} bt_scatter_instance;                        /* 56 bytes */
+typedef struct bt_scatter_stats {
+    uint64_t total, written;                  /* instances the list has; instances copied out (min(total, cap)) */
+    uint64_t cells, cells_no_data;            /* cells of the listed tiles (count * c * c); those of step 3 */
+    uint64_t per_rule[BT_SCATTER_MAX_RULES];  /* instances per rule, of the whole list */
+    uint32_t launches, _padding;
+} bt_scatter_stats;
+bt_status bt_atlas_scatter_instances(bt_atlas* atlas, uint32_t height_attachment, uint32_t mask_attachment /* or BT_SCATTER_NO_MASK */,
+                                     const bt_terrain_model* model, const bt_tile_coordinate* coords, uint32_t count,
+                                     const bt_scatter_rule* rules, uint32_t rule_count, uint32_t seed, float jitter,
+                                     bt_scatter_instance* out_host, uint64_t cap, uint64_t* out_first /* count + 1 entries, may be NULL */,
+                                     bt_scatter_stats* stats);
 
 /* Rendering ("what does the terrain look like from here": preview thumbnails of a preprocessed dataset, headless visual checks of an
  * edit, a depth or normal image for a tool that is not wgpu, top-down maps).  The reference's renderer is Bevy / wgpu and stays out of

@@ -5,6 +5,7 @@
 #                                                               tools/kernel_resources.sh normal bt_normal.hip   (tile_tree_normal_kernel, tile_normals_kernel)
 #                                                               tools/kernel_resources.sh edit bt_edit.hip   (edit_brush / edit_paint / edit_region / edit_gather / edit_smooth / edit_downsample)
 #                                                               tools/kernel_resources.sh splat bt_splat.hip   (edit_splat_kernel)
+#                                                               tools/kernel_resources.sh scatter bt_scatter.hip   (scatter_decide_kernel, scatter_scan_kernel, scatter_emit_kernel)
 #                                                               tools/kernel_resources.sh collide bt_collide.hip   (collide_kernel; `sweep` for sweep_kernel)
 #                                                               tools/kernel_resources.sh path bt_path.hip   (path_prepare_kernel, path_relax_kernel, path_next_kernel)
 R=$(cd "$(dirname "$0")/.." && pwd)
