@@ -101,18 +101,6 @@ uint32_t ctx_io_threads(const bt_ctx* ctx) {
     return std::max(1u, std::min(16u, usable_cpus()));
 }
 
-bt_status ctx_staging(bt_ctx* ctx, size_t bytes) {
-    if (ctx->staging_bytes >= bytes && ctx->staging[0]) return BT_OK;
-    for (void*& p : ctx->staging) {
-        if (p) hipHostFree(p);
-        p = nullptr;
-    }
-    ctx->staging_bytes = 0;
-    for (void*& p : ctx->staging) BT_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    ctx->staging_bytes = bytes;
-    return BT_OK;
-}
-
 bt_status Scratch::reserve(bt_ctx* ctx, uint64_t need, bool with_pinned_twin) {
     if (bytes >= need) return BT_OK;
     if (dev) BT_HIP(hipStreamSynchronize(ctx->stream));  // work in flight may use the buffer that goes away
@@ -176,16 +164,14 @@ bt_status bt_ctx_create(int32_t device, void* stream, bt_ctx** out) {
 void bt_ctx_destroy(bt_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
-    for (void* p : ctx->staging)
-        if (p) hipHostFree(p);
+    ctx->staging.release(true);
     if (ctx->ev_begin) hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     for (auto& kept : ctx->spare_rasters) hipFree(kept.first);
     for (bt::Scratch* s : ctx->scratch()) s->release();
-    if (ctx->edit_dev) hipFree(ctx->edit_dev);
-    if (ctx->edit_host) hipHostFree(ctx->edit_host);
-    if (ctx->edit_copied) hipEventDestroy(ctx->edit_copied);
+    ctx->plan_ring.release();
+    if (ctx->plan_ring.copied) hipEventDestroy(ctx->plan_ring.copied);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->save_stream) hipStreamDestroy(ctx->save_stream);
     delete ctx;
@@ -224,21 +210,11 @@ bt_status bt_ctx_trim(bt_ctx* ctx, uint64_t* freed_bytes) {
         freed += kept.second;
     }
     ctx->spare_rasters.clear();
-    for (void*& s : ctx->staging)
-        if (s) {
-            BT_HIP(hipHostFree(s));
-            s = nullptr;
-            freed += ctx->staging_bytes;
-        }
-    ctx->staging_bytes = 0;
     hipError_t failed = hipSuccess;
+    freed += ctx->staging.release(false, &failed);  // (the events stay until bt_ctx_destroy)
     for (bt::Scratch* s : ctx->scratch()) freed += s->release(&failed);
+    freed += ctx->plan_ring.release(&failed);
     BT_HIP(failed);
-    if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
-    if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
-    freed += 2u * ctx->edit_bytes;
-    ctx->edit_dev = ctx->edit_host = nullptr;
-    ctx->edit_bytes = ctx->edit_used = 0;
     if (freed_bytes) *freed_bytes = freed;
     return BT_OK;
 }

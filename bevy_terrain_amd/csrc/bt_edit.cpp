@@ -215,47 +215,6 @@ void build_plan(const bt_atlas* a, const Attachment& at, uint32_t lod, const std
     plan.stats.changed_count = uint32_t(plan.changed.size());
 }
 
-}  // namespace
-
-uint64_t bt::PlanRing::add(const void* src, uint64_t bytes) {
-    records.push_back({src, bytes, size});
-    size += (bytes + 15u) & ~uint64_t(15);
-    if (src) upload = size;
-    return records.back().at;
-}
-
-bt_status bt::PlanRing::commit(bt_ctx* ctx, uint8_t** dev) {
-    const uint64_t need = (size + 255u) & ~uint64_t(255);
-    if (!ctx->edit_copied) BT_HIP(hipEventCreateWithFlags(&ctx->edit_copied, hipEventDisableTiming));
-    if (need > ctx->edit_bytes) {
-        if (ctx->edit_bytes) BT_HIP(hipStreamSynchronize(ctx->stream));  // launches in flight read the buffers that go away
-        if (ctx->edit_dev) BT_HIP(hipFree(ctx->edit_dev));
-        if (ctx->edit_host) BT_HIP(hipHostFree(ctx->edit_host));
-        ctx->edit_dev = ctx->edit_host = nullptr;
-        ctx->edit_bytes = ctx->edit_used = 0;
-        const uint64_t bytes = std::max<uint64_t>(1ull << 20, 2u * need);
-        BT_HIP(hipMalloc(&ctx->edit_dev, bytes));
-        BT_HIP(hipHostMalloc(&ctx->edit_host, bytes, hipHostMallocDefault));
-        ctx->edit_bytes = bytes;
-    }
-    if (ctx->edit_used + need > ctx->edit_bytes) {
-        // the ring wraps: the pinned records of earlier calls must have been copied (their device halves are safe: this call's copy and
-        // kernels are ordered behind theirs on the stream)
-        BT_HIP(hipEventSynchronize(ctx->edit_copied));
-        ctx->edit_used = 0;
-    }
-    uint8_t* host = (uint8_t*)ctx->edit_host + ctx->edit_used;
-    *dev = (uint8_t*)ctx->edit_dev + ctx->edit_used;
-    ctx->edit_used += need;
-    for (const Record& r : records)
-        if (r.src && r.bytes) memcpy(host + r.at, r.src, r.bytes);
-    BT_HIP(hipMemcpyAsync(*dev, host, upload, hipMemcpyHostToDevice, ctx->stream));
-    BT_HIP(hipEventRecord(ctx->edit_copied, ctx->stream));  // what the wrap of a later call waits for
-    return BT_OK;
-}
-
-namespace {
-
 // (bt_ctx::edit_region is the device buffer a first step reads its texels from: the staged rectangle of write_region, the new texels of smooth_height)
 
 // The first step of a plan, the one that writes the rectangles of the edited tiles (the steps after it are the same for every call): the
@@ -268,12 +227,10 @@ struct FirstStep {
     // bt_splat_rule[count] (== splat.count)
     const void* stamps = nullptr;
     uint32_t count = 0, kernel_radius = 0;
-    // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart; copied: the events of the staging
-    // buffers, for bt_atlas_write_region to wait on
+    // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart
     const void* texels = nullptr;
     uint64_t row_pitch = 0;
     uint32_t x0 = 0, y0 = 0, width = 0, height = 0;
-    hipEvent_t copied[bt_ctx::kStagingBuffers] = {};
     // splat: the heights the rules read (their attachment's meta and level 0, the model, the LOD), the mode and the fallback texel
     SplatSource splat{};
     // prepare() -> launch()
@@ -311,18 +268,16 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
 bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
     const uint64_t total = row_bytes * height;
     if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
-    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
-        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
-    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
+    StagingRing& ring = ctx->staging;
+    if (bt_status s = ring.reserve(size_t(row_bytes), size_t(std::min<uint64_t>(total, 32ull << 20)))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ring.bytes() / row_bytes));
     uint32_t chunk = 0;
     for (uint32_t row = 0; row < height; row += chunk_rows, chunk++) {
-        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
-        hipError_t e = copied[k] ? hipEventSynchronize(copied[k]) : hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
-        for (uint32_t r = 0; r < rows && e == hipSuccess; r++)
-            memcpy((uint8_t*)ctx->staging[k] + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)ctx->edit_region.dev + row * row_bytes, ctx->staging[k], rows * row_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(copied[k], ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "bt_atlas_write_region staging");
+        const uint32_t k = chunk % StagingRing::kBuffers, rows = std::min(chunk_rows, height - row);
+        if (bt_status s = ring.wait(k)) return s;
+        for (uint32_t r = 0; r < rows; r++) memcpy((uint8_t*)ring.buffer(k) + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
+        BT_HIP(hipMemcpyAsync((uint8_t*)ctx->edit_region.dev + row * row_bytes, ring.buffer(k), rows * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (bt_status s = ring.record(k, ctx->stream)) return s;
     }
     return BT_OK;
 }
@@ -765,13 +720,9 @@ bt_status bt_atlas_write_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
     first.texels = texels, first.row_pitch = row_pitch;
     first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
     bt_status rc = edit_boxes(a, ai, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, stats);
-    for (hipEvent_t ev : first.copied)  // the staging buffers are free again once the copies have run: the one wait of this call
-        if (ev) {
-            const hipError_t e = hipEventSynchronize(ev);
-            if (e != hipSuccess && rc == BT_OK) rc = hip_fail(e, "bt_atlas_write_region staging");
-            hipEventDestroy(ev);
-        }
-    return rc;
+    // the one wait of this call, for its staging copies (the ring's rule no longer needs it: whether it can go is a later question)
+    const bt_status drained = a->ctx->staging.drain();
+    return rc ? rc : drained;
 }
 
 }  // extern "C"
@@ -807,36 +758,17 @@ bt_status bt::region_gather(const bt_atlas* a, uint32_t ai, uint32_t side, uint3
 bt_status bt::region_stage_out(bt_ctx* ctx, const void* src, void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height, const char* what) {
     // the rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
     const uint64_t total = row_bytes * height;
-    if (!ctx->staging[0] || ctx->staging_bytes < row_bytes)
-        if (bt_status s = ctx_staging(ctx, size_t(std::max<uint64_t>(row_bytes, std::min<uint64_t>(total, 32ull << 20))))) return s;
-    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ctx->staging_bytes / row_bytes));
-    struct Landing {
-        hipEvent_t copied = nullptr;
-        uint32_t row = 0, rows = 0;  // rows != 0: a chunk is on its way into the buffer
-    } landing[bt_ctx::kStagingBuffers];
-    hipError_t e = hipSuccess;
-    auto empty = [&](uint32_t k) {
-        Landing& l = landing[k];
-        if (!l.rows || e != hipSuccess) return;
-        e = hipEventSynchronize(l.copied);
-        for (uint32_t r = 0; r < l.rows && e == hipSuccess; r++)
-            memcpy((uint8_t*)texels + (uint64_t(l.row) + r) * row_pitch, (const uint8_t*)ctx->staging[k] + r * row_bytes, row_bytes);
-        l.rows = 0;
+    StagingRing& ring = ctx->staging;
+    if (bt_status s = ring.reserve(size_t(row_bytes), size_t(std::min<uint64_t>(total, 32ull << 20)))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ring.bytes() / row_bytes));
+    auto rows_of = [&](uint32_t chunk) { return std::min(chunk_rows, height - chunk * chunk_rows); };
+    auto enqueue = [&](uint32_t chunk, uint32_t k) {
+        return hipMemcpyAsync(ring.buffer(k), (const uint8_t*)src + uint64_t(chunk) * chunk_rows * row_bytes, rows_of(chunk) * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
     };
-    uint32_t chunk = 0;
-    for (uint32_t row = 0; row < height && e == hipSuccess; row += chunk_rows, chunk++) {
-        const uint32_t k = chunk % bt_ctx::kStagingBuffers, rows = std::min(chunk_rows, height - row);
-        empty(k);
-        if (e == hipSuccess && !landing[k].copied) e = hipEventCreateWithFlags(&landing[k].copied, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], (const uint8_t*)src + row * row_bytes, rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(landing[k].copied, ctx->stream);
-        if (e == hipSuccess) landing[k].row = row, landing[k].rows = rows;
-    }
-    for (uint32_t i = 0; i < bt_ctx::kStagingBuffers; i++) empty((chunk + i) % bt_ctx::kStagingBuffers);  // the oldest first
-    if (e != hipSuccess) hipStreamSynchronize(ctx->stream);  // nothing may still be landing in the context's buffers when the call returns
-    for (Landing& l : landing)
-        if (l.copied) hipEventDestroy(l.copied);
-    return e == hipSuccess ? BT_OK : hip_fail(e, what);
+    auto landed = [&](uint32_t chunk, uint32_t k) {
+        for (uint32_t r = 0; r < rows_of(chunk); r++) memcpy((uint8_t*)texels + (uint64_t(chunk) * chunk_rows + r) * row_pitch, (const uint8_t*)ring.buffer(k) + r * row_bytes, row_bytes);
+    };
+    return stage_out_chunks(ring, ctx->stream, (height + chunk_rows - 1u) / chunk_rows, what, enqueue, landed);
 }
 
 extern "C" {

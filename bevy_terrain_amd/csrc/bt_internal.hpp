@@ -188,16 +188,15 @@ struct Scratch {
 
 }  // namespace bt
 
+#include "bt_staging.hpp"  // the rings a context owns
+
 struct bt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    // pinned staging buffers of the tile save / load paths: allocated on first use (pinning 100 MB costs tens of
-    // milliseconds), kept for the life of the context
-    static constexpr uint32_t kStagingBuffers = 3;
-    void* staging[kStagingBuffers] = {};
-    size_t staging_bytes = 0;
+    // the pinned buffers of every chunked transfer between host memory and the device (tile files, regions, normal maps)
+    bt::StagingRing staging;
     // streamed runs: uploads and downloads on their own queues beside the kernels' stream (created on first use)
     hipStream_t copy_stream = nullptr, save_stream = nullptr;
     // released raster allocations are kept for the next queue (hipMalloc + hipFree of a 512 MB source cost ~1.5 ms of the
@@ -251,18 +250,12 @@ struct bt_ctx {
     // one chunk of it, and the instance list on the device
     bt::Scratch scatter;
     std::array<bt::Scratch*, 8> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
-    // the edit calls and bt_height_bounds_update: the plans (items, stamps, stitch tasks; scatter records, windows) of the calls in flight,
-    // pinned and on the device, handed out as a ring (a call's records must stay in the pinned half until its copy has run: edit_copied is
-    // recorded behind each call's copy and waited for when the ring wraps).  Only bt::PlanRing (bt_edit.cpp) hands it out (kept until bt_ctx_trim)
-    void* edit_dev = nullptr;
-    void* edit_host = nullptr;
-    uint64_t edit_bytes = 0, edit_used = 0;
-    hipEvent_t edit_copied = nullptr;
+    // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
+    bt::PlanRingState plan_ring;
 };
 
 namespace bt {
-bt_status ctx_staging(bt_ctx* ctx, size_t bytes_per_buffer);  // ensures ctx->staging[*] hold at least that much
-uint32_t usable_cpus();                  // CPUs this process may use: affinity mask capped by the cgroup CPU quota
+uint32_t usable_cpus();                 // CPUs this process may use: affinity mask capped by the cgroup CPU quota
 uint32_t ctx_io_threads(const bt_ctx* ctx);  // the resolved thread count of the save / load paths
 }
 
@@ -476,28 +469,6 @@ inline uint32_t shard_holder(const ::bt_preprocessor* p, uint32_t attachment, ui
                 return piece.owner_rank;
     return atlas_index % p->shard_world;
 }
-
-// bt_edit.cpp: the records of one call (an edit's plan, a bounds update's) on their way through the context's plan ring (bt_ctx::edit_*).
-// add() the host records, each 16-byte aligned; then, optionally, device_only() bytes behind them; every offset returned is relative to
-// the device base commit() hands back.  commit(), once: reserves pinned and device bytes of the ring, copies the records (they must still
-// be where add() saw them) into the pinned half, enqueues the ONE copy to the device half on the context's stream and records
-// edit_copied behind it, which the ring waits for before it wraps onto pinned records.
-class PlanRing {
-public:
-    uint64_t add(const void* src, uint64_t bytes);
-    template <typename T>
-    uint64_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
-    uint64_t device_only(uint64_t bytes) { return add(nullptr, bytes); }  // after the last add() of a host record
-    bt_status commit(bt_ctx* ctx, uint8_t** dev);
-
-private:
-    struct Record {
-        const void* src;  // NULL: device only
-        uint64_t bytes, at;
-    };
-    std::vector<Record> records;
-    uint64_t size = 0, upload = 0;  // of all records; of those up to the last host record: what the copy moves
-};
 
 // bt_edit.cpp, the halves of bt_atlas_read_region that bt_atlas_path_field shares.  region_check: what the read refuses of attachment,
 // side, lod and rectangle (`what` names the entry point).  region_gather: the rectangle's texels of the layers -> `dst` on the device

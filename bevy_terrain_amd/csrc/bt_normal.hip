@@ -176,16 +176,14 @@ extern "C" bt_status bt_atlas_tile_normals(bt_atlas* a, uint32_t ai, const bt_te
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // chunks of tiles whose normal maps fit 32 MiB; each goes kernel -> device scratch -> pinned staging -> out, three in flight
-    constexpr uint32_t kBuffers = bt_ctx::kStagingBuffers;
+    constexpr uint32_t kBuffers = StagingRing::kBuffers;
     const uint64_t chunk = std::min<uint64_t>(count, std::max<uint64_t>(1u, (32ull << 20) / tile_bytes));
     const uint64_t chunk_bytes = chunk * tile_bytes, list_bytes = (uint64_t(count) * sizeof(BakeTile) + 255u) & ~255ull;
     const uint32_t chunks = uint32_t((count + chunk - 1u) / chunk);
     const uint64_t need = list_bytes + std::min<uint64_t>(kBuffers, chunks) * chunk_bytes;
     if (bt_status st = ctx->normal.reserve(ctx, need)) return st;
-    if (ctx->staging_bytes < chunk_bytes || !ctx->staging[0]) {
-        BT_HIP(hipStreamSynchronize(s));  // (no copy may be in flight when the staging buffers are replaced)
-        if (bt_status st = ctx_staging(ctx, std::max<size_t>(32ull << 20, chunk_bytes))) return st;
-    }
+    StagingRing& ring = ctx->staging;
+    if (bt_status st = ring.reserve(size_t(chunk_bytes), 32ull << 20)) return st;
     uint8_t* dev = (uint8_t*)ctx->normal.dev;
     BakeArgs args{};
     args.atlas = (const uint16_t*)at.level0;  // a read: no layer is marked written
@@ -202,39 +200,17 @@ extern "C" bt_status bt_atlas_tile_normals(bt_atlas* a, uint32_t ai, const bt_te
     }
     args.bands = (c + args.band_rows - 1u) / args.band_rows;
     const size_t lds = args.halo == kNoWindow ? 0 : size_t(std::min<uint64_t>(args.band_rows + 2ull * args.halo, T) * row_bytes);
-    hipEvent_t copied[kBuffers] = {};
-    bt_status rc = BT_OK;
-    hipError_t e = hipMemcpyAsync(dev, tiles.data(), count * sizeof(BakeTile), hipMemcpyHostToDevice, s);
-    for (uint32_t k = 0; k < kBuffers && k < chunks && e == hipSuccess; k++) e = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
-    auto collect = [&](uint32_t ci) {  // chunk ci has been enqueued: wait for its copy, hand it to the caller
-        const uint32_t k = ci % kBuffers;
-        const uint64_t first = ci * chunk, n = std::min<uint64_t>(chunk, count - first);
-        const hipError_t w = hipEventSynchronize(copied[k]);
-        if (w == hipSuccess) memcpy(out + first * tile_bytes, ctx->staging[k], n * tile_bytes);
-        return w;
-    };
-    uint32_t enqueued = 0, collected = 0;
-    for (; enqueued < chunks && e == hipSuccess; enqueued++) {
-        const uint32_t k = enqueued % kBuffers;
-        if (enqueued >= kBuffers) {
-            e = collect(collected++);
-            if (e != hipSuccess) break;
-        }
-        const uint64_t first = enqueued * chunk, n = std::min<uint64_t>(chunk, count - first);
-        args.tiles = (const BakeTile*)dev + first;
+    BT_HIP(hipMemcpyAsync(dev, tiles.data(), count * sizeof(BakeTile), hipMemcpyHostToDevice, s));
+    auto tiles_of = [&](uint32_t ci) { return std::min<uint64_t>(chunk, count - ci * chunk); };
+    auto enqueue = [&](uint32_t ci, uint32_t k) {
+        args.tiles = (const BakeTile*)dev + ci * chunk;
         args.out = (uint32_t*)(dev + list_bytes + k * chunk_bytes);
-        tile_normals_kernel<<<uint32_t(n) * args.bands, kBakeThreads, lds, s>>>(args);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->staging[k], args.out, n * tile_bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(copied[k], s);
-        if (e != hipSuccess) break;
-    }
-    while (e == hipSuccess && collected < enqueued) e = collect(collected++);
-    if (e != hipSuccess) {
-        rc = hip_fail(e, who);
-        (void)hipStreamSynchronize(s);
-    }
-    for (hipEvent_t ev : copied)
-        if (ev) (void)hipEventDestroy(ev);
+        tile_normals_kernel<<<uint32_t(tiles_of(ci)) * args.bands, kBakeThreads, lds, s>>>(args);
+        const hipError_t e = hipGetLastError();
+        return e != hipSuccess ? e : hipMemcpyAsync(ring.buffer(k), args.out, tiles_of(ci) * tile_bytes, hipMemcpyDeviceToHost, s);
+    };
+    auto landed = [&](uint32_t ci, uint32_t k) { memcpy(out + ci * chunk * tile_bytes, ring.buffer(k), tiles_of(ci) * tile_bytes); };
+    const bt_status rc = stage_out_chunks(ring, s, chunks, who, enqueue, landed);
+    if (rc != BT_OK) (void)hipStreamSynchronize(s);  // (the kernels write the scratch; `tiles` leaves with this call)
     return rc;
 }

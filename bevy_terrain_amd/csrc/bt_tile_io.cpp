@@ -141,19 +141,13 @@ void FileWriters::run() {
 TileSaver::~TileSaver() {
     if (writers_)
         for (uint32_t k = 0; k < kBuffers; k++) writers_->wait_buffer(k);
-    for (uint32_t k = 0; k < kBuffers; k++)
-        if (copied_[k]) hipEventDestroy(copied_[k]);
 }
 
 bt_status TileSaver::begin() {
     BT_HIP(hipSetDevice(a_->ctx->device));
     size_t largest = 32ull << 20;
     for (const Attachment& at : a_->attachments) largest = std::max<size_t>(largest, at.tile_bytes);
-    if (bt_status s = ctx_staging(a_->ctx, largest)) return s;
-    for (uint32_t k = 0; k < kBuffers; k++) {
-        hipError_t e = hipEventCreateWithFlags(&copied_[k], hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(e, "save events");
-    }
+    if (bt_status s = a_->ctx->staging.reserve(largest)) return s;
     // 16 writers: measured on tmpfs and the overlay disk, 6 / 8 / 12 / 16 / 24 / 32 / 64 / 128 threads write at 29 / 34 / 42 /
     // 46-49 / 46 / 35 / 4 / 5 GB/s — beyond ~24 the page-cache allocation lock dominates
     // (the count follows the CPUs the process may use, not the machine's hardware threads: bt_ctx_set_io_threads)
@@ -167,7 +161,7 @@ bt_status TileSaver::begin() {
 
 bt_status TileSaver::add(uint32_t ai, const std::string& dir, Tiles tiles, bool taper) {
     const Attachment& at = a_->attachments[ai];
-    void** pinned = a_->ctx->staging;
+    StagingRing& ring = a_->ctx->staging;
     if (std::find(dirs_.begin(), dirs_.end(), dir) == dirs_.end()) {
         if (bt_status s = make_dirs(dir)) return s;
         dirs_.push_back(dir);
@@ -184,6 +178,8 @@ bt_status TileSaver::add(uint32_t ai, const std::string& dir, Tiles tiles, bool 
         const uint32_t k = uint32_t(chunks_++ % kBuffers);
         trace_stamp("  saver chunk: tiles", hi - lo);
         writers_->wait_buffer(k);
+        if (bt_status s = ring.wait(k)) return s;  // no wait unless an earlier call failed: hand_over has waited for the chunk that was here
+        void* pinned = ring.buffer(k);
         trace_stamp("  saver chunk: buffer free", k);
         // runs of consecutive layers; equally long runs at a constant layer stride (a band of tile rows in the x-major
         // atlas order: 4 layers every 32) travel as ONE pitched copy instead of one call per run
@@ -196,26 +192,26 @@ bt_status TileSaver::add(uint32_t ai, const std::string& dir, Tiles tiles, bool 
         const uint64_t stride = regular ? uint64_t(tiles[runs[1].first].first) - tiles[runs[0].first].first : 0;
         for (size_t q = 1; regular && q < runs.size(); q++)
             regular = runs[q].second == runs[0].second && uint64_t(tiles[runs[q].first].first) - tiles[runs[q - 1].first].first == stride;
+        hipError_t e = hipSuccess;
+        bt_status gathered = BT_OK;
         if (regular) {
-            hipError_t e = hipMemcpy2DAsync(pinned[k], at.tile_bytes * runs[0].second, (const uint8_t*)at.level0 + at.tile_bytes * tiles[lo].first,
-                                            at.tile_bytes * stride, at.tile_bytes * runs[0].second, runs.size(), hipMemcpyDeviceToHost, stream_);
-            if (e != hipSuccess) return hip_fail(e, "tile download");
+            e = hipMemcpy2DAsync(pinned, at.tile_bytes * runs[0].second, (const uint8_t*)at.level0 + at.tile_bytes * tiles[lo].first,
+                                 at.tile_bytes * stride, at.tile_bytes * runs[0].second, runs.size(), hipMemcpyDeviceToHost, stream_);
         } else if (runs.size() > 2 && hi - lo <= 64 && at.tile_bytes % 16u == 0) {
             // an irregular chunk (the lower LODs behind a band's tiles, a cube's face-edge tiles, merged hand-overs): ONE gather kernel that
             // writes the pinned buffer over PCIe instead of one copy-engine call per run — a burst of small copy calls stalled the issuing
             // thread for 15 - 20 ms now and then (config 2's 37-tile chunk: 2.2 -> 21.0 ms between two stamps, round 6 traces), the kernel never
             uint32_t layers[64];
             for (size_t i = lo; i < hi; i++) layers[i - lo] = tiles[i].first;
-            if (bt_status s = launch_gather_layers(stream_, at.level0, layers, uint32_t(hi - lo), pinned[k], at.tile_bytes)) return s;
+            gathered = launch_gather_layers(stream_, at.level0, layers, uint32_t(hi - lo), pinned, at.tile_bytes);
         } else {
-            for (const auto& [i, run] : runs) {
-                hipError_t e = hipMemcpyAsync((uint8_t*)pinned[k] + at.tile_bytes * (i - lo), (const uint8_t*)at.level0 + at.tile_bytes * tiles[i].first,
-                                              at.tile_bytes * run, hipMemcpyDeviceToHost, stream_);
-                if (e != hipSuccess) return hip_fail(e, "tile download");
-            }
+            for (const auto& [i, run] : runs)
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync((uint8_t*)pinned + at.tile_bytes * (i - lo), (const uint8_t*)at.level0 + at.tile_bytes * tiles[i].first, at.tile_bytes * run, hipMemcpyDeviceToHost, stream_);
         }
-        hipError_t e = hipEventRecord(copied_[k], stream_);
+        const bt_status recorded = ring.record(k, stream_);  // (behind a failed copy too: the ones before it are on their way)
         if (e != hipSuccess) return hip_fail(e, "tile download");
+        if (gathered || recorded) return gathered ? gathered : recorded;
         trace_stamp("  saver chunk: copy issued", k);
         if (bt_status s = hand_over()) return s;  // the chunk enqueued BEFORE this one: wait for its copies, queue its files
         trace_stamp("  saver chunk: previous chunk handed over", k);
@@ -239,13 +235,12 @@ bt_status TileSaver::hand_over() {
     if (!have_in_flight_) return BT_OK;
     have_in_flight_ = false;
     const Attachment& at = a_->attachments[in_flight_ai_];
-    hipError_t e = hipEventSynchronize(copied_[in_flight_buffer_]);
-    if (e != hipSuccess) return hip_fail(e, "tile download");
+    if (bt_status s = a_->ctx->staging.wait(in_flight_buffer_)) return s;
     std::vector<FileWriters::Job> jobs;
     for (size_t i = 0; i < in_flight_.size(); i++) {
         char name[64];
         bt_tile_name(in_flight_[i].second, name, sizeof name);
-        jobs.push_back({in_flight_dir_ + "/" + name + ".bin", (const uint8_t*)a_->ctx->staging[in_flight_buffer_] + at.tile_bytes * i, size_t(at.tile_bytes), in_flight_buffer_});
+        jobs.push_back({in_flight_dir_ + "/" + name + ".bin", (const uint8_t*)a_->ctx->staging.buffer(in_flight_buffer_) + at.tile_bytes * i, size_t(at.tile_bytes), in_flight_buffer_});
     }
     writers_->push(std::move(jobs));
     return BT_OK;
@@ -292,19 +287,13 @@ bt_status bt_atlas_load_tiles(bt_atlas* a, uint32_t ai, const char* directory, c
     if (!count) return BT_OK;
     BT_HIP(hipSetDevice(a->ctx->device));
     // files -> three pinned buffers (reader threads) -> H2D on the context's stream: chunk c + 1 is read while chunk c uploads
-    constexpr uint32_t kBuffers = bt_ctx::kStagingBuffers;
+    constexpr uint32_t kBuffers = StagingRing::kBuffers;
     const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (32ull << 20) / at.tile_bytes)));
-    if (bt_status s = ctx_staging(a->ctx, std::max<size_t>(32ull << 20, at.tile_bytes))) return s;
-    void** pinned = a->ctx->staging;
+    StagingRing& ring = a->ctx->staging;
+    if (bt_status s = ring.reserve(std::max<size_t>(32ull << 20, at.tile_bytes))) return s;
     std::vector<uint32_t> layers;
-    hipEvent_t uploaded[kBuffers] = {};
-    bool in_flight[kBuffers] = {};
     bt_status rc = BT_OK;
-    for (uint32_t k = 0; k < kBuffers && rc == BT_OK; k++) {
-        hipError_t e = hipEventCreateWithFlags(&uploaded[k], hipEventDisableTiming);
-        if (e != hipSuccess) rc = hip_fail(e, "load events");
-    }
-    if (rc == BT_OK) {
+    {
         FileWriters readers(ctx_io_threads(a->ctx), kBuffers);
         const uint32_t chunks = (count + chunk - 1) / chunk;
         std::vector<std::vector<uint32_t>> index(kBuffers);
@@ -314,23 +303,16 @@ bt_status bt_atlas_load_tiles(bt_atlas* a, uint32_t ai, const char* directory, c
             if (bt_status s = readers.status()) return s;
             const bt_status copies = for_each_layer_run(0, index[k].size(), [&](size_t t) { return index[k][t]; }, false, [&](size_t t, size_t run) -> bt_status {
                 a->attachments[ai].mark_written(index[k][t], uint32_t(run));  // runs of consecutive layers are one copy
-                hipError_t e = hipMemcpyAsync((uint8_t*)at.level0 + at.tile_bytes * index[k][t], (const uint8_t*)pinned[k] + at.tile_bytes * t,
+                hipError_t e = hipMemcpyAsync((uint8_t*)at.level0 + at.tile_bytes * index[k][t], (const uint8_t*)ring.buffer(k) + at.tile_bytes * t,
                                               at.tile_bytes * run, hipMemcpyHostToDevice, a->ctx->stream);
                 return e != hipSuccess ? hip_fail(e, "tile upload") : BT_OK;
             });
-            if (copies) return copies;
-            hipError_t e = hipEventRecord(uploaded[k], a->ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "tile upload");
-            in_flight[k] = true;
-            return BT_OK;
+            const bt_status recorded = ring.record(k, a->ctx->stream);  // (behind a failed copy too: the ones before it are on their way)
+            return copies ? copies : recorded;
         };
         for (uint32_t c = 0; c < chunks && rc == BT_OK; c++) {
             const uint32_t k = c % kBuffers, first = c * chunk, n = std::min(chunk, count - first);
-            if (in_flight[k]) {  // the buffer's previous upload must have left it
-                hipError_t e = hipEventSynchronize(uploaded[k]);
-                if (e != hipSuccess) rc = hip_fail(e, "tile upload");
-                in_flight[k] = false;
-            }
+            rc = ring.wait(k);  // the buffer's previous upload must have left it
             std::vector<FileWriters::Job> jobs;
             index[k].clear();
             for (uint32_t t = 0; t < n && rc == BT_OK; t++) {
@@ -341,7 +323,7 @@ bt_status bt_atlas_load_tiles(bt_atlas* a, uint32_t ai, const char* directory, c
                 layers.push_back(tile.atlas_index);
                 char name[64];
                 bt_tile_name(coords[first + t], name, sizeof name);
-                FileWriters::Job job{std::string(directory) + "/" + name + ".bin", (const uint8_t*)pinned[k] + at.tile_bytes * t, size_t(at.tile_bytes), k};
+                FileWriters::Job job{std::string(directory) + "/" + name + ".bin", (const uint8_t*)ring.buffer(k) + at.tile_bytes * t, size_t(at.tile_bytes), k};
                 job.read = true;
                 jobs.push_back(std::move(job));
             }
@@ -350,11 +332,9 @@ bt_status bt_atlas_load_tiles(bt_atlas* a, uint32_t ai, const char* directory, c
         }
         if (rc == BT_OK) rc = upload(chunks - 1);
         for (uint32_t k = 0; k < kBuffers; k++) readers.wait_buffer(k);  // (error paths: nobody may still write into the buffers)
-        hipError_t e = hipStreamSynchronize(a->ctx->stream);  // the staging buffers belong to the context: free for the next call
-        if (rc == BT_OK && e != hipSuccess) rc = hip_fail(e, "tile upload");
+        const bt_status drained = ring.drain();  // every chunk's copies are recorded: the call stays synchronous with respect to its uploads
+        if (rc == BT_OK) rc = drained;
     }
-    for (uint32_t k = 0; k < kBuffers; k++)
-        if (uploaded[k]) hipEventDestroy(uploaded[k]);
     return rc ? rc : mip_filled_layers(a, ai, layers);
 }
 
@@ -372,8 +352,10 @@ bt_status bt_atlas_update(bt_atlas* a, const char* assets_root, uint32_t max_loa
     uint64_t largest = 0;
     for (const Attachment& at : a->attachments) largest = std::max(largest, at.tile_bytes);
     const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (32ull << 20) / std::max<uint64_t>(largest, 1))));
-    if (bt_status s = ctx_staging(a->ctx, std::max<size_t>(32ull << 20, largest))) return s;
-    void* pinned = a->ctx->staging[0];
+    StagingRing& ring = a->ctx->staging;
+    if (bt_status s = ring.reserve(std::max<size_t>(32ull << 20, largest))) return s;
+    if (bt_status s = ring.wait(0)) return s;
+    void* pinned = ring.buffer(0);  // the one buffer this call uses, synchronously
     std::vector<std::vector<uint32_t>> mip_layers(a->attachments.size());
     uint32_t budget = max_loads ? max_loads : 0xFFFFFFFFu, done = 0, bad = 0;
     bt_status rc = BT_OK;
@@ -410,6 +392,7 @@ bt_status bt_atlas_update(bt_atlas* a, const char* assets_root, uint32_t max_loa
                                           hipMemcpyHostToDevice, a->ctx->stream);
             if (e != hipSuccess) rc = hip_fail(e, "tile upload");
         }
+        if (rc != BT_OK) ring.record(0, a->ctx->stream);  // (the copies before the failed one are on their way)
         if (rc == BT_OK) {
             hipError_t e = hipStreamSynchronize(a->ctx->stream);  // the pinned buffer is refilled next
             if (e != hipSuccess) rc = hip_fail(e, "tile upload");

@@ -73,7 +73,7 @@ class FileWriters {
     std::string error_;
 };
 
-// Download + write tiles: D2H through three pinned buffers on `stream` (runs of consecutive layers are one copy), files written by
+// Download + write tiles: D2H through the context's staging ring on `stream` (runs of consecutive layers are one copy), files written by
 // the writer threads while the next chunk downloads.  add() may be called many times (the streamed run hands over band after band,
 // attachment after attachment); the tiles of one add() are written in atlas-index order.
 class TileSaver {
@@ -89,12 +89,11 @@ class TileSaver {
     uint64_t saved_bytes() const { return saved_bytes_; }
 
   private:
-    static constexpr uint32_t kBuffers = bt_ctx::kStagingBuffers;
+    static constexpr uint32_t kBuffers = StagingRing::kBuffers;
     bt_status hand_over();
     bt_atlas* a_;
     hipStream_t stream_;
     size_t chunks_ = 0;
-    hipEvent_t copied_[kBuffers] = {};
     std::unique_ptr<FileWriters> writers_;
     std::vector<std::string> dirs_;  // directories that exist by now
     Tiles in_flight_;

@@ -27,7 +27,7 @@ F = np.float32
 BAND_ROWS = 32       # bt_normal.hip: kBakeBandRows
 LDS_BYTES = 40 << 10  # bt_normal.hip: kBakeLdsBytes
 CHUNK_BYTES = 32 << 20  # bt_atlas_tile_normals: the maps of one chunk of tiles fit 32 MiB
-RING_SLOTS = 3       # bt_ctx::kStagingBuffers
+RING_SLOTS = 3       # bt::StagingRing::kBuffers
 ROLL_SHARE = 0.9
 
 # side 100 (scale 50: dist = 50 / (c * 2^lod)), heights 0 .. 25: one 16-bit step is 0.0004, the rasters below move by thousands per texel
