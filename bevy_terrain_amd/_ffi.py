@@ -294,6 +294,19 @@ class EditStatsC(C.Structure):
                 ("changed_count", C.c_uint32)]
 
 
+ERODE_MAX_CELLS, ERODE_MAX_STEPS, ERODE_BLOCK = 1 << 22, 4096, 32
+
+
+class ErosionParamsC(C.Structure):
+    _fields_ = [("min_height", C.c_float), ("max_height", C.c_float), ("cell_size", C.c_float), ("dt", C.c_float), ("rain", C.c_float),
+                ("evaporation", C.c_float), ("gravity", C.c_float), ("capacity", C.c_float), ("erode", C.c_float), ("deposit", C.c_float),
+                ("min_tilt", C.c_float), ("min_depth", C.c_float), ("steps", C.c_uint32), ("_padding", C.c_uint32 * 3)]
+
+
+class ErosionStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
+
+
 class BoundsUpdateStatsC(C.Structure):
     _fields_ = [("tiles_listed", C.c_uint32), ("layers_reduced", C.c_uint32), ("launches", C.c_uint32), ("_pad", C.c_uint32),
                 ("entries_written", C.c_uint64)]
@@ -372,6 +385,8 @@ PROTOTYPES = {
     "bt_atlas_save_tiles": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
     "bt_atlas_path_field": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(PathCostC), _P(PathGoalC), _u32, _P(C.c_uint8), _P(C.c_float),
                                    _P(C.c_uint8), _P(PathStatsC)]),
+    "bt_atlas_erode_height": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ErosionParamsC), _P(C.c_uint8), _P(C.c_float), _P(C.c_float),
+                                     _P(TileCoordinateC), _u32, _P(ErosionStatsC)]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

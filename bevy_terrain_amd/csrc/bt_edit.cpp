@@ -1,5 +1,5 @@
 // bt_atlas_edit_height / bt_atlas_smooth_height / bt_atlas_paint / bt_atlas_splat_from_height / bt_atlas_scatter_instances (its checks) / bt_atlas_write_region / bt_atlas_read_region /
-// bt_atlas_save_tiles: the host half of in-place editing.
+// bt_atlas_erode_height (the simulation's kernels: bt_erode.hip) / bt_atlas_save_tiles: the host half of in-place editing.
 //
 // An edit changes centre texels of existing tiles of one LOD and then restores what the atlas state derives from them (the invariant F of
 // include/bevy_terrain_amd.h): the ancestors' centres, the aprons of every written tile and of its existing neighbours, the mips.  The plan
@@ -227,7 +227,8 @@ struct FirstStep {
     // bt_splat_rule[count] (== splat.count)
     const void* stamps = nullptr;
     uint32_t count = 0, kernel_radius = 0;
-    // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart
+    // region: width x height texels whose (0, 0) is mosaic texel (x0, y0), rows row_pitch bytes apart; nullptr: the rectangle is already in
+    // ctx->edit_region, put there on the stream by the caller (bt_atlas_erode_height)
     const void* texels = nullptr;
     uint64_t row_pitch = 0;
     uint32_t x0 = 0, y0 = 0, width = 0, height = 0;
@@ -248,7 +249,7 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
         case kBrush: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_edit_stamp)); return BT_OK;
         case kPaint: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_paint_stamp)); return BT_OK;
         case kSplat: stamps_at = ring.add(stamps, uint64_t(count) * sizeof(bt_splat_rule)); return BT_OK;
-        case kRegion: return stage_region(ctx, uint64_t(width) * m.pixel_size);
+        case kRegion: return texels ? stage_region(ctx, uint64_t(width) * m.pixel_size) : BT_OK;
         case kSmooth: {
             uint64_t scratch_dwords = 0;
             for (const EditItem& it : items) {
@@ -266,20 +267,8 @@ bt_status FirstStep::prepare(bt_ctx* ctx, const AttachmentMeta& m, const std::ve
 
 // the rectangle, tightly packed: host rows -> pinned staging -> device scratch, in chunks of whole rows
 bt_status FirstStep::stage_region(bt_ctx* ctx, uint64_t row_bytes) {
-    const uint64_t total = row_bytes * height;
-    if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
-    StagingRing& ring = ctx->staging;
-    if (bt_status s = ring.reserve(size_t(row_bytes), size_t(std::min<uint64_t>(total, 32ull << 20)))) return s;
-    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ring.bytes() / row_bytes));
-    uint32_t chunk = 0;
-    for (uint32_t row = 0; row < height; row += chunk_rows, chunk++) {
-        const uint32_t k = chunk % StagingRing::kBuffers, rows = std::min(chunk_rows, height - row);
-        if (bt_status s = ring.wait(k)) return s;
-        for (uint32_t r = 0; r < rows; r++) memcpy((uint8_t*)ring.buffer(k) + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
-        BT_HIP(hipMemcpyAsync((uint8_t*)ctx->edit_region.dev + row * row_bytes, ring.buffer(k), rows * row_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (bt_status s = ring.record(k, ctx->stream)) return s;
-    }
-    return BT_OK;
+    if (bt_status s = ctx->edit_region.reserve(ctx, row_bytes * height)) return s;
+    return region_stage_in(ctx, ctx->edit_region.dev, texels, row_bytes, row_pitch, height);
 }
 
 bt_status FirstStep::launch(bt_ctx* ctx, const Attachment& at, const uint8_t* ring, const EditItem* items, uint32_t n, uint32_t max_rows) const {
@@ -755,6 +744,22 @@ bt_status bt::region_gather(const bt_atlas* a, uint32_t ai, uint32_t side, uint3
     return launch_edit_gather(ctx->stream, at.meta, at.level0, (const EditItem*)(dev + items_at), uint32_t(items.size()), max_rows, dst, x0, y0, width);
 }
 
+bt_status bt::region_stage_in(bt_ctx* ctx, void* dst, const void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height) {
+    const uint64_t total = row_bytes * height;
+    StagingRing& ring = ctx->staging;
+    if (bt_status s = ring.reserve(size_t(row_bytes), size_t(std::min<uint64_t>(total, 32ull << 20)))) return s;
+    const uint32_t chunk_rows = uint32_t(std::min<uint64_t>(height, ring.bytes() / row_bytes));
+    uint32_t chunk = 0;
+    for (uint32_t row = 0; row < height; row += chunk_rows, chunk++) {
+        const uint32_t k = chunk % StagingRing::kBuffers, rows = std::min(chunk_rows, height - row);
+        if (bt_status s = ring.wait(k)) return s;
+        for (uint32_t r = 0; r < rows; r++) memcpy((uint8_t*)ring.buffer(k) + r * row_bytes, (const uint8_t*)texels + (uint64_t(row) + r) * row_pitch, row_bytes);
+        BT_HIP(hipMemcpyAsync((uint8_t*)dst + row * row_bytes, ring.buffer(k), rows * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (bt_status s = ring.record(k, ctx->stream)) return s;
+    }
+    return BT_OK;
+}
+
 bt_status bt::region_stage_out(bt_ctx* ctx, const void* src, void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height, const char* what) {
     // the rectangle -> pinned staging -> host rows, in chunks of whole rows: a buffer is emptied before the chunk after next lands
     const uint64_t total = row_bytes * height;
@@ -795,6 +800,140 @@ bt_status bt_atlas_read_region(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t
     if (bt_status s = ctx->edit_region.reserve(ctx, total)) return s;
     if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, ctx->edit_region.dev, tiles_missing)) return s;
     return region_stage_out(ctx, ctx->edit_region.dev, texels, row_bytes, row_pitch, height, "bt_atlas_read_region staging");
+}
+
+}  // extern "C"
+
+namespace {
+
+// the first defect of the erosion parameters, or nullptr
+const char* bad_erosion(const bt_erosion_params& p) {
+    auto finite_from = [](float v, float lo, bool open) { return std::isfinite(v) && (open ? v > lo : v >= lo); };
+    if (!std::isfinite(p.min_height) || !std::isfinite(p.max_height)) return "min_height / max_height (not finite)";
+    if (!finite_from(p.max_height - p.min_height, 0.0f, true)) return "max_height - min_height (finite and > 0)";
+    if (!finite_from(p.cell_size, 0.0f, true)) return "cell_size (finite and > 0)";
+    if (!finite_from(p.dt, 0.0f, true)) return "dt (finite and > 0)";
+    if (!finite_from(p.rain, 0.0f, false)) return "rain (finite and >= 0)";
+    if (!finite_from(p.evaporation, 0.0f, false)) return "evaporation (finite and >= 0)";
+    if (!finite_from(p.gravity, 0.0f, true)) return "gravity (finite and > 0)";
+    if (!finite_from(p.capacity, 0.0f, false)) return "capacity (finite and >= 0)";
+    if (!(p.erode >= 0.0f && p.erode <= 1.0f) || !(p.deposit >= 0.0f && p.deposit <= 1.0f)) return "erode / deposit (in [0, 1])";
+    if (!(p.min_tilt >= 0.0f && p.min_tilt <= 1.0f)) return "min_tilt (in [0, 1])";
+    if (!finite_from(p.min_depth, 0.0f, true)) return "min_depth (finite and > 0)";
+    if (p.steps == 0u || p.steps > BT_ERODE_MAX_STEPS) return "steps (1 .. BT_ERODE_MAX_STEPS)";
+    return nullptr;
+}
+
+// the index of the first entry of a host plane that is negative or not finite, or `cells`
+uint64_t first_bad_entry(const float* plane, uint64_t cells) {
+    for (uint64_t i = 0; i < cells; i++)
+        if (!(plane[i] >= 0.0f) || !std::isfinite(plane[i])) return i;
+    return cells;
+}
+
+uint64_t align256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
+
+}  // namespace
+
+extern "C" {
+
+bt_status bt_atlas_erode_height(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                const bt_erosion_params* params, const uint8_t* weight_host, float* water_host, float* sediment_host, bt_tile_coordinate* changed,
+                                uint32_t changed_cap, bt_erosion_stats* stats) {
+    const char* who = "bt_atlas_erode_height";
+    if (stats) *stats = bt_erosion_stats{};
+    if (!a || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", who, !a ? "atlas" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, who)) return s;
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("%s: attachment format %u (heights are R16)", who, at.meta.format);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!params) {
+        set_error("%s: NULL params", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (const char* bad = bad_erosion(*params)) {
+        set_error("%s: %s", who, bad);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t cells = uint64_t(width) * height;
+    if (cells > BT_ERODE_MAX_CELLS) {
+        set_error("%s: %u x %u cells, at most %u", who, width, height, BT_ERODE_MAX_CELLS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!cells) return BT_OK;
+    for (const float* plane : {(const float*)water_host, (const float*)sediment_host}) {
+        if (!plane) continue;
+        const uint64_t bad = first_bad_entry(plane, cells);
+        if (bad < cells) {
+            set_error("%s: %s[%llu] = %g (finite and >= 0)", who, plane == water_host ? "water_host" : "sediment_host", (unsigned long long)bad, double(plane[bad]));
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+    }
+
+    const bt_erosion_params& p = *params;
+    ErodeConsts c{};
+    c.min_height = p.min_height, c.range = p.max_height - p.min_height, c.cell_size = p.cell_size, c.dt = p.dt;
+    c.capacity = p.capacity, c.erode = p.erode, c.deposit = p.deposit, c.min_tilt = p.min_tilt, c.min_depth = p.min_depth;
+    c.rain_dt = p.dt * p.rain;
+    c.cf = (p.dt * p.gravity) * p.cell_size;
+    c.l2 = p.cell_size * p.cell_size;
+    c.two_l = 2.0f * p.cell_size;
+    const float e = p.evaporation * p.dt;
+    c.keep = 1.0f - (e < 1.0f ? e : 1.0f);
+
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    // the planes of the call, carved from one buffer: the gathered texels, the activity and weight bytes, 2 x 7 float planes
+    const uint64_t plane = align256(cells * 4u);
+    const uint64_t at_raw = 0, at_act = at_raw + align256(cells * 2u), at_weight = at_act + align256(cells), at_state = at_weight + (weight_host ? align256(cells) : 0u);
+    if (bt_status s = ctx->erode.reserve(ctx, at_state + 14u * plane)) return s;
+    if (bt_status s = ctx->edit_region.reserve(ctx, cells * 2u)) return s;
+    uint8_t* base = (uint8_t*)ctx->erode.dev;
+    uint16_t* raw = (uint16_t*)(base + at_raw);
+    uint8_t* act = base + at_act;
+    uint8_t* weight = weight_host ? base + at_weight : nullptr;
+    ErodePlanes planes[2];
+    for (uint32_t i = 0; i < 2u; i++) {
+        float* first = (float*)(base + at_state + i * 7u * plane);
+        const uint64_t stride = plane / 4u;
+        planes[i].b = first, planes[i].d = first + stride, planes[i].s = first + 2u * stride;
+        for (uint32_t k = 0; k < 4u; k++) planes[i].f[k] = first + (3u + k) * stride;
+    }
+
+    uint32_t tiles_missing = 0;
+    if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, raw, &tiles_missing)) return s;
+    if (weight)
+        if (bt_status s = region_stage_in(ctx, weight, weight_host, width, width, height)) return s;
+    if (water_host)
+        if (bt_status s = region_stage_in(ctx, planes[0].d, water_host, uint64_t(width) * 4u, uint64_t(width) * 4u, height)) return s;
+    if (sediment_host)
+        if (bt_status s = region_stage_in(ctx, planes[0].s, sediment_host, uint64_t(width) * 4u, uint64_t(width) * 4u, height)) return s;
+    if (bt_status s = launch_erode_init(stream, raw, water_host != nullptr, sediment_host != nullptr, planes[0], act, uint32_t(cells), c)) return s;
+    for (uint32_t step = 0; step < p.steps; step++)
+        if (bt_status s = launch_erode_step(stream, planes[step & 1u], planes[(step + 1u) & 1u], act, width, height, c)) return s;
+    const ErodePlanes& last = planes[p.steps & 1u];
+    if (bt_status s = launch_erode_finish(stream, raw, last.b, weight, (uint16_t*)ctx->edit_region.dev, uint32_t(cells), c)) return s;
+    if (water_host)
+        if (bt_status s = region_stage_out(ctx, last.d, water_host, uint64_t(width) * 4u, uint64_t(width) * 4u, height, "bt_atlas_erode_height staging")) return s;
+    if (sediment_host)
+        if (bt_status s = region_stage_out(ctx, last.s, sediment_host, uint64_t(width) * 4u, uint64_t(width) * 4u, height, "bt_atlas_erode_height staging")) return s;
+
+    FirstStep first{FirstStep::kRegion};  // texels nullptr: the rectangle is on the device
+    first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
+    bt_edit_stats edit{};
+    bt_status rc = edit_boxes(a, ai, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, &edit);
+    const bt_status drained = ctx->staging.drain();  // the staging copies of the weight plane (the only wait of a call without water and sediment)
+    if (stats) {
+        stats->cells = uint32_t(cells), stats->tiles_missing = tiles_missing, stats->steps = p.steps, stats->sim_launches = p.steps + 2u;
+        stats->edit = edit;
+    }
+    return rc ? rc : drained;
 }
 
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {

@@ -249,7 +249,10 @@ struct bt_ctx {
     // bt_atlas_scatter_instances: the totals, the tile list and the firsts of one call, the block records, block offsets and cell bytes of
     // one chunk of it, and the instance list on the device
     bt::Scratch scatter;
-    std::array<bt::Scratch*, 8> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_erode_height: the planes of one call on the device (the gathered texels, the activity bytes, the weight bytes and the seven
+    // state planes twice)
+    bt::Scratch erode;
+    std::array<bt::Scratch*, 9> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
 };
@@ -478,6 +481,25 @@ inline uint32_t shard_holder(const ::bt_preprocessor* p, uint32_t attachment, ui
 bt_status region_check(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, const char* what);
 bt_status region_gather(const bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, void* dst, uint32_t* tiles_missing);
 bt_status region_stage_out(bt_ctx* ctx, const void* src, void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height, const char* what);
+// the way in (bt_atlas_write_region's rectangle, the host planes of bt_atlas_erode_height): `height` host rows row_pitch apart -> pinned staging ->
+// tightly packed rows at `dst` on the device, enqueued; the ring's events cover the copies (the caller drains it before it returns)
+bt_status region_stage_in(bt_ctx* ctx, void* dst, const void* texels, uint64_t row_bytes, uint64_t row_pitch, uint32_t height);
+
+// bt_erode.hip: the kernels of bt_atlas_erode_height.  Planes are width x height, row-major
+struct ErodePlanes {  // one side of the ping-pong
+    float *b, *d, *s, *f[4];
+};
+struct ErodeConsts {  // the parameters the kernels read and the host constants of the header, each formed once
+    float min_height, range, cell_size, dt, capacity, erode, deposit, min_tilt, min_depth;
+    float rain_dt, cf, l2, two_l, keep;
+};
+constexpr uint32_t kErodeBlock = BT_ERODE_BLOCK;  // a workgroup's cells are kErodeBlock x kErodeBlock
+// raw texels -> b, the fluxes (0) and the activity bytes; water / sediment: p.d / p.s hold the caller's plane (kept on active cells), else set to 0
+bt_status launch_erode_init(hipStream_t stream, const uint16_t* raw, bool water, bool sediment, const ErodePlanes& p, uint8_t* act, uint32_t cells, const ErodeConsts& c);
+// one step: in -> out
+bt_status launch_erode_step(hipStream_t stream, const ErodePlanes& in, const ErodePlanes& out, const uint8_t* act, uint32_t width, uint32_t height, const ErodeConsts& c);
+// the blend (weight: bytes on the device, or nullptr) and the quantisation -> the staged rectangle of R16 texels
+bt_status launch_erode_finish(hipStream_t stream, const uint16_t* raw, const float* bT, const uint8_t* weight, uint16_t* texels, uint32_t cells, const ErodeConsts& c);
 
 // bt_path.hip: the kernels of bt_atlas_path_field.  Planes are width x height, row-major; D holds the bits of non-negative floats
 struct PathPlanes {

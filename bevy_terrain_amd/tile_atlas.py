@@ -251,6 +251,34 @@ class PathCost:
                               float(self.climb_weight), float(self.descend_weight), 0)
 
 
+@dataclass
+class ErosionParams:
+    """bt_erosion_params: the constants of TileAtlas.erode_height.  A raw texel is the height min_height + (max_height - min_height) * raw /
+    65535; cell_size is the world length of one texel.  Per step of length dt: `rain` * dt of water falls on every cell, water flows to the
+    4-neighbours by the height differences of the water surface (gravity), a cell's carrying capacity is capacity * max(sin(slope), min_tilt) *
+    speed (the speed taken over a depth of at least min_depth); it takes `erode` of what it lacks from the ground or leaves `deposit` of what
+    it has too much, the sediment travels with the water, and evaporation * dt of the water goes.  Stability is the caller's: dt * gravity *
+    depth / cell_size^2 well below 1."""
+    min_height: float = 0.0
+    max_height: float = 1.0
+    cell_size: float = 1.0
+    dt: float = 0.05
+    rain: float = 0.5
+    evaporation: float = 0.3
+    gravity: float = 9.81
+    capacity: float = 0.05
+    erode: float = 0.3
+    deposit: float = 0.3
+    min_tilt: float = 0.05
+    min_depth: float = 0.01
+    steps: int = 1
+
+    def _c(self):
+        return _ffi.ErosionParamsC(float(self.min_height), float(self.max_height), float(self.cell_size), float(self.dt), float(self.rain), float(self.evaporation),
+                                   float(self.gravity), float(self.capacity), float(self.erode), float(self.deposit), float(self.min_tilt), float(self.min_depth),
+                                   int(self.steps), (C.c_uint32 * 3)(0, 0, 0))
+
+
 PATH_TRACE_STATUS = {_ffi.PATH_TRACE_OK: "ok", _ffi.PATH_TRACE_BLOCKED: "blocked", _ffi.PATH_TRACE_UNREACHABLE: "unreachable", _ffi.PATH_TRACE_LOOP: "loop"}
 
 
@@ -597,6 +625,40 @@ class TileAtlas:
             cost_out.ctypes.data_as(C.POINTER(C.c_float)) if want_cost else None,
             next_out.ctypes.data_as(C.POINTER(C.c_uint8)) if want_next else None, C.byref(stats)))
         return cost_out, next_out, {name: getattr(stats, name) for name, _ in _ffi.PathStatsC._fields_}
+
+    def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
+                     water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
+        """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the
+        w x h window of centre texels at mosaic position (x0, y0) of `lod` on `side` of an R16 attachment (texels without data, tiles the
+        atlas does not hold and the window's edge are walls), blends the new heights over the old ones by the optional (h, w) uint8 `weight`
+        plane (255: all of the change, 0: the texel is kept), writes them back and restores the ancestors, the aprons and the mips as
+        write_region does.  `water` / `sediment`: optional (h, w) float32 planes (finite, >= 0) the simulation starts from; where given, the
+        plane after the last step comes back and the call is synchronous, otherwise it starts from 0 and the call only enqueues.  Fluxes
+        start at 0 in every call.  Returns (changed, stats, water, sediment): changed tiles as write_region lists them, bt_erosion_stats as a
+        dict (its "edit" entry: the bt_edit_stats of the write-back), and the two planes (None where none was given)."""
+        lod = self.lod_count - 1 if lod is None else lod
+
+        def plane(array, dtype, name):
+            if array is None:
+                return None
+            array = np.array(array, dtype=dtype, order="C")  # a copy: the call writes into it
+            if array.shape != (h, w):
+                raise ValueError(f"erode_height: a {name} plane of shape {array.shape} for a window of {(h, w)}")
+            return array
+
+        weight_c, water_c, sediment_c = plane(weight, np.uint8, "weight"), plane(water, np.float32, "water"), plane(sediment, np.float32, "sediment")
+        cap = max(self.atlas_size, 1)
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.ErosionStatsC()
+        params_c = params._c()
+        _ffi.check(_ffi.lib().bt_atlas_erode_height(
+            self._h, attachment_index, side, lod, x0, y0, w, h, C.byref(params_c),
+            weight_c.ctypes.data_as(C.POINTER(C.c_uint8)) if weight_c is not None else None,
+            water_c.ctypes.data_as(C.POINTER(C.c_float)) if water_c is not None else None,
+            sediment_c.ctypes.data_as(C.POINTER(C.c_float)) if sediment_c is not None else None, changed, cap, C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.ErosionStatsC._fields_ if name != "edit"}
+        out["edit"] = {name: getattr(stats.edit, name) for name, _ in _ffi.EditStatsC._fields_}
+        return [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))], out, water_c, sediment_c
 
     def write_region(self, attachment_index: int, texels: np.ndarray, x0: int, y0: int, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_write_region: copy `texels` ((h, w) uint16 for R16, (h, w, 4) uint8 for Rgba8; zeros allowed) verbatim over the centre

@@ -1651,6 +1651,89 @@ enum { BT_PATH_TRACE_OK = 0, BT_PATH_TRACE_BLOCKED = 1, BT_PATH_TRACE_UNREACHABL
 bt_status bt_path_trace(const uint8_t* next, uint32_t width, uint32_t height, uint32_t start_x, uint32_t start_y, uint32_t* out_xy,
                         uint32_t cap, uint32_t* count_out, uint32_t* status_out);
 
+/* ---------------- hydraulic erosion: a simulation over a rectangle of heights, written back as an edit
+ * EROSION (bt_atlas_erode_height; R16 only).  The shallow-water "pipe" model on a grid: rain, outflow fluxes between 4-neighbours, a
+ * velocity from the fluxes, erosion or deposition towards a carrying capacity, sediment carried WITH the fluxes (a share of a cell's
+ * sediment leaves with every share of its water: a fixed stencil, conservative, no data-dependent reach), evaporation.
+ * Arithmetic: IEEE binary32 with subnormals kept, one rounding per written operation, no contraction; / and sqrt are correctly rounded;
+ * pos(x) = x > 0 ? x : 0 (a NaN goes to 0); ((a + b) + c) + d is summed in that order.  Which NaN an invalid operation gives (its sign and
+ * payload) is left open; everything else is a function of the input, bit for bit.
+ * Cells and state.  The window is the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` (the rectangle of
+ * bt_atlas_read_region; inside one face).  Cell (x, y) is mosaic texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index
+ * y * width + x.  raw = the centre texel.  A cell is ACTIVE when raw != 0 and the atlas holds its tile; every other cell is a WALL, and so
+ * is everything outside the window (the simulation is closed).  A wall holds no water and no sediment, has no flux in or out, and is never
+ * written.  An active cell has b (height), d (water), s (sediment) and f[0..3], the outflow towards neighbour k = 0..3 =
+ * (1,0), (0,1), (-1,0), (0,-1); opp(k) = (k + 2) & 3.
+ * Initial state.  range = max_height - min_height;  b = min_height + range * (f32(raw) / 65535);  d and s from water_host / sediment_host
+ * (width * height floats each; 0 where the pointer is NULL; forced to 0 on walls);  f = 0: fluxes do not survive the call, so two calls of
+ * n steps differ from one of 2n by the restart of the fluxes.
+ * Host constants, each formed once:  rain_dt = dt * rain;  cf = (dt * gravity) * cell_size;  l2 = cell_size * cell_size;
+ * two_l = 2 * cell_size;  e = evaporation * dt;  keep = 1 - (e < 1 ? e : 1).
+ * One step = phase A over all cells, then B over all cells, then C over all cells.  For an active cell, n_k its neighbour k:
+ *   A.  d1 = d + rain_dt;  H = b + d1
+ *       f'[k] = n_k active ? pos(f[k] + cf * (H - H_(n_k))) : 0
+ *       out = ((f'[0] + f'[1]) + f'[2]) + f'[3]
+ *       if out * dt > d1 * l2:  K = (d1 * l2) / (out * dt);  f'[k] = f'[k] * K for every k;  out is summed again
+ *   B.  in_k = n_k active ? f'_(n_k)[opp(k)] : 0;  in = ((in_0 + in_1) + in_2) + in_3
+ *       d2 = pos(d1 + (dt * (in - out)) / l2)
+ *       dm = 0.5 * (d1 + d2);  dm = dm > min_depth ? dm : min_depth
+ *       wx = 0.5 * ((in_2 - f'[2]) + (f'[0] - in_0));  wy = 0.5 * ((in_3 - f'[3]) + (f'[1] - in_1))
+ *       vx = wx / (cell_size * dm);  vy = wy / (cell_size * dm);  speed = sqrt(vx * vx + vy * vy)
+ *       b_k = n_k active ? b_(n_k) : b;  gx = (b_0 - b_2) / two_l;  gy = (b_1 - b_3) / two_l;  g2 = gx * gx + gy * gy
+ *       sin_a = sqrt(g2 / (1 + g2));  sin_a = sin_a > min_tilt ? sin_a : min_tilt
+ *       C = (capacity * sin_a) * speed
+ *       C > s:      x = erode * (C - s);    b1 = b - x;  s1 = s + x
+ *       otherwise:  x = deposit * (s - C);  b1 = b + x;  s1 = s - x
+ *   C.  vol = d1 * l2;  m[k] = vol > 0 ? s1 * ((f'[k] * dt) / vol) : 0
+ *       mo = ((m[0] + m[1]) + m[2]) + m[3];  mi = the same sum of mi_k = n_k active ? m_(n_k)[opp(k)] : 0
+ *       s2 = pos((s1 - mo) + mi);  d3 = d2 * keep
+ *       the next state: b1, d3, s2, f'.
+ * After `steps` steps, with b0 the initial and bT the final height of an active cell:  w = weight_host ? f32(weight) / 255 : 1
+ * (weight_host: width * height bytes);  h = b0 + (bT - b0) * w.  The texel keeps its value byte for byte when the cell is a wall, when
+ * w == 0, when bT == b0 bit for bit, or when h is not finite.  Otherwise, with q = (h - min_height) / range and
+ * clamp(q) = q < 0 ? 0 : q > 1 ? 1 : q,
+ *       t' = max(1, floor(0.5 + 65535 * clamp(q)))
+ * Holes are neither made nor filled.  Sediment still in suspension is not deposited: it comes back in sediment_host or is lost.  Stability
+ * (dt against cell_size, gravity and the depths) is the caller's concern; a height that is not finite cannot reach the atlas.
+ * The call.  water_host / sediment_host, where given, are read before and written after the steps (d and s of the last step; 0 on walls),
+ * and the call is then synchronous.  With both NULL it enqueues on the context's stream and returns as bt_atlas_write_region does.  The new
+ * texels are written and the invariant F restored exactly as by bt_atlas_write_region of them over the same rectangle, from the device: the same
+ * plan, the same `changed` order, the same bt_edit_stats (stats->edit).  Launches: the gather of bt_atlas_read_region, one init launch, one
+ * launch per step (a workgroup owns BT_ERODE_BLOCK x BT_ERODE_BLOCK cells and recomputes a halo of three around them: the result does not depend on
+ * the block size), one finish launch (stats->sim_launches = steps + 2), then those of the edit.  No atomics, no host round trip between the
+ * steps.  The planes stay in the context until bt_ctx_trim: 60 bytes per cell and the staged rectangle.
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL changed with changed_cap > 0; NULL params; a parameter
+ * outside the range its field names below; steps 0 or above BT_ERODE_MAX_STEPS; width * height above BT_ERODE_MAX_CELLS; an entry of
+ * water_host or sediment_host that is negative or not finite.  BT_ERR_UNSUPPORTED: a non-R16 attachment, an odd centre size.  width == 0 or
+ * height == 0 (with valid arguments otherwise; the host planes are not looked at): BT_OK, nothing touched. */
+#define BT_ERODE_MAX_CELLS (1u << 22)
+#define BT_ERODE_MAX_STEPS 4096u
+#define BT_ERODE_BLOCK 32u
+typedef struct bt_erosion_params {
+    float min_height, max_height;   /* world heights of raw 0 and 65535; finite, with a finite positive difference */
+    float cell_size;                /* l: world length of a texel; finite, > 0 */
+    float dt;                       /* finite, > 0 */
+    float rain;                     /* water height added per unit time; finite, >= 0 */
+    float evaporation;              /* per unit time; finite, >= 0 */
+    float gravity;                  /* finite, > 0 */
+    float capacity;                 /* Kc; finite, >= 0 */
+    float erode, deposit;           /* Ks, Kd; finite, in [0, 1] */
+    float min_tilt;                 /* lower bound of sin(alpha); in [0, 1] */
+    float min_depth;                /* lower bound of the depth a velocity is divided by; finite, > 0 */
+    uint32_t steps;                 /* 1 .. BT_ERODE_MAX_STEPS */
+    uint32_t _padding[3];
+} bt_erosion_params;                /* 64 bytes */
+typedef struct bt_erosion_stats {
+    uint32_t cells, tiles_missing, steps, sim_launches; /* width * height; tiles of the rectangle the atlas does not hold; params->steps; steps + 2 */
+    bt_edit_stats edit;                                 /* of the write-back */
+} bt_erosion_stats;
+bt_status bt_atlas_erode_height(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                uint32_t width, uint32_t height, const bt_erosion_params* params,
+                                const uint8_t* weight_host /* may be NULL */, float* water_host /* may be NULL: in and out */,
+                                float* sediment_host /* may be NULL: in and out */, bt_tile_coordinate* changed, uint32_t changed_cap,
+                                bt_erosion_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
