@@ -303,6 +303,16 @@ class ErosionParamsC(C.Structure):
                 ("min_tilt", C.c_float), ("min_depth", C.c_float), ("steps", C.c_uint32), ("_padding", C.c_uint32 * 3)]
 
 
+DRAIN_MAX_CELLS, DRAIN_BLOCK = 1 << 22, 32
+DRAIN_OUTLET, DRAIN_VOID = 8, 255
+
+
+class DrainageStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("voids", C.c_uint32), ("outlets", C.c_uint32), ("tiles_missing", C.c_uint32), ("filled", C.c_uint32), ("flats", C.c_uint32),
+                ("max_flat_distance", C.c_uint32), ("max_accumulation", C.c_uint32), ("outflow", C.c_uint32), ("sweeps_fill", C.c_uint32),
+                ("sweeps_flat", C.c_uint32), ("sweeps_accumulate", C.c_uint32), ("launches", C.c_uint32), ("_padding", C.c_uint32 * 3)]
+
+
 class ErosionStatsC(C.Structure):
     _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
 
@@ -387,6 +397,8 @@ PROTOTYPES = {
                                    _P(C.c_uint8), _P(PathStatsC)]),
     "bt_atlas_erode_height": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ErosionParamsC), _P(C.c_uint8), _P(C.c_float), _P(C.c_float),
                                      _P(TileCoordinateC), _u32, _P(ErosionStatsC)]),
+    "bt_atlas_drainage": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(C.c_uint8), _P(C.c_uint8), _P(C.c_uint16), _P(_u32), _P(C.c_uint8), _P(_u32),
+                                 _P(DrainageStatsC)]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

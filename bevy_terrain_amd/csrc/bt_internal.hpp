@@ -252,7 +252,10 @@ struct bt_ctx {
     // bt_atlas_erode_height: the planes of one call on the device (the gathered texels, the activity bytes, the weight bytes and the seven
     // state planes twice)
     bt::Scratch erode;
-    std::array<bt::Scratch*, 9> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_drainage: the planes of one call on the device (raw texels, the two host masks, z, W, F, the directions, A, the block flags);
+    // and its words with a pinned twin (the per-sweep counters of a batch, the counts of bt_drainage_stats)
+    bt::Scratch drain, drain_words;
+    std::array<bt::Scratch*, 11> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode, &drain, &drain_words}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
 };
@@ -524,6 +527,37 @@ bt_status launch_path_prepare(hipStream_t stream, const PathPlanes& p, const bt_
 bt_status launch_path_relax(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked);
 // the next plane by the header's rule, and the count of reachable cells
 bt_status launch_path_next(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, const bt_path_goal* goals, uint32_t goal_count, PathCounts* counts);
+
+// bt_drain.hip: the kernels of bt_atlas_drainage.  Planes are width x height, row-major
+struct DrainPlanes {
+    const uint16_t* raw;    // the gathered texels
+    const uint8_t* mask;    // the caller's void mask on the device, or nullptr
+    const uint8_t* weight;  // the caller's weights on the device, or nullptr (every w = 1)
+    uint16_t* z;            // heights; 0 = void (raw 0, a missing tile or the mask)
+    uint16_t* W;            // the filled level; 0 on void cells
+    uint32_t* F;            // the flat distance; 0 on void cells
+    uint8_t* dir;           // the direction plane
+    uint32_t* A;            // the accumulation; 0 on void cells
+    uint32_t width, height;
+    uint32_t blocks_x, blocks_y;  // of kDrainBlock x kDrainBlock cells
+};
+struct DrainCounts {  // the device words of bt_drainage_stats
+    uint32_t voids, outlets, filled, flats, max_flat_distance, max_accumulation, outflow, _padding;
+};
+constexpr uint32_t kDrainBlock = BT_DRAIN_BLOCK;
+constexpr uint32_t kDrainRounds = 64;  // rounds of one block in one sweep, at most
+enum DrainRule : uint32_t { kDrainFill = 0, kDrainFlat = 1, kDrainAccumulate = 2 };
+// prepare: z, the initial X of the fill (z on outlets, 65535 on other active cells, 0 on void ones) in W, the counts of void cells and outlets
+bt_status launch_drain_prepare(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts);
+// one sweep of one rule: every block whose flag in `active` is set clears it, relaxes its cells in LDS (at most `rounds` rounds), writes back the cells
+// it changed and sets the flags of the blocks that have to look again in `activate`; *marked counts the blocks that set a flag
+bt_status launch_drain_relax(hipStream_t stream, DrainRule rule, const DrainPlanes& p, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked);
+// the seed of the flat relaxation from the final W: F = 0 on drain cells and void ones, 0xFFFFFFFF elsewhere
+bt_status launch_drain_flat_seed(hipStream_t stream, const DrainPlanes& p);
+// the direction plane by the header's rule from the final W and F, and the seed of the accumulation: A = w (0 on void cells)
+bt_status launch_drain_direction(hipStream_t stream, const DrainPlanes& p);
+// the counts that need the final planes: filled, flats, the two maxima and the outflow
+bt_status launch_drain_finish(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

@@ -626,6 +626,41 @@ class TileAtlas:
             next_out.ctypes.data_as(C.POINTER(C.c_uint8)) if want_next else None, C.byref(stats)))
         return cost_out, next_out, {name: getattr(stats, name) for name, _ in _ffi.PathStatsC._fields_}
 
+    def drainage(self, attachment_index: int, x0: int, y0: int, w: int, h: int, void: Optional[np.ndarray] = None, weight: Optional[np.ndarray] = None,
+                 lod: Optional[int] = None, side: int = 0, want_filled: bool = True, want_flat: bool = True, want_direction: bool = True,
+                 want_accumulation: bool = True):
+        """bt_atlas_drainage: where water collects and where it runs in the w x h window of centre texels at mosaic position (x0, y0) of `lod`
+        on `side` of an R16 attachment, by the header's DRAINAGE section, in integers.  Texels without data, tiles the atlas does not hold
+        and cells where the optional (h, w) mask `void` is non-zero are void; an active cell beside a void one or on the window's edge is an
+        outlet.  Returns (filled, flat, direction, accumulation, stats): filled (h, w) uint16, the level the depressions fill to (filled -
+        height = the lake's depth; 0 on void cells); flat (h, w) uint32, the distance inside a level area to the nearest cell that drains
+        lower; direction (h, w) uint8: 0..7 the neighbour the water goes to ((1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1)),
+        8 an outlet, 255 void (trace_path follows it downstream); accumulation (h, w) uint32: the sum of `weight` ((h, w) uint8, 1 where
+        None) over the cell and everything that drains through it; stats: bt_drainage_stats as a dict.  want_* False: that plane is not
+        copied out and None comes back in its place.  All planes are exact: byte for byte what priority-flood, a breadth-first search and a
+        topological sum give.  Ordered behind the queued work; synchronous; a read."""
+        lod = self.lod_count - 1 if lod is None else lod
+
+        def plane(array, name):
+            if array is None:
+                return None
+            array = np.ascontiguousarray(array, dtype=np.uint8)
+            if array.shape != (h, w):
+                raise ValueError(f"drainage: a {name} plane of shape {array.shape} for a window of {(h, w)}")
+            return array
+
+        void_c, weight_c = plane(void, "void"), plane(weight, "weight")
+        outs = [np.zeros((h, w), dtype=t) if want else None
+                for t, want in ((np.uint16, want_filled), (np.uint32, want_flat), (np.uint8, want_direction), (np.uint32, want_accumulation))]
+        types = (C.c_uint16, C.c_uint32, C.c_uint8, C.c_uint32)
+        stats = _ffi.DrainageStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_drainage(
+            self._h, attachment_index, side, lod, x0, y0, w, h,
+            void_c.ctypes.data_as(C.POINTER(C.c_uint8)) if void_c is not None else None,
+            weight_c.ctypes.data_as(C.POINTER(C.c_uint8)) if weight_c is not None else None,
+            *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, types)], C.byref(stats)))
+        return (*outs, {name: getattr(stats, name) for name, _ in _ffi.DrainageStatsC._fields_ if name != "_padding"})
+
     def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
                      water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the

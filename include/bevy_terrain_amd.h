@@ -1734,6 +1734,71 @@ bt_status bt_atlas_erode_height(bt_atlas* atlas, uint32_t attachment_index, uint
                                 float* sediment_host /* may be NULL: in and out */, bt_tile_coordinate* changed, uint32_t changed_cap,
                                 bt_erosion_stats* stats /* may be NULL */);
 
+/* ---------------- drainage: filled lakes, flow directions and drained area over a rectangle of heights
+ * DRAINAGE (bt_atlas_drainage; R16 only).  Integers throughout: no float appears, so every plane is a function of the input byte for byte.
+ * Window: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of an R16 attachment (the rectangle of
+ * bt_atlas_read_region; inside one face: water does not cross a cube edge).  Cell (x, y), 0 <= x < width, 0 <= y < height, is mosaic
+ * texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index i = y * width + x.
+ * Cells.  raw = the centre texel.  The cell is VOID when raw == 0 (no data), when its tile is one the atlas does not hold (such texels read
+ * as 0), or when void_host[i] != 0 (the optional host mask).  Every other cell is ACTIVE with the height z = raw, the integer.
+ * Neighbours.  k = 0..7 with (dx, dy) = (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1), as in the path field.  All eight
+ * count; there is no corner rule.
+ * Outlets.  An active cell is an OUTLET when any of its eight neighbours lies outside the window or is void: water leaves the window at its
+ * edge and into no-data.  Every 8-connected set of active cells therefore holds an outlet, and everything below is finite.
+ * Filled level W(c) (u16): the minimum over all 8-connected paths of active cells from c to an outlet of the largest z on the path, c and
+ * the outlet included.  This is what priority-flood computes.  Equally: start from X = z on outlets and +inf on every other cell and relax
+ *     X(c) = max(z(c), min_k X(n_k))
+ * FROM ABOVE, in any order: every value held is the bottleneck of a real path (or +inf), so the relaxation stops at W.  "From above" is part
+ * of the definition: the fixed point of that equation is not unique (two adjacent pit cells hold each other at any level below their rim),
+ * and W is the largest one.  65535 serves as +inf: it bounds every W.  W - z is the depth of the lake over the cell.
+ * Flat distance F(c) (u32).  c is a DRAIN cell when it is an outlet or has a neighbour with W(n_k) < W(c).  F = 0 on drain cells; otherwise
+ *     F(c) = 1 + min F(n_k) over the neighbours with W(n_k) == W(c).
+ * F is finite on every active cell: a cell that is neither kind of drain cell has min_k W(n_k) == W(c), and its optimal path runs through
+ * cells of that W until the first one with a lower neighbour, or the outlet.
+ * Direction (u8).  BT_DRAIN_VOID on a void cell.  BT_DRAIN_OUTLET on an outlet.  On any other drain cell: among the k with
+ * d_k = W(c) - W(n_k) > 0 the k with the largest score_k = d_k * d_k * (k odd ? 1 : 2), formed in 64 bits (it reaches 2 * 65534^2), the
+ * smallest k on a tie: steepest descent with a diagonal run of sqrt(2), without a rounding.  On any other cell: the smallest k with
+ * W(n_k) == W(c) and F(n_k) == F(c) - 1.  The receiver of a cell is strictly smaller in (W, F), so the directions form a forest rooted at
+ * the outlets.  BT_DRAIN_OUTLET == BT_PATH_GOAL and BT_DRAIN_VOID == BT_PATH_BLOCKED on purpose: bt_path_trace follows a direction plane
+ * downstream from any active cell to its outlet as it stands, and ends BT_PATH_TRACE_OK.
+ * Accumulation A(c) (u32).  w(c) = weight_host ? weight_host[i] : 1 (the optional u8 plane: rainfall, say).
+ *     A(c) = w(c) + the sum of A(d) over the cells d whose receiver is c;  A = 0 on void cells.
+ * With at most BT_DRAIN_MAX_CELLS cells of weight <= 255 no A reaches 2^32.
+ * Outputs: filled_out (u16; 0 on void), flat_out (u32; 0 on void), direction_out (u8), accumulation_out (u32), each width * height,
+ * row-major, and stats; each may be NULL.  bt_drainage_stats: every field but sweeps_fill, sweeps_flat, sweeps_accumulate and launches is
+ * a function of the input; those four describe the schedule and may differ from run to run.
+ * The call: synchronous, host arrays in and out, ordered behind the work queued on the context's stream; a read: no layer is marked
+ * written.  Launches: the gather of bt_atlas_read_region (counted as one); one prepare launch (void and outlet classes, the initial X);
+ * the fill relaxation; one launch that seeds F; the flat relaxation; one launch for the direction plane, which also seeds A = w; the
+ * accumulation (X = w + the sum over the neighbours that point at the cell, ascending from w: over a forest that has one fixed point);
+ * one finish launch for the counts: launches = 5 + sweeps_fill + sweeps_flat + sweeps_accumulate.  Each relaxation is enqueued in batches
+ * of 4, 8, 16, then 32 sweeps; in a sweep a workgroup owns BT_DRAIN_BLOCK x BT_DRAIN_BLOCK cells and works only when a neighbour or itself
+ * flagged it; after each batch the last sweep's count of blocks that still had work is read back, and 0 ends the loop (more than
+ * width * height sweeps: BT_ERR_INTERNAL).  No result depends on the block size or the schedule.  The scratch, 17 bytes per cell, stays in
+ * the context until bt_ctx_trim.
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; width * height above BT_DRAIN_MAX_CELLS.
+ * BT_ERR_UNSUPPORTED: a non-R16 attachment, an odd centre size.  width == 0 or height == 0 (with valid arguments otherwise): BT_OK,
+ * nothing touched. */
+#define BT_DRAIN_MAX_CELLS (1u << 22)
+#define BT_DRAIN_BLOCK 32u
+enum { BT_DRAIN_OUTLET = 8, BT_DRAIN_VOID = 255 }; /* values of the direction plane besides k = 0..7 */
+typedef struct bt_drainage_stats {
+    uint32_t cells, voids, outlets;                           /* width * height; void cells; outlets */
+    uint32_t tiles_missing;                                   /* tiles of the rectangle the atlas does not hold */
+    uint32_t filled, flats;                                   /* cells with W > z; cells with F > 0 */
+    uint32_t max_flat_distance, max_accumulation;             /* the largest F; the largest A */
+    uint32_t outflow;                                         /* the sum of A over the outlets = the sum of w over the active cells */
+    uint32_t sweeps_fill, sweeps_flat, sweeps_accumulate;     /* relaxation launches of the three fixed points */
+    uint32_t launches;                                        /* all kernel launches of the call, the gather counted as one */
+    uint32_t _padding[3];
+} bt_drainage_stats; /* 64 bytes */
+bt_status bt_atlas_drainage(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                            uint32_t width, uint32_t height, const uint8_t* void_host /* may be NULL */,
+                            const uint8_t* weight_host /* may be NULL */, uint16_t* filled_out /* may be NULL */,
+                            uint32_t* flat_out /* may be NULL */, uint8_t* direction_out /* may be NULL */,
+                            uint32_t* accumulation_out /* may be NULL */, bt_drainage_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
