@@ -2,66 +2,13 @@
 //
 // The call checks its arguments, gathers the rectangle's texels on the device by the plan of bt_atlas_read_region, prepares the planes, and
 // then brings three relaxations to their fixed points one after the other: the filled level, the flat distance (which reads the final
-// level), and, behind the direction plane, the accumulation (which reads the final directions).  Each enqueues sweeps of the relaxation
-// kernel in batches (4, 8, 16, then 32 at a time): after each batch the LAST sweep's count of blocks that flagged work for the sweep after
-// it comes back, and 0 ends the loop.  A sweep in which no block is flagged does nothing, so sweeps past convergence cost a launch each and
-// change nothing.  No result depends on the schedule (the header says why).
-#include <cstdlib>
+// level), and, behind the direction plane, the accumulation (which reads the final directions).  Each starts with every block flagged and
+// runs the sweeps of the block relaxation (relax_sweeps, bt_relax.hpp).  No result depends on the schedule (the header says why).
 #include <cstring>
 
-#include "bt_internal.hpp"
+#include "bt_relax.hpp"
 
 using namespace bt;
-
-namespace {
-
-constexpr uint32_t kBatchFirst = 4, kBatchMax = 32;
-
-// rounds of a block per sweep.  The profiling build (tools/, -DBT_DEBUG_HOOKS) takes it from BT_DRAIN_ROUNDS for tools/drainage_bench.py
-uint32_t drain_rounds() {
-#ifdef BT_DEBUG_HOOKS
-    if (const char* v = getenv("BT_DRAIN_ROUNDS")) return uint32_t(std::min(std::max(atoi(v), 1), 4096));
-#endif
-    return kDrainRounds;
-}
-
-uint64_t align256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
-
-// what one relaxation needs besides the planes
-struct Sweeper {
-    hipStream_t stream;
-    const DrainPlanes& p;
-    uint32_t* flags[2];
-    uint32_t* marked;             // kBatchMax counters on the device
-    const uint32_t* marked_host;  // the pinned word the last one of a batch comes back in
-    uint32_t rounds;
-
-    // every block flagged, then sweeps until one flags nothing; *sweeps_out: how many were launched
-    bt_status run(DrainRule rule, const char* name, uint32_t* sweeps_out) {
-        const uint64_t cells = uint64_t(p.width) * p.height, blocks = uint64_t(p.blocks_x) * p.blocks_y;
-        BT_HIP(hipMemsetD32Async(hipDeviceptr_t(flags[0]), 1, blocks, stream));
-        BT_HIP(hipMemsetAsync(flags[1], 0, blocks * 4u, stream));
-        uint32_t sweeps = 0;
-        bool converged = false;
-        for (uint32_t batch = kBatchFirst; !converged && sweeps < cells; batch = std::min(2u * batch, kBatchMax)) {
-            const uint32_t n = uint32_t(std::min<uint64_t>(batch, cells - sweeps));
-            BT_HIP(hipMemsetAsync(marked, 0, n * 4u, stream));
-            for (uint32_t i = 0; i < n; i++, sweeps++)
-                if (bt_status s = launch_drain_relax(stream, rule, p, rounds, flags[sweeps & 1u], flags[(sweeps + 1u) & 1u], marked + i)) return s;
-            BT_HIP(hipMemcpyAsync((void*)marked_host, marked + (n - 1u), 4u, hipMemcpyDeviceToHost, stream));
-            BT_HIP(hipStreamSynchronize(stream));
-            converged = marked_host[0] == 0u;
-        }
-        *sweeps_out = sweeps;
-        if (!converged) {
-            set_error("bt_atlas_drainage: no fixed point of the %s after %u sweeps of %llu cells", name, sweeps, (unsigned long long)cells);
-            return BT_ERR_INTERNAL;
-        }
-        return BT_OK;
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -89,9 +36,7 @@ bt_status bt_atlas_drainage(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lo
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
     // the planes of the call, carved from one buffer
-    DrainPlanes p{};
-    p.width = width, p.height = height;
-    p.blocks_x = (width + kDrainBlock - 1u) / kDrainBlock, p.blocks_y = (height + kDrainBlock - 1u) / kDrainBlock;
+    DrainPlanes p{RelaxGrid::of(width, height)};
     const uint64_t blocks = uint64_t(p.blocks_x) * p.blocks_y;
     const uint64_t at_raw = 0, at_mask = at_raw + align256(cells * 2u), at_weight = at_mask + (void_host ? align256(cells) : 0u),
                    at_z = at_weight + (weight_host ? align256(cells) : 0u), at_w = at_z + align256(cells * 2u), at_f = at_w + align256(cells * 2u),
@@ -120,13 +65,27 @@ bt_status bt_atlas_drainage(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lo
     if (bt_status s = launch_drain_prepare(stream, p, counts)) return s;
     launches++;
 
-    Sweeper sweeper{stream, p, {(uint32_t*)(base + at_flags), (uint32_t*)(base + at_flags) + blocks}, sweep_marked, sweep_marked_host, drain_rounds()};
+    uint32_t* flags[2] = {(uint32_t*)(base + at_flags), (uint32_t*)(base + at_flags) + blocks};
+    const uint32_t rounds = relax_rounds("BT_DRAIN_ROUNDS");
+    // one relaxation: every block flagged, then sweeps until one flags nothing; *sweeps: how many were launched
+    auto relax = [&](DrainRule rule, const char* name, uint32_t* sweeps) -> bt_status {
+        BT_HIP(hipMemsetD32Async(hipDeviceptr_t(flags[0]), 1, blocks, stream));
+        BT_HIP(hipMemsetAsync(flags[1], 0, blocks * 4u, stream));
+        bool converged = false;
+        auto sweep = [&](uint32_t* active, uint32_t* activate, uint32_t* marked) { return launch_drain_relax(stream, rule, p, rounds, active, activate, marked); };
+        if (bt_status s = relax_sweeps(stream, cells, flags, sweep_marked, sweep_marked_host, sweep, sweeps, &converged)) return s;
+        if (!converged) {
+            set_error("bt_atlas_drainage: no fixed point of the %s after %u sweeps of %llu cells", name, *sweeps, (unsigned long long)cells);
+            return BT_ERR_INTERNAL;
+        }
+        return BT_OK;
+    };
     uint32_t sweeps_fill = 0, sweeps_flat = 0, sweeps_accumulate = 0;
-    if (bt_status s = sweeper.run(kDrainFill, "filled level", &sweeps_fill)) return s;
+    if (bt_status s = relax(kDrainFill, "filled level", &sweeps_fill)) return s;
     if (bt_status s = launch_drain_flat_seed(stream, p)) return s;
-    if (bt_status s = sweeper.run(kDrainFlat, "flat distance", &sweeps_flat)) return s;
+    if (bt_status s = relax(kDrainFlat, "flat distance", &sweeps_flat)) return s;
     if (bt_status s = launch_drain_direction(stream, p)) return s;
-    if (bt_status s = sweeper.run(kDrainAccumulate, "accumulation", &sweeps_accumulate)) return s;
+    if (bt_status s = relax(kDrainAccumulate, "accumulation", &sweeps_accumulate)) return s;
     if (bt_status s = launch_drain_finish(stream, p, counts)) return s;
     launches += 3u + sweeps_fill + sweeps_flat + sweeps_accumulate;
     BT_HIP(hipMemcpyAsync((void*)counts_host, counts, sizeof(DrainCounts), hipMemcpyDeviceToHost, stream));

@@ -2,103 +2,98 @@
 //
 // drain_prepare_kernel    raw texels + the caller's mask -> z (0 = void), the initial X of the fill in W (z on outlets, 65535 on the other
 //                         active cells, 0 on void ones), the counts of void cells and outlets.
-// drain_relax_kernel      one sweep of one of three rules, the block scheme of bt_path.hip.  A workgroup owns kDrainBlock x kDrainBlock cells; it
-//                         leaves at once unless its flag is set.  It stages two words per cell, a fixed one (`a`) and the value that moves (`x`),
-//                         for its cells plus a one-cell halo in LDS, and relaxes in LDS until nothing changed in the workgroup or `rounds` rounds
-//                         (kDrainRounds) have run.  It writes back the cells it changed (one writer per cell, naturally aligned stores, no global
-//                         atomics), and flags the blocks whose halo those cells are in, and itself when it stopped at the round limit.  Sweeps are
-//                         ordered by the kernel boundary alone.  The rules and why a halo value read while a neighbour rewrites it, or a stale
-//                         one, cannot move the fixed point: at each rule below.
+// relax_kernel            <FillRule>, <FlatRule>, <AccumulateRule>: one sweep of the block relaxation, described in bt_relax.hpp.  The rules
+//                         and why a halo value read while a neighbour rewrites it, or a stale one, cannot move the fixed point: at each
+//                         rule below.
 // drain_flat_seed_kernel  the final W -> F = 0 on drain cells (and void ones), 0xFFFFFFFF elsewhere.
 // drain_direction_kernel  the direction plane by the header's rule, and A = w.
 // drain_finish_kernel     the counts of bt_drainage_stats that need the final planes.
 //
-// Everything is integer arithmetic.  LDS: 2 x 34 x 34 dwords = 9248 bytes a workgroup (9512 with the words of the barrier reductions); a
-// half-wave reads 32 consecutive dwords of a row (ds_read_b32 banks by dword mod 32 within a 32-lane half: no conflict).  38 VGPRs at most,
-// no scratch: the 256 threads, not the registers or the LDS, bound the workgroups of a CU (tools/kernel_resources.sh drain bt_drain.hip).
-#include "bt_internal.hpp"
+// Everything is integer arithmetic.  The relaxations: 38 VGPRs at most, no scratch: the 256 threads, not the registers or the LDS, bound the
+// workgroups of a CU (tools/kernel_resources.sh relax bt_drain.hip).
+#include "bt_relax.hpp"
 
 namespace bt {
 
 namespace {
 
-constexpr uint32_t kDrainThreads = 256;
-constexpr uint32_t kDrainTile = kDrainBlock + 2u;  // the block and its halo
-constexpr uint32_t kDrainOwn = kDrainBlock * kDrainBlock / kDrainThreads;  // cells of a thread: rows ly, ly + 8, ly + 16, ly + 24
+constexpr uint32_t kDrainThreads = 256;  // of the per-cell kernels (prepare, seed, direction, finish)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-// neighbour k = 0..7: (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1)
-__host__ __device__ constexpr int drain_dx(int k) { return k == 0 || k == 1 || k == 7 ? 1 : k >= 3 && k <= 5 ? -1 : 0; }
-__host__ __device__ constexpr int drain_dy(int k) { return k >= 1 && k <= 3 ? 1 : k >= 5 ? -1 : 0; }
 
 __device__ __forceinline__ bool drain_inside(const DrainPlanes& p, int x, int y) { return x >= 0 && y >= 0 && x < int(p.width) && y < int(p.height); }
 
-// The three rules.  load: the two words of a cell inside the window (outside it: kOutsideA, kNone); relax: the new x of a cell from its own
-// words and the tile (t: its index in the tile); store: x back into its plane.
+// The three rules.  What all of them share: the cell's state is its fixed word a, and x is kNone outside the window.
+struct DrainRuleBase {
+    DrainPlanes p;
+    using Cell = uint32_t;
+    static constexpr uint32_t kOutsideX = kNone;
+    __device__ __forceinline__ uint32_t cell(const uint32_t* s_a, uint32_t t) const { return s_a[t]; }
+};
 
 // X = max(z, min over neighbours), descending.  a = z (0: void or outside), x = X (kNone on void cells: a void neighbour never is the
 // minimum that counts, and an outlet, which has one, starts at z and cannot fall).  Every X held anywhere, at any time, is 65535 or the
 // bottleneck of a real path to an outlet, hence >= W; a stale or half-way halo value is such a value too, so a block can only stop above W
 // or at it, never below, and the flags bring it back until nothing can fall.
-struct FillRule {
+struct FillRule : DrainRuleBase {
     static constexpr uint32_t kOutsideA = 0u;
-    static __device__ __forceinline__ void load(const DrainPlanes& p, uint64_t c, uint32_t& a, uint32_t& x) {
+    __device__ __forceinline__ void load(uint64_t c, uint32_t& a, uint32_t& x) const {
         a = p.z[c];
         x = a ? uint32_t(p.W[c]) : kNone;
     }
-    static __device__ __forceinline__ uint32_t relax(const uint32_t* s_a, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) {
+    __device__ __forceinline__ uint32_t relax(const uint32_t*, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) const {
         if (a == 0u) return x;
         uint32_t m = kNone;
 #pragma unroll
-        for (int k = 0; k < 8; k++) m = min(m, s_x[int(t) + drain_dy(k) * int(kDrainTile) + drain_dx(k)]);
+        for (int k = 0; k < 8; k++) m = min(m, s_x[tile_neighbour(t, k)]);
         return min(x, max(a, m));
     }
-    static __device__ __forceinline__ void store(const DrainPlanes& p, uint64_t c, uint32_t x) { p.W[c] = uint16_t(x); }
+    __device__ __forceinline__ void store(uint64_t c, uint32_t x) const { p.W[c] = uint16_t(x); }
 };
 
 // X = 1 + min over the neighbours of equal W, descending.  a = the final W (kNone: void or outside, equal to no cell's), x = F (0 on drain
 // cells, which never move, kNone = not reached yet).  Every finite X held is the length of a real walk through cells of one W to a drain
 // cell, hence >= F; a stale or half-way halo value is one too.
-struct FlatRule {
+struct FlatRule : DrainRuleBase {
     static constexpr uint32_t kOutsideA = kNone;
-    static __device__ __forceinline__ void load(const DrainPlanes& p, uint64_t c, uint32_t& a, uint32_t& x) {
+    __device__ __forceinline__ void load(uint64_t c, uint32_t& a, uint32_t& x) const {
         const bool is_void = p.z[c] == 0u;
         a = is_void ? kNone : uint32_t(p.W[c]);
         x = is_void ? kNone : p.F[c];
     }
-    static __device__ __forceinline__ uint32_t relax(const uint32_t* s_a, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) {
+    __device__ __forceinline__ uint32_t relax(const uint32_t* s_a, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) const {
         if (a == kNone || x == 0u) return x;
         uint32_t m = kNone;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const int n = int(t) + drain_dy(k) * int(kDrainTile) + drain_dx(k);
+            const int n = tile_neighbour(t, k);
             if (s_a[n] == a) m = min(m, s_x[n]);
         }
         return m == kNone ? x : min(x, m + 1u);
     }
-    static __device__ __forceinline__ void store(const DrainPlanes& p, uint64_t c, uint32_t x) { p.F[c] = x; }
+    __device__ __forceinline__ void store(uint64_t c, uint32_t x) const { p.F[c] = x; }
 };
 
 // X = w + the sum over the neighbours whose direction points at the cell, ascending from X = w.  a = direction | w << 8 (direction
 // BT_DRAIN_VOID: void or outside), x = A.  The receivers form a forest, so the equations have one solution, by induction from the leaves; a
 // value only grows, every value held is w plus a sum of values its donors held at some time, hence <= A, and a stale or half-way halo value
 // is one such: a block can only stop below A or at it, and a donor that grows afterwards flags the block again.
-struct AccumulateRule {
+struct AccumulateRule : DrainRuleBase {
     static constexpr uint32_t kOutsideA = BT_DRAIN_VOID;
-    static __device__ __forceinline__ void load(const DrainPlanes& p, uint64_t c, uint32_t& a, uint32_t& x) {
+    __device__ __forceinline__ void load(uint64_t c, uint32_t& a, uint32_t& x) const {
         a = uint32_t(p.dir[c]) | (p.weight ? uint32_t(p.weight[c]) : 1u) << 8;
         x = p.A[c];
     }
-    static __device__ __forceinline__ uint32_t relax(const uint32_t* s_a, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) {
+    __device__ __forceinline__ uint32_t relax(const uint32_t* s_a, const uint32_t* s_x, uint32_t t, uint32_t a, uint32_t x) const {
         if ((a & 255u) == BT_DRAIN_VOID) return x;
         uint32_t sum = a >> 8;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const int n = int(t) + drain_dy(k) * int(kDrainTile) + drain_dx(k);
+            const int n = tile_neighbour(t, k);
             if ((s_a[n] & 255u) == uint32_t((k + 4) & 7)) sum += s_x[n];  // neighbour k steps by -(dx, dy) of k: it points here
         }
         return sum;
     }
-    static __device__ __forceinline__ void store(const DrainPlanes& p, uint64_t c, uint32_t x) { p.A[c] = x; }
+    __device__ __forceinline__ void store(uint64_t c, uint32_t x) const { p.A[c] = x; }
 };
 
 __global__ __launch_bounds__(kDrainThreads) void drain_prepare_kernel(DrainPlanes p, DrainCounts* __restrict__ counts) {
@@ -114,7 +109,7 @@ __global__ __launch_bounds__(kDrainThreads) void drain_prepare_kernel(DrainPlane
         const int x = int(i % p.width), y = int(i / p.width);
         is_void = !active(x, y);
         if (!is_void)
-            for (int k = 0; k < 8; k++) outlet |= !active(x + drain_dx(k), y + drain_dy(k));
+            for (int k = 0; k < 8; k++) outlet |= !active(x + neighbour_dx(k), y + neighbour_dy(k));
         const uint16_t z = is_void ? uint16_t(0) : p.raw[i];
         p.z[i] = z;
         p.W[i] = is_void ? uint16_t(0) : outlet ? z : uint16_t(65535);
@@ -122,81 +117,6 @@ __global__ __launch_bounds__(kDrainThreads) void drain_prepare_kernel(DrainPlane
     const uint32_t voids = __syncthreads_count(is_void), outlets = __syncthreads_count(outlet);
     if (threadIdx.x == 0 && voids) atomicAdd(&counts->voids, voids);
     if (threadIdx.x == 0 && outlets) atomicAdd(&counts->outlets, outlets);
-}
-
-// bits of the flag mask a block collects: the neighbour blocks in whose halo a changed cell lies, and the block itself
-enum : uint32_t { kLeft = 1, kRight = 2, kUp = 4, kDown = 8, kUpLeft = 16, kUpRight = 32, kDownLeft = 64, kDownRight = 128, kSelf = 256 };
-
-template <class Rule>
-__global__ __launch_bounds__(kDrainThreads) void drain_relax_kernel(DrainPlanes p, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked) {
-    const uint32_t block = blockIdx.y * p.blocks_x + blockIdx.x;
-    if (active[block] == 0u) return;  // the same word for every thread, and only this workgroup writes it (below, behind a barrier)
-    __shared__ uint32_t s_a[kDrainTile * kDrainTile];
-    __shared__ uint32_t s_x[kDrainTile * kDrainTile];
-    __shared__ uint32_t s_mask;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) s_mask = 0u;
-    const int gx0 = int(blockIdx.x * kDrainBlock) - 1, gy0 = int(blockIdx.y * kDrainBlock) - 1;
-    for (uint32_t i = tid; i < kDrainTile * kDrainTile; i += kDrainThreads) {
-        const int gx = gx0 + int(i % kDrainTile), gy = gy0 + int(i / kDrainTile);
-        uint32_t a = Rule::kOutsideA, x = kNone;
-        if (drain_inside(p, gx, gy)) Rule::load(p, uint64_t(gy) * p.width + uint32_t(gx), a, x);
-        s_a[i] = a;
-        s_x[i] = x;
-    }
-    __syncthreads();
-    if (tid == 0) active[block] = 0u;
-
-    const uint32_t lx = tid % kDrainBlock, ly0 = tid / kDrainBlock;
-    uint32_t a[kDrainOwn], x[kDrainOwn], x_in[kDrainOwn];
-#pragma unroll
-    for (uint32_t j = 0; j < kDrainOwn; j++) {
-        const uint32_t t = (ly0 + j * (kDrainThreads / kDrainBlock) + 1u) * kDrainTile + lx + 1u;
-        a[j] = s_a[t];
-        x[j] = x_in[j] = s_x[t];
-    }
-    int more = 1;
-    for (uint32_t round = 0; round < rounds && more; round++) {
-        int changed = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kDrainOwn; j++) {
-            const uint32_t t = (ly0 + j * (kDrainThreads / kDrainBlock) + 1u) * kDrainTile + lx + 1u;
-            const uint32_t next = Rule::relax(s_a, s_x, t, a[j], x[j]);
-            if (next != x[j]) {
-                x[j] = next;
-                s_x[t] = next;
-                changed = 1;
-            }
-        }
-        more = __syncthreads_or(changed);
-    }
-    uint32_t mask = 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < kDrainOwn; j++) {
-        if (x[j] == x_in[j]) continue;
-        const uint32_t ly = ly0 + j * (kDrainThreads / kDrainBlock);
-        // inside the window: a cell outside it holds kOutsideA and no rule moves it
-        Rule::store(p, uint64_t(blockIdx.y * kDrainBlock + ly) * p.width + blockIdx.x * kDrainBlock + lx, x[j]);
-        const bool l = lx == 0u, r = lx == kDrainBlock - 1u, u = ly == 0u, dn = ly == kDrainBlock - 1u;
-        mask |= (l ? kLeft : 0u) | (r ? kRight : 0u) | (u ? kUp : 0u) | (dn ? kDown : 0u) | (l && u ? kUpLeft : 0u) | (r && u ? kUpRight : 0u) |
-                (l && dn ? kDownLeft : 0u) | (r && dn ? kDownRight : 0u);
-    }
-    if (mask) atomicOr(&s_mask, mask);
-    __syncthreads();
-    if (tid != 0) return;
-    mask = s_mask | (more ? uint32_t(kSelf) : 0u);
-    const uint32_t bx = blockIdx.x, by = blockIdx.y;
-    const bool hl = bx > 0u, hr = bx + 1u < p.blocks_x, hu = by > 0u, hd = by + 1u < p.blocks_y;
-    uint32_t set = 0u;
-    auto flag = [&](uint32_t bit, bool exists, int dx, int dy) {
-        if (!(mask & bit) || !exists) return;
-        activate[uint32_t(int(by) + dy) * p.blocks_x + uint32_t(int(bx) + dx)] = 1u;
-        set = 1u;
-    };
-    flag(kLeft, hl, -1, 0), flag(kRight, hr, 1, 0), flag(kUp, hu, 0, -1), flag(kDown, hd, 0, 1);
-    flag(kUpLeft, hl && hu, -1, -1), flag(kUpRight, hr && hu, 1, -1), flag(kDownLeft, hl && hd, -1, 1), flag(kDownRight, hr && hd, 1, 1);
-    flag(kSelf, true, 0, 0);
-    if (set) atomicAdd(marked, 1u);
 }
 
 __global__ __launch_bounds__(kDrainThreads) void drain_flat_seed_kernel(DrainPlanes p) {
@@ -209,7 +129,7 @@ __global__ __launch_bounds__(kDrainThreads) void drain_flat_seed_kernel(DrainPla
         const uint32_t w = p.W[i];
         bool drain = false;
         for (int k = 0; k < 8; k++) {
-            const int nx = x + drain_dx(k), ny = y + drain_dy(k);
+            const int nx = x + neighbour_dx(k), ny = y + neighbour_dy(k);
             if (!drain_inside(p, nx, ny)) {
                 drain = true;
                 continue;
@@ -235,7 +155,7 @@ __global__ __launch_bounds__(kDrainThreads) void drain_direction_kernel(DrainPla
         uint64_t best = 0u;
         uint32_t steepest = kNone, level = kNone;
         for (int k = 7; k >= 0; k--) {  // descending k: the smallest stays on a tie
-            const int nx = x + drain_dx(k), ny = y + drain_dy(k);
+            const int nx = x + neighbour_dx(k), ny = y + neighbour_dy(k);
             if (!drain_inside(p, nx, ny)) {
                 outlet = true;
                 continue;
@@ -292,44 +212,39 @@ __global__ __launch_bounds__(kDrainThreads) void drain_finish_kernel(DrainPlanes
     }
 }
 
-bt_status drain_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BT_OK : hip_fail(e, what);
-}
-
 uint32_t flat_grid(const DrainPlanes& p) { return uint32_t((uint64_t(p.width) * p.height + kDrainThreads - 1u) / kDrainThreads); }
 
 }  // namespace
 
 bt_status launch_drain_prepare(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts) {
     drain_prepare_kernel<<<dim3(flat_grid(p)), kDrainThreads, 0, stream>>>(p, counts);
-    return drain_launched("drain_prepare_kernel");
+    return launched("drain_prepare_kernel");
 }
 
 bt_status launch_drain_relax(hipStream_t stream, DrainRule rule, const DrainPlanes& p, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked) {
     const dim3 grid(p.blocks_x, p.blocks_y);
     if (rule == kDrainFill)
-        drain_relax_kernel<FillRule><<<grid, kDrainThreads, 0, stream>>>(p, rounds, active, activate, marked);
+        relax_kernel<<<grid, kRelaxThreads, 0, stream>>>(FillRule{{p}}, RelaxGrid(p), rounds, active, activate, marked);
     else if (rule == kDrainFlat)
-        drain_relax_kernel<FlatRule><<<grid, kDrainThreads, 0, stream>>>(p, rounds, active, activate, marked);
+        relax_kernel<<<grid, kRelaxThreads, 0, stream>>>(FlatRule{{p}}, RelaxGrid(p), rounds, active, activate, marked);
     else
-        drain_relax_kernel<AccumulateRule><<<grid, kDrainThreads, 0, stream>>>(p, rounds, active, activate, marked);
-    return drain_launched("drain_relax_kernel");
+        relax_kernel<<<grid, kRelaxThreads, 0, stream>>>(AccumulateRule{{p}}, RelaxGrid(p), rounds, active, activate, marked);
+    return launched("drain_relax_kernel");  // relax_kernel<Rule>, under the name bt_last_error() has always given it
 }
 
 bt_status launch_drain_flat_seed(hipStream_t stream, const DrainPlanes& p) {
     drain_flat_seed_kernel<<<dim3(flat_grid(p)), kDrainThreads, 0, stream>>>(p);
-    return drain_launched("drain_flat_seed_kernel");
+    return launched("drain_flat_seed_kernel");
 }
 
 bt_status launch_drain_direction(hipStream_t stream, const DrainPlanes& p) {
     drain_direction_kernel<<<dim3(flat_grid(p)), kDrainThreads, 0, stream>>>(p);
-    return drain_launched("drain_direction_kernel");
+    return launched("drain_direction_kernel");
 }
 
 bt_status launch_drain_finish(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts) {
     drain_finish_kernel<<<dim3(flat_grid(p)), kDrainThreads, 0, stream>>>(p, counts);
-    return drain_launched("drain_finish_kernel");
+    return launched("drain_finish_kernel");
 }
 
 }  // namespace bt

@@ -831,8 +831,6 @@ uint64_t first_bad_entry(const float* plane, uint64_t cells) {
     return cells;
 }
 
-uint64_t align256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
-
 }  // namespace
 
 extern "C" {

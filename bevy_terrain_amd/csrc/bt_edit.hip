@@ -347,11 +347,6 @@ __global__ __launch_bounds__(kEditThreads) void edit_downsample_kernel(Attachmen
     }
 }
 
-bt_status edit_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BT_OK : hip_fail(e, what);
-}
-
 dim3 edit_grid(uint32_t n, uint32_t max_rows) { return dim3(n, (max_rows + kEditRows - 1u) / kEditRows); }
 
 }  // namespace
@@ -360,14 +355,14 @@ bt_status launch_edit_brush(hipStream_t stream, const AttachmentMeta& m, void* a
                             const bt_edit_stamp* stamps, uint32_t stamp_count) {
     if (!n || !max_rows) return BT_OK;
     edit_brush_kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, (uint16_t*)atlas, items, stamps, stamp_count);
-    return edit_launched("edit_brush_kernel");
+    return launched("edit_brush_kernel");
 }
 
 bt_status launch_edit_paint(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
                             const bt_paint_stamp* stamps, uint32_t stamp_count) {
     if (!n || !max_rows) return BT_OK;
     edit_paint_kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, (uint32_t*)atlas, items, stamps, stamp_count);
-    return edit_launched("edit_paint_kernel");
+    return launched("edit_paint_kernel");
 }
 
 bt_status launch_edit_gather(hipStream_t stream, const AttachmentMeta& m, const void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
@@ -375,7 +370,7 @@ bt_status launch_edit_gather(hipStream_t stream, const AttachmentMeta& m, const 
     if (!n || !max_rows) return BT_OK;
     const auto kernel = m.format == BT_FORMAT_R16 ? edit_gather_kernel<BT_FORMAT_R16> : edit_gather_kernel<BT_FORMAT_RGBA8>;
     kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, dst, rx0, ry0, dst_width);
-    return edit_launched("edit_gather_kernel");
+    return launched("edit_gather_kernel");
 }
 
 bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows,
@@ -383,7 +378,7 @@ bt_status launch_edit_region(hipStream_t stream, const AttachmentMeta& m, void* 
     if (!n || !max_rows) return BT_OK;
     const auto kernel = m.format == BT_FORMAT_R16 ? edit_region_kernel<BT_FORMAT_R16> : edit_region_kernel<BT_FORMAT_RGBA8>;
     kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items, src, rx0, ry0, src_width);
-    return edit_launched("edit_region_kernel");
+    return launched("edit_region_kernel");
 }
 
 bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, const uint64_t* offsets, uint32_t n, uint32_t max_rows,
@@ -397,16 +392,16 @@ bt_status launch_edit_smooth(hipStream_t stream, const AttachmentMeta& m, void* 
         case 4: edit_smooth_kernel<4><<<grid, kEditThreads, 0, stream>>>(m, (const uint16_t*)atlas, items, offsets, stamps, stamp_count, (uint32_t*)scratch); break;
         default: set_error("edit_smooth_kernel: kernel_radius %u", kernel_radius); return BT_ERR_INVALID_ARGUMENT;
     }
-    if (bt_status s = edit_launched("edit_smooth_kernel")) return s;
+    if (bt_status s = launched("edit_smooth_kernel")) return s;
     edit_smooth_copy_kernel<<<grid, kEditThreads, 0, stream>>>(m, (uint16_t*)atlas, items, offsets, (const uint32_t*)scratch);
-    return edit_launched("edit_smooth_copy_kernel");
+    return launched("edit_smooth_copy_kernel");
 }
 
 bt_status launch_edit_downsample(hipStream_t stream, const AttachmentMeta& m, void* atlas, const EditItem* items, uint32_t n, uint32_t max_rows) {
     if (!n || !max_rows) return BT_OK;
     const auto kernel = m.format == BT_FORMAT_R16 ? edit_downsample_kernel<BT_FORMAT_R16> : edit_downsample_kernel<BT_FORMAT_RGBA8>;
     kernel<<<edit_grid(n, max_rows), kEditThreads, 0, stream>>>(m, atlas, items);
-    return edit_launched("edit_downsample_kernel");
+    return launched("edit_downsample_kernel");
 }
 
 }  // namespace bt

@@ -229,26 +229,21 @@ __global__ __launch_bounds__(kErodeThreads) void erode_finish_kernel(const uint1
     texels[i] = uint16_t(o);
 }
 
-bt_status erode_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BT_OK : hip_fail(e, what);
-}
-
 }  // namespace
 
 bt_status launch_erode_init(hipStream_t stream, const uint16_t* raw, bool water, bool sediment, const ErodePlanes& p, uint8_t* act, uint32_t cells, const ErodeConsts& c) {
     erode_init_kernel<<<dim3((cells + kErodeThreads - 1u) / kErodeThreads), kErodeThreads, 0, stream>>>(raw, water, sediment, p, act, cells, c);
-    return erode_launched("erode_init_kernel");
+    return launched("erode_init_kernel");
 }
 
 bt_status launch_erode_step(hipStream_t stream, const ErodePlanes& in, const ErodePlanes& out, const uint8_t* act, uint32_t width, uint32_t height, const ErodeConsts& c) {
     erode_step_kernel<<<dim3((width + kErodeBlock - 1u) / kErodeBlock, (height + kErodeBlock - 1u) / kErodeBlock), kErodeThreads, 0, stream>>>(in, out, act, width, height, c);
-    return erode_launched("erode_step_kernel");
+    return launched("erode_step_kernel");
 }
 
 bt_status launch_erode_finish(hipStream_t stream, const uint16_t* raw, const float* bT, const uint8_t* weight, uint16_t* texels, uint32_t cells, const ErodeConsts& c) {
     erode_finish_kernel<<<dim3((cells + kErodeThreads - 1u) / kErodeThreads), kErodeThreads, 0, stream>>>(raw, bT, weight, texels, cells, c);
-    return erode_launched("erode_finish_kernel");
+    return launched("erode_finish_kernel");
 }
 
 }  // namespace bt

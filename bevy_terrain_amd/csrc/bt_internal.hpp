@@ -32,6 +32,15 @@ bt_status check_model(const bt_terrain_model* m, const char* who);
         if (_e != hipSuccess) return bt::hip_fail(_e, #expr); \
     } while (0)
 
+// behind a kernel launch: what the launch left, `what` naming the kernel
+inline bt_status launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BT_OK : hip_fail(e, what);
+}
+
+// offsets of the arrays carved from one device buffer: each 256-byte aligned, as an allocation of its own is
+inline uint64_t align256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
+
 inline bool operator_eq(const bt_tile_coordinate& a, const bt_tile_coordinate& b) {
     return a.side == b.side && a.lod == b.lod && a.x == b.x && a.y == b.y;
 }
@@ -504,32 +513,36 @@ bt_status launch_erode_step(hipStream_t stream, const ErodePlanes& in, const Ero
 // the blend (weight: bytes on the device, or nullptr) and the quantisation -> the staged rectangle of R16 texels
 bt_status launch_erode_finish(hipStream_t stream, const uint16_t* raw, const float* bT, const uint8_t* weight, uint16_t* texels, uint32_t cells, const ErodeConsts& c);
 
+// bt_relax.hpp: the window of a block relaxation and its blocks of kRelaxBlock x kRelaxBlock cells, one workgroup each
+constexpr uint32_t kRelaxBlock = BT_DRAIN_BLOCK;
+struct RelaxGrid {
+    uint32_t width, height;
+    uint32_t blocks_x, blocks_y;
+    static RelaxGrid of(uint32_t width, uint32_t height) { return {width, height, (width + kRelaxBlock - 1u) / kRelaxBlock, (height + kRelaxBlock - 1u) / kRelaxBlock}; }
+};
+
 // bt_path.hip: the kernels of bt_atlas_path_field.  Planes are width x height, row-major; D holds the bits of non-negative floats
-struct PathPlanes {
+struct PathPlanes : RelaxGrid {
     const uint16_t* raw;   // the gathered texels
     const uint8_t* mask;   // the caller's mask on the device, or nullptr
     float* h;              // heights; NaN = blocked (raw 0, a missing tile or the mask)
     uint32_t* D;           // the field, as bits
     uint8_t* next;         // between prepare and next: 1 marks a cell that some goal entry names
-    uint32_t width, height;
-    uint32_t blocks_x, blocks_y;  // of kPathBlock x kPathBlock cells
 };
 struct PathCounts {  // the device words of bt_path_stats
     uint32_t blocked, reachable, goals_blocked, _padding;
 };
-constexpr uint32_t kPathBlock = 32;
-constexpr uint32_t kPathRounds = 64;  // rounds of one block in one sweep, at most
 // prepare: h and the count of blocked cells; the goals (device list) into D (memset to +inf before) by atomicMin, their cells
 // marked in `next` (memset to 0 before) and the 3 x 3 blocks around each in `flags` (memset to 0 before); blocked goals counted
 bt_status launch_path_prepare(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, const bt_path_goal* goals, uint32_t goal_count, uint32_t* flags, PathCounts* counts);
-// one sweep: every block whose flag in `active` is set clears it, relaxes its cells in LDS (at most `rounds` rounds) and sets the flags of the blocks that have to
-// look again in `activate`; *marked counts the blocks that set a flag
+// one sweep of relax_kernel (bt_relax.hpp): every block whose flag in `active` is set clears it, relaxes its cells in LDS (at most `rounds` rounds), writes back
+// the cells it changed and sets the flags of the blocks that have to look again in `activate`; *marked counts the blocks that set a flag
 bt_status launch_path_relax(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked);
 // the next plane by the header's rule, and the count of reachable cells
 bt_status launch_path_next(hipStream_t stream, const PathPlanes& p, const bt_path_cost& cost, float cell_diag, const bt_path_goal* goals, uint32_t goal_count, PathCounts* counts);
 
 // bt_drain.hip: the kernels of bt_atlas_drainage.  Planes are width x height, row-major
-struct DrainPlanes {
+struct DrainPlanes : RelaxGrid {
     const uint16_t* raw;    // the gathered texels
     const uint8_t* mask;    // the caller's void mask on the device, or nullptr
     const uint8_t* weight;  // the caller's weights on the device, or nullptr (every w = 1)
@@ -538,19 +551,14 @@ struct DrainPlanes {
     uint32_t* F;            // the flat distance; 0 on void cells
     uint8_t* dir;           // the direction plane
     uint32_t* A;            // the accumulation; 0 on void cells
-    uint32_t width, height;
-    uint32_t blocks_x, blocks_y;  // of kDrainBlock x kDrainBlock cells
 };
 struct DrainCounts {  // the device words of bt_drainage_stats
     uint32_t voids, outlets, filled, flats, max_flat_distance, max_accumulation, outflow, _padding;
 };
-constexpr uint32_t kDrainBlock = BT_DRAIN_BLOCK;
-constexpr uint32_t kDrainRounds = 64;  // rounds of one block in one sweep, at most
 enum DrainRule : uint32_t { kDrainFill = 0, kDrainFlat = 1, kDrainAccumulate = 2 };
 // prepare: z, the initial X of the fill (z on outlets, 65535 on other active cells, 0 on void ones) in W, the counts of void cells and outlets
 bt_status launch_drain_prepare(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts);
-// one sweep of one rule: every block whose flag in `active` is set clears it, relaxes its cells in LDS (at most `rounds` rounds), writes back the cells
-// it changed and sets the flags of the blocks that have to look again in `activate`; *marked counts the blocks that set a flag
+// one sweep of one rule, as launch_path_relax
 bt_status launch_drain_relax(hipStream_t stream, DrainRule rule, const DrainPlanes& p, uint32_t rounds, uint32_t* active, uint32_t* activate, uint32_t* marked);
 // the seed of the flat relaxation from the final W: F = 0 on drain cells and void ones, 0xFFFFFFFF elsewhere
 bt_status launch_drain_flat_seed(hipStream_t stream, const DrainPlanes& p);

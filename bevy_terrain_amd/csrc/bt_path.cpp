@@ -2,20 +2,16 @@
 // include/bevy_terrain_amd.h).
 //
 // The field call checks its arguments, gathers the rectangle's texels on the device by the plan of bt_atlas_read_region, prepares the
-// planes, and then enqueues sweeps of the relaxation kernel in batches (4, 8, 16, then 32 at a time): after each batch the LAST sweep's count
-// of blocks that flagged work for the sweep after it comes back, and 0 ends the loop.  A sweep in which no block is flagged does nothing, so
-// sweeps past convergence cost a launch each and change nothing.  The result does not depend on the schedule (the header says why).
+// planes, flags the 3 x 3 blocks around every goal, and then runs the sweeps of the block relaxation to its fixed point (relax_sweeps,
+// bt_relax.hpp).  The result does not depend on the schedule (the header says why).
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
-#include "bt_internal.hpp"
+#include "bt_relax.hpp"
 
 using namespace bt;
 
 namespace {
-
-constexpr uint32_t kBatchFirst = 4, kBatchMax = 32;
 
 bt_status refuse(const char* fmt, const char* what) {
     set_error(fmt, what);
@@ -32,16 +28,6 @@ const char* bad_cost(const bt_path_cost& c) {
         if (!std::isfinite(w) || !(w >= 0.0f)) return "a weight (finite and >= 0)";
     return nullptr;
 }
-
-// rounds of a block per sweep.  The profiling build (tools/, -DBT_DEBUG_HOOKS) takes it from BT_PATH_ROUNDS for tools/path_bench.py
-uint32_t path_rounds() {
-#ifdef BT_DEBUG_HOOKS
-    if (const char* v = getenv("BT_PATH_ROUNDS")) return uint32_t(std::min(std::max(atoi(v), 1), 4096));
-#endif
-    return kPathRounds;
-}
-
-uint64_t align256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
 
 }  // namespace
 
@@ -83,9 +69,7 @@ bt_status bt_atlas_path_field(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t 
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
     // the planes of the call, carved from one buffer
-    PathPlanes p{};
-    p.width = width, p.height = height;
-    p.blocks_x = (width + kPathBlock - 1u) / kPathBlock, p.blocks_y = (height + kPathBlock - 1u) / kPathBlock;
+    PathPlanes p{RelaxGrid::of(width, height)};
     const uint64_t blocks = uint64_t(p.blocks_x) * p.blocks_y;
     uint64_t at_raw = 0, at_mask = at_raw + align256(cells * 2u), at_h = at_mask + (blocked_host ? align256(cells) : 0u), at_d = at_h + align256(cells * 4u),
              at_next = at_d + align256(cells * 4u), at_flags = at_next + align256(cells), total = at_flags + align256(2u * blocks * 4u);
@@ -119,18 +103,11 @@ bt_status bt_atlas_path_field(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t 
     launches++;
 
     const float cell_diag = cost->cell_size * 1.41421356f;
-    const uint32_t rounds = path_rounds();
+    const uint32_t rounds = relax_rounds("BT_PATH_ROUNDS");
     uint32_t sweeps = 0;
     bool converged = false;
-    for (uint32_t batch = kBatchFirst; !converged && sweeps < cells; batch = std::min(2u * batch, kBatchMax)) {
-        const uint32_t n = uint32_t(std::min<uint64_t>(batch, cells - sweeps));
-        BT_HIP(hipMemsetAsync(sweep_marked, 0, n * 4u, stream));
-        for (uint32_t i = 0; i < n; i++, sweeps++)
-            if (bt_status s = launch_path_relax(stream, p, *cost, cell_diag, rounds, flags[sweeps & 1u], flags[(sweeps + 1u) & 1u], sweep_marked + i)) return s;
-        BT_HIP(hipMemcpyAsync((void*)sweep_marked_host, sweep_marked + (n - 1u), 4u, hipMemcpyDeviceToHost, stream));
-        BT_HIP(hipStreamSynchronize(stream));
-        converged = sweep_marked_host[0] == 0u;
-    }
+    auto sweep = [&](uint32_t* active, uint32_t* activate, uint32_t* marked) { return launch_path_relax(stream, p, *cost, cell_diag, rounds, active, activate, marked); };
+    if (bt_status s = relax_sweeps(stream, cells, flags, sweep_marked, sweep_marked_host, sweep, &sweeps, &converged)) return s;
     launches += sweeps;
     if (!converged) {
         set_error("bt_atlas_path_field: no fixed point after %u sweeps of %llu cells", sweeps, (unsigned long long)cells);
@@ -164,7 +141,6 @@ bt_status bt_path_trace(const uint8_t* next, uint32_t width, uint32_t height, ui
         set_error("bt_path_trace: %s", !next ? "NULL next" : !status_out ? "NULL status_out" : cap && !out_xy ? "NULL out_xy with cap > 0" : "an empty window or a start outside it");
         return BT_ERR_INVALID_ARGUMENT;
     }
-    static const int dx[8] = {1, 1, 0, -1, -1, -1, 0, 1}, dy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
     const uint64_t cells = uint64_t(width) * height;
     uint32_t x = start_x, y = start_y, status = BT_PATH_TRACE_LOOP;
     uint64_t count = 0;
@@ -181,7 +157,7 @@ bt_status bt_path_trace(const uint8_t* next, uint32_t width, uint32_t height, ui
             break;
         }
         if (n > 7u || step == cells) break;  // a byte that is no direction; or width * height steps without a goal
-        const int64_t nx = int64_t(x) + dx[n], ny = int64_t(y) + dy[n];
+        const int64_t nx = int64_t(x) + neighbour_dx(n), ny = int64_t(y) + neighbour_dy(n);
         if (nx < 0 || ny < 0 || nx >= int64_t(width) || ny >= int64_t(height)) break;  // points outside the window
         x = uint32_t(nx), y = uint32_t(ny);
     }

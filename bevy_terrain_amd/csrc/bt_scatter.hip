@@ -349,8 +349,6 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_emit_kernel(ScatterPa
     }
 }
 
-uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
-
 }  // namespace
 
 bt_status scatter_run(bt_ctx* ctx, const ScatterJob& job, const std::vector<ScatterTile>& tiles, bt_scatter_instance* out, uint64_t cap, uint64_t* out_first,

@@ -70,8 +70,6 @@ bt_status staged_batch(const char* who, bt_tile_tree* t, const char* in_name, co
     return BT_OK;
 }
 
-uint64_t pad256(uint64_t v) { return (v + 255u) & ~255ull; }
-
 // a plane of results in scratch and where the caller wants it (host NULL: not wanted)
 struct Plane {
     void* host;
@@ -230,9 +228,9 @@ bt_status render(const char* who, bool shadowed, bt_tile_tree* t, bt_atlas* a, u
     bt_ctx* ctx = t->ctx;
     BT_HIP(hipSetDevice(ctx->device));
     // the scratch: the counters, then the planes that were asked for, each from a 256-byte boundary (the shadow plane last)
-    const uint64_t t_off = 256u, n_off = t_off + (out_t ? pad256(8u * pixels) : 0u), c_off = n_off + (out_normal ? pad256(12u * pixels) : 0u),
-                   s_off = c_off + (out_rgba ? pad256(4u * pixels) : 0u), o_off = s_off + (out_status ? pad256(pixels) : 0u),
-                   need = o_off + (out_shadow ? pad256(pixels) : 0u);
+    const uint64_t t_off = 256u, n_off = t_off + (out_t ? align256(8u * pixels) : 0u), c_off = n_off + (out_normal ? align256(12u * pixels) : 0u),
+                   s_off = c_off + (out_rgba ? align256(4u * pixels) : 0u), o_off = s_off + (out_status ? align256(pixels) : 0u),
+                   need = o_off + (out_shadow ? align256(pixels) : 0u);
     if (bt_status st = ctx->render.reserve(ctx, need)) return st;
     uint8_t* dev = (uint8_t*)ctx->render.dev;
     RenderArgs args{};
@@ -293,8 +291,8 @@ bt_status bt_tile_tree_sun_occlusion(bt_tile_tree* t, bt_atlas* a, uint32_t ai, 
     BT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // the scratch (the ray queries': bt_ctx::raycast): the counters, the points, the directions, the statuses, each from a 256-byte boundary
-    const uint64_t p_bytes = 24ull * count, d_bytes = 24ull * direction_count, p_off = 256u, d_off = p_off + pad256(p_bytes), s_off = d_off + pad256(d_bytes);
-    if (bt_status st = ctx->raycast.reserve(ctx, s_off + pad256(rays))) return st;
+    const uint64_t p_bytes = 24ull * count, d_bytes = 24ull * direction_count, p_off = 256u, d_off = p_off + align256(p_bytes), s_off = d_off + align256(d_bytes);
+    if (bt_status st = ctx->raycast.reserve(ctx, s_off + align256(rays))) return st;
     uint8_t* dev = (uint8_t*)ctx->raycast.dev;
     BT_HIP(hipMemcpyAsync(dev + p_off, positions, p_bytes, hipMemcpyHostToDevice, s));
     BT_HIP(hipMemcpyAsync(dev + d_off, directions, d_bytes, hipMemcpyHostToDevice, s));

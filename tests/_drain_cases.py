@@ -15,7 +15,7 @@ import _drain_model as M
 import _paint_model as PM
 import _splat_cases as SC
 
-ROUNDS = 64  # kDrainRounds: rounds of one block in one sweep, at most
+ROUNDS = 64  # kRelaxRounds: rounds of one block in one sweep, at most
 BLOCK = 32
 
 

@@ -61,10 +61,10 @@ def summarise(path, calls):
         name = r["Kernel_Name"]
         if "drain_prepare_kernel" in name:
             groups.append({k: [0.0, 0] for k in KERNELS})
-        if not groups or "drain_" not in name:
+        if not groups:
             continue
         for k in KERNELS:
-            if k in name:
+            if k in name and (k.startswith("drain_") or "relax_kernel" in name):  # the rules: relax_kernel<Rule> of bt_relax.hpp
                 groups[-1][k][0] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
                 groups[-1][k][1] += 1
     assert len(groups) == calls, (len(groups), calls)
@@ -93,7 +93,7 @@ def report(args):
              f"{'kernel':38s}  ms per call  dispatches"]
     for k in KERNELS:
         ms, n = trace.get(k, [float("nan"), 0])
-        name = k if k.startswith("drain_") else "drain_relax_kernel<" + k + ">"
+        name = k if k.startswith("drain_") else "relax_kernel<" + k + ">"
         lines.append(f"{name:38s}  {ms:11.3f}  {n:10d}")
     for note in args.note or []:
         lines += [""] + note.split("\\n")

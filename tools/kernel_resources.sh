@@ -7,9 +7,9 @@
 #                                                               tools/kernel_resources.sh splat bt_splat.hip   (edit_splat_kernel)
 #                                                               tools/kernel_resources.sh scatter bt_scatter.hip   (scatter_decide_kernel, scatter_scan_kernel, scatter_emit_kernel)
 #                                                               tools/kernel_resources.sh collide bt_collide.hip   (collide_kernel; `sweep` for sweep_kernel)
-#                                                               tools/kernel_resources.sh path bt_path.hip   (path_prepare_kernel, path_relax_kernel, path_next_kernel)
+#                                                               tools/kernel_resources.sh path bt_path.hip   (path_prepare_kernel, path_next_kernel; `relax` for relax_kernel<PathRule> of bt_relax.hpp)
 #                                                               tools/kernel_resources.sh erode bt_erode.hip   (erode_init_kernel, erode_step_kernel, erode_finish_kernel)
-#                                                               tools/kernel_resources.sh drain bt_drain.hip   (drain_prepare_kernel, drain_relax_kernel x 3 rules, drain_flat_seed_kernel, drain_direction_kernel, drain_finish_kernel)
+#                                                               tools/kernel_resources.sh drain bt_drain.hip   (drain_prepare_kernel, drain_flat_seed_kernel, drain_direction_kernel, drain_finish_kernel; `relax` for relax_kernel<FillRule / FlatRule / AccumulateRule>)
 R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/bevy_terrain_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I../../include -I. -S --cuda-device-only -o /tmp/bt_fused_gfx950.s "${2:-bt_fused.hip}" 2>/dev/null

@@ -79,10 +79,10 @@ def summarise(path, calls):
         name = r["Kernel_Name"]
         if "path_prepare_kernel" in name:
             groups.append({"relax_ms": 0.0, "relax_dispatches": 0, "prepare_ms": 0.0, "next_ms": 0.0})
-        if not groups or "path_" not in name:
+        if not groups:
             continue
         ms = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-        if "path_relax_kernel" in name:
+        if "relax_kernel" in name and "PathRule" in name:  # relax_kernel<PathRule> of bt_relax.hpp
             groups[-1]["relax_ms"] += ms
             groups[-1]["relax_dispatches"] += 1
         elif "path_prepare_kernel" in name:
