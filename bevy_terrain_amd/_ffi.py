@@ -313,6 +313,19 @@ class DrainageStatsC(C.Structure):
                 ("sweeps_flat", C.c_uint32), ("sweeps_accumulate", C.c_uint32), ("launches", C.c_uint32), ("_padding", C.c_uint32 * 3)]
 
 
+VIEWSHED_NONE, VIEWSHED_MAX_OBSERVERS, VIEWSHED_MAX_SIDE, VIEWSHED_MAX_CELLS = 0xFFFFFFFF, 64, 32768, 1 << 22
+
+
+class ViewshedObserverC(C.Structure):
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("eye_height", C.c_uint32), ("radius", C.c_uint32)]
+
+
+class ViewshedStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("voids", C.c_uint32), ("tiles_missing", C.c_uint32), ("observers_used", C.c_uint32), ("observers_skipped", C.c_uint32),
+                ("covered", C.c_uint32), ("visible", C.c_uint32), ("max_clearance", C.c_uint32), ("samples", C.c_uint64), ("launches", C.c_uint32),
+                ("_padding", C.c_uint32 * 5)]
+
+
 class ErosionStatsC(C.Structure):
     _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
 
@@ -399,6 +412,8 @@ PROTOTYPES = {
                                      _P(TileCoordinateC), _u32, _P(ErosionStatsC)]),
     "bt_atlas_drainage": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(C.c_uint8), _P(C.c_uint8), _P(C.c_uint16), _P(_u32), _P(C.c_uint8), _P(_u32),
                                  _P(DrainageStatsC)]),
+    "bt_atlas_viewshed": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ViewshedObserverC), _u32, _u32, _P(_u32), _P(C.c_uint8), _P(C.c_uint64),
+                                 _P(ViewshedStatsC)]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

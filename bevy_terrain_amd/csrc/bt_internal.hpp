@@ -264,7 +264,12 @@ struct bt_ctx {
     // bt_atlas_drainage: the planes of one call on the device (raw texels, the two host masks, z, W, F, the directions, A, the block flags);
     // and its words with a pinned twin (the per-sweep counters of a batch, the counts of bt_drainage_stats)
     bt::Scratch drain, drain_words;
-    std::array<bt::Scratch*, 11> scratch() { return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode, &drain, &drain_words}; }  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_viewshed: the planes of one call on the device (raw texels, their transpose, the clearance, the count, the mask); and the
+    // counts of bt_viewshed_stats with a pinned twin
+    bt::Scratch viewshed, viewshed_words;
+    std::array<bt::Scratch*, 13> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+        return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode, &drain, &drain_words, &viewshed, &viewshed_words};
+    }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
 };
@@ -566,6 +571,29 @@ bt_status launch_drain_flat_seed(hipStream_t stream, const DrainPlanes& p);
 bt_status launch_drain_direction(hipStream_t stream, const DrainPlanes& p);
 // the counts that need the final planes: filled, flats, the two maxima and the outflow
 bt_status launch_drain_finish(hipStream_t stream, const DrainPlanes& p, DrainCounts* counts);
+
+// bt_viewshed.hip: the kernels of bt_atlas_viewshed.  Planes are width x height, row-major
+struct ViewshedPlanes {
+    uint32_t width, height;
+    const uint16_t* raw;      // the gathered texels: 0 = void
+    uint16_t* transposed;     // raw with the axes exchanged: cell (x, y) at x * height + y
+    uint32_t* clearance;      // BT_VIEWSHED_NONE on void cells and on cells no used observer covers
+    uint8_t* count;
+    uint64_t* mask;           // or nullptr: not asked for
+    uint32_t target_height;
+    uint32_t observer_count;
+    bt_viewshed_observer observers[BT_VIEWSHED_MAX_OBSERVERS];  // in the kernel arguments: every wave reads them as scalars
+};
+struct ViewshedCounts {  // the device words of bt_viewshed_stats
+    uint32_t voids, observers_used, observers_skipped, covered, visible, max_clearance;
+    unsigned long long samples;
+};
+// raw -> transposed
+bt_status launch_viewshed_transpose(hipStream_t stream, const ViewshedPlanes& p);
+// the line walk: the three output planes, in two launches (the x-major lines on the transposed plane, then the y-major ones)
+bt_status launch_viewshed_walk(hipStream_t stream, const ViewshedPlanes& p);
+// the counts
+bt_status launch_viewshed_finish(hipStream_t stream, const ViewshedPlanes& p, ViewshedCounts* counts);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

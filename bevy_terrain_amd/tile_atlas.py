@@ -661,6 +661,26 @@ class TileAtlas:
             *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, types)], C.byref(stats)))
         return (*outs, {name: getattr(stats, name) for name, _ in _ffi.DrainageStatsC._fields_ if name != "_padding"})
 
+    def viewshed(self, attachment_index: int, x0: int, y0: int, w: int, h: int, observers, target_height: int = 0, lod: Optional[int] = None, side: int = 0,
+                 clearance: bool = True, count: bool = True, mask: bool = False):
+        """bt_atlas_viewshed: what `observers` see of the w x h window of centre texels at mosaic position (x0, y0) of `lod` on `side` of an
+        R16 attachment, by the header's VIEWSHED section, in integers.  observers: an (N, 4) integer array or a list of (x, y, eye_height,
+        radius) (shorter tuples: eye_height 0, radius 0 = unlimited), in cells of the window, 64 at most; one on a cell without data is
+        skipped.  Returns (clearance, count, mask, stats): clearance (h, w) uint32, the smallest whole height above the ground of the cell
+        that any observer covering it sees (VIEWSHED_NONE: no data, or no observer covers it); count (h, w) uint8, the observers that see a
+        target of `target_height` on the cell; mask (h, w) uint64, bit o set for exactly those observers; stats: bt_viewshed_stats as a
+        dict.  clearance / count / mask False: that plane is not copied out and None comes back in its place.  All planes are exact.
+        Ordered behind the queued work; synchronous; a read."""
+        lod = self.lod_count - 1 if lod is None else lod
+        rows = [tuple(int(v) for v in o) for o in (observers.tolist() if isinstance(observers, np.ndarray) else observers)]
+        arr = (_ffi.ViewshedObserverC * max(len(rows), 1))(*[_ffi.ViewshedObserverC(*(o + (0, 0))[:4]) for o in rows])
+        outs = [np.zeros((h, w), dtype=t) if want else None for t, want in ((np.uint32, clearance), (np.uint8, count), (np.uint64, mask))]
+        types = (C.c_uint32, C.c_uint8, C.c_uint64)
+        stats = _ffi.ViewshedStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_viewshed(self._h, attachment_index, side, lod, x0, y0, w, h, arr, len(rows), target_height,
+                                                *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, types)], C.byref(stats)))
+        return (*outs, {name: getattr(stats, name) for name, _ in _ffi.ViewshedStatsC._fields_ if name != "_padding"})
+
     def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
                      water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the

@@ -1799,6 +1799,68 @@ bt_status bt_atlas_drainage(bt_atlas* atlas, uint32_t attachment_index, uint32_t
                             uint32_t* flat_out /* may be NULL */, uint8_t* direction_out /* may be NULL */,
                             uint32_t* accumulation_out /* may be NULL */, bt_drainage_stats* stats /* may be NULL */);
 
+/* ---------------- viewshed: what a set of observers can see of a rectangle of heights
+ * VIEWSHED (bt_atlas_viewshed; R16 only).  Integers throughout: no float appears, so every plane is a function of the input byte for byte.
+ * The ground is flat: the curvature of the earth and refraction are out of scope.
+ * Window: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of an R16 attachment (the rectangle of
+ * bt_atlas_read_region).  Cell (x, y) is mosaic texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index i = y * width + x.
+ * Cells.  raw = the centre texel.  The cell is VOID when raw == 0 (no data) or when its tile is one the atlas does not hold (such texels
+ * read as 0; the tiles are counted in tiles_missing).  Every other cell is ACTIVE with the height z = raw, the integer.  On a sight line a
+ * void cell is ground of height 0.
+ * Observers: up to BT_VIEWSHED_MAX_OBSERVERS of bt_viewshed_observer {x, y, eye_height, radius}, in cells of the window.  The eye is at
+ * E = z(O) + eye_height.  radius == 0: unlimited; otherwise the observer COVERS the cells with dx^2 + dy^2 <= radius^2 (in 64 bits).  An
+ * observer on a void cell is SKIPPED and counted (the path field's rule for goals on blocked cells); every other one is USED.  Two
+ * observers on one cell are two observers.
+ * The line from O to a target T: dx = tx - ox, dy = ty - oy, n = max(|dx|, |dy|).  Its n - 1 interior points are P_j = O + (dx, dy) j / n,
+ * j = 1..n-1.  On the major axis (x when |dx| >= |dy|; on an exact diagonal either, with the same result) the coordinate of P_j is an
+ * integer.  On the minor axis it is o + m j / n with m the signed minor difference: q = floor(m j / n), the true floor, towards minus
+ * infinity, and r = m j - q n in [0, n).  The ground at P_j is the linear interpolation of the cells at minor positions o + q and
+ * o + q + 1, kept as a numerator over n:  G_j = z_a (n - r) + z_b r  (z_b is not read when r == 0).  With this floor the line from T to
+ * O meets the same points with the same weights, so two cells see each other or neither does when eye and target heights are equal.
+ * Clearance.  S_j = G_j - E n.  The line of sight to a target top at height Z passes P_j iff (Z - E) j >= S_j: grazing counts as seen.  So
+ * Z - E >= M = max_j ceil(S_j / j), the ceiling of the signed rational towards plus infinity (found as the largest rational by
+ * cross-multiplication, with one division at the end: the ceiling is monotone).  C_o(T) = max(0, E + M - z(T)), and 0 when n <= 1: the
+ * smallest whole height above the ground at T that observer o sees.  It does not depend on target_height.
+ * Bounds: width, height <= BT_VIEWSHED_MAX_SIDE; width * height <= BT_VIEWSHED_MAX_CELLS; eye_height, target_height <= 65535.  Hence
+ * G_j < 2^31, E n < 2^32, |S_j| < 2^32, every cross product < 2^48, and C < 2^31 + 2^17: nothing saturates.
+ * Outputs, each may be NULL, row-major.  clearance_out (u32): the minimum of C_o over the used observers that cover the cell;
+ * BT_VIEWSHED_NONE on a void cell and on a cell no used observer covers.  count_out (u8): the number of used, covering observers with
+ * C_o <= target_height; 0 on void cells.  mask_out (u64): bit o set for exactly those observers, o the index in the caller's array.
+ * bt_viewshed_stats: every field but launches is a function of the input.
+ * The call: synchronous, host arrays in and out, ordered behind the work queued on the context's stream; a read: no layer is marked
+ * written.  Launches: the gather of bt_atlas_read_region (counted as one); one that transposes the texels; the line walk in two, the
+ * x-major lines on the transposed texels and then the y-major ones, a wave to 64 consecutive targets along the minor axis, the observers
+ * looped inside it (no atomic: no result depends on a schedule); one finish launch for the counts: launches = 5.  The scratch, 9 bytes
+ * per cell and 8 more when the mask is asked for, stays in the context until bt_ctx_trim.
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL observers; observer_count 0 or above
+ * BT_VIEWSHED_MAX_OBSERVERS; an eye_height or target_height above 65535; a side above BT_VIEWSHED_MAX_SIDE; width * height above
+ * BT_VIEWSHED_MAX_CELLS; an observer outside the window.  BT_ERR_UNSUPPORTED: a non-R16 attachment, an odd centre size.  width == 0 or
+ * height == 0 (with valid arguments otherwise; no observer can lie in such a window, and none is looked at): BT_OK, nothing touched. */
+#define BT_VIEWSHED_NONE 0xFFFFFFFFu
+#define BT_VIEWSHED_MAX_OBSERVERS 64u
+#define BT_VIEWSHED_MAX_SIDE 32768u
+#define BT_VIEWSHED_MAX_CELLS (1u << 22)
+typedef struct bt_viewshed_observer {
+    uint32_t x, y;        /* the cell, in the window */
+    uint32_t eye_height;  /* above the ground at the cell, <= 65535 */
+    uint32_t radius;      /* in cells; 0 = unlimited */
+} bt_viewshed_observer; /* 16 bytes */
+typedef struct bt_viewshed_stats {
+    uint32_t cells, voids;                           /* width * height; void cells */
+    uint32_t tiles_missing;                          /* tiles of the rectangle the atlas does not hold */
+    uint32_t observers_used, observers_skipped;      /* on active cells; on void ones */
+    uint32_t covered, visible;                       /* active cells at least one used observer covers; cells with count > 0 */
+    uint32_t max_clearance;                          /* the largest clearance that is not BT_VIEWSHED_NONE (0: there is none) */
+    uint64_t samples;                                /* the sum of max(n - 1, 0) over the (used observer, covered active cell) pairs */
+    uint32_t launches;                               /* all kernel launches of the call, the gather counted as one */
+    uint32_t _padding[5];
+} bt_viewshed_stats; /* 64 bytes */
+bt_status bt_atlas_viewshed(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                            uint32_t width, uint32_t height, const bt_viewshed_observer* observers, uint32_t observer_count,
+                            uint32_t target_height, uint32_t* clearance_out /* may be NULL */, uint8_t* count_out /* may be NULL */,
+                            uint64_t* mask_out /* may be NULL */, bt_viewshed_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
