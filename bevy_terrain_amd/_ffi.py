@@ -326,6 +326,26 @@ class ViewshedStatsC(C.Structure):
                 ("_padding", C.c_uint32 * 5)]
 
 
+DISTANCE_NONE, DISTANCE_MAX_SIDE, DISTANCE_MAX_CELLS, DISTANCE_BAND = 0xFFFFFFFF, 8192, 1 << 22, 32
+DISTANCE_FROM_TEXELS, DISTANCE_INVERT, DISTANCE_BAKE_NEAR = 1, 2, 1
+# bt_distance.hip: the threads of a workgroup (columns of a group of the column phase, the stride of a row's cells in the row phase) and the
+# cells of a workgroup of the finish launch (kDistanceThreads, kDistanceThreads * kFinishCells); tests place windows around them
+DISTANCE_THREADS, DISTANCE_FINISH_CELLS = 256, 1024
+
+
+class DistanceSeedsC(C.Structure):
+    _fields_ = [("channel", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DistanceBakeC(C.Structure):
+    _fields_ = [("attachment", C.c_uint32), ("channel", C.c_uint32), ("reach", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DistanceStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("seeds", C.c_uint32), ("tiles_missing", C.c_uint32), ("max_dist2", C.c_uint32), ("sum_dist2", C.c_uint64),
+                ("launches", C.c_uint32), ("_padding", C.c_uint32), ("edit", EditStatsC)]
+
+
 class ErosionStatsC(C.Structure):
     _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
 
@@ -414,6 +434,8 @@ PROTOTYPES = {
                                  _P(DrainageStatsC)]),
     "bt_atlas_viewshed": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ViewshedObserverC), _u32, _u32, _P(_u32), _P(C.c_uint8), _P(C.c_uint64),
                                  _P(ViewshedStatsC)]),
+    "bt_atlas_distance_field": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(DistanceSeedsC), _P(C.c_uint8), _P(_u32), _P(_u32), _P(DistanceBakeC),
+                                       _P(TileCoordinateC), _u32, _P(DistanceStatsC)]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

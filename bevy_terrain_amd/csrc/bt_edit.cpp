@@ -934,6 +934,124 @@ bt_status bt_atlas_erode_height(bt_atlas* a, uint32_t ai, uint32_t side, uint32_
     return rc ? rc : drained;
 }
 
+// The host half of the DISTANCE section of the header (the kernels: bt_distance.hip).  It lives here for the bake, which is the device-side
+// write-back of bt_atlas_erode_height: the merged rectangle in ctx->edit_region and a region first step without host texels.
+bt_status bt_atlas_distance_field(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                  const bt_distance_seeds* seeds, const uint8_t* seed_host, uint32_t* dist2_out, uint32_t* nearest_out, const bt_distance_bake* bake,
+                                  bt_tile_coordinate* changed, uint32_t changed_cap, bt_distance_stats* stats) {
+    const char* who = "bt_atlas_distance_field";
+    if (stats) *stats = bt_distance_stats{};
+    if (!a || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", who, !a ? "atlas" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, who)) return s;
+    const Attachment& at = a->attachments[ai];
+    const bool wide = at.meta.format == BT_FORMAT_RGBA8;
+    if (!seeds) {
+        set_error("%s: NULL seeds", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool from_texels = (seeds->flags & BT_DISTANCE_FROM_TEXELS) != 0u;
+    const uint32_t top = wide ? 255u : 65535u;
+    const char* bad = (seeds->flags & ~uint32_t(BT_DISTANCE_FROM_TEXELS | BT_DISTANCE_INVERT)) ? "unknown flag bits"
+                      : !from_texels && !seed_host                                            ? "neither BT_DISTANCE_FROM_TEXELS nor seed_host"
+                      : seeds->channel > (wide ? 3u : 0u)                                     ? "channel (0..3 on Rgba8, 0 on R16)"
+                      : seeds->hi > top                                                       ? "hi above the largest texel value"
+                      : from_texels && seeds->lo > seeds->hi                                  ? "lo > hi"
+                                                                                              : nullptr;
+    if (bad) {
+        set_error("%s: seeds: %s (channel %u, lo %u, hi %u, flags %#x)", who, bad, seeds->channel, seeds->lo, seeds->hi, seeds->flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (width > BT_DISTANCE_MAX_SIDE || height > BT_DISTANCE_MAX_SIDE) {
+        set_error("%s: a side of %u x %u above %u", who, width, height, BT_DISTANCE_MAX_SIDE);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t cells = uint64_t(width) * height;
+    if (cells > BT_DISTANCE_MAX_CELLS) {
+        set_error("%s: %u x %u cells, at most %u", who, width, height, BT_DISTANCE_MAX_CELLS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bake) {
+        const char* bad_bake = bake->attachment >= a->attachments.size()               ? "attachment out of range"
+                               : bake->channel > 3u                                    ? "channel (0..3)"
+                               : bake->reach == 0u || bake->reach > 65535u             ? "reach (1..65535)"
+                               : (bake->flags & ~uint32_t(BT_DISTANCE_BAKE_NEAR)) != 0u ? "unknown flag bits"
+                                                                                       : nullptr;
+        if (bad_bake) {
+            set_error("%s: bake: %s (attachment %u, channel %u, reach %u, flags %#x)", who, bad_bake, bake->attachment, bake->channel, bake->reach, bake->flags);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        const AttachmentMeta& dm = a->attachments[bake->attachment].meta;
+        if (dm.format != BT_FORMAT_RGBA8 || dm.texture_size != at.meta.texture_size || dm.border_size != at.meta.border_size) {
+            set_error("%s: bake: attachment %u (format %u, texture_size %u, border_size %u): an Rgba8 attachment of the source's texture_size %u and border_size %u", who,
+                      bake->attachment, dm.format, dm.texture_size, dm.border_size, at.meta.texture_size, at.meta.border_size);
+            return BT_ERR_UNSUPPORTED;
+        }
+    }
+    if (!cells) return BT_OK;  // an empty window: nothing to do
+
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    DistancePlanes p{};
+    p.width = width, p.height = height, p.bands = (height + kDistanceBand - 1u) / kDistanceBand;
+    // the planes of the call, carved from one buffer
+    const uint64_t summary = align256(uint64_t(p.bands) * width * 2u);
+    const uint64_t at_raw = 0, at_host = at_raw + align256(cells * at.meta.pixel_size), at_first = at_host + (seed_host ? align256(cells) : 0u), at_last = at_first + summary,
+                   at_r = at_last + summary, at_dist2 = at_r + align256(cells * 2u), at_nearest = at_dist2 + align256(cells * 4u), total = at_nearest + align256(cells * 4u);
+    if (bt_status s = ctx->distance.reserve(ctx, total)) return s;
+    if (bt_status s = ctx->distance_words.reserve(ctx, 256, true)) return s;
+    if (bake)
+        if (bt_status s = ctx->edit_region.reserve(ctx, cells * 4u)) return s;
+    uint8_t* base = (uint8_t*)ctx->distance.dev;
+    p.raw = base + at_raw;
+    p.host = seed_host ? base + at_host : nullptr;
+    p.wide = wide, p.shift = 8u * seeds->channel, p.value_mask = top;
+    p.lo = from_texels ? seeds->lo : 1u, p.hi = from_texels ? seeds->hi : 0u;
+    p.invert = (seeds->flags & BT_DISTANCE_INVERT) != 0u;
+    p.first = (uint16_t*)(base + at_first), p.last = (uint16_t*)(base + at_last), p.r = (uint16_t*)(base + at_r);
+    p.dist2 = (uint32_t*)(base + at_dist2), p.nearest = (uint32_t*)(base + at_nearest);
+    DistanceBake merge{};
+    if (bake) merge.texels = (uint32_t*)ctx->edit_region.dev, merge.shift = 8u * bake->channel, merge.near = bake->flags & BT_DISTANCE_BAKE_NEAR, merge.reach2 = uint64_t(bake->reach) * bake->reach;
+    DistanceCounts* counts = (DistanceCounts*)ctx->distance_words.dev;
+    const DistanceCounts* counts_host = (const DistanceCounts*)ctx->distance_words.host;
+
+    uint32_t tiles_missing = 0;
+    if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, base + at_raw, &tiles_missing)) return s;
+    if (seed_host)
+        if (bt_status s = region_stage_in(ctx, base + at_host, seed_host, width, width, height)) return s;
+    if (bake)
+        if (bt_status s = region_gather(a, bake->attachment, side, lod, x0, y0, width, height, ctx->edit_region.dev, nullptr)) return s;
+    BT_HIP(hipMemsetAsync(counts, 0, sizeof(DistanceCounts), stream));
+    if (bt_status s = launch_distance_columns(stream, p)) return s;
+    if (bt_status s = launch_distance_rows(stream, p)) return s;
+    if (bt_status s = launch_distance_finish(stream, p, merge, counts)) return s;
+    BT_HIP(hipMemcpyAsync((void*)counts_host, counts, sizeof(DistanceCounts), hipMemcpyDeviceToHost, stream));
+    const char* what = "bt_atlas_distance_field staging";
+    if (dist2_out)
+        if (bt_status s = region_stage_out(ctx, p.dist2, dist2_out, uint64_t(width) * 4u, uint64_t(width) * 4u, height, what)) return s;
+    if (nearest_out)
+        if (bt_status s = region_stage_out(ctx, p.nearest, nearest_out, uint64_t(width) * 4u, uint64_t(width) * 4u, height, what)) return s;
+    bt_edit_stats edit{};
+    bt_status rc = BT_OK;
+    if (bake) {
+        FirstStep first{FirstStep::kRegion};  // texels nullptr: the rectangle is on the device
+        first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
+        rc = edit_boxes(a, bake->attachment, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, &edit);
+    }
+    const bt_status drained = ctx->staging.drain();  // the staging copies of the seed plane
+    BT_HIP(hipStreamSynchronize(stream));
+    if (stats) {
+        stats->cells = uint32_t(cells), stats->seeds = counts_host->seeds, stats->tiles_missing = tiles_missing;
+        stats->max_dist2 = counts_host->max_dist2, stats->sum_dist2 = counts_host->sum_dist2;
+        stats->launches = bake ? 7u : 6u;  // the gather, the three of the column phase, the row phase, the finish; a bake's gather
+        stats->edit = edit;
+    }
+    return rc ? rc : drained;
+}
+
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {
     if (!a || !directory || (count && !coords)) {
         set_error("bt_atlas_save_tiles: NULL %s", !a ? "atlas" : !directory ? "directory" : "coords");

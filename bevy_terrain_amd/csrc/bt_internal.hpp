@@ -267,8 +267,12 @@ struct bt_ctx {
     // bt_atlas_viewshed: the planes of one call on the device (raw texels, their transpose, the clearance, the count, the mask); and the
     // counts of bt_viewshed_stats with a pinned twin
     bt::Scratch viewshed, viewshed_words;
-    std::array<bt::Scratch*, 13> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
-        return {&bounds, &raycast, &normal, &render, &edit_region, &path, &path_words, &scatter, &erode, &drain, &drain_words, &viewshed, &viewshed_words};
+    // bt_atlas_distance_field: the planes of one call on the device (raw texels, the host seed plane, the band summaries, r, dist2,
+    // nearest); and the counts of bt_distance_stats with a pinned twin
+    bt::Scratch distance, distance_words;
+    std::array<bt::Scratch*, 15> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+        return {&bounds,     &raycast, &normal,      &render,   &edit_region,    &path,     &path_words,    &scatter,
+                &erode,      &drain,   &drain_words, &viewshed, &viewshed_words, &distance, &distance_words};
     }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
@@ -594,6 +598,40 @@ bt_status launch_viewshed_transpose(hipStream_t stream, const ViewshedPlanes& p)
 bt_status launch_viewshed_walk(hipStream_t stream, const ViewshedPlanes& p);
 // the counts
 bt_status launch_viewshed_finish(hipStream_t stream, const ViewshedPlanes& p, ViewshedCounts* counts);
+
+// bt_distance.hip: the kernels of bt_atlas_distance_field.  Planes are width x height, row-major
+constexpr uint32_t kDistanceBand = BT_DISTANCE_BAND;  // rows of a band of the column phase: a band's seeds are the bits of one word
+struct DistancePlanes {
+    uint32_t width, height, bands;  // bands = ceil(height / kDistanceBand)
+    const void* raw;                // the gathered texels: u16 (R16) or u32 (Rgba8)
+    const uint8_t* host;            // the caller's seed plane on the device, or nullptr
+    uint32_t wide;                  // 1: Rgba8 texels
+    uint32_t shift;                 // of the texel to its channel: 8 * channel
+    uint32_t value_mask;            // 0xFFFF or 0xFF
+    uint32_t lo, hi;                // from_texels: lo <= v <= hi; a band no v lies in (lo 1, hi 0) without FROM_TEXELS
+    uint32_t invert;                // 0 or 1
+    uint16_t* first;                // bands x width: a band's first seed row per column, 0xFFFF = none; after the carry: the first seed row below the band
+    uint16_t* last;                 // its last seed row; after the carry: the last seed row above the band
+    uint16_t* r;                    // the row of the column's nearest seed, the upper on a tie; 0xFFFF = none
+    uint32_t* dist2;
+    uint32_t* nearest;
+};
+struct DistanceBake {  // the byte the finish launch merges into the staged rectangle
+    uint32_t* texels;  // the destination's Rgba8 texels on the device, or nullptr: no bake
+    uint32_t shift;    // 8 * channel
+    uint32_t near;     // 0 or 1: 255 - b
+    uint64_t reach2;   // reach * reach
+};
+struct DistanceCounts {  // the device words of bt_distance_stats
+    uint32_t seeds, max_dist2;
+    unsigned long long sum_dist2;
+};
+// the column phase in its three launches: the band summaries, the carry across the bands, r
+bt_status launch_distance_columns(hipStream_t stream, const DistancePlanes& p);
+// the row phase: dist2 and nearest
+bt_status launch_distance_rows(hipStream_t stream, const DistancePlanes& p);
+// the counts, and the baked byte
+bt_status launch_distance_finish(hipStream_t stream, const DistancePlanes& p, const DistanceBake& bake, DistanceCounts* counts);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

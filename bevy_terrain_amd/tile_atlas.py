@@ -681,6 +681,50 @@ class TileAtlas:
                                                 *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, types)], C.byref(stats)))
         return (*outs, {name: getattr(stats, name) for name, _ in _ffi.ViewshedStatsC._fields_ if name != "_padding"})
 
+    def distance_field(self, attachment_index: int, x0: int, y0: int, w: int, h: int, *, lo: Optional[int] = None, hi: Optional[int] = None, channel: int = 0,
+                       seeds: Optional[np.ndarray] = None, invert: bool = False, bake=None, lod: Optional[int] = None, side: int = 0,
+                       dist2: bool = True, nearest: bool = True):
+        """bt_atlas_distance_field: the exact Euclidean distance transform of the w x h window of centre texels at mosaic position (x0, y0)
+        of `lod` on `side` of an R16 or Rgba8 attachment, by the header's DISTANCE section, in integers.  A cell is a seed when its texel
+        value (the raw u16; byte `channel` of an Rgba8 texel) lies in [lo, hi] (either given: BT_DISTANCE_FROM_TEXELS; lo alone reaches up to
+        the format's largest value, hi alone down to 0), or when the optional (h, w) uint8 plane `seeds` is non-zero there; `invert`
+        exchanges seeds and the rest.  Returns (dist2,
+        nearest, stats): dist2 (h, w) uint32, the squared distance in cells to the nearest seed; nearest (h, w) uint32, the index
+        y * w + x of that seed, the smallest on a tie; both DISTANCE_NONE without a seed; stats: bt_distance_stats as a dict.  dist2 /
+        nearest False: that plane is not copied out and None comes back in its place.  bake: (attachment, channel, reach) or
+        (attachment, channel, reach, near) or a dict of those names: byte `channel` of that Rgba8 attachment becomes
+        min(255, floor(255 * distance / reach)) over the window, 255 minus that with `near`, and the atlas is updated as by write_region;
+        stats["edit"] is then its bt_edit_stats and stats["changed"] the changed tiles.  Ordered behind the queued work; synchronous; a
+        read without `bake`."""
+        lod = self.lod_count - 1 if lod is None else lod
+        flags = (_ffi.DISTANCE_INVERT if invert else 0) | (_ffi.DISTANCE_FROM_TEXELS if lo is not None or hi is not None else 0)
+        formats = self.config.attachments
+        top = 255 if attachment_index < len(formats) and formats[attachment_index].format == AttachmentFormat.Rgba8 else 65535
+        seeds_c = _ffi.DistanceSeedsC(channel, 0 if lo is None else lo, (top if flags & _ffi.DISTANCE_FROM_TEXELS else 0) if hi is None else hi, flags)
+        plane = None
+        if seeds is not None:
+            plane = np.ascontiguousarray(seeds, dtype=np.uint8)
+            if plane.shape != (h, w):
+                raise ValueError(f"distance_field: a seeds plane of shape {plane.shape} for a window of {(h, w)}")
+        bake_c = None
+        if bake is not None:
+            if isinstance(bake, dict):
+                bake = (bake["attachment"], bake["channel"], bake["reach"], bake.get("near", False))
+            bake = tuple(bake) + (False,) * (4 - len(bake))
+            bake_c = _ffi.DistanceBakeC(bake[0], bake[1], bake[2], _ffi.DISTANCE_BAKE_NEAR if bake[3] else 0)
+        outs = [np.zeros((h, w), dtype=np.uint32) if want else None for want in (dist2, nearest)]
+        cap = max(self.atlas_size, 1)
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.DistanceStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_distance_field(
+            self._h, attachment_index, side, lod, x0, y0, w, h, C.byref(seeds_c), plane.ctypes.data_as(C.POINTER(C.c_uint8)) if plane is not None else None,
+            *[o.ctypes.data_as(C.POINTER(C.c_uint32)) if o is not None else None for o in outs], C.byref(bake_c) if bake_c is not None else None, changed, cap,
+            C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.DistanceStatsC._fields_ if name not in ("edit", "_padding")}
+        out["edit"] = {name: getattr(stats.edit, name) for name, _ in _ffi.EditStatsC._fields_}
+        out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
+        return (*outs, out)
+
     def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
                      water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the

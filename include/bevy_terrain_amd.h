@@ -1861,6 +1861,86 @@ bt_status bt_atlas_viewshed(bt_atlas* atlas, uint32_t attachment_index, uint32_t
                             uint32_t target_height, uint32_t* clearance_out /* may be NULL */, uint8_t* count_out /* may be NULL */,
                             uint64_t* mask_out /* may be NULL */, bt_viewshed_stats* stats /* may be NULL */);
 
+/* ---------------- distance field: the exact squared distance to the nearest seed cell of a rectangle, and which seed it is
+ * DISTANCE (bt_atlas_distance_field; R16 and Rgba8).  Integers throughout: no float appears, so every plane is a function of the input byte
+ * for byte.  The field is purely geometric: there is no void class.
+ * Window: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of attachment attachment_index (the rectangle
+ * of bt_atlas_read_region; inside one face).  Cell (x, y) is mosaic texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index
+ * i = y * width + x.  Texels of tiles the atlas does not hold read as 0; the tiles are counted in tiles_missing.
+ * Seeds: bt_distance_seeds {channel, lo, hi, flags}.  v(c) = the raw u16 of an R16 texel (channel must be 0), byte `channel` (0..3) of an
+ * Rgba8 one.
+ *     from_texels(c) = (flags & BT_DISTANCE_FROM_TEXELS) && lo <= v(c) && v(c) <= hi
+ *     from_host(c)   = seed_host && seed_host[i] != 0                     (seed_host: an optional plane of width * height bytes)
+ *     seed(c)        = (from_texels(c) || from_host(c)) XOR ((flags & BT_DISTANCE_INVERT) != 0)
+ * So: a sea level is FROM_TEXELS with lo = 0, hi = the level; no-data and missing tiles are lo = hi = 0; rivers are a host plane made from
+ * bt_atlas_drainage's accumulation_out; INVERT gives the distance to the outside from within.
+ * Field.  S = the set of seed cells.  For every cell c = (x, y):
+ *     dist2(c)   = the minimum over s = (sx, sy) in S of (x - sx)^2 + (y - sy)^2                                    (u32)
+ *     nearest(c) = the smallest index sy * width + sx among the seeds that attain that minimum                      (u32)
+ * Both are BT_DISTANCE_NONE when S is empty.  A seed has dist2 = 0 and nearest = its own index.
+ * Bounds: width, height <= BT_DISTANCE_MAX_SIDE; width * height <= BT_DISTANCE_MAX_CELLS.  Hence dist2 < 2^27: nothing saturates.
+ * The separable reading, which an implementation may rely on.  Per column x, r(x, y) is the row of the seed of column x nearest to row y,
+ * the upper one (the smaller row) on a tie; none when the column holds no seed.  Then (dist2, nearest)(x, y) is the lexicographic minimum
+ * over the columns i that hold a seed of ((x - i)^2 + (y - r(i, y))^2, r(i, y), i): a seed of column i that attains the minimum is a
+ * nearest one of its column, and of two such seeds r is the one with the smaller index.
+ * Bake (optional): bt_distance_bake {attachment, channel, reach, flags} writes a proximity byte into channel `channel` of the Rgba8
+ * attachment `attachment` of the same atlas, over the same rectangle.
+ *     b(c) = min(255, isqrt64((uint64(dist2) * 65025) / (uint64(reach) * reach))),   isqrt64 = the floor square root;  255 when dist2 is NONE
+ * which is floor(255 * sqrt(dist2) / reach) capped at 255, exactly: the floor of the square root of a floor is the floor of the square
+ * root.  reach is 1..65535.  With BT_DISTANCE_BAKE_NEAR the byte is 255 - b: 255 on the seeds, 0 from `reach` on.  The other three bytes of
+ * every texel keep their values.  The write is an edit like any other: the destination rectangle is gathered, the byte merged on the
+ * device, and the texels written and the invariant F restored exactly as by bt_atlas_write_region of them over the rectangle: the same
+ * plan, the same `changed` order, the same bt_edit_stats (stats->edit).  The destination may be the source attachment (seed on one
+ * channel, bake another).  Without `bake` the call is a read: no layer is marked written, and `changed` is not written.
+ * Outputs: dist2_out, nearest_out (u32, width * height, row-major) and stats; each may be NULL.  bt_distance_stats: every field but
+ * launches is a function of the input.
+ * The call: synchronous, host arrays in and out through the context's staging ring, ordered behind the work queued on the context's
+ * stream.  Launches: the gather of bt_atlas_read_region (counted as one); the column phase in three: a lane to a column of a band of
+ * BT_DISTANCE_BAND rows notes the band's first and last seed row, a lane to a column carries them across the bands, and a lane to a column
+ * of a band writes r for its rows; the row phase: a workgroup to a row, that row of r in LDS, a lane to a cell searching outwards from its
+ * own column until dx^2 exceeds the best distance; one finish launch for the counts, which also merges the baked byte: launches = 6.  With
+ * a bake the gather of the destination is one more, launches = 7, and the launches of the edit follow in stats->edit.launches.  The count
+ * depends on the arguments only.  No result depends on a schedule.  The scratch stays in the context until bt_ctx_trim: 10 bytes per cell
+ * and the texel (2 or 4), 1 more with seed_host, 4 bytes per column and band, and with a bake the staged rectangle (4 per cell).
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL seeds; neither FROM_TEXELS nor seed_host; unknown flag
+ * bits; lo > hi with FROM_TEXELS; a channel above 3, or non-zero on R16; hi above 65535 on R16, above 255 on Rgba8; a side above
+ * BT_DISTANCE_MAX_SIDE; width * height above BT_DISTANCE_MAX_CELLS; NULL changed with changed_cap > 0; in a bake: an attachment out of
+ * range, a channel above 3, reach 0 or above 65535, unknown flag bits.  BT_ERR_UNSUPPORTED: an odd centre size; a bake destination that is
+ * not Rgba8, or whose texture_size or border_size differs from the source's.  width == 0 or height == 0 (with valid arguments otherwise;
+ * seed_host is not looked at): BT_OK, nothing touched. */
+#define BT_DISTANCE_NONE 0xFFFFFFFFu
+#define BT_DISTANCE_MAX_SIDE 8192u
+#define BT_DISTANCE_MAX_CELLS (1u << 22)
+#define BT_DISTANCE_BAND 32u
+enum { BT_DISTANCE_FROM_TEXELS = 1, BT_DISTANCE_INVERT = 2 }; /* bt_distance_seeds.flags */
+enum { BT_DISTANCE_BAKE_NEAR = 1 };                           /* bt_distance_bake.flags */
+typedef struct bt_distance_seeds {
+    uint32_t channel;  /* of an Rgba8 texel, 0..3; 0 on R16 */
+    uint32_t lo, hi;   /* the band of texel values that are seeds, both ends included (FROM_TEXELS) */
+    uint32_t flags;    /* BT_DISTANCE_FROM_TEXELS | BT_DISTANCE_INVERT */
+} bt_distance_seeds; /* 16 bytes */
+typedef struct bt_distance_bake {
+    uint32_t attachment;  /* the Rgba8 attachment that takes the byte */
+    uint32_t channel;     /* 0..3 */
+    uint32_t reach;       /* in cells, 1..65535: the distance at which b reaches 255 */
+    uint32_t flags;       /* BT_DISTANCE_BAKE_NEAR */
+} bt_distance_bake; /* 16 bytes */
+typedef struct bt_distance_stats {
+    uint32_t cells, seeds;      /* width * height; seed cells */
+    uint32_t tiles_missing;     /* tiles of the rectangle the source attachment does not hold */
+    uint32_t max_dist2;         /* the largest dist2 (0 when S is empty) */
+    uint64_t sum_dist2;         /* the sum of dist2 over the cells (0 when S is empty) */
+    uint32_t launches;          /* the kernel launches of the call before the edit's, the gathers counted as one each */
+    uint32_t _padding;
+    bt_edit_stats edit;         /* of the bake's write-back; zero without a bake */
+} bt_distance_stats; /* 64 bytes */
+bt_status bt_atlas_distance_field(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                  uint32_t width, uint32_t height, const bt_distance_seeds* seeds,
+                                  const uint8_t* seed_host /* may be NULL */, uint32_t* dist2_out /* may be NULL */,
+                                  uint32_t* nearest_out /* may be NULL */, const bt_distance_bake* bake /* may be NULL */,
+                                  bt_tile_coordinate* changed, uint32_t changed_cap, bt_distance_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
