@@ -79,16 +79,87 @@ def plateau(hole):
     return plant
 
 
-def serpentine(raw):
-    """32 x 32, one block: ridges of 60000, a level channel of 1000 one cell wide along the odd rows 1..29 (x = 1..30), joined alternately at
-    x = 30 and x = 1, inside a ring of ridge (the window's edge) whose one gap is (0, 1): some 460 cells to walk, seven times ROUNDS"""
-    z = np.full((32, 32), 60000, np.uint16)
-    for i, y in enumerate(range(1, 30, 2)):
-        z[y, 1:31] = 1000
-        if y + 1 < 30:
-            z[y + 1, 30 if i % 2 == 0 else 1] = 1000
-    z[1, 0] = 1000
-    return z
+def serpentine_channel(n):
+    """(n, n) bool: a channel one cell wide along the odd rows 1..n - 3 (x = 1..n - 2), joined alternately at x = n - 2 and x = 1.  Row 1 is
+    walked from the left; where n = 32 the last row, 29, is walked from the left too and ends at (30, 29)"""
+    c = np.zeros((n, n), bool)
+    for i, y in enumerate(range(1, n - 2, 2)):
+        c[y, 1:n - 1] = True
+        if y + 1 < n - 2:
+            c[y + 1, n - 2 if i % 2 == 0 else 1] = True
+    return c
+
+
+def banded_channel():
+    """(96, 96) bool, nine blocks: three bands, one per column of blocks (x = 1..30, 33..62, 65..94), each a serpentine over the odd rows
+    1..93 with rows of 30 cells; the first band is walked downwards from (1, 1), the second upwards, the third downwards again, joined by
+    (31..32, 93) and (63..64, 1).  4372 cells, 68 times ROUNDS; some 470 of them in every block, which the walk enters once, through an
+    edge: leftwards never, rightwards twice, downwards four times, upwards twice.  Rows as wide as the window would let a sweep that runs
+    its blocks one after the other carry the news through three blocks; rows of one block do not"""
+    c = np.zeros((96, 96), bool)
+    for band in range(3):
+        x0, x1 = 32 * band + 1, 32 * band + 30
+        rows = list(range(1, 94, 2))[::-1 if band % 2 else 1]
+        for i, y in enumerate(rows):
+            c[y, x0:x1 + 1] = True
+            if i + 1 < len(rows):
+                c[(y + rows[i + 1]) // 2, x1 if i % 2 == 0 else x0] = True
+        if band < 2:
+            c[rows[-1], x1 + 1:x1 + 3] = True
+    return c
+
+
+def serpentine(n):
+    """n x n: ridges of 60000, a level channel of 1000 inside a ring of ridge (the window's edge) whose one gap is (0, 1).  n = 32, one
+    block: serpentine_channel, some 460 cells to walk, seven times ROUNDS.  n = 96: banded_channel"""
+    def plant(raw):
+        c = serpentine_channel(n) if n == 32 else banded_channel()
+        c[1, 0] = True
+        return np.where(c, 1000, 60000).astype(np.uint16)
+    return plant
+
+
+# the bit a block sets for the neighbour block at (dx, dy), by name (tests/_relax_model.BITS)
+BIT_NAMES = {(-1, 0): "left", (1, 0): "right", (0, -1): "up", (0, 1): "down", (-1, -1): "up_left", (1, -1): "up_right", (-1, 1): "down_left", (1, 1): "down_right"}
+CROSSINGS = {  # name: (kind, mirrored in x, mirrored in y): the bit the serpentine's block sets when the news leaves it
+    "down_right": ("corner", False, False), "down_left": ("corner", True, False), "up_right": ("corner", False, True), "up_left": ("corner", True, True),
+    "right": ("right", False, False), "left": ("right", True, False), "down": ("down", False, False), "up": ("down", False, True),
+}
+
+
+def crossing_channel(bit, far_open=False):
+    """(64, 64) bool, four blocks: the serpentine of one block (serpentine_channel(32), more than 4 x ROUNDS cells) in block (0, 0), a tail
+    to the block's border, ONE step into the next block, and a straight channel there that ends one cell short of the window's edge, or on
+    it (far_open).  The channel is connected by cardinal steps but for the corner's one diagonal step.
+      corner: tail (30, 30), (31, 30), (31, 31); the step to (32, 32); then row 32: only a corner cell of block (0, 0) touches block (1, 1)
+      right:  tail (31, 29); the step to (32, 29); then row 29
+      down:   tail (30, 30), (30, 31); the step to (30, 32); then column 30
+    and mirrored in x and / or y for the other bits (the serpentine stays one of rows, which lanes walk in lockstep)"""
+    kind, mirror_x, mirror_y = CROSSINGS[bit]
+    c = np.zeros((64, 64), bool)
+    c[:32, :32] = serpentine_channel(32)
+    end = 64 if far_open else 63
+    if kind == "corner":
+        c[30, 30] = c[30, 31] = c[31, 31] = True
+        c[32, 32:end] = True
+    elif kind == "right":
+        c[29, 31:end] = True
+    else:
+        c[30:end, 30] = True
+    return c[::-1 if mirror_y else 1, ::-1 if mirror_x else 1]
+
+
+def crossing(bit, upstream):
+    """64 x 64: ridges of 60000 around crossing_channel(bit) at 1000.  upstream False: the one outlet of the channel is the gap beside the
+    serpentine's first cell, so the level and the flat distance walk the serpentine for more than four sweeps and then step into a block
+    that went quiet long before.  upstream True: the outlet is the far channel's end on the window's edge, so the sums walk that way"""
+    def plant(raw):
+        c = crossing_channel(bit, far_open=upstream).copy()
+        if not upstream:
+            _, mirror_x, mirror_y = CROSSINGS[bit]
+            c[62 if mirror_y else 1, 63 if mirror_x else 0] = True
+        return np.where(c, 1000, 60000).astype(np.uint16)
+    return plant
 
 
 # drops (cardinal a, diagonal b) of the centre of a 3 x 3: Pell pairs, b^2 - 2 a^2 = -1 or +1 by turns, so the scores 2 a^2 and b^2 differ by
@@ -131,7 +202,7 @@ SCENES = {
     "bowl_with_island_lake": Scene("planar_72", (70, 71, 70, 70), plant=bowl(True), reach={"lake_in_four_blocks", "spill_in_a_fifth", "two_lake_levels"}),
     "plateau": Scene("planar_72", (70, 71, 70, 70), plant=plateau(False), reach={"flat_34"}),
     "plateau_with_a_hole": Scene("planar_72", (70, 71, 70, 70), plant=plateau(True), reach={"outlet_inside"}),
-    "serpentine": Scene("planar_72", (75, 77, 32, 32), plant=serpentine, reach={"long_chain", "long_flat"}),
+    "serpentine": Scene("planar_72", (75, 77, 32, 32), plant=serpentine(32), reach={"long_chain", "long_flat"}),
     # void cells
     "random_void": Scene("planar_72", (70, 71, 50, 45), plant=random_void(0.3, 5), reach={"planted_zeros"}),
     "missing_tiles": Scene("partial", (0, 0, 48, 48), reach={"tiles_missing"}),
@@ -151,6 +222,16 @@ for _w in (31, 32, 33, 63, 64, 65):
         SCENES[f"w{_w}_h{_h}"] = Scene("planar_72", (3, 5, _w, _h))
         SCENES[f"w{_w}_h{_h}_quantised"] = Scene("planar_72", (3, 5, _w, _h), plant=quantised, reach={"big_flats"})
         SIZES += [f"w{_w}_h{_h}", f"w{_w}_h{_h}_quantised"]
+# the protocol of the block relaxation (tests/_relax_model.py, tests/test_relax_model.py): a crossing per flag bit, in both roles, and the
+# long walk into the host loop's steady batch
+CROSSING_SCENES = []  # every corner in both roles; of the edges those that no other scene already needs (test_relax_model.py names which does)
+for _bit, _roles in (("down_right", (False, True)), ("down_left", (False, True)), ("up_right", (False, True)), ("up_left", (False, True)), ("left", (False, True)),
+                     ("right", (True,)), ("up", (True,))):
+    for _upstream in _roles:
+        _name = f"crossing_{_bit}_upstream" if _upstream else f"crossing_{_bit}"
+        SCENES[_name] = Scene("planar_72", (70, 71, 64, 64), plant=crossing(_bit, _upstream), reach={"long_chain", "long_flat", ("late_sum_" if _upstream else "late_level_") + _bit})
+        CROSSING_SCENES.append(_name)
+SCENES["long_walk"] = Scene("planar_72", (151, 69, 96, 96), plant=serpentine(96), reach={"long_chain", "long_flat", "walk_of_56_sweeps"})
 SCORES = []
 for _i, (_a, _b) in enumerate(SCORE_PAIRS):
     SCENES[f"score_{_a}_{_b}"] = Scene("planar_b2", (19, 21, 5, 5), plant=score_window(_a, _b, _i % 4), reach={"scores_one_apart_or_past_32_bits"})
@@ -213,6 +294,16 @@ def scene_reaches(name):
     start = np.unravel_index(np.argmax(F), F.shape)
     out["long_flat"] = stats["max_flat_distance"] > 4 * ROUNDS
     out["long_chain"] = direction[start] != M.VOID and M.chain_length(direction, (int(start[1]), int(start[0]))) > 4 * ROUNDS
+    out["walk_of_56_sweeps"] = out["long_chain"] and min(stats["max_flat_distance"], M.chain_length(direction, (int(start[1]), int(start[0])))) > 56 * ROUNDS
+    # a step of the flow from one block into another, late: the level and the flat distance come UP the flow, out of the receiver's block
+    # (F counts the cells they walked), the sums go DOWN it, out of the donor's block (A counts at least the cells they were summed over)
+    for (x, y), (rx, ry) in M.receivers(direction).items():
+        step = (x // BLOCK - rx // BLOCK, y // BLOCK - ry // BLOCK)
+        if step != (0, 0) and W[y, x] == W[ry, rx]:
+            if F[y, x] > 4 * ROUNDS:
+                out["late_level_" + BIT_NAMES[step]] = True
+            if A[y, x] > 4 * ROUNDS and M.chain_length(direction, (x, y)) <= BLOCK + 2:
+                out["late_sum_" + BIT_NAMES[(-step[0], -step[1])]] = True
     inner = (h - 2) * (w - 2)
     out["one_outlet_takes_all"] = scene["weight"] is not None and stats["max_accumulation"] == 255 * (inner + 1) and bool((np.sort(A[direction == M.OUTLET])[:-1] == 255).all())
     if name.startswith("score_"):

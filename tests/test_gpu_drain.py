@@ -114,6 +114,25 @@ def test_serpentine_outlasts_the_round_limit(device, atlases):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", DC.CROSSING_SCENES)
+def test_a_late_crossing_wakes_a_block_that_went_quiet(device, atlases, name):
+    """more than 4 x 64 cells of serpentine lie between the outlet and the step into the next block (upstream: between the channel's
+    head and it), walked one cell a round along rows: the news crosses after the first batch of 4 sweeps, into a block that the one flag
+    bit of the scene's name wakes (tests/test_relax_model.py: without that bit the schedule model fails in every block order)"""
+    _, stats = check_scene(atlases(name), name)
+    assert stats["sweeps_fill"] > 4 and stats["sweeps_flat"] > 4 and stats["sweeps_accumulate"] > 4, stats  # each walks the serpentine, one way or the other
+
+
+@pytest.mark.gpu
+def test_long_walk_reaches_the_steady_batch(device, atlases):
+    """4372 cells in rows of 30, one cell a round and 64 rounds a sweep: 68 sweeps if no round ever carried the news further than a cell,
+    and only a row's end, where the walk changes rows and may change waves, can.  More than 4 + 8 + 16 = 28 sweeps means that batches of
+    kBatchMax = 32 ran, whose count comes back from the last of the 32 counters"""
+    _, stats = check_scene(atlases("long_walk"), "long_walk")
+    assert stats["sweeps_fill"] > 28 and stats["sweeps_flat"] > 28 and stats["sweeps_accumulate"] > 28, stats
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", DC.SCORES)
 def test_score_arithmetic(device, atlases, name):
     check_scene(atlases(name), name)

@@ -28,21 +28,25 @@ def device():
 
 @pytest.fixture(scope="module")
 def atlases(device):
-    """one device atlas per (spec, plants) of the scenes, made on first use"""
+    """one device atlas per (spec, planted walls) of the scenes, made on first use, and one per spec for the scenes that plant whole texels"""
     made = {}
 
     def get(name):
         scene = PC.SCENES[name]
-        key = (scene["spec"], name if scene["plants"] else None)
+        walls = [p for p in scene["plants"] if p[2].dtype == bool]
+        key = (scene["spec"], name if walls else "texels" if scene["plants"] else None)
+        x0, y0, _, _ = scene["rect"]
         if key not in made:
             atlas = device_atlas(device, scene["spec"])
-            x0, y0, _, _ = scene["rect"]
-            for x, y, walls in scene["plants"]:  # a wall is a no-data texel: the region is read, cut and written back
-                h, w = walls.shape
+            for x, y, wall in walls:  # a wall is a no-data texel: the region is read, cut and written back
+                h, w = wall.shape
                 part, _ = atlas.read_region(H, x0 + x, y0 + y, w, h, side=scene["side"])
-                part[walls] = 0
+                part[wall] = 0
                 atlas.write_region(H, part, x0 + x, y0 + y, side=scene["side"])
             made[key] = atlas
+        for x, y, texels in scene["plants"]:  # whole texels: the scenes that plant them share one atlas and write theirs before their call
+            if texels.dtype != bool:
+                made[key].write_region(H, texels, x0 + x, y0 + y, side=scene["side"])
         return made[key]
 
     return get
@@ -104,8 +108,33 @@ def test_host_mask(device, atlases, name):
 
 @pytest.mark.gpu
 def test_maze_needs_several_batches(device, atlases):
+    """the maze is the path field's long walk: a route of 72 x 64 cells along rows, which a wave walks in lockstep, one cell a round and 64
+    rounds a sweep; only a row's end, where the route changes rows and may change waves, can carry the news further in a round.  More than
+    4 + 8 + 16 = 28 sweeps means that batches of kBatchMax = 32 ran, whose count comes back from the last of the 32 counters (the schedule
+    model's fastest block order needs 97: tests/test_relax_model.py)"""
     _, _, stats = check_scene(atlases("maze"), "maze")
-    assert stats["sweeps"] > 4 + 8, stats  # more than the first two batches: the loop went round at least three times
+    assert stats["sweeps"] > 4 + 8 + 16, stats
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PC.CROSSING_SCENES)
+def test_a_late_crossing_wakes_a_block_that_went_quiet(device, atlases, name):
+    """more than 4 x 64 cells of corridor lie between the goal and the one step into the next block: the field crosses after the first
+    batch of 4 sweeps, into a block that the one flag bit of the scene's name wakes.  At a corner the step is diagonal between two
+    pillars, free cells too steep to step on, which keep the rule against cutting corners satisfied and carry nothing themselves"""
+    _, nxt, stats = check_scene(atlases(name), name)
+    assert stats["sweeps"] > 4, stats
+    if name != "crossing_up":
+        assert (nxt == _ffi.PATH_UNREACHABLE).sum() == 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["goal_in_a_corner", "goal_on_an_edge"])
+def test_a_goal_walled_in_within_its_block_leaves_through_the_next(device, atlases, name):
+    """the goal changes nothing in its own block, which therefore flags nothing: the blocks around it run because path_prepare_kernel
+    flagged all 3 x 3"""
+    cost, _, _ = check_scene(atlases(name), name)
+    assert np.isfinite(cost).sum() >= 8
 
 
 @pytest.mark.gpu
