@@ -346,6 +346,24 @@ class DistanceStatsC(C.Structure):
                 ("launches", C.c_uint32), ("_padding", C.c_uint32), ("edit", EditStatsC)]
 
 
+SKYLINE_MAX_DIRECTIONS, SKYLINE_MAX_COMPONENT, SKYLINE_MAX_SIDE, SKYLINE_MAX_CELLS = 64, 1024, 32768, 1 << 22
+SKYLINE_STACK_BUDGET, SKYLINE_BAKE_SHADE = 256 << 20, 1
+
+
+class SkylineDirectionC(C.Structure):
+    _fields_ = [("dx", C.c_int32), ("dy", C.c_int32), ("sun_num", C.c_uint32), ("sun_den", C.c_uint32)]
+
+
+class SkylineBakeC(C.Structure):
+    _fields_ = [("attachment", C.c_uint32), ("channel", C.c_uint32), ("flags", C.c_uint32), ("_padding", C.c_uint32)]
+
+
+class SkylineStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("voids", C.c_uint32), ("tiles_missing", C.c_uint32), ("directions", C.c_uint32), ("lines", C.c_uint32),
+                ("longest_line", C.c_uint32), ("max_steps", C.c_uint32), ("launches", C.c_uint32), ("lit", C.c_uint64), ("sum_steps", C.c_uint64),
+                ("edit", EditStatsC)]
+
+
 class ErosionStatsC(C.Structure):
     _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
 
@@ -436,6 +454,9 @@ PROTOTYPES = {
                                  _P(ViewshedStatsC)]),
     "bt_atlas_distance_field": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(DistanceSeedsC), _P(C.c_uint8), _P(_u32), _P(_u32), _P(DistanceBakeC),
                                        _P(TileCoordinateC), _u32, _P(DistanceStatsC)]),
+    "bt_skyline_line_count": (_i32, [_u32, _u32, C.c_int32, C.c_int32, _P(_u32), _P(_u32)]),
+    "bt_atlas_skyline": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(SkylineDirectionC), _u32, _P(C.c_uint16), _P(C.c_int32), _P(C.c_uint64),
+                                _P(C.c_uint8), _P(SkylineBakeC), _P(TileCoordinateC), _u32, _P(SkylineStatsC)]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

@@ -1052,6 +1052,129 @@ bt_status bt_atlas_distance_field(bt_atlas* a, uint32_t ai, uint32_t side, uint3
     return rc ? rc : drained;
 }
 
+// The call of the SKYLINE section of the header (the kernels: bt_skyline.hip; the line geometry and the plan: bt_skyline.cpp).  It lives
+// here for the bake, as bt_atlas_distance_field does.
+bt_status bt_atlas_skyline(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                           const bt_skyline_direction* directions, uint32_t direction_count, uint16_t* steps_out, int32_t* rise_out, uint64_t* mask_out, uint8_t* count_out,
+                           const bt_skyline_bake* bake, bt_tile_coordinate* changed, uint32_t changed_cap, bt_skyline_stats* stats) {
+    const char* who = "bt_atlas_skyline";
+    if (stats) *stats = bt_skyline_stats{};
+    if (!a || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", who, !a ? "atlas" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, who)) return s;
+    const Attachment& at = a->attachments[ai];
+    if (at.meta.format != BT_FORMAT_R16) {
+        set_error("%s: attachment format %u (heights are R16)", who, at.meta.format);
+        return BT_ERR_UNSUPPORTED;
+    }
+    if (!directions) {
+        set_error("%s: NULL directions", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (direction_count == 0u || direction_count > BT_SKYLINE_MAX_DIRECTIONS) {
+        set_error("%s: %u directions, 1 to %u", who, direction_count, BT_SKYLINE_MAX_DIRECTIONS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    uint32_t which = 0;
+    if (const char* bad = skyline_bad_direction(directions, direction_count, &which)) {
+        const bt_skyline_direction& d = directions[which];
+        set_error("%s: direction %u: %s (dx %d, dy %d, sun_num %u, sun_den %u)", who, which, bad, d.dx, d.dy, d.sun_num, d.sun_den);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (width > BT_SKYLINE_MAX_SIDE || height > BT_SKYLINE_MAX_SIDE) {
+        set_error("%s: a side of %u x %u above %u", who, width, height, BT_SKYLINE_MAX_SIDE);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t cells = uint64_t(width) * height;
+    if (cells > BT_SKYLINE_MAX_CELLS) {
+        set_error("%s: %u x %u cells, at most %u", who, width, height, BT_SKYLINE_MAX_CELLS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bake) {
+        const char* bad_bake = bake->attachment >= a->attachments.size()                 ? "attachment out of range"
+                               : bake->channel > 3u                                      ? "channel (0..3)"
+                               : (bake->flags & ~uint32_t(BT_SKYLINE_BAKE_SHADE)) != 0u ? "unknown flag bits"
+                                                                                         : nullptr;
+        if (bad_bake) {
+            set_error("%s: bake: %s (attachment %u, channel %u, flags %#x)", who, bad_bake, bake->attachment, bake->channel, bake->flags);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        const AttachmentMeta& dm = a->attachments[bake->attachment].meta;
+        if (dm.format != BT_FORMAT_RGBA8 || dm.texture_size != at.meta.texture_size || dm.border_size != at.meta.border_size) {
+            set_error("%s: bake: attachment %u (format %u, texture_size %u, border_size %u): an Rgba8 attachment of the source's texture_size %u and border_size %u", who,
+                      bake->attachment, dm.format, dm.texture_size, dm.border_size, at.meta.texture_size, at.meta.border_size);
+            return BT_ERR_UNSUPPORTED;
+        }
+    }
+    if (!cells) return BT_OK;  // an empty window: nothing to do
+
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const SkylinePlan plan = skyline_plan(width, height, directions, direction_count, bake != nullptr);
+    // the planes of the call, carved from one buffer; the per-direction ones lie plane after plane, so a batch stages out as one rectangle
+    const uint64_t at_raw = 0, at_transposed = at_raw + align256(cells * 2u), at_mask = at_transposed + align256(cells * 2u), at_count = at_mask + align256(cells * 8u),
+                   at_stack = at_count + align256(cells), at_rise = at_stack + align256(plan.batch * cells * 4u), at_steps = at_rise + align256(plan.batch * cells * 4u),
+                   total = at_steps + align256(plan.batch * cells * 2u);
+    if (bt_status s = ctx->skyline.reserve(ctx, total)) return s;
+    if (bt_status s = ctx->skyline_words.reserve(ctx, 256, true)) return s;
+    if (bake)
+        if (bt_status s = ctx->edit_region.reserve(ctx, cells * 4u)) return s;
+    uint8_t* base = (uint8_t*)ctx->skyline.dev;
+    SkylinePlanes p{};
+    p.width = width, p.height = height;
+    p.raw = (const uint16_t*)(base + at_raw), p.transposed = (uint16_t*)(base + at_transposed);
+    p.stack = (uint32_t*)(base + at_stack), p.steps = (uint16_t*)(base + at_steps), p.rise = (int32_t*)(base + at_rise);
+    p.mask = (uint64_t*)(base + at_mask), p.count = base + at_count;
+    p.direction_count = direction_count;
+    memcpy(p.directions, directions, sizeof(bt_skyline_direction) * direction_count);
+    SkylineBake merge{};
+    if (bake) merge.texels = (uint32_t*)ctx->edit_region.dev, merge.shift = 8u * bake->channel, merge.shade = bake->flags & BT_SKYLINE_BAKE_SHADE;
+    SkylineCounts* counts = (SkylineCounts*)ctx->skyline_words.dev;
+    const SkylineCounts* counts_host = (const SkylineCounts*)ctx->skyline_words.host;
+
+    uint32_t tiles_missing = 0;
+    if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, base + at_raw, &tiles_missing)) return s;
+    if (bake)
+        if (bt_status s = region_gather(a, bake->attachment, side, lod, x0, y0, width, height, ctx->edit_region.dev, nullptr)) return s;
+    BT_HIP(hipMemsetAsync(counts, 0, sizeof(SkylineCounts), stream));
+    if (bt_status s = launch_skyline_transpose(stream, p)) return s;
+    const char* what = "bt_atlas_skyline staging";
+    for (uint32_t first = 0; first < direction_count; first += plan.batch) {
+        p.first = first, p.batch = std::min(plan.batch, direction_count - first);
+        const bool last = first + p.batch == direction_count;
+        if (bt_status s = launch_skyline_walk(stream, p)) return s;
+        if (bt_status s = launch_skyline_finish(stream, p, last ? merge : SkylineBake{}, last, counts)) return s;
+        // the batch's planes leave before the next batch overwrites them: the staging waits for its copies
+        if (steps_out)
+            if (bt_status s = region_stage_out(ctx, p.steps, steps_out + first * cells, uint64_t(width) * 2u, uint64_t(width) * 2u, p.batch * height, what)) return s;
+        if (rise_out)
+            if (bt_status s = region_stage_out(ctx, p.rise, rise_out + first * cells, uint64_t(width) * 4u, uint64_t(width) * 4u, p.batch * height, what)) return s;
+    }
+    BT_HIP(hipMemcpyAsync((void*)counts_host, counts, sizeof(SkylineCounts), hipMemcpyDeviceToHost, stream));
+    if (mask_out)
+        if (bt_status s = region_stage_out(ctx, p.mask, mask_out, uint64_t(width) * 8u, uint64_t(width) * 8u, height, what)) return s;
+    if (count_out)
+        if (bt_status s = region_stage_out(ctx, p.count, count_out, width, width, height, what)) return s;
+    bt_edit_stats edit{};
+    bt_status rc = BT_OK;
+    if (bake) {
+        FirstStep first{FirstStep::kRegion};  // texels nullptr: the rectangle is on the device
+        first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
+        rc = edit_boxes(a, bake->attachment, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, &edit);
+    }
+    BT_HIP(hipStreamSynchronize(stream));
+    if (stats) {
+        stats->cells = uint32_t(cells), stats->voids = counts_host->voids, stats->tiles_missing = tiles_missing, stats->directions = direction_count;
+        stats->lines = plan.lines, stats->longest_line = plan.longest_line, stats->max_steps = counts_host->max_steps, stats->launches = plan.launches;
+        stats->lit = counts_host->lit, stats->sum_steps = counts_host->sum_steps;
+        stats->edit = edit;
+    }
+    return rc;
+}
+
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {
     if (!a || !directory || (count && !coords)) {
         set_error("bt_atlas_save_tiles: NULL %s", !a ? "atlas" : !directory ? "directory" : "coords");

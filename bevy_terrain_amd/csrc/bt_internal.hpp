@@ -270,9 +270,12 @@ struct bt_ctx {
     // bt_atlas_distance_field: the planes of one call on the device (raw texels, the host seed plane, the band summaries, r, dist2,
     // nearest); and the counts of bt_distance_stats with a pinned twin
     bt::Scratch distance, distance_words;
-    std::array<bt::Scratch*, 15> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
-        return {&bounds,     &raycast, &normal,      &render,   &edit_region,    &path,     &path_words,    &scatter,
-                &erode,      &drain,   &drain_words, &viewshed, &viewshed_words, &distance, &distance_words};
+    // bt_atlas_skyline: the planes of one call on the device (raw texels, their transpose, the mask, the count, and per direction of a
+    // batch the hull stack, steps and rise); and the counts of bt_skyline_stats with a pinned twin
+    bt::Scratch skyline, skyline_words;
+    std::array<bt::Scratch*, 17> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+        return {&bounds, &raycast,     &normal,   &render,         &edit_region, &path,           &path_words, &scatter,      &erode,
+                &drain,  &drain_words, &viewshed, &viewshed_words, &distance,    &distance_words, &skyline,    &skyline_words};
     }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
@@ -632,6 +635,45 @@ bt_status launch_distance_columns(hipStream_t stream, const DistancePlanes& p);
 bt_status launch_distance_rows(hipStream_t stream, const DistancePlanes& p);
 // the counts, and the baked byte
 bt_status launch_distance_finish(hipStream_t stream, const DistancePlanes& p, const DistanceBake& bake, DistanceCounts* counts);
+
+// bt_skyline.hip: the kernels of bt_atlas_skyline.  Planes are width x height, row-major; the per-direction ones hold a batch
+struct SkylinePlanes {
+    uint32_t width, height;
+    const uint16_t* raw;      // the gathered texels
+    uint16_t* transposed;     // raw with the axes exchanged: cell (x, y) at x * height + y
+    uint32_t* stack;          // batch x cells hull entries below the two in registers: major coordinate << 16 | z
+    uint16_t* steps;          // batch x cells
+    int32_t* rise;            // batch x cells
+    uint64_t* mask;
+    uint8_t* count;
+    uint32_t direction_count;  // of the call
+    uint32_t first, batch;     // the directions of this batch: first .. first + batch - 1
+    bt_skyline_direction directions[BT_SKYLINE_MAX_DIRECTIONS];  // in the kernel arguments: every wave reads them as scalars
+};
+struct SkylineBake {   // the byte the last finish launch merges into the staged rectangle
+    uint32_t* texels;  // the destination's Rgba8 texels on the device, or nullptr: no bake
+    uint32_t shift;    // 8 * channel
+    uint32_t shade;    // 0 or 1: 255 - b
+};
+struct SkylineCounts {  // the device words of bt_skyline_stats
+    uint32_t voids, max_steps;
+    unsigned long long lit, sum_steps;
+};
+struct SkylinePlan {  // bt_skyline.cpp: what the call does, from its arguments alone
+    uint32_t batch;     // directions in flight: B of the header
+    uint32_t batches;   // ceil(direction_count / batch)
+    uint32_t launches;  // of bt_skyline_stats
+    uint32_t lines, longest_line;
+};
+SkylinePlan skyline_plan(uint32_t width, uint32_t height, const bt_skyline_direction* directions, uint32_t direction_count, bool bake);
+// the first defect of the directions as text, or nullptr; *which: the index of the direction
+const char* skyline_bad_direction(const bt_skyline_direction* directions, uint32_t direction_count, uint32_t* which);
+// raw -> transposed
+bt_status launch_skyline_transpose(hipStream_t stream, const SkylinePlanes& p);
+// the hull walk of the batch: steps and rise
+bt_status launch_skyline_walk(hipStream_t stream, const SkylinePlanes& p);
+// the batch's bits into the mask and the running counts; last: count, the void count and the baked byte
+bt_status launch_skyline_finish(hipStream_t stream, const SkylinePlanes& p, const SkylineBake& bake, bool last, SkylineCounts* counts);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

@@ -725,6 +725,67 @@ class TileAtlas:
         out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
         return (*outs, out)
 
+    @staticmethod
+    def sun_directions(azimuth_deg, elevation_deg, cell_size: float, raw_unit: float, resolution: int = 64):
+        """Real sun angles -> the (dx, dy, sun_num, sun_den) rows of `skyline`, an (N, 4) int64 array.  azimuth_deg and elevation_deg:
+        scalars or equally long sequences.  Azimuth 0 is +x and turns towards +y.  cell_size: the width of a cell and raw_unit: the height of
+        one raw unit, in the same world unit.  The rounding: (dx, dy) = floor(resolution * (cos, sin) + 0.5), so the azimuth is met within
+        about 0.5 / resolution radians (resolution <= 1024); the sun's rise per step of the major axis,
+        tan(elevation) * cell_size * hypot(dx, dy) / max(|dx|, |dy|) / raw_unit, is taken as a floor over sun_den = 4096 (a product within
+        2^-40 of a whole number counts as that number), so the sun stands at most 1/4096 of a raw unit per step lower than asked and no
+        cell is lit that the real sun leaves in shadow on these lines; it is capped at 2^31 - 1 (an elevation of 90 and near it).
+        Elevations below 0 are refused: suns below the horizontal are out of scope."""
+        az, el = np.atleast_1d(np.asarray(azimuth_deg, dtype=np.float64)), np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
+        az, el = np.broadcast_arrays(az, el)
+        if not 1 <= resolution <= _ffi.SKYLINE_MAX_COMPONENT:
+            raise ValueError(f"sun_directions: resolution {resolution}, 1 to {_ffi.SKYLINE_MAX_COMPONENT}")
+        if (el < 0).any() or (el > 90).any() or not (cell_size > 0 and raw_unit > 0):
+            raise ValueError("sun_directions: elevations in [0, 90], cell_size and raw_unit above 0")
+        rows = np.zeros((len(az), 4), dtype=np.int64)
+        for i, (a, e) in enumerate(zip(az.tolist(), el.tolist())):
+            dx, dy = math.floor(resolution * math.cos(math.radians(a)) + 0.5), math.floor(resolution * math.sin(math.radians(a)) + 0.5)
+            per_step = cell_size * math.hypot(dx, dy) / max(abs(dx), abs(dy)) / raw_unit
+            num = (1 << 31) - 1 if e >= 90.0 else min((1 << 31) - 1, math.floor(math.tan(math.radians(e)) * per_step * 4096.0 * (1.0 + 2.0 ** -40)))
+            rows[i] = (dx, dy, num, 4096)
+        return rows
+
+    def skyline(self, attachment_index: int, x0: int, y0: int, w: int, h: int, directions, *, lod: Optional[int] = None, side: int = 0,
+                steps: bool = True, rise: bool = True, mask: bool = True, count: bool = True, bake=None):
+        """bt_atlas_skyline: the horizon of every cell of the w x h window of centre texels at mosaic position (x0, y0) of `lod` on `side`
+        of an R16 attachment in each of `directions`, by the header's SKYLINE section, in integers.  directions: an (N, 4) integer array or
+        a list of (dx, dy, sun_num, sun_den) (see sun_directions; shorter tuples: sun_num 0, sun_den 1, a sun on the horizontal), 64 at
+        most.  Returns (steps, rise, mask, count, stats): steps (N, h, w) uint16 and rise (N, h, w) int32, the distance in steps of the
+        major axis and the height difference of each cell's horizon cell towards (dx, dy) (0 and 0 at the window's edge); mask (h, w)
+        uint64, bit k set where the cell is lit by direction k (rise * sun_den <= steps * sun_num); count (h, w) uint8, the set bits;
+        stats: bt_skyline_stats as a dict.  steps / rise / mask / count False: that plane is not copied out and None comes back in its
+        place.  bake: (attachment, channel) or (attachment, channel, shade) or a dict of those names: byte `channel` of that Rgba8
+        attachment becomes floor(255 * count / N) over the window, 255 minus that with `shade`, and the atlas is updated as by
+        write_region; stats["edit"] is then its bt_edit_stats and stats["changed"] the changed tiles.  All planes are exact.  Ordered behind
+        the queued work; synchronous; a read without `bake`."""
+        lod = self.lod_count - 1 if lod is None else lod
+        rows = [tuple(int(v) for v in d) for d in (directions.tolist() if isinstance(directions, np.ndarray) else directions)]
+        arr = (_ffi.SkylineDirectionC * max(len(rows), 1))(*[_ffi.SkylineDirectionC(*(d + (0, 1)[len(d) - 2:])[:4]) for d in rows])
+        n = len(rows)
+        shapes = (((n, h, w), np.uint16, steps), ((n, h, w), np.int32, rise), ((h, w), np.uint64, mask), ((h, w), np.uint8, count))
+        outs = [np.zeros(shape, dtype=t) if want else None for shape, t, want in shapes]
+        types = (C.c_uint16, C.c_int32, C.c_uint64, C.c_uint8)
+        bake_c = None
+        if bake is not None:
+            if isinstance(bake, dict):
+                bake = (bake["attachment"], bake["channel"], bake.get("shade", False))
+            bake = tuple(bake) + (False,) * (3 - len(bake))
+            bake_c = _ffi.SkylineBakeC(bake[0], bake[1], _ffi.SKYLINE_BAKE_SHADE if bake[2] else 0, 0)
+        cap = max(self.atlas_size, 1)
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.SkylineStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_skyline(
+            self._h, attachment_index, side, lod, x0, y0, w, h, arr, n, *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, types)],
+            C.byref(bake_c) if bake_c is not None else None, changed, cap, C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.SkylineStatsC._fields_ if name != "edit"}
+        out["edit"] = {name: getattr(stats.edit, name) for name, _ in _ffi.EditStatsC._fields_}
+        out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
+        return (*outs, out)
+
     def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
                      water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the

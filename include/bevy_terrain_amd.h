@@ -1941,6 +1941,101 @@ bt_status bt_atlas_distance_field(bt_atlas* atlas, uint32_t attachment_index, ui
                                   uint32_t* nearest_out /* may be NULL */, const bt_distance_bake* bake /* may be NULL */,
                                   bt_tile_coordinate* changed, uint32_t changed_cap, bt_distance_stats* stats /* may be NULL */);
 
+/* ---------------- skyline: the horizon of every cell of a rectangle of heights in a set of directions, sun hours, a shadow bake
+ * SKYLINE (bt_atlas_skyline; R16 only).  Integers throughout: no float appears, so every plane is a function of the input byte for byte.
+ * Out of scope: a distance cap on the line (it breaks the hull below); a receiver height above the ground (it needs a tangent search
+ * into the hull); the curvature of the earth; suns below the horizontal.
+ * Window: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of an R16 attachment (the rectangle of
+ * bt_atlas_read_region).  Cell (x, y) is mosaic texel (x0 + x, y0 + y); planes are row-major, cell (x, y) at index i = y * width + x.
+ * z(c) = the raw u16.  Texels without data, and texels of tiles the atlas does not hold, read as 0 and are ground of height 0; the tiles
+ * are counted in tiles_missing and the cells with z == 0 in voids.  There is no void class for results: every plane is a function of
+ * the z plane alone.
+ * Directions: up to BT_SKYLINE_MAX_DIRECTIONS of bt_skyline_direction {dx, dy, sun_num, sun_den}.  (dx, dy) points towards the sun, in
+ * cells, not both 0, |dx|, |dy| <= BT_SKYLINE_MAX_COMPONENT.  The sun rises sun_num / sun_den raw height units per step of the major
+ * axis; sun_den is 1..65535 and sun_num <= 2^31 - 1.
+ * Digital lines.  The major axis is x when |dx| >= |dy|, otherwise y; the wording is for x-major, y-major exchanges the axes.
+ * n = |dx|, s = sign(dx), m = dy * s.  off(x) = floor((2 x m + n) / (2 n)), the true floor, towards minus infinity, x counted in the
+ * window.  Cell (x, y) lies on line j = y - off(x).  Every cell lies on exactly one line; the cells of a line inside the window occupy a
+ * contiguous range of x; since off(0) = 0 and off moves by at most one per step, the lines are the j from -max(off) to
+ * height - 1 - min(off), height + |off(width - 1)| of them.  Scaling (dx, dy) by a positive integer gives the same lines, (-dx, -dy) the
+ * same lines walked the other way, and an exact diagonal the same lines on either axis.  The cells AHEAD of a are the cells b of its
+ * line with (x_b - x_a) s > 0, at t = |x_b - x_a| steps.
+ * Skyline.  For direction k and cell a, the HORIZON CELL is, among the cells ahead, the one that maximises the rational (z_b - z_a) / t,
+ * negatives included; on a tie the nearest one.  steps[k][a] = its t (u16), rise[k][a] = z_b - z_a (i32); both 0 when no cell is ahead.
+ * Bounds: width, height <= BT_SKYLINE_MAX_SIDE; width * height <= BT_SKYLINE_MAX_CELLS.  Hence t <= 32767, |rise| <= 65535 and every
+ * cross product rise * t' is at most 65535 * 32767 < 2^31; they are formed in 64 bits anyway.
+ * Sun.  Cell a is LIT by direction k iff rise * sun_den <= steps * sun_num, in 64 bits (< 2^32 against < 2^46): grazing counts as lit,
+ * as in VIEWSHED, and a cell with nothing ahead is lit.  mask (u64): bit k set iff lit by direction k.  count (u8): the number of set
+ * bits.
+ * The hull reading, which an implementation may rely on.  Walk a line against its direction, keeping the upper convex hull of the cells
+ * walked so far as a stack, the nearest on top.  For the new cell a, pop the top p while there is a q beneath it with
+ * (z_q - z_a) t_p > (z_p - z_a) t_q.  The test is strict, so a collinear p stays: that is the nearest-on-a-tie rule.  The top is then a's
+ * horizon cell; push a.  Each cell is pushed once and popped at most once, so a direction costs a number of steps linear in the cells.
+ * Bake (optional): bt_skyline_bake {attachment, channel, flags, _padding} writes b = floor(255 * count / direction_count) into channel
+ * `channel` of the Rgba8 attachment `attachment` of the same atlas, over the same rectangle; with BT_SKYLINE_BAKE_SHADE the byte is
+ * 255 - b.  With one direction it is a shadow map of 0 and 255.  The other three bytes of every texel keep their values.  The write is
+ * an edit like any other: the destination rectangle is gathered, the byte merged on the device, and the texels written and the atlas
+ * invariant restored exactly as by bt_atlas_write_region of them over the rectangle: the same plan, the same `changed` order, the same
+ * bt_edit_stats (stats->edit).  Without `bake` the call is a read: no layer is marked written, and `changed` is not written.
+ * Outputs, each may be NULL.  steps_out (u16) and rise_out (i32): direction_count planes of width * height, direction-major.  mask_out
+ * (u64) and count_out (u8): one plane.  bt_skyline_stats: every field but launches is a function of the input.
+ * bt_skyline_line_count(width, height, dx, dy, &lines, &longest): the number of lines of one direction and the cells of the longest,
+ * without a device; 0 and 0 for an empty window.  It refuses a zero vector and a component above BT_SKYLINE_MAX_COMPONENT.
+ * The call: synchronous, host arrays in and out through the context's staging ring, ordered behind the work queued on the context's
+ * stream.  Launches: the gather of bt_atlas_read_region (counted as one); one that transposes the texels; then per batch of directions
+ * the walk and a finish.  The walk runs the batch's directions as a grid dimension.  The lines j and j + (length of the minor axis) are
+ * never in the window at the same major coordinate, so they share a lane, one after the other: a lane to each of the minor axis'
+ * residues, a wave to 64 consecutive lines.  x-major directions walk the transposed texels and y-major ones the texels as they lie, so
+ * consecutive lanes read consecutive addresses at each step.  The top two hull entries stay in registers and the rest lies in scratch,
+ * 4 bytes a cell and direction in flight; a batch is B = min(direction_count, max(1, floor(BT_SKYLINE_STACK_BUDGET / (4 * width *
+ * height)))) directions, 16 at 2^22 cells.  The finish, a lane to a cell, ORs the batch's bits into the mask (one writer per cell, no
+ * atomic); the last one also forms count and the baked byte.  launches = 2 + 2 * ceil(direction_count / B), one more with a bake for
+ * the gather of the destination, whose edit's launches follow in stats->edit.launches.  The count depends on the arguments only.  No
+ * result depends on a schedule.  The scratch stays in the context until bt_ctx_trim: 13 bytes per cell, 10 more per direction of a
+ * batch, and with a bake the staged rectangle (4 per cell).
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL directions; direction_count 0 or above
+ * BT_SKYLINE_MAX_DIRECTIONS; a zero vector; a component above BT_SKYLINE_MAX_COMPONENT; sun_den 0 or above 65535; sun_num above
+ * 2^31 - 1; a side above BT_SKYLINE_MAX_SIDE; width * height above BT_SKYLINE_MAX_CELLS; NULL changed with changed_cap > 0; in a bake:
+ * an attachment out of range, a channel above 3, unknown flag bits.  BT_ERR_UNSUPPORTED: a non-R16 attachment; an odd centre size; a
+ * bake destination that is not Rgba8, or whose texture_size or border_size differs from the source's.  width == 0 or height == 0 (with
+ * valid arguments otherwise): BT_OK, nothing touched. */
+#define BT_SKYLINE_MAX_DIRECTIONS 64u
+#define BT_SKYLINE_MAX_COMPONENT 1024
+#define BT_SKYLINE_MAX_SIDE 32768u
+#define BT_SKYLINE_MAX_CELLS (1u << 22)
+#define BT_SKYLINE_STACK_BUDGET (256ull << 20) /* bytes of hull-stack scratch in flight */
+enum { BT_SKYLINE_BAKE_SHADE = 1 }; /* bt_skyline_bake.flags */
+typedef struct bt_skyline_direction {
+    int32_t  dx, dy;            /* towards the sun, in cells; not both 0; |dx|, |dy| <= BT_SKYLINE_MAX_COMPONENT */
+    uint32_t sun_num, sun_den;  /* the sun's rise in raw height units per step of the major axis: num / den; den 1..65535, num <= 2^31 - 1 */
+} bt_skyline_direction; /* 16 bytes */
+typedef struct bt_skyline_bake {
+    uint32_t attachment;  /* the Rgba8 attachment that takes the byte */
+    uint32_t channel;     /* 0..3 */
+    uint32_t flags;       /* BT_SKYLINE_BAKE_SHADE */
+    uint32_t _padding;
+} bt_skyline_bake; /* 16 bytes */
+typedef struct bt_skyline_stats {
+    uint32_t cells, voids;      /* width * height; cells with z == 0 */
+    uint32_t tiles_missing;     /* tiles of the rectangle the source attachment does not hold */
+    uint32_t directions;        /* direction_count */
+    uint32_t lines;             /* the lines, summed over the directions */
+    uint32_t longest_line;      /* the cells of the longest line of any direction */
+    uint32_t max_steps;         /* the largest entry of the steps planes */
+    uint32_t launches;          /* the kernel launches of the call before the edit's, the gathers counted as one each */
+    uint64_t lit;               /* the sum of count over the cells */
+    uint64_t sum_steps;         /* the sum of the steps planes */
+    bt_edit_stats edit;         /* of the bake's write-back; zero without a bake */
+} bt_skyline_stats; /* 80 bytes */
+bt_status bt_skyline_line_count(uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t* lines /* may be NULL */,
+                                uint32_t* longest /* may be NULL */);
+bt_status bt_atlas_skyline(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                           uint32_t width, uint32_t height, const bt_skyline_direction* directions, uint32_t direction_count,
+                           uint16_t* steps_out /* may be NULL */, int32_t* rise_out /* may be NULL */, uint64_t* mask_out /* may be NULL */,
+                           uint8_t* count_out /* may be NULL */, const bt_skyline_bake* bake /* may be NULL */, bt_tile_coordinate* changed,
+                           uint32_t changed_cap, bt_skyline_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
