@@ -8,14 +8,14 @@ library raises if libbevy_terrain_amd.so is missing.
 """
 from .terrain import (AttachmentConfig, AttachmentFormat, TerrainConfig, TerrainModel, TerrainViewConfig,
                       TileCoordinate)
-from .tile_atlas import Device, EditStamp, ErosionParams, HeightBounds, PaintStamp, PathCost, ScatterRule, SmoothStamp, SplatRule, TileAtlas, generate_mipmaps, mosaic_position, tc_decode, tc_encode, trace_path
+from .tile_atlas import Device, EditStamp, ErosionParams, HeightBounds, PaintStamp, PathCost, ScatterRule, SmoothStamp, SplatRule, TileAtlas, generate_mipmaps, mosaic_position, packed_tile_bound, packed_tile_check, tc_decode, tc_encode, trace_path
 from .preprocess import AssetServer, PreprocessDataset, Preprocessor, SphericalDataset
 from .tiling_prepass import TilingPrepass, cull_horizon, cull_planes, make_view_state
 from .tile_tree import TERRAIN_VERTEX_DTYPE, RenderCamera, TileTree, model_approximation_from_config, raycast_terrain, render_rays, sample_attachment, sample_height, sample_normal, view_state_from_config, write_ppm
 
 __all__ = [
     "AttachmentConfig", "AttachmentFormat", "TerrainConfig", "TerrainModel", "TerrainViewConfig", "TileCoordinate",
-    "Device", "EditStamp", "ErosionParams", "HeightBounds", "PaintStamp", "PathCost", "ScatterRule", "SmoothStamp", "SplatRule", "TileAtlas", "generate_mipmaps", "mosaic_position", "tc_decode", "tc_encode", "trace_path",
+    "Device", "EditStamp", "ErosionParams", "HeightBounds", "PaintStamp", "PathCost", "ScatterRule", "SmoothStamp", "SplatRule", "TileAtlas", "generate_mipmaps", "mosaic_position", "packed_tile_bound", "packed_tile_check", "tc_decode", "tc_encode", "trace_path",
     "AssetServer", "PreprocessDataset", "Preprocessor", "SphericalDataset",
     "TilingPrepass", "cull_horizon", "cull_planes", "make_view_state",
     "TERRAIN_VERTEX_DTYPE", "RenderCamera", "TileTree", "model_approximation_from_config", "raycast_terrain", "render_rays", "sample_attachment", "sample_height", "sample_normal", "view_state_from_config", "write_ppm",

@@ -350,6 +350,9 @@ SKYLINE_MAX_DIRECTIONS, SKYLINE_MAX_COMPONENT, SKYLINE_MAX_SIDE, SKYLINE_MAX_CEL
 SKYLINE_STACK_BUDGET, SKYLINE_BAKE_SHADE = 256 << 20, 1
 
 
+PACK_STRIP_ROWS, TILE_FILES_BIN, TILE_FILES_PACKED = 32, 0, 1
+
+
 class SkylineDirectionC(C.Structure):
     _fields_ = [("dx", C.c_int32), ("dy", C.c_int32), ("sun_num", C.c_uint32), ("sun_den", C.c_uint32)]
 
@@ -457,6 +460,13 @@ PROTOTYPES = {
     "bt_skyline_line_count": (_i32, [_u32, _u32, C.c_int32, C.c_int32, _P(_u32), _P(_u32)]),
     "bt_atlas_skyline": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(SkylineDirectionC), _u32, _P(C.c_uint16), _P(C.c_int32), _P(C.c_uint64),
                                 _P(C.c_uint8), _P(SkylineBakeC), _P(TileCoordinateC), _u32, _P(SkylineStatsC)]),
+    "bt_packed_tile_bound": (_i32, [_u32, _u32, _P(_u64)]),
+    "bt_packed_tile_check": (_i32, [_vp, _u64, _P(_u32), _P(_u32)]),
+    "bt_atlas_pack_tiles": (_i32, [_vp, _u32, _P(_u32), _u32, _vp, _u64, _P(_u64)]),
+    "bt_atlas_unpack_tiles": (_i32, [_vp, _u32, _P(_u32), _u32, _vp, _P(_u64)]),
+    "bt_atlas_save_tiles_packed": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
+    "bt_atlas_load_tiles_packed": (_i32, [_vp, _u32, C.c_char_p, _P(TileCoordinateC), _u32]),
+    "bt_atlas_set_tile_files": (_i32, [_vp, _u32]),
     "bt_path_trace": (_i32, [_P(C.c_uint8), _u32, _u32, _u32, _u32, _P(_u32), _u32, _P(_u32), _P(_u32)]),
     "bt_tc_encode": (_u64, [_P(TileCoordinateC), _u32, _vp, _u64]),
     "bt_tc_decode": (C.c_int64, [_vp, _u64, _P(TileCoordinateC), _u32]),

@@ -273,9 +273,13 @@ struct bt_ctx {
     // bt_atlas_skyline: the planes of one call on the device (raw texels, their transpose, the mask, the count, and per direction of a
     // batch the hull stack, steps and rise); and the counts of bt_skyline_stats with a pinned twin
     bt::Scratch skyline, skyline_words;
-    std::array<bt::Scratch*, 17> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // the packed tile calls (bt_pack.cpp): the streams, strip offsets and strip sizes of one chunk on the device; and the stream starts
+    // of a packed chunk with a pinned twin
+    bt::Scratch pack, pack_words;
+    std::array<bt::Scratch*, 19> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
         return {&bounds, &raycast,     &normal,   &render,         &edit_region, &path,           &path_words, &scatter,      &erode,
-                &drain,  &drain_words, &viewshed, &viewshed_words, &distance,    &distance_words, &skyline,    &skyline_words};
+                &drain,  &drain_words, &viewshed, &viewshed_words, &distance,    &distance_words, &skyline,    &skyline_words,
+                &pack,   &pack_words};
     }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
@@ -299,6 +303,7 @@ struct bt_atlas {
     uint64_t state_version = 1;                    // bumped whenever tile_states changes (device copies are rebuilt lazily)
     // the Save tasks of the preprocessor runs since the last bt_preprocessor_save (preprocessor.rs:378-380)
     std::vector<bt::AtlasTileAttachment> to_save;
+    uint32_t tile_files = BT_TILE_FILES_BIN;  // what bt_atlas_update reads (bt_atlas_set_tile_files)
 };
 
 namespace bt {
@@ -674,6 +679,38 @@ bt_status launch_skyline_transpose(hipStream_t stream, const SkylinePlanes& p);
 bt_status launch_skyline_walk(hipStream_t stream, const SkylinePlanes& p);
 // the batch's bits into the mask and the running counts; last: count, the void count and the baked byte
 bt_status launch_skyline_finish(hipStream_t stream, const SkylinePlanes& p, const SkylineBake& bake, bool last, SkylineCounts* counts);
+
+// bt_pack.hip: the kernels of the packed tile calls (the format: PACKED TILES in the header).  One wave per strip of a tile; a chunk holds
+// at most kPackChunk tiles, whose layers and stream starts travel in the kernel arguments
+constexpr uint32_t kPackChunk = 64;
+struct PackShape {  // of one attachment's tiles
+    uint32_t T, planes, bits, gpr, strips;
+    uint32_t W;     // groups = width bytes of a tile
+    uint32_t head;  // 16 + pad8(W): a stream's bytes before its payload
+    uint64_t tile_bytes;
+    uint64_t bound() const { return head + 8ull * bits * W; }  // the largest stream: a group takes 64 lanes' bits, the dead ones included
+    static PackShape of(uint32_t format, uint32_t T) {
+        PackShape s{};
+        s.T = T, s.planes = format == BT_FORMAT_R16 ? 1u : 4u, s.bits = format == BT_FORMAT_R16 ? 16u : 8u;
+        s.gpr = (T + 63u) / 64u, s.strips = (T + BT_PACK_STRIP_ROWS - 1u) / BT_PACK_STRIP_ROWS;
+        s.W = s.planes * T * s.gpr, s.head = 16u + ((s.W + 7u) & ~7u);
+        s.tile_bytes = uint64_t(T) * T * (format == BT_FORMAT_R16 ? 2u : 4u);
+        return s;
+    }
+};
+struct PackTiles {
+    uint32_t count;
+    uint32_t layers[kPackChunk];
+};
+// measure: strip_bytes[q * strips + s] = the payload bytes of strip s of tile q; scan: starts[q] (count + 1 of them) = where tile q's stream begins
+// in the chunk's output, strip_off[q * strips + s] = where that strip's payload begins; emit: the streams into `out`
+bt_status launch_pack_measure(hipStream_t stream, uint32_t format, const PackShape& s, const void* level0, const PackTiles& tiles, uint32_t* strip_bytes);
+bt_status launch_pack_scan(hipStream_t stream, const PackShape& s, uint32_t count, const uint32_t* strip_bytes, uint64_t* starts, uint64_t* strip_off);
+bt_status launch_pack_emit(hipStream_t stream, uint32_t format, const PackShape& s, const void* level0, const PackTiles& tiles, const uint64_t* starts,
+                           const uint64_t* strip_off, uint8_t* out);
+// decode: validated streams in `packed` (stream q at starts[q], its strips' payloads at strip_off[q * strips + s], both device tables) -> the layers
+bt_status launch_pack_decode(hipStream_t stream, uint32_t format, const PackShape& s, void* level0, const PackTiles& tiles, const uint8_t* packed,
+                             const uint64_t* starts, const uint64_t* strip_off);
 
 // the three forms of the tiling prepass with the view's approximate_height optionally taken from device memory (bt_frame_update);
 // form: 0 = bt_tiling_prepass_run, 1 = _run_unordered, 2 = _run_plain

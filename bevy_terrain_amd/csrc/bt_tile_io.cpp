@@ -258,9 +258,9 @@ bt_status save_tiles(bt_atlas* a, uint32_t ai, const char* directory, std::vecto
 
 using namespace bt;
 
-// The tail of both load paths: these layers of attachment `ai` have been filled, in any order and possibly one of them twice; ONE batched
+// The tail of every load path: these layers of attachment `ai` have been filled, in any order and possibly one of them twice; ONE batched
 // mip-chain pass per run of consecutive layers
-static bt_status mip_filled_layers(bt_atlas* a, uint32_t ai, std::vector<uint32_t>& layers) {
+bt_status bt::mip_filled_layers(bt_atlas* a, uint32_t ai, std::vector<uint32_t>& layers) {
     if (a->attachments[ai].mips.size() <= 1) return BT_OK;
     std::sort(layers.begin(), layers.end());
     return for_each_layer_run(0, layers.size(), [&](size_t i) { return layers[i]; }, true, [&](size_t i, size_t n) {
@@ -348,6 +348,7 @@ bt_status bt_atlas_update(bt_atlas* a, const char* assets_root, uint32_t max_loa
     if (loaded) *loaded = 0;
     if (failed) *failed = 0;
     if (a->to_load.empty()) return BT_OK;
+    if (a->tile_files == BT_TILE_FILES_PACKED) return update_packed(a, assets_root, max_loads, loaded, failed);  // "{coord}.btp", decoded on the device
     BT_HIP(hipSetDevice(a->ctx->device));
     uint64_t largest = 0;
     for (const Attachment& at : a->attachments) largest = std::max(largest, at.tile_bytes);

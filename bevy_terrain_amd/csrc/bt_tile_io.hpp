@@ -105,6 +105,11 @@ class TileSaver {
 
 bt_status save_tiles(bt_atlas* a, uint32_t ai, const char* directory, TileSaver::Tiles tiles);
 
+// the tail of every load path (bt_tile_io.cpp): these layers of attachment `ai` have been filled; one mip-chain pass per run of consecutive layers (sorts the list)
+bt_status mip_filled_layers(bt_atlas* a, uint32_t ai, std::vector<uint32_t>& layers);
+// bt_atlas_update while the atlas reads packed tile files (bt_pack.cpp)
+bt_status update_packed(bt_atlas* a, const char* assets_root, uint32_t max_loads, uint32_t* loaded, uint32_t* failed);
+
 bt_status make_dirs(const std::string& dir);  // mkdir -p
 bt_status write_file(const std::string& path, const void* data, size_t bytes);
 void remove_tree(const std::string& dir);  // rm -r; a directory that does not exist is fine

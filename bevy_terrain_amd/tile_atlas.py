@@ -838,6 +838,64 @@ class TileAtlas:
         arr = (_ffi.TileCoordinateC * max(len(coords), 1))(*[c._c() for c in coords])
         _ffi.check(_ffi.lib().bt_atlas_save_tiles(self._h, attachment_index, directory.encode(), arr, len(coords)))
 
+    # --- packed tiles (the header's PACKED TILES section)
+    def pack_tiles(self, attachment_index: int, layers, sizes_only: bool = False, capacity: Optional[int] = None) -> Tuple[bytes, np.ndarray]:
+        """bt_atlas_pack_tiles: the listed layers (any order, repeats allowed) encoded on the device.  Returns (bytes, offsets): stream i is
+        bytes[offsets[i]:offsets[i + 1]].  sizes_only: dst_host = NULL, bytes is empty.  capacity: the size of the buffer handed over (a
+        sizing call sets it otherwise); one that is too small raises BtError (BT_ERR_OVERFLOW) whose `offsets` attribute is filled."""
+        layers = np.ascontiguousarray(layers, dtype=np.uint32)
+        n = len(layers)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        lp, op = layers.ctypes.data_as(C.POINTER(C.c_uint32)), offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        if sizes_only or capacity is None:
+            _ffi.check(_ffi.lib().bt_atlas_pack_tiles(self._h, attachment_index, lp, n, None, 0, op))
+            if sizes_only:
+                return b"", offsets
+            capacity = int(offsets[n])
+        out = np.zeros(max(capacity, 1), dtype=np.uint8)
+        try:
+            _ffi.check(_ffi.lib().bt_atlas_pack_tiles(self._h, attachment_index, lp, n, out.ctypes.data_as(C.c_void_p), capacity, op))
+        except _ffi.BtError as e:
+            e.offsets = offsets
+            raise
+        return out[:int(offsets[n])].tobytes(), offsets
+
+    def unpack_tiles(self, attachment_index: int, layers, data, offsets):
+        """bt_atlas_unpack_tiles: stream i = data[offsets[i]:offsets[i + 1]] decoded on the device into layers[i], then the mip levels."""
+        layers = np.ascontiguousarray(layers, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offsets) != len(layers) + 1:
+            raise ValueError(f"unpack_tiles: {len(layers)} layers need {len(layers) + 1} offsets, not {len(offsets)}")
+        buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)  # (never an empty buffer)
+        if len(layers) and int(offsets.max()) > len(buf) - 1:
+            raise ValueError("unpack_tiles: offsets past the end of data")
+        _ffi.check(_ffi.lib().bt_atlas_unpack_tiles(self._h, attachment_index, layers.ctypes.data_as(C.POINTER(C.c_uint32)), len(layers),
+                                                    buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return self
+
+    def _packed_files(self, fn, attachment_index, directory, coords):
+        if coords is None:
+            _ffi.check(fn(self._h, attachment_index, directory.encode(), None, 0))
+        else:
+            coords = list(coords)
+            arr = (_ffi.TileCoordinateC * max(len(coords), 1))(*[c._c() for c in coords])
+            _ffi.check(fn(self._h, attachment_index, directory.encode(), arr, len(coords)))
+        return self
+
+    def save_tiles_packed(self, attachment_index: int, directory: str, coords=None):
+        """bt_atlas_save_tiles_packed: "{directory}/{coord}.btp" of the listed tiles; coords=None: every existing tile."""
+        return self._packed_files(_ffi.lib().bt_atlas_save_tiles_packed, attachment_index, directory, coords)
+
+    def load_tiles_packed(self, attachment_index: int, directory: str, coords=None):
+        """bt_atlas_load_tiles_packed: load_tiles for "{directory}/{coord}.btp", decoded on the device; coords=None: every tile of the
+        loaded tile config."""
+        return self._packed_files(_ffi.lib().bt_atlas_load_tiles_packed, attachment_index, directory, coords)
+
+    def set_tile_files(self, packed: bool):
+        """bt_atlas_set_tile_files: update() reads "{coord}.btp" (packed=True) or "{coord}.bin" (the default)."""
+        _ffi.check(_ffi.lib().bt_atlas_set_tile_files(self._h, _ffi.TILE_FILES_PACKED if packed else _ffi.TILE_FILES_BIN))
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             if device_open(getattr(self, "device", None)):
@@ -916,6 +974,21 @@ def generate_mipmaps(device: Device, fmt: AttachmentFormat, level0: np.ndarray, 
     _ffi.check(_ffi.lib().bt_generate_mipmaps(device._h, fmt.id(), T, mip_level_count, level0.ctypes.data_as(C.c_void_p),
                                               out.ctypes.data_as(C.c_void_p), out.nbytes))
     return out
+
+
+def packed_tile_bound(fmt: AttachmentFormat, texture_size: int) -> int:
+    """bt_packed_tile_bound: the largest packed stream of a texture_size^2 tile of `fmt` (needs no device)."""
+    out = C.c_uint64()
+    _ffi.check(_ffi.lib().bt_packed_tile_bound(fmt.id(), texture_size, C.byref(out)))
+    return out.value
+
+
+def packed_tile_check(data) -> Tuple[AttachmentFormat, int]:
+    """bt_packed_tile_check: (format, texture_size) of a valid packed stream; raises BtError naming the first violated rule (needs no device)."""
+    data = bytes(data)
+    fmt, size = C.c_uint32(), C.c_uint32()
+    _ffi.check(_ffi.lib().bt_packed_tile_check(C.c_char_p(data), len(data), C.byref(fmt), C.byref(size)))
+    return next(f for f in AttachmentFormat if f.id() == fmt.value), size.value
 
 
 def tc_encode(coords: List[TileCoordinate]) -> bytes:

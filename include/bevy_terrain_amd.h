@@ -2036,6 +2036,63 @@ bt_status bt_atlas_skyline(bt_atlas* atlas, uint32_t attachment_index, uint32_t 
                            uint8_t* count_out /* may be NULL */, const bt_skyline_bake* bake /* may be NULL */, bt_tile_coordinate* changed,
                            uint32_t changed_cap, bt_skyline_stats* stats /* may be NULL */);
 
+/* ---------------------------------------------------------------- PACKED TILES
+ * A lossless tile codec that the device encodes and decodes itself: only packed bytes cross the file system and PCIe, and the atlas ends
+ * up byte-identical to one loaded from `.bin`.  `.bin` stays the default everywhere; everything here is opt-in.
+ *
+ * One packed tile holds one layer of one attachment: T x T texels, R16 or Rgba8, self-contained.
+ * PLANES.  R16: one plane of b = 16-bit values.  Rgba8: four planes of b = 8-bit values, plane c being byte c of the texel.
+ * STRIPS.  The rows are cut into strips of S = BT_PACK_STRIP_ROWS rows (the last one shorter when T % S != 0), coded independently.
+ * RESIDUAL.  r = v(x, y) - v(x-1, y) - v(x, y-1) + v(x-1, y-1) (mod 2^b); a term with x-1 < 0, or whose row lies above the strip's first
+ * row, is 0.  Decoding is a 2-D inclusive prefix sum mod 2^b: along the row over the whole tile width, then down the columns of the strip.
+ * ZIGZAG.  r read as signed s in [-2^(b-1), 2^(b-1)): z = 2s for s >= 0, z = -2s - 1 otherwise; b bits again.
+ * GROUPS.  64 consecutive values of one row of one plane; gpr = ceil(T / 64) groups per row.  Lanes of the last group with x >= T have
+ * z = 0 when encoding; their bits are ignored when decoding.  The group's width w is the bit length of the largest z among its real
+ * lanes, 0 <= w <= b.  Its payload is w little-endian 64-bit words, bit i of word k being bit k of lane i's z (bit planes): 8 w bytes,
+ * always 8-byte aligned.  w = 0 costs nothing; w = b is the raw escape.
+ * ORDER.  Groups are ordered by (y, plane c, group g): index (y * planes + c) * gpr + g, for the widths and for the payload.
+ * STREAM (= the file "{coord}.btp").  Bytes 0-3 'B' 'T' 'P' '1'; 4 the format (BT_FORMAT_R16 / BT_FORMAT_RGBA8); 5 the strip rows (32);
+ * 6-7 T, u16 LE; 8-11 the payload bytes, u32 LE; 12-15 zero; then W = planes * T * gpr width bytes, one per group; zero bytes up to a
+ * multiple of 8; then the 8 * sum(w) payload bytes.  There is no offset table: offsets are prefix sums of the widths.
+ * CANONICAL AND ACCEPTED.  The encoder emits the minimal w, so a tile has exactly one encoding, byte-identical from run to run; the
+ * decoder accepts any w <= b.
+ * VALIDITY, all checked on the host before anything is launched (after that no device read can leave the stream): size >= 16; the magic;
+ * the format one of the two; strip rows == 32; T >= 1; bytes 12-15 and the padding zero; every width <= b; the payload field == 8 sum(w);
+ * the size == 16 + pad8(W) + payload.
+ * BOUND.  bound(format, T) = 16 + pad8(W) + 8 b W: the raw size plus one byte per 64 values plus at most 23.
+ *
+ * bt_packed_tile_bound / bt_packed_tile_check need no device.  check: BT_ERR_IO with a text naming the first violated rule;
+ * BT_ERR_UNSUPPORTED for a header whose format (Rg16 / Rgb8) or strip height this version does not read; format / texture_size (each may
+ * be NULL) are filled once the header's fields are readable.
+ *
+ * bt_atlas_pack_tiles: the listed layers (any order, repeats allowed) -> streams, stream i at dst_host + offsets[i], offsets[count] the
+ * total.  dst_host == NULL fills `offsets` only; a dst_bytes that is too small is BT_ERR_OVERFLOW with `offsets` still filled.  A read
+ * (not a write for bt_run_stats.prev_zero_launches).  Three launches per chunk (measure, scan, emit), no atomics.
+ * bt_atlas_unpack_tiles: the inverse, stream i (offsets[i] .. offsets[i+1]) into layers[i], followed by the mip levels of those layers;
+ * the layers count as written exactly as after bt_atlas_load_tiles.  A repeated layer, a layer out of range, a stream whose format or T
+ * is not the attachment's: BT_ERR_INVALID_ARGUMENT; an invalid stream: what bt_packed_tile_check says; in each case no layer is touched.
+ * bt_atlas_save_tiles_packed / bt_atlas_load_tiles_packed: bt_atlas_save_tiles / bt_atlas_load_tiles for "{directory}/{coord}.btp";
+ * coords == NULL: every existing tile.  A missing or invalid file is BT_ERR_IO.
+ * bt_atlas_set_tile_files: what bt_atlas_update reads, "{coord}.bin" (BT_TILE_FILES_BIN, the default) or "{coord}.btp"
+ * (BT_TILE_FILES_PACKED, decoded on the device batch by batch); a missing or invalid file leaves the tile Loading and counts as failed.
+ * All of them work in chunks of at most 64 tiles or 32 MiB of raw texels through the context's staging ring; the scratch stays in the
+ * context until bt_ctx_trim.  NULL handles or required pointers: BT_ERR_INVALID_ARGUMENT.  Attachments that are not R16 / Rgba8, a
+ * texture_size above 65535 or a tile whose bound does not fit the payload field: BT_ERR_UNSUPPORTED.  count == 0: BT_OK (offsets[0] = 0). */
+#define BT_PACK_STRIP_ROWS 32u
+#define BT_TILE_FILES_BIN 0u
+#define BT_TILE_FILES_PACKED 1u
+bt_status bt_packed_tile_bound(uint32_t format, uint32_t texture_size, uint64_t* bytes);
+bt_status bt_packed_tile_check(const void* bytes, uint64_t size, uint32_t* format /* may be NULL */, uint32_t* texture_size /* may be NULL */);
+bt_status bt_atlas_pack_tiles(bt_atlas* atlas, uint32_t attachment_index, const uint32_t* layers, uint32_t count, void* dst_host /* may be NULL */,
+                              uint64_t dst_bytes, uint64_t* offsets /* count + 1 */);
+bt_status bt_atlas_unpack_tiles(bt_atlas* atlas, uint32_t attachment_index, const uint32_t* layers, uint32_t count, const void* src_host,
+                                const uint64_t* offsets /* count + 1 */);
+bt_status bt_atlas_save_tiles_packed(bt_atlas* atlas, uint32_t attachment_index, const char* directory, const bt_tile_coordinate* coords /* may be NULL */,
+                                     uint32_t count);
+bt_status bt_atlas_load_tiles_packed(bt_atlas* atlas, uint32_t attachment_index, const char* directory, const bt_tile_coordinate* coords /* may be NULL */,
+                                     uint32_t count);
+bt_status bt_atlas_set_tile_files(bt_atlas* atlas, uint32_t tile_files);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Exhaustive device check that the kernels' 3-operation unorm16 -> f32 conversion equals the correctly
  * rounded division t / 65535.0f for all 65536 texel values; *failures must come back 0. */
