@@ -367,6 +367,34 @@ class SkylineStatsC(C.Structure):
                 ("edit", EditStatsC)]
 
 
+SHAPES_NONE, SHAPES_NO_ENTRY, SHAPES_MAX_SHAPES, SHAPES_MAX_ENTRIES, SHAPES_MAX_VERTICES = 0xFFFF, 0xFFFFFFFF, 4096, 65536, 1 << 20
+SHAPES_MAX_COORD, SHAPES_MAX_HALF_WIDTH, SHAPES_MAX_SIDE, SHAPES_MAX_CELLS = 1 << 23, 1 << 20, 8192, 1 << 22
+# bt_shapes.hip: the edges of a chunk of vertices in LDS and the cells of a workgroup's block; tests place contours and windows around them
+SHAPES_CHUNK, SHAPES_BLOCK_W, SHAPES_BLOCK_H = 256, 64, 16
+SHAPE_POLYGON, SHAPE_STROKE = 0, 1
+SHAPE_NONZERO, SHAPE_CLOSED, SHAPE_MORE = 1, 2, 4
+SHAPE_SET, SHAPE_MAX, SHAPE_MIN, SHAPE_ADD, SHAPE_SUB = 0, 1, 2, 3, 4
+SHAPES_DRY_RUN = 1
+
+
+class ShapeVertexC(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32)]
+
+
+class ShapeC(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("first_vertex", C.c_uint32), ("vertex_count", C.c_uint32), ("half_width", C.c_uint32),
+                ("op", C.c_uint32), ("value", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class ShapeBoxC(C.Structure):
+    _fields_ = [("x_lo", C.c_uint16), ("y_lo", C.c_uint16), ("x_hi", C.c_uint16), ("y_hi", C.c_uint16)]
+
+
+class ShapesStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("shapes", C.c_uint32), ("shapes_culled", C.c_uint32), ("tiles_missing", C.c_uint32), ("covered", C.c_uint64),
+                ("written", C.c_uint64), ("box", ShapeBoxC), ("launches", C.c_uint32), ("_padding", C.c_uint32), ("edit", EditStatsC)]
+
+
 class ErosionStatsC(C.Structure):
     _fields_ = [("cells", C.c_uint32), ("tiles_missing", C.c_uint32), ("steps", C.c_uint32), ("sim_launches", C.c_uint32), ("edit", EditStatsC)]
 
@@ -460,6 +488,9 @@ PROTOTYPES = {
     "bt_skyline_line_count": (_i32, [_u32, _u32, C.c_int32, C.c_int32, _P(_u32), _P(_u32)]),
     "bt_atlas_skyline": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(SkylineDirectionC), _u32, _P(C.c_uint16), _P(C.c_int32), _P(C.c_uint64),
                                 _P(C.c_uint8), _P(SkylineBakeC), _P(TileCoordinateC), _u32, _P(SkylineStatsC)]),
+    "bt_shapes_check": (_i32, [_P(ShapeVertexC), _u32, _P(ShapeC), _u32, _u32, _u32, _P(ShapeBoxC), _P(_u32), _P(_u32)]),
+    "bt_atlas_rasterize_shapes": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ShapeVertexC), _u32, _P(ShapeC), _u32, _u32, _P(C.c_uint8),
+                                         _P(C.c_uint16), _P(TileCoordinateC), _u32, _P(ShapesStatsC)]),
     "bt_packed_tile_bound": (_i32, [_u32, _u32, _P(_u64)]),
     "bt_packed_tile_check": (_i32, [_vp, _u64, _P(_u32), _P(_u32)]),
     "bt_atlas_pack_tiles": (_i32, [_vp, _u32, _P(_u32), _u32, _vp, _u64, _P(_u64)]),

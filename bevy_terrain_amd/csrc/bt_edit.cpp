@@ -1175,6 +1175,115 @@ bt_status bt_atlas_skyline(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod
     return rc;
 }
 
+// The call of the SHAPES section of the header (the kernel: bt_shapes.hip; the rules, the boxes and the records: bt_shapes.cpp).  It lives
+// here for the write-back, as bt_atlas_distance_field does.
+bt_status bt_atlas_rasterize_shapes(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t channel,
+                                    const bt_shape_vertex* vertices, uint32_t vertex_count, const bt_shape* shapes, uint32_t entry_count, uint32_t flags, uint8_t* count_out,
+                                    uint16_t* last_out, bt_tile_coordinate* changed, uint32_t changed_cap, bt_shapes_stats* stats) {
+    const char* who = "bt_atlas_rasterize_shapes";
+    if (stats) *stats = bt_shapes_stats{};
+    if (!a || (changed_cap && !changed)) {
+        set_error("%s: NULL %s", who, !a ? "atlas" : "changed with changed_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, who)) return s;
+    const Attachment& at = a->attachments[ai];
+    const bool wide = at.meta.format == BT_FORMAT_RGBA8;
+    const char* bad = (flags & ~uint32_t(BT_SHAPES_DRY_RUN)) != 0u                      ? "unknown flag bits"
+                      : channel > (wide ? 3u : 0u)                                      ? "channel (0..3 on Rgba8, 0 on R16)"
+                      : (!vertices && vertex_count) || (!shapes && entry_count)         ? "NULL vertices or shapes with a non-zero count"
+                                                                                        : nullptr;
+    if (bad) {
+        set_error("%s: %s (channel %u, flags %#x)", who, bad, channel, flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (width > BT_SHAPES_MAX_SIDE || height > BT_SHAPES_MAX_SIDE) {
+        set_error("%s: a side of %u x %u above %u", who, width, height, BT_SHAPES_MAX_SIDE);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t cells = uint64_t(width) * height;
+    if (cells > BT_SHAPES_MAX_CELLS) {
+        set_error("%s: %u x %u cells, at most %u", who, width, height, BT_SHAPES_MAX_CELLS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (!cells || !entry_count) return BT_OK;  // an empty window or an empty list: nothing to do
+    std::vector<ShapeRecord> records;
+    uint32_t shape_count = 0, bad_entry = BT_SHAPES_NO_ENTRY;
+    const char* defect = shapes_check(vertices, vertex_count, shapes, entry_count, width, height, nullptr, &records, &shape_count, &bad_entry);
+    if (!defect && wide)
+        for (uint32_t i = 0; i < entry_count && !defect; i++)
+            if (shapes[i].value > 255u) defect = "value above 255 on Rgba8", bad_entry = i;
+    if (defect) {
+        if (bad_entry != BT_SHAPES_NO_ENTRY)
+            set_error("%s: entry %u: %s", who, bad_entry, defect);
+        else
+            set_error("%s: %s", who, defect);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+
+    // the planes outside U; U's part is staged over them
+    if (count_out) memset(count_out, 0, cells);
+    if (last_out) memset(last_out, 0xFF, cells * 2u);
+    bt_shape_box u{1, 1, 0, 0};
+    for (const ShapeRecord& r : records) {
+        if (u.x_lo > u.x_hi) u = r.box;
+        u.x_lo = std::min(u.x_lo, r.box.x_lo), u.y_lo = std::min(u.y_lo, r.box.y_lo), u.x_hi = std::max(u.x_hi, r.box.x_hi), u.y_hi = std::max(u.y_hi, r.box.y_hi);
+    }
+    if (stats) stats->cells = uint32_t(cells), stats->shapes = shape_count, stats->shapes_culled = shape_count - uint32_t(records.size()), stats->box = u;
+    if (records.empty()) return BT_OK;  // U is empty: nothing is written
+
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const uint32_t uw = uint32_t(u.x_hi) - u.x_lo + 1u, uh = uint32_t(u.y_hi) - u.y_lo + 1u, ux0 = x0 + u.x_lo, uy0 = y0 + u.y_lo;
+    const uint64_t ucells = uint64_t(uw) * uh;
+    const uint64_t vertex_bytes = uint64_t(vertex_count) * sizeof(bt_shape_vertex), entry_bytes = uint64_t(entry_count) * sizeof(bt_shape),
+                   record_bytes = records.size() * sizeof(ShapeRecord);
+    const uint64_t at_vertices = 0, at_entries = at_vertices + align256(vertex_bytes), at_records = at_entries + align256(entry_bytes), at_count = at_records + align256(record_bytes),
+                   at_last = at_count + align256(ucells), total = at_last + align256(ucells * 2u);
+    if (bt_status s = ctx->shapes.reserve(ctx, total)) return s;
+    if (bt_status s = ctx->shapes_words.reserve(ctx, 256, true)) return s;
+    if (bt_status s = ctx->edit_region.reserve(ctx, ucells * at.meta.pixel_size)) return s;
+    uint8_t* base = (uint8_t*)ctx->shapes.dev;
+    ShapesJob job{};
+    job.vertices = (const bt_shape_vertex*)(base + at_vertices), job.entries = (const bt_shape*)(base + at_entries), job.records = (const ShapeRecord*)(base + at_records);
+    job.record_count = uint32_t(records.size()), job.wide = wide, job.shift = 8u * channel, job.u = u;
+    job.texels = ctx->edit_region.dev, job.count = base + at_count, job.last = (uint16_t*)(base + at_last);
+    job.counts = (ShapesCounts*)ctx->shapes_words.dev;
+    const ShapesCounts* counts_host = (const ShapesCounts*)ctx->shapes_words.host;
+
+    uint32_t tiles_missing = 0;
+    if (bt_status s = region_gather(a, ai, side, lod, ux0, uy0, uw, uh, job.texels, &tiles_missing)) return s;
+    // the three arrays, each as one row
+    if (bt_status s = region_stage_in(ctx, base + at_vertices, vertices, vertex_bytes, vertex_bytes, 1)) return s;
+    if (bt_status s = region_stage_in(ctx, base + at_entries, shapes, entry_bytes, entry_bytes, 1)) return s;
+    if (bt_status s = region_stage_in(ctx, base + at_records, records.data(), record_bytes, record_bytes, 1)) return s;
+    BT_HIP(hipMemsetAsync(job.counts, 0, sizeof(ShapesCounts), stream));
+    if (bt_status s = launch_shapes_raster(stream, job)) return s;
+    BT_HIP(hipMemcpyAsync((void*)counts_host, job.counts, sizeof(ShapesCounts), hipMemcpyDeviceToHost, stream));
+    const char* what = "bt_atlas_rasterize_shapes staging";
+    const uint64_t origin = uint64_t(u.y_lo) * width + u.x_lo;
+    if (count_out)
+        if (bt_status s = region_stage_out(ctx, job.count, count_out + origin, uw, width, uh, what)) return s;
+    if (last_out)
+        if (bt_status s = region_stage_out(ctx, job.last, last_out + origin, uint64_t(uw) * 2u, uint64_t(width) * 2u, uh, what)) return s;
+    bt_edit_stats edit{};
+    bt_status rc = BT_OK;
+    if (!(flags & BT_SHAPES_DRY_RUN)) {
+        FirstStep first{FirstStep::kRegion};  // texels nullptr: the rectangle is on the device
+        first.x0 = ux0, first.y0 = uy0, first.width = uw, first.height = uh;
+        rc = edit_boxes(a, ai, lod, {Box{side, {ux0, uy0, ux0 + uw - 1u, uy0 + uh - 1u}}}, first, changed, changed_cap, &edit);
+    }
+    const bt_status drained = ctx->staging.drain();  // the staging copies of the list
+    BT_HIP(hipStreamSynchronize(stream));
+    if (stats) {
+        stats->tiles_missing = tiles_missing, stats->covered = counts_host->covered, stats->written = counts_host->written;
+        stats->launches = 2u;  // the gather and the raster
+        stats->edit = edit;
+    }
+    return rc ? rc : drained;
+}
+
 bt_status bt_atlas_save_tiles(bt_atlas* a, uint32_t ai, const char* directory, const bt_tile_coordinate* coords, uint32_t count) {
     if (!a || !directory || (count && !coords)) {
         set_error("bt_atlas_save_tiles: NULL %s", !a ? "atlas" : !directory ? "directory" : "coords");

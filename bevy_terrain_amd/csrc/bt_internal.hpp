@@ -276,10 +276,13 @@ struct bt_ctx {
     // the packed tile calls (bt_pack.cpp): the streams, strip offsets and strip sizes of one chunk on the device; and the stream starts
     // of a packed chunk with a pinned twin
     bt::Scratch pack, pack_words;
-    std::array<bt::Scratch*, 19> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_rasterize_shapes: the vertices, the entries, the shape records and the two planes of U on the device; and the counts of
+    // bt_shapes_stats with a pinned twin
+    bt::Scratch shapes, shapes_words;
+    std::array<bt::Scratch*, 21> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
         return {&bounds, &raycast,     &normal,   &render,         &edit_region, &path,           &path_words, &scatter,      &erode,
                 &drain,  &drain_words, &viewshed, &viewshed_words, &distance,    &distance_words, &skyline,    &skyline_words,
-                &pack,   &pack_words};
+                &pack,   &pack_words,  &shapes,   &shapes_words};
     }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
@@ -679,6 +682,37 @@ bt_status launch_skyline_transpose(hipStream_t stream, const SkylinePlanes& p);
 bt_status launch_skyline_walk(hipStream_t stream, const SkylinePlanes& p);
 // the batch's bits into the mask and the running counts; last: count, the void count and the baked byte
 bt_status launch_skyline_finish(hipStream_t stream, const SkylinePlanes& p, const SkylineBake& bake, bool last, SkylineCounts* counts);
+
+// bt_shapes.cpp / bt_shapes.hip: bt_shapes_check's rules and the raster kernel of bt_atlas_rasterize_shapes (SHAPES in the header)
+struct ShapeRecord {  // one shape with a box inside the window, as the kernel reads it (uniformly)
+    uint32_t first_entry, entry_count;  // of the entry array
+    bt_shape_box box;                   // in cells of the window
+    uint32_t k;                         // the shape's number in the list
+    uint32_t kind, flags, op, value;    // of its entries (they agree)
+    uint32_t half_width;
+};
+static_assert(sizeof(ShapeRecord) == 40, "ten words");
+struct ShapesCounts {  // the device words of bt_shapes_stats
+    unsigned long long covered, written;
+};
+struct ShapesJob {
+    const bt_shape_vertex* vertices;
+    const bt_shape* entries;
+    const ShapeRecord* records;
+    uint32_t record_count;
+    uint32_t wide;           // 1: Rgba8 texels
+    uint32_t shift;          // of the texel to its channel: 8 * channel
+    bt_shape_box u;          // the written rectangle, in cells of the window
+    void* texels;            // U's texels, (u.x_hi - u.x_lo + 1) a row: u16 (R16) or u32 (Rgba8); folded in place
+    uint8_t* count;          // U's planes, rows as the texels'
+    uint16_t* last;
+    ShapesCounts* counts;
+};
+// The first defect of a list as text (nullptr: none) and *bad_entry, the entry it names (BT_SHAPES_NO_ENTRY: not one entry's).  boxes
+// (may be nullptr): one per shape; records (may be nullptr): the shapes whose box is not empty, in list order; *shape_count: all shapes
+const char* shapes_check(const bt_shape_vertex* vertices, uint32_t vertex_count, const bt_shape* shapes, uint32_t entry_count, uint32_t width, uint32_t height,
+                         bt_shape_box* boxes, std::vector<ShapeRecord>* records, uint32_t* shape_count, uint32_t* bad_entry);
+bt_status launch_shapes_raster(hipStream_t stream, const ShapesJob& job);
 
 // bt_pack.hip: the kernels of the packed tile calls (the format: PACKED TILES in the header).  One wave per strip of a tile; a chunk holds
 // at most kPackChunk tiles, whose layers and stream starts travel in the kernel arguments

@@ -786,6 +786,76 @@ class TileAtlas:
         out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
         return (*outs, out)
 
+    _SHAPE_OPS = {"set": _ffi.SHAPE_SET, "max": _ffi.SHAPE_MAX, "min": _ffi.SHAPE_MIN, "add": _ffi.SHAPE_ADD, "sub": _ffi.SHAPE_SUB}
+
+    @staticmethod
+    def pack_shapes(shapes, fixed: bool = False):
+        """Python shapes -> (vertices, entries) as bt_atlas_rasterize_shapes takes them: an (N, 2) int32 array and an (E, 8) uint32 array
+        in the field order of bt_shape.  A shape is a dict.  {"polygon": ring or [outer, hole, ...], "nonzero": False, "op": "set",
+        "value": 1}: a ring is a list of (x, y); every ring becomes one contour, linked by BT_SHAPE_MORE.  {"stroke": [(x, y), ...],
+        "half_width": r, "closed": False, "op": "set", "value": 1}.  op: "set", "max", "min", "add", "sub" or the BT_SHAPE_* number.
+        Coordinates and half_width are floats in cells relative to the window's origin, a texel's centre being the integer itself.  THE
+        ROUNDING, made once, here: v -> floor(256 v + 0.5), to the nearest 1/256 cell, a half upwards; from then on everything is exact.
+        fixed=True: the numbers are already integers in 1/256 cell and are taken as they are."""
+        q = (lambda v: int(v)) if fixed else (lambda v: int(math.floor(float(v) * 256.0 + 0.5)))
+        vertices, entries = [], []
+        for s in shapes:
+            op = s.get("op", "set")
+            op = TileAtlas._SHAPE_OPS[op] if isinstance(op, str) else int(op)
+            value = int(s.get("value", 1))
+            if "polygon" in s:
+                rings = s["polygon"]
+                if len(rings) and not isinstance(rings[0][0], (tuple, list, np.ndarray)):
+                    rings = [rings]
+                for i, ring in enumerate(rings):
+                    flags = (_ffi.SHAPE_NONZERO if s.get("nonzero") else 0) | (_ffi.SHAPE_MORE if i + 1 < len(rings) else 0)
+                    entries.append((_ffi.SHAPE_POLYGON, flags, len(vertices), len(ring), 0, op, value, 0))
+                    vertices += [(q(x), q(y)) for x, y in ring]
+            else:
+                points = s["stroke"]
+                entries.append((_ffi.SHAPE_STROKE, _ffi.SHAPE_CLOSED if s.get("closed") else 0, len(vertices), len(points), q(s.get("half_width", 0)), op, value, 0))
+                vertices += [(q(x), q(y)) for x, y in points]
+        return np.array(vertices, dtype=np.int32).reshape(-1, 2), np.array(entries, dtype=np.uint32).reshape(-1, 8)
+
+    @staticmethod
+    def check_shapes(vertices: np.ndarray, entries: np.ndarray, w: int, h: int):
+        """bt_shapes_check, without a device: (boxes, shapes) of a packed list for a w x h window, boxes an (shapes, 4) uint16 array of
+        (x_lo, y_lo, x_hi, y_hi) in cells, (1, 1, 0, 0) for an empty one.  A list that breaks a rule raises BtError naming the entry."""
+        vertices, entries = np.ascontiguousarray(vertices, dtype=np.int32), np.ascontiguousarray(entries, dtype=np.uint32)
+        boxes = np.zeros((max(len(entries), 1), 4), dtype=np.uint16)
+        count = C.c_uint32()
+        _ffi.check(_ffi.lib().bt_shapes_check(vertices.ctypes.data_as(C.POINTER(_ffi.ShapeVertexC)), len(vertices), entries.ctypes.data_as(C.POINTER(_ffi.ShapeC)),
+                                              len(entries), w, h, boxes.ctypes.data_as(C.POINTER(_ffi.ShapeBoxC)), C.byref(count), None))
+        return boxes[:count.value].copy(), count.value
+
+    def rasterize_shapes(self, attachment_index: int, x0: int, y0: int, w: int, h: int, shapes, *, channel: int = 0, lod: Optional[int] = None, side: int = 0,
+                         dry_run: bool = False, fixed: bool = False, count: bool = True, last: bool = True):
+        """bt_atlas_rasterize_shapes: polygons (with holes) and strokes rasterised into the w x h window of centre texels at mosaic position
+        (x0, y0) of `lod` on `side` of an R16 or Rgba8 attachment (byte `channel` of an Rgba8 texel), by the header's SHAPES section, in
+        integers.  shapes: a list of dicts as pack_shapes takes them (floats in cells, rounded once to 1/256 cell; fixed=True: integers in
+        1/256 cell), or a (vertices, entries) pair packed already.  Every shape that covers a cell folds its op and value into the texel in
+        list order; the written rectangle is the union of the shapes' boxes, and the atlas is updated as by write_region of it.  Returns
+        (count, last, stats): count (h, w) uint8, the shapes that cover each cell, capped at 255; last (h, w) uint16, the last of them,
+        SHAPES_NONE where none does; stats: bt_shapes_stats as a dict, "box" as (x_lo, y_lo, x_hi, y_hi), "edit" the bt_edit_stats of the
+        write-back and "changed" the changed tiles.  count / last False: that plane is not copied out and None comes back.  dry_run: the
+        planes and the counts only; nothing is written.  Ordered behind the queued work; synchronous."""
+        lod = self.lod_count - 1 if lod is None else lod
+        vertices, entries = shapes if isinstance(shapes, tuple) else self.pack_shapes(shapes, fixed)
+        vertices, entries = np.ascontiguousarray(vertices, dtype=np.int32), np.ascontiguousarray(entries, dtype=np.uint32)
+        outs = [np.zeros((h, w), dtype=t) if want else None for t, want in ((np.uint8, count), (np.uint16, last))]
+        cap = max(self.atlas_size, 1)
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.ShapesStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_rasterize_shapes(
+            self._h, attachment_index, side, lod, x0, y0, w, h, channel, vertices.ctypes.data_as(C.POINTER(_ffi.ShapeVertexC)), len(vertices),
+            entries.ctypes.data_as(C.POINTER(_ffi.ShapeC)), len(entries), _ffi.SHAPES_DRY_RUN if dry_run else 0,
+            *[o.ctypes.data_as(C.POINTER(t)) if o is not None else None for o, t in zip(outs, (C.c_uint8, C.c_uint16))], changed, cap, C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.ShapesStatsC._fields_ if name not in ("edit", "_padding", "box")}
+        out["box"] = (stats.box.x_lo, stats.box.y_lo, stats.box.x_hi, stats.box.y_hi)
+        out["edit"] = {name: getattr(stats.edit, name) for name, _ in _ffi.EditStatsC._fields_}
+        out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
+        return (*outs, out)
+
     def erode_height(self, attachment_index: int, x0: int, y0: int, w: int, h: int, params: "ErosionParams", weight: Optional[np.ndarray] = None,
                      water: Optional[np.ndarray] = None, sediment: Optional[np.ndarray] = None, lod: Optional[int] = None, side: int = 0):
         """bt_atlas_erode_height: hydraulic erosion.  Runs params.steps steps of the simulation the header's EROSION section defines over the

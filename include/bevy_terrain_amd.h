@@ -2036,6 +2036,123 @@ bt_status bt_atlas_skyline(bt_atlas* atlas, uint32_t attachment_index, uint32_t 
                            uint8_t* count_out /* may be NULL */, const bt_skyline_bake* bake /* may be NULL */, bt_tile_coordinate* changed,
                            uint32_t changed_cap, bt_skyline_stats* stats /* may be NULL */);
 
+/* ---------------- shapes: polygons and strokes rasterised into a rectangle of a layer, exactly
+ * SHAPES (bt_atlas_rasterize_shapes, bt_shapes_check; R16 and Rgba8).  Integers throughout: no float appears and there is no tolerance
+ * anywhere, so every plane and every texel is a function of the input byte for byte.
+ * Window: the width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of attachment attachment_index (the rectangle
+ * of bt_atlas_read_region; inside one face).  Cell (cx, cy) is mosaic texel (x0 + cx, y0 + cy); planes are row-major, cell (cx, cy) at
+ * index cy * width + cx.  Bounds: width, height <= BT_SHAPES_MAX_SIDE; width * height <= BT_SHAPES_MAX_CELLS.
+ * Coordinates: bt_shape_vertex {x, y}, int32, in units of 1/256 cell relative to the window's origin.  The sample point of cell (cx, cy)
+ * is P = (256 cx, 256 cy): as for the brushes, a texel's position is the integer itself.  |x|, |y| <= BT_SHAPES_MAX_COORD = 2^23, so a
+ * shape may lie partly or wholly outside the window.  Widths: a difference of two points is below 2^25 and fits int32; a dot or cross
+ * product of two differences is below 2^51 and fits int64; the square of a cross product needs 128 bits.
+ * Entries and shapes.  The list is an array of bt_shape {kind, flags, first_vertex, vertex_count, half_width, op, value, _pad}, 32 bytes
+ * each; an entry's vertices are vertices[first_vertex .. first_vertex + vertex_count).  kind: BT_SHAPE_POLYGON (one contour) or
+ * BT_SHAPE_STROKE (a polyline with a width).  flags: BT_SHAPE_NONZERO (polygon: the non-zero fill rule; otherwise even-odd),
+ * BT_SHAPE_MORE (polygon: the next entry is a further contour of the same polygon), BT_SHAPE_CLOSED (stroke).  A SHAPE is a stroke entry
+ * or a maximal run of polygon entries linked by MORE; the entries of a run agree in kind, op, value and NONZERO, and the last entry of
+ * the list does not carry MORE.  Shapes are numbered k = 0, 1, ... in list order.  Limits: at most BT_SHAPES_MAX_SHAPES shapes,
+ * BT_SHAPES_MAX_ENTRIES entries and BT_SHAPES_MAX_VERTICES vertices; a contour has >= 3 vertices and a stroke >= 1; half_width <=
+ * BT_SHAPES_MAX_HALF_WIDTH (1/256 cell) and is 0 on a polygon; value <= 65535; _pad is 0; vertex ranges lie inside the array.
+ * Coverage of P by a polygon.  The winding number w is a sum over every contour of the shape and every edge a -> b of it (consecutive
+ * vertices, the last back to the first).  With c = (b - a) x (P - a) = (b.x - a.x)(P.y - a.y) - (b.y - a.y)(P.x - a.x) in int64:
+ *     +1 when a.y <= P.y < b.y and c > 0;        -1 when b.y <= P.y < a.y and c < 0.
+ * P is covered when w != 0 (NONZERO) or w is odd (even-odd).  Hence a horizontal edge never counts; a sample point exactly on an edge or
+ * a vertex is decided by the rule alone (the axis-aligned square with corners on the sample points (2, 2) and (6, 6) covers the cells
+ * 2..5 on both axes, whichever way round it is listed); reversing a contour negates w.
+ * Coverage of P by a stroke, r = half_width.  Its segments are (v_i, v_i+1); with CLOSED and n >= 2 also (v_n-1, v_0); with n == 1 the
+ * degenerate (v_0, v_0).  P is covered when some segment a, b passes: with d = b - a, e = P - a, L = d.d, t = e.d,
+ *     L == 0 or t <= 0:  e.e <= r^2;       t >= L:  (P - b).(P - b) <= r^2;       otherwise:  (d x e)^2 <= r^2 L, compared in 128 bits.
+ * Round caps and round joins follow from the union; r = 0 covers exactly the sample points that lie on a segment.
+ * Planes.  count(c) = min(255, the number of shapes that cover c) (u8).  last(c) = the largest k that covers c, BT_SHAPES_NONE when none
+ * does (u16).
+ * Fold.  The running value starts at the texel's value, and the shapes that cover the cell apply in list order: op BT_SHAPE_SET (value),
+ * _MAX, _MIN, _ADD (running + value), _SUB (running - value).  R16: a texel equal to 0 (no data) is never changed and every result is
+ * clamped to [1, 65535]: holes are neither filled nor made, as with the brushes.  Rgba8: `channel` 0..3 selects the byte, value <= 255,
+ * the result is clamped to [0, 255], the other three bytes keep their values; there is no hole rule, as with the distance field's bake.
+ * Boxes.  The box of shape k, per axis, over all its vertices, with r = half_width (0 for a polygon) and n = width or height:
+ *     lo = max(0, ceil((min - r) / 256)),   hi = min(n - 1, floor((max + r) / 256)),   the division mathematical;
+ * empty when lo > hi on either axis, written {1, 1, 0, 0}.  No cell outside its box is covered.  Stroke: a covered P lies within r of a
+ * point of a segment, hence within r of [min, max] on each axis.  Polygon: an edge counts only with P.y in its y-range, and only when it
+ * meets the row of P strictly to the right of P (c = (b.y - a.y)(x_edge - P.x)), so beyond max x nothing counts, and before min x every
+ * edge in range counts, which sums to 0 on a closed contour.
+ * bt_shapes_check validates a list by the rules above and writes the boxes (boxes_out, one per shape, may be NULL), the number of shapes
+ * (shape_count_out, may be NULL) and, on a refusal, the index of the offending entry (bad_entry_out, may be NULL; BT_SHAPES_NO_ENTRY
+ * when the defect is not one entry's, and on success), without a device; the device call uses the same function.
+ * The write.  U = the union box of all shapes.  Without BT_SHAPES_DRY_RUN the texels of U are gathered, folded on the device and
+ * written, and the invariant F restored exactly as by bt_atlas_write_region of those texels over U: the same plan, the same `changed`
+ * order, the same bt_edit_stats (stats->edit).  Time is proportional to U, not to the window.  With U empty: BT_OK, nothing written.
+ * With DRY_RUN the call is a read: no layer is marked written, `changed` is not written, stats->edit is zero; both planes are produced.
+ * Outputs: count_out (u8) and last_out (u16), width * height, row-major, each may be NULL; outside U they are 0 and BT_SHAPES_NONE.
+ * bt_shapes_stats: cells = width * height; shapes; shapes_culled = shapes with an empty box; covered = cells with count > 0; written =
+ * texels of U whose folded value differs from the gathered one; tiles_missing = tiles of U the atlas does not hold (their texels are
+ * gathered as 0, folded and counted like any other, and not stored); box = U.  Every field but launches is a function of the input.
+ * The call: synchronous, host arrays in and out through the context's staging ring, ordered behind the work queued on the context's
+ * stream.  Launches: the gather of U (counted as one) and ONE raster launch: launches = 2, or 0 when U is empty; the launches of the
+ * edit follow in stats->edit.launches.  The count depends on the arguments only.  The raster: a workgroup of 256 lanes owns a block of
+ * BT_SHAPES_BLOCK_W x BT_SHAPES_BLOCK_H cells of U, a lane BT_SHAPES_BLOCK_H / 4 cells of one column, whose running value, count, last
+ * and winding number stay in registers across the whole list.  The shapes are walked in list order; one whose box misses the block is
+ * skipped.  Vertices are staged through LDS BT_SHAPES_CHUNK edges at a time (the chunk also holds the end of its last edge, so an edge
+ * that spans two chunks and the closing edge need nothing special).  A wave tests 64 edges of the chunk at a time, a lane to an edge,
+ * and walks only those that can touch its cells: an edge whose y-range misses the wave's rows is skipped, and one that lies wholly to
+ * one side of the block is resolved without the cross product; neither changes a result.  No atomics but one add
+ * per workgroup to each of `covered` and `written`.  No result depends on a schedule.  The scratch stays in the context until
+ * bt_ctx_trim: the vertices, the entries, 32 bytes per shape, and 3 bytes and a texel per cell of U.
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL vertices or shapes with a non-zero count; everything
+ * bt_shapes_check refuses (the message names the entry); a channel above 3, or non-zero on R16; a value above 255 on Rgba8; unknown
+ * bits in `flags`; a side above BT_SHAPES_MAX_SIDE; width * height above BT_SHAPES_MAX_CELLS; NULL changed with changed_cap > 0.
+ * BT_ERR_UNSUPPORTED: an odd centre size; Rg16 or Rgb8.  entry_count == 0, width == 0 or height == 0 (with valid arguments otherwise;
+ * the list is not looked at): BT_OK, nothing touched. */
+#define BT_SHAPES_NONE 0xFFFFu
+#define BT_SHAPES_NO_ENTRY 0xFFFFFFFFu
+#define BT_SHAPES_MAX_SHAPES 4096u
+#define BT_SHAPES_MAX_ENTRIES 65536u
+#define BT_SHAPES_MAX_VERTICES (1u << 20)
+#define BT_SHAPES_MAX_COORD (1 << 23)
+#define BT_SHAPES_MAX_HALF_WIDTH (1u << 20)
+#define BT_SHAPES_MAX_SIDE 8192u
+#define BT_SHAPES_MAX_CELLS (1u << 22)
+#define BT_SHAPES_CHUNK 256u
+#define BT_SHAPES_BLOCK_W 64u
+#define BT_SHAPES_BLOCK_H 16u
+enum { BT_SHAPE_POLYGON = 0, BT_SHAPE_STROKE = 1 };                         /* bt_shape.kind */
+enum { BT_SHAPE_NONZERO = 1, BT_SHAPE_CLOSED = 2, BT_SHAPE_MORE = 4 };      /* bt_shape.flags */
+enum { BT_SHAPE_SET = 0, BT_SHAPE_MAX = 1, BT_SHAPE_MIN = 2, BT_SHAPE_ADD = 3, BT_SHAPE_SUB = 4 }; /* bt_shape.op */
+enum { BT_SHAPES_DRY_RUN = 1 };                                             /* bt_atlas_rasterize_shapes flags */
+typedef struct bt_shape_vertex {
+    int32_t x, y;  /* 1/256 cell, relative to the window's origin; |x|, |y| <= BT_SHAPES_MAX_COORD */
+} bt_shape_vertex; /* 8 bytes */
+typedef struct bt_shape {
+    uint32_t kind, flags;                 /* BT_SHAPE_POLYGON / _STROKE; BT_SHAPE_NONZERO | _MORE (polygon), BT_SHAPE_CLOSED (stroke) */
+    uint32_t first_vertex, vertex_count;  /* of `vertices` */
+    uint32_t half_width;                  /* a stroke's r in 1/256 cell; 0 on a polygon */
+    uint32_t op, value;                   /* BT_SHAPE_SET .. _SUB and its operand */
+    uint32_t _pad;                        /* 0 */
+} bt_shape; /* 32 bytes */
+typedef struct bt_shape_box {
+    uint16_t x_lo, y_lo, x_hi, y_hi;  /* cells of the window, both ends included; empty: {1, 1, 0, 0} */
+} bt_shape_box; /* 8 bytes */
+typedef struct bt_shapes_stats {
+    uint32_t cells, shapes;       /* width * height; shapes of the list */
+    uint32_t shapes_culled;       /* shapes with an empty box */
+    uint32_t tiles_missing;       /* tiles of U the attachment does not hold */
+    uint64_t covered;             /* cells with count > 0 */
+    uint64_t written;             /* texels whose value changed */
+    bt_shape_box box;             /* U */
+    uint32_t launches;            /* the kernel launches of the call before the edit's, the gather counted as one */
+    uint32_t _padding;
+    bt_edit_stats edit;           /* of the write-back; zero with BT_SHAPES_DRY_RUN */
+} bt_shapes_stats; /* 80 bytes */
+bt_status bt_shapes_check(const bt_shape_vertex* vertices, uint32_t vertex_count, const bt_shape* shapes, uint32_t entry_count, uint32_t width,
+                          uint32_t height, bt_shape_box* boxes_out /* may be NULL */, uint32_t* shape_count_out /* may be NULL */,
+                          uint32_t* bad_entry_out /* may be NULL */);
+bt_status bt_atlas_rasterize_shapes(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                    uint32_t width, uint32_t height, uint32_t channel, const bt_shape_vertex* vertices, uint32_t vertex_count,
+                                    const bt_shape* shapes, uint32_t entry_count, uint32_t flags, uint8_t* count_out /* may be NULL */,
+                                    uint16_t* last_out /* may be NULL */, bt_tile_coordinate* changed, uint32_t changed_cap,
+                                    bt_shapes_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- PACKED TILES
  * A lossless tile codec that the device encodes and decodes itself: only packed bytes cross the file system and PCIe, and the atlas ends
  * up byte-identical to one loaded from `.bin`.  `.bin` stays the default everywhere; everything here is opt-in.
