@@ -346,6 +346,33 @@ class DistanceStatsC(C.Structure):
                 ("launches", C.c_uint32), ("_padding", C.c_uint32), ("edit", EditStatsC)]
 
 
+REGIONS_NONE, REGIONS_MAX_SIDE, REGIONS_MAX_CELLS = 0xFFFFFFFF, 8192, 1 << 22
+REGIONS_FROM_TEXELS, REGIONS_INVERT, REGIONS_EIGHT = 1, 2, 4
+# bt_regions.hip: the cells across a block of the local launch and the consecutive cells of a workgroup of the linear launches; tests place
+# windows and scenes around them
+REGIONS_BLOCK, REGIONS_CHUNK = 32, 1024
+
+
+class RegionsRuleC(C.Structure):
+    _fields_ = [("channel", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("max_step", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RegionsBakeC(C.Structure):
+    _fields_ = [("attachment", C.c_uint32), ("channel", C.c_uint32), ("min_area", C.c_uint32), ("max_area", C.c_uint32), ("value", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class RegionC(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("area", C.c_uint32), ("x_min", C.c_uint16), ("y_min", C.c_uint16), ("x_max", C.c_uint16), ("y_max", C.c_uint16),
+                ("v_min", C.c_uint16), ("v_max", C.c_uint16), ("edges", C.c_uint32), ("v_sum", C.c_uint64)]
+
+
+class RegionsStatsC(C.Structure):
+    _fields_ = [("cells", C.c_uint32), ("members", C.c_uint32), ("regions", C.c_uint32), ("regions_written", C.c_uint32), ("largest_area", C.c_uint32),
+                ("largest_label", C.c_uint32), ("tiles_missing", C.c_uint32), ("baked", C.c_uint32), ("launches", C.c_uint32), ("_padding", C.c_uint32 * 3),
+                ("edit", EditStatsC)]
+
+
 SKYLINE_MAX_DIRECTIONS, SKYLINE_MAX_COMPONENT, SKYLINE_MAX_SIDE, SKYLINE_MAX_CELLS = 64, 1024, 32768, 1 << 22
 SKYLINE_STACK_BUDGET, SKYLINE_BAKE_SHADE = 256 << 20, 1
 
@@ -491,6 +518,8 @@ PROTOTYPES = {
     "bt_shapes_check": (_i32, [_P(ShapeVertexC), _u32, _P(ShapeC), _u32, _u32, _u32, _P(ShapeBoxC), _P(_u32), _P(_u32)]),
     "bt_atlas_rasterize_shapes": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(ShapeVertexC), _u32, _P(ShapeC), _u32, _u32, _P(C.c_uint8),
                                          _P(C.c_uint16), _P(TileCoordinateC), _u32, _P(ShapesStatsC)]),
+    "bt_atlas_label_regions": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _P(RegionsRuleC), _P(C.c_uint8), _P(_u32), _P(_u32), _P(RegionC), _u32,
+                                      _P(RegionsBakeC), _P(TileCoordinateC), _u32, _P(RegionsStatsC)]),
     "bt_packed_tile_bound": (_i32, [_u32, _u32, _P(_u64)]),
     "bt_packed_tile_check": (_i32, [_vp, _u64, _P(_u32), _P(_u32)]),
     "bt_atlas_pack_tiles": (_i32, [_vp, _u32, _P(_u32), _u32, _vp, _u64, _P(_u64)]),

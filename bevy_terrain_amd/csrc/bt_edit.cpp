@@ -1052,6 +1052,143 @@ bt_status bt_atlas_distance_field(bt_atlas* a, uint32_t ai, uint32_t side, uint3
     return rc ? rc : drained;
 }
 
+// The host half of the REGIONS section of the header (the kernels: bt_regions.hip).  It lives here for the bake, as
+// bt_atlas_distance_field does.
+bt_status bt_atlas_label_regions(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                 const bt_regions_rule* rule, const uint8_t* member_host, uint32_t* label_out, uint32_t* id_out, bt_region* regions_out, uint32_t region_cap,
+                                 const bt_regions_bake* bake, bt_tile_coordinate* changed, uint32_t changed_cap, bt_regions_stats* stats) {
+    const char* who = "bt_atlas_label_regions";
+    if (stats) *stats = bt_regions_stats{};
+    if (!a || (changed_cap && !changed) || (region_cap && !regions_out)) {
+        set_error("%s: NULL %s", who, !a ? "atlas" : (changed_cap && !changed) ? "changed with changed_cap > 0" : "regions_out with region_cap > 0");
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bt_status s = check_region(a, ai, side, lod, x0, y0, width, height, kTexels, who)) return s;
+    const Attachment& at = a->attachments[ai];
+    const bool wide = at.meta.format == BT_FORMAT_RGBA8;
+    if (!rule) {
+        set_error("%s: NULL rule", who);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const bool from_texels = (rule->flags & BT_REGIONS_FROM_TEXELS) != 0u;
+    const uint32_t top = wide ? 255u : 65535u;
+    const char* bad = (rule->flags & ~uint32_t(BT_REGIONS_FROM_TEXELS | BT_REGIONS_INVERT | BT_REGIONS_EIGHT)) ? "unknown flag bits"
+                      : !from_texels && !member_host                                                         ? "neither BT_REGIONS_FROM_TEXELS nor member_host"
+                      : rule->channel > (wide ? 3u : 0u)                                                     ? "channel (0..3 on Rgba8, 0 on R16)"
+                      : rule->hi > top                                                                       ? "hi above the largest texel value"
+                      : from_texels && rule->lo > rule->hi                                                   ? "lo > hi"
+                      : rule->max_step > 65535u                                                              ? "max_step (0..65535)"
+                                                                                                             : nullptr;
+    if (bad) {
+        set_error("%s: rule: %s (channel %u, lo %u, hi %u, max_step %u, flags %#x)", who, bad, rule->channel, rule->lo, rule->hi, rule->max_step, rule->flags);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (width > BT_REGIONS_MAX_SIDE || height > BT_REGIONS_MAX_SIDE) {
+        set_error("%s: a side of %u x %u above %u", who, width, height, BT_REGIONS_MAX_SIDE);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t cells = uint64_t(width) * height;
+    if (cells > BT_REGIONS_MAX_CELLS) {
+        set_error("%s: %u x %u cells, at most %u", who, width, height, BT_REGIONS_MAX_CELLS);
+        return BT_ERR_INVALID_ARGUMENT;
+    }
+    if (bake) {
+        const char* bad_bake = bake->attachment >= a->attachments.size() ? "attachment out of range"
+                               : bake->channel > 3u                      ? "channel (0..3)"
+                               : bake->min_area > bake->max_area         ? "min_area > max_area"
+                               : bake->value > 255u                      ? "value (0..255)"
+                               : bake->flags != 0u                       ? "unknown flag bits"
+                                                                         : nullptr;
+        if (bad_bake) {
+            set_error("%s: bake: %s (attachment %u, channel %u, min_area %u, max_area %u, value %u, flags %#x)", who, bad_bake, bake->attachment, bake->channel, bake->min_area,
+                      bake->max_area, bake->value, bake->flags);
+            return BT_ERR_INVALID_ARGUMENT;
+        }
+        const AttachmentMeta& dm = a->attachments[bake->attachment].meta;
+        if (dm.format != BT_FORMAT_RGBA8 || dm.texture_size != at.meta.texture_size || dm.border_size != at.meta.border_size) {
+            set_error("%s: bake: attachment %u (format %u, texture_size %u, border_size %u): an Rgba8 attachment of the source's texture_size %u and border_size %u", who,
+                      bake->attachment, dm.format, dm.texture_size, dm.border_size, at.meta.texture_size, at.meta.border_size);
+            return BT_ERR_UNSUPPORTED;
+        }
+    }
+    if (!cells) return BT_OK;  // an empty window: nothing to do
+
+    bt_ctx* ctx = a->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    RegionsPlanes p{};
+    p.width = width, p.height = height;
+    p.region_cap = uint32_t(std::min<uint64_t>(region_cap, cells));  // there are no more regions than cells
+    // the planes of the call, carved from one buffer
+    const uint64_t chunks = (cells + kRegionsChunk - 1u) / kRegionsChunk, plane = align256(cells * 4u);
+    const uint64_t at_raw = 0, at_host = at_raw + align256(cells * at.meta.pixel_size), at_P = at_host + (member_host ? align256(cells) : 0u), at_id = at_P + plane,
+                   at_area = at_id + plane, at_rank = at_area + plane, at_chunks = at_rank + plane, at_accum = at_chunks + align256(chunks * 4u),
+                   at_table = at_accum + align256(p.region_cap * sizeof(RegionAccum)), total = at_table + align256(p.region_cap * sizeof(bt_region));
+    if (bt_status s = ctx->regions.reserve(ctx, total)) return s;
+    if (bt_status s = ctx->regions_words.reserve(ctx, 256, true)) return s;
+    if (bake)
+        if (bt_status s = ctx->edit_region.reserve(ctx, cells * 4u)) return s;
+    uint8_t* base = (uint8_t*)ctx->regions.dev;
+    p.raw = base + at_raw;
+    p.host = member_host ? base + at_host : nullptr;
+    p.wide = wide, p.shift = 8u * rule->channel, p.value_mask = top;
+    p.lo = from_texels ? rule->lo : 1u, p.hi = from_texels ? rule->hi : 0u;
+    p.invert = (rule->flags & BT_REGIONS_INVERT) != 0u, p.eight = (rule->flags & BT_REGIONS_EIGHT) != 0u;
+    p.max_step = rule->max_step;
+    p.P = (uint32_t*)(base + at_P), p.id = (uint32_t*)(base + at_id), p.area = (uint32_t*)(base + at_area), p.rank = (uint32_t*)(base + at_rank);
+    p.chunk_roots = (uint32_t*)(base + at_chunks), p.accum = (RegionAccum*)(base + at_accum);
+    bt_region* table = (bt_region*)(base + at_table);
+    RegionsBake merge{};
+    if (bake) merge.texels = (uint32_t*)ctx->edit_region.dev, merge.shift = 8u * bake->channel, merge.min_area = bake->min_area, merge.max_area = bake->max_area, merge.value = bake->value;
+    RegionsCounts* counts = (RegionsCounts*)ctx->regions_words.dev;
+    const RegionsCounts* counts_host = (const RegionsCounts*)ctx->regions_words.host;
+
+    uint32_t tiles_missing = 0;
+    if (bt_status s = region_gather(a, ai, side, lod, x0, y0, width, height, base + at_raw, &tiles_missing)) return s;
+    if (member_host)
+        if (bt_status s = region_stage_in(ctx, base + at_host, member_host, width, width, height)) return s;
+    if (bake)
+        if (bt_status s = region_gather(a, bake->attachment, side, lod, x0, y0, width, height, ctx->edit_region.dev, nullptr)) return s;
+    BT_HIP(hipMemsetAsync(counts, 0, sizeof(RegionsCounts), stream));
+    if (p.region_cap) BT_HIP(hipMemsetAsync(p.accum, 0, p.region_cap * sizeof(RegionAccum), stream));
+    if (bt_status s = launch_regions_label(stream, p, counts)) return s;
+    if (bt_status s = launch_regions_emit(stream, p)) return s;
+    if (bt_status s = launch_regions_finish(stream, p, merge, counts, table)) return s;
+    BT_HIP(hipMemcpyAsync((void*)counts_host, counts, sizeof(RegionsCounts), hipMemcpyDeviceToHost, stream));
+    const char* what = "bt_atlas_label_regions staging";
+    if (label_out)
+        if (bt_status s = region_stage_out(ctx, p.P, label_out, uint64_t(width) * 4u, uint64_t(width) * 4u, height, what)) return s;
+    if (id_out)
+        if (bt_status s = region_stage_out(ctx, p.id, id_out, uint64_t(width) * 4u, uint64_t(width) * 4u, height, what)) return s;
+    bt_edit_stats edit{};
+    bt_status rc = BT_OK;
+    if (bake) {
+        FirstStep first{FirstStep::kRegion};  // texels nullptr: the rectangle is on the device
+        first.x0 = x0, first.y0 = y0, first.width = width, first.height = height;
+        rc = edit_boxes(a, bake->attachment, lod, {Box{side, {x0, y0, x0 + width - 1u, y0 + height - 1u}}}, first, changed, changed_cap, &edit);
+    }
+    const bt_status drained = ctx->staging.drain();  // the staging copies of the member plane
+    BT_HIP(hipStreamSynchronize(stream));
+    // the records: how many there are is known only now; rows of 1024 records and one of the rest
+    const uint32_t written = std::min(counts_host->regions, region_cap);
+    if (written) {
+        constexpr uint32_t kRow = 1024;
+        const uint32_t rows = written / kRow, rest = written % kRow;
+        if (rows)
+            if (bt_status s = region_stage_out(ctx, table, regions_out, kRow * sizeof(bt_region), kRow * sizeof(bt_region), rows, what)) return s;
+        if (rest)
+            if (bt_status s = region_stage_out(ctx, table + uint64_t(rows) * kRow, regions_out + uint64_t(rows) * kRow, rest * sizeof(bt_region), rest * sizeof(bt_region), 1, what)) return s;
+    }
+    if (stats) {
+        stats->cells = uint32_t(cells), stats->members = counts_host->members, stats->regions = counts_host->regions, stats->regions_written = written;
+        stats->largest_area = uint32_t(counts_host->largest >> 32), stats->largest_label = BT_REGIONS_NONE - uint32_t(counts_host->largest);
+        stats->tiles_missing = tiles_missing, stats->baked = counts_host->baked;
+        stats->launches = bake ? 8u : 7u;  // the gather, local, seams, flatten, scan, emit, finish; a bake's gather
+        stats->edit = edit;
+    }
+    return rc ? rc : drained;
+}
+
 // The call of the SKYLINE section of the header (the kernels: bt_skyline.hip; the line geometry and the plan: bt_skyline.cpp).  It lives
 // here for the bake, as bt_atlas_distance_field does.
 bt_status bt_atlas_skyline(bt_atlas* a, uint32_t ai, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,

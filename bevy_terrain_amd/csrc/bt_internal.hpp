@@ -279,10 +279,13 @@ struct bt_ctx {
     // bt_atlas_rasterize_shapes: the vertices, the entries, the shape records and the two planes of U on the device; and the counts of
     // bt_shapes_stats with a pinned twin
     bt::Scratch shapes, shapes_words;
-    std::array<bt::Scratch*, 21> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
+    // bt_atlas_label_regions: the planes of one call on the device (raw texels, the host member plane, P, id, area, rank, the chunk
+    // counts, the accumulators and the records); and the counts of bt_regions_stats with a pinned twin
+    bt::Scratch regions, regions_words;
+    std::array<bt::Scratch*, 23> scratch() {  // all of them: bt_ctx_trim, bt_ctx_destroy
         return {&bounds, &raycast,     &normal,   &render,         &edit_region, &path,           &path_words, &scatter,      &erode,
                 &drain,  &drain_words, &viewshed, &viewshed_words, &distance,    &distance_words, &skyline,    &skyline_words,
-                &pack,   &pack_words,  &shapes,   &shapes_words};
+                &pack,   &pack_words,  &shapes,   &shapes_words,   &regions,     &regions_words};
     }  // all of them: bt_ctx_trim, bt_ctx_destroy
     // the edit calls and bt_height_bounds_update: the plans of the calls in flight (bt::PlanRing::commit hands it out)
     bt::PlanRingState plan_ring;
@@ -713,6 +716,50 @@ struct ShapesJob {
 const char* shapes_check(const bt_shape_vertex* vertices, uint32_t vertex_count, const bt_shape* shapes, uint32_t entry_count, uint32_t width, uint32_t height,
                          bt_shape_box* boxes, std::vector<ShapeRecord>* records, uint32_t* shape_count, uint32_t* bad_entry);
 bt_status launch_shapes_raster(hipStream_t stream, const ShapesJob& job);
+
+// bt_regions.hip: the kernels of bt_atlas_label_regions (REGIONS in the header).  Planes are width x height, row-major
+constexpr uint32_t kRegionsBlock = BT_REGIONS_BLOCK;  // cells across a block of the local launch
+constexpr uint32_t kRegionsChunk = BT_REGIONS_CHUNK;  // consecutive cells of a workgroup of the linear launches
+struct RegionAccum {  // what the emit launch folds a region's cells into: all zeros at first, so the minima are kept as maxima of complements
+    uint32_t label, area;
+    uint32_t not_x_min, not_y_min, x_max, y_max, not_v_min, v_max;
+    uint32_t edges, _padding;
+    unsigned long long v_sum;
+};
+static_assert(sizeof(RegionAccum) == 48, "twelve words");
+struct RegionsPlanes {
+    uint32_t width, height;
+    const void* raw;         // the gathered texels: u16 (R16) or u32 (Rgba8)
+    const uint8_t* host;     // the caller's member plane on the device, or nullptr
+    uint32_t wide;           // 1: Rgba8 texels
+    uint32_t shift;          // of the texel to its channel: 8 * channel
+    uint32_t value_mask;     // 0xFFFF or 0xFF
+    uint32_t lo, hi;         // from_texels: lo <= v <= hi; a band no v lies in (lo 1, hi 0) without FROM_TEXELS
+    uint32_t invert, eight;  // 0 or 1 each
+    uint32_t max_step;
+    uint32_t region_cap;     // records of `accum`: min(the caller's region_cap, cells)
+    uint32_t* P;             // the parent plane; after the flatten launch: label
+    uint32_t* id;
+    uint32_t* area;          // at a label: the cells of its region
+    uint32_t* rank;          // at a label: its rank among the labels of its chunk
+    uint32_t* chunk_roots;   // per chunk: its labels; after the scan launch: the labels of the chunks before it
+    RegionAccum* accum;
+};
+struct RegionsBake {   // the byte the finish launch merges into the staged rectangle
+    uint32_t* texels;  // the destination's Rgba8 texels on the device, or nullptr: no bake
+    uint32_t shift;    // 8 * channel
+    uint32_t min_area, max_area, value;
+};
+struct RegionsCounts {  // the device words of bt_regions_stats
+    uint32_t members, regions, baked, _padding;
+    unsigned long long largest;  // area << 32 | ~label of the largest region, the smallest label among equals; 0 without a region
+};
+// the local, seam, flatten and scan launches: P becomes label, area, rank and chunk_roots are filled, counts->members and ->regions
+bt_status launch_regions_label(hipStream_t stream, const RegionsPlanes& p, RegionsCounts* counts);
+// id, and the accumulators of the regions with an id below region_cap
+bt_status launch_regions_emit(hipStream_t stream, const RegionsPlanes& p);
+// the largest region, the baked byte, the records
+bt_status launch_regions_finish(hipStream_t stream, const RegionsPlanes& p, const RegionsBake& bake, RegionsCounts* counts, bt_region* table);
 
 // bt_pack.hip: the kernels of the packed tile calls (the format: PACKED TILES in the header).  One wave per strip of a tile; a chunk holds
 // at most kPackChunk tiles, whose layers and stream starts travel in the kernel arguments

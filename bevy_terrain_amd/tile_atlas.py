@@ -725,6 +725,57 @@ class TileAtlas:
         out["changed"] = [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))]
         return (*outs, out)
 
+    REGION_DTYPE = np.dtype([("label", "<u4"), ("area", "<u4"), ("x_min", "<u2"), ("y_min", "<u2"), ("x_max", "<u2"), ("y_max", "<u2"), ("v_min", "<u2"),
+                             ("v_max", "<u2"), ("edges", "<u4"), ("v_sum", "<u8")])  # bt_region, 32 bytes
+
+    def label_regions(self, attachment_index: int, x0: int, y0: int, w: int, h: int, *, lo: Optional[int] = None, hi: Optional[int] = None, channel: int = 0,
+                      members: Optional[np.ndarray] = None, invert: bool = False, eight: bool = False, max_step: int = 65535, bake=None,
+                      lod: Optional[int] = None, side: int = 0, label: bool = True, id: bool = True, region_cap: Optional[int] = None):
+        """bt_atlas_label_regions: the connected regions of a mask over the w x h window of centre texels at mosaic position (x0, y0) of
+        `lod` on `side` of an R16 or Rgba8 attachment, by the header's REGIONS section, in integers.  A cell is a member when its texel value
+        (the raw u16; byte `channel` of an Rgba8 texel) lies in [lo, hi] (either given: BT_REGIONS_FROM_TEXELS; lo alone reaches up to the
+        format's largest value, hi alone down to 0), or when the optional (h, w) uint8 plane `members` is non-zero there; `invert`
+        exchanges members and the rest.  Two adjacent members (with `eight` also across a corner) whose values differ by at most max_step
+        are linked.  Returns (label, id, regions, stats): label (h, w) uint32, the smallest cell index y * w + x of the cell's region; id
+        (h, w) uint32, the rank of that label, 0 .. regions - 1; both REGIONS_NONE where the cell is no member; regions: a structured
+        array (REGION_DTYPE) of the first min(regions, region_cap) records in id order (region_cap None: every region, w * h records of
+        room); stats: bt_regions_stats as a dict.  label / id False: that plane is not copied out and None comes back in its place.
+        bake: (attachment, channel, min_area, max_area, value) or a dict of those names: byte `channel` of that Rgba8 attachment becomes
+        `value` on the members whose region's area lies in [min_area, max_area], and the atlas is updated as by write_region; a fifth
+        element, the changed tiles, is then returned as well, and stats["edit"] is its bt_edit_stats.  Ordered behind the queued work;
+        synchronous; a read without `bake`."""
+        lod = self.lod_count - 1 if lod is None else lod
+        flags = (_ffi.REGIONS_INVERT if invert else 0) | (_ffi.REGIONS_EIGHT if eight else 0) | (_ffi.REGIONS_FROM_TEXELS if lo is not None or hi is not None else 0)
+        formats = self.config.attachments
+        top = 255 if attachment_index < len(formats) and formats[attachment_index].format == AttachmentFormat.Rgba8 else 65535
+        rule_c = _ffi.RegionsRuleC(channel, 0 if lo is None else lo, (top if flags & _ffi.REGIONS_FROM_TEXELS else 0) if hi is None else hi, max_step, flags)
+        plane = None
+        if members is not None:
+            plane = np.ascontiguousarray(members, dtype=np.uint8)
+            if plane.shape != (h, w):
+                raise ValueError(f"label_regions: a members plane of shape {plane.shape} for a window of {(h, w)}")
+        bake_c = None
+        if bake is not None:
+            if isinstance(bake, dict):
+                bake = (bake["attachment"], bake["channel"], bake.get("min_area", 0), bake.get("max_area", 0xFFFFFFFF), bake["value"])
+            bake_c = _ffi.RegionsBakeC(*bake, 0)
+        outs = [np.zeros((h, w), dtype=np.uint32) if want else None for want in (label, id)]
+        region_cap = w * h if region_cap is None else region_cap
+        table = np.zeros(region_cap, dtype=self.REGION_DTYPE)
+        cap = max(self.atlas_size, 1)
+        changed = (_ffi.TileCoordinateC * cap)()
+        stats = _ffi.RegionsStatsC()
+        _ffi.check(_ffi.lib().bt_atlas_label_regions(
+            self._h, attachment_index, side, lod, x0, y0, w, h, C.byref(rule_c), plane.ctypes.data_as(C.POINTER(C.c_uint8)) if plane is not None else None,
+            *[o.ctypes.data_as(C.POINTER(C.c_uint32)) if o is not None else None for o in outs], table.ctypes.data_as(C.POINTER(_ffi.RegionC)) if region_cap else None,
+            region_cap, C.byref(bake_c) if bake_c is not None else None, changed, cap, C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in _ffi.RegionsStatsC._fields_ if name not in ("edit", "_padding")}
+        out["edit"] = {name: getattr(stats.edit, name) for name, _ in _ffi.EditStatsC._fields_}
+        result = (*outs, table[:stats.regions_written].copy() if region_cap > stats.regions_written else table, out)
+        if bake_c is None:
+            return result
+        return (*result, [TileCoordinate._from_c(changed[i]) for i in range(min(stats.edit.changed_count, cap))])
+
     @staticmethod
     def sun_directions(azimuth_deg, elevation_deg, cell_size: float, raw_unit: float, resolution: int = 64):
         """Real sun angles -> the (dx, dy, sun_num, sun_den) rows of `skyline`, an (N, 4) int64 array.  azimuth_deg and elevation_deg:

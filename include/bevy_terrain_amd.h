@@ -2153,6 +2153,107 @@ bt_status bt_atlas_rasterize_shapes(bt_atlas* atlas, uint32_t attachment_index, 
                                     uint16_t* last_out /* may be NULL */, bt_tile_coordinate* changed, uint32_t changed_cap,
                                     bt_shapes_stats* stats /* may be NULL */);
 
+/* ---------------- regions: the connected regions of a mask over a rectangle of a layer, their table, a bake by area
+ * REGIONS (bt_atlas_label_regions; R16 and Rgba8).  Integers throughout: no float appears, so every plane and every record is a function
+ * of the input byte for byte.
+ * Window: DISTANCE's.  The width x height rectangle of centre texels at mosaic (x0, y0) of `lod` on `side` of attachment attachment_index
+ * (the rectangle of bt_atlas_read_region; inside one face).  Cell (x, y) is mosaic texel (x0 + x, y0 + y); planes are row-major, cell
+ * (x, y) at index i = y * width + x.  Texels of tiles the atlas does not hold read as 0; the tiles are counted in tiles_missing.
+ * Bounds: width, height <= BT_REGIONS_MAX_SIDE; width * height <= BT_REGIONS_MAX_CELLS.
+ * Rule: bt_regions_rule {channel, lo, hi, max_step, flags}.  v(c) = the raw u16 of an R16 texel (channel must be 0), byte `channel` (0..3)
+ * of an Rgba8 one.
+ *     from_texels(c) = (flags & BT_REGIONS_FROM_TEXELS) && lo <= v(c) && v(c) <= hi
+ *     from_host(c)   = member_host && member_host[i] != 0                 (member_host: an optional plane of width * height bytes)
+ *     member(c)      = (from_texels(c) || from_host(c)) XOR ((flags & BT_REGIONS_INVERT) != 0)
+ * Two members a and b are linked when they are adjacent (they share an edge; with BT_REGIONS_EIGHT an edge or a corner) and
+ * |v(a) - v(b)| <= max_step (0..65535, on both formats).  A region is a class of the transitive closure of "linked".  So: max_step 65535
+ * gives the plain components of the mask; max_step 0 cuts a classification map into areas of one value; a small max_step on heights gives
+ * the areas one can walk without a step higher than that.  v is the texel's whatever made the cell a member (a host plane included).
+ * Planes (u32, width * height):
+ *     label(c) = the smallest cell index of c's region                      BT_REGIONS_NONE where c is no member
+ *     id(c)    = the rank of label(c) among all labels in ascending order   BT_REGIONS_NONE where c is no member
+ * so ids are dense, 0 .. regions - 1, in the row-major order of the regions' first cells.
+ * Table: regions_out[region_cap] of bt_region, the first min(regions, region_cap) records written in id order, the rest of the array
+ * untouched.  Of region r: label; area, its cells; x_min .. y_max, its bounding box in cells of the window; v_min, v_max and v_sum, the
+ * smallest, the largest and the sum of v over its cells; edges, the number of pairs (a cell c of r, one of the four edge neighbours n of c)
+ * with n outside the window or label(n) != label(c): the perimeter in cell edges, whatever the connectivity.
+ * bt_regions_stats: cells = width * height; members; regions; regions_written = min(regions, region_cap); largest_area, the area of the
+ * largest region (0 without one) and largest_label, the smallest label among the regions of that area (BT_REGIONS_NONE without one);
+ * tiles_missing; baked, the cells the bake wrote; launches.  Every field but launches is a function of the input; launches is a function
+ * of the arguments alone, never of the texels.
+ * Bake (optional): bt_regions_bake {attachment, channel, min_area, max_area, value, flags}.  For every member whose region's area lies in
+ * [min_area, max_area], byte `channel` of the texel of the Rgba8 attachment `attachment` of the same atlas becomes `value` (0..255), over
+ * the same rectangle; every other byte of the rectangle keeps its value.  No flag is defined: flags must be 0.  The write is an edit like
+ * any other: the destination rectangle is gathered, the byte merged on the device, and the texels written and the invariant F restored
+ * exactly as by bt_atlas_write_region of them over the rectangle: the same plan, the same `changed` order, the same bt_edit_stats
+ * (stats->edit).  The destination may be the source attachment: a despeckle is one call (members byte == 255, max_area 15, value 0).
+ * Without `bake` the call is a read: no layer is marked written, and `changed` is not written.
+ * Outputs: label_out, id_out, regions_out, stats; each may be NULL (regions_out only with region_cap == 0).
+ * The call: synchronous, host arrays in and out through the context's staging ring, ordered behind the work queued on the context's
+ * stream.  A union-find over a parent plane P with P[c] <= c, links made only from a root to a smaller index, so the root of a region is
+ * its smallest cell.  Launches: the gather of bt_atlas_read_region (counted as one); local: a workgroup to a block of BT_REGIONS_BLOCK x
+ * BT_REGIONS_BLOCK cells resolves the block's own components in LDS; seams: a lane to each cell of a block's last column and last row
+ * unites it with its linked neighbours in the blocks beside, below and diagonally below; flatten: in chunks of BT_REGIONS_CHUNK
+ * consecutive cells, label = the root, the chunk's labels counted and ranked, the areas added; scan: the prefix sums of the chunks'
+ * counts; emit: id, and the members folded into their regions' records by integer atomics, what shares a label reduced in the wave and
+ * the workgroup first; finish: the largest region, the baked byte, the records: launches = 7.  With a bake the gather of the destination is one more,
+ * launches = 8, and the launches of the edit follow in stats->edit.launches.  The count depends on the arguments only, not on how the
+ * regions wind: that is the point of the form.  No result depends on a schedule.  The scratch stays in the context until bt_ctx_trim: 16
+ * bytes per cell and the texel (2 or 4), 1 more with member_host, 80 per record of min(region_cap, cells), and with a bake the staged
+ * rectangle (4 per cell).
+ * Refusals, all before anything is queued, with the outputs untouched and *stats zeroed.  BT_ERR_INVALID_ARGUMENT: what
+ * bt_atlas_read_region refuses of atlas, attachment, side, lod and rectangle; NULL rule; neither FROM_TEXELS nor member_host; unknown flag
+ * bits; lo > hi with FROM_TEXELS; a channel above 3, or non-zero on R16; hi above 65535 on R16, above 255 on Rgba8; max_step above 65535;
+ * a side above BT_REGIONS_MAX_SIDE; width * height above BT_REGIONS_MAX_CELLS; NULL regions_out with region_cap > 0; NULL changed with
+ * changed_cap > 0; in a bake: an attachment out of range, a channel above 3, min_area > max_area, value above 255, flag bits.
+ * BT_ERR_UNSUPPORTED: an odd centre size; a bake destination that is not Rgba8, or whose texture_size or border_size differs from the
+ * source's.  width == 0 or height == 0 (with valid arguments otherwise; member_host is not looked at): BT_OK, nothing touched. */
+#define BT_REGIONS_NONE 0xFFFFFFFFu
+#define BT_REGIONS_MAX_SIDE 8192u
+#define BT_REGIONS_MAX_CELLS (1u << 22)
+#define BT_REGIONS_BLOCK 32u
+#define BT_REGIONS_CHUNK 1024u
+enum { BT_REGIONS_FROM_TEXELS = 1, BT_REGIONS_INVERT = 2, BT_REGIONS_EIGHT = 4 }; /* bt_regions_rule.flags */
+typedef struct bt_regions_rule {
+    uint32_t channel;   /* of an Rgba8 texel, 0..3; 0 on R16 */
+    uint32_t lo, hi;    /* the band of texel values that are members, both ends included (FROM_TEXELS) */
+    uint32_t max_step;  /* 0..65535: the largest |v(a) - v(b)| across a link */
+    uint32_t flags;     /* BT_REGIONS_FROM_TEXELS | BT_REGIONS_INVERT | BT_REGIONS_EIGHT */
+} bt_regions_rule; /* 20 bytes */
+typedef struct bt_regions_bake {
+    uint32_t attachment;          /* the Rgba8 attachment that takes the byte */
+    uint32_t channel;             /* 0..3 */
+    uint32_t min_area, max_area;  /* the areas whose regions are written, both ends included */
+    uint32_t value;               /* 0..255 */
+    uint32_t flags;               /* 0 */
+} bt_regions_bake; /* 24 bytes */
+typedef struct bt_region {
+    uint32_t label;                        /* offset 0: the smallest cell index of the region */
+    uint32_t area;                         /* 4: its cells */
+    uint16_t x_min, y_min, x_max, y_max;   /* 8, 10, 12, 14: its bounding box in cells of the window */
+    uint16_t v_min, v_max;                 /* 16, 18: the smallest and the largest v of its cells */
+    uint32_t edges;                        /* 20: its perimeter in cell edges */
+    uint64_t v_sum;                        /* 24: the sum of v over its cells */
+} bt_region; /* 32 bytes */
+typedef struct bt_regions_stats {
+    uint32_t cells, members;        /* width * height; member cells */
+    uint32_t regions;               /* regions of the window */
+    uint32_t regions_written;       /* min(regions, region_cap) */
+    uint32_t largest_area;          /* 0 without a region */
+    uint32_t largest_label;         /* the smallest label among the regions of that area; BT_REGIONS_NONE without a region */
+    uint32_t tiles_missing;         /* tiles of the rectangle the source attachment does not hold */
+    uint32_t baked;                 /* cells the bake wrote */
+    uint32_t launches;              /* the kernel launches of the call before the edit's, the gathers counted as one each */
+    uint32_t _padding[3];
+    bt_edit_stats edit;             /* of the bake's write-back; zero without a bake */
+} bt_regions_stats; /* 80 bytes */
+bt_status bt_atlas_label_regions(bt_atlas* atlas, uint32_t attachment_index, uint32_t side, uint32_t lod, uint32_t x0, uint32_t y0,
+                                 uint32_t width, uint32_t height, const bt_regions_rule* rule,
+                                 const uint8_t* member_host /* may be NULL */, uint32_t* label_out /* may be NULL */,
+                                 uint32_t* id_out /* may be NULL */, bt_region* regions_out /* may be NULL with region_cap 0 */,
+                                 uint32_t region_cap, const bt_regions_bake* bake /* may be NULL */, bt_tile_coordinate* changed,
+                                 uint32_t changed_cap, bt_regions_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------------- PACKED TILES
  * A lossless tile codec that the device encodes and decodes itself: only packed bytes cross the file system and PCIe, and the atlas ends
  * up byte-identical to one loaded from `.bin`.  `.bin` stays the default everywhere; everything here is opt-in.

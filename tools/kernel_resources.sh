@@ -15,6 +15,7 @@
 #                                                               tools/kernel_resources.sh skyline bt_skyline.hip   (skyline_walk_kernel, skyline_finish_kernel; the transpose is the viewshed's)
 #                                                               tools/kernel_resources.sh pack bt_pack.hip   (pack_measure_kernel, pack_emit_kernel, pack_decode_kernel, each <false / true> = R16 / Rgba8; pack_scan_kernel)
 #                                                               tools/kernel_resources.sh shapes bt_shapes.hip   (shapes_raster_kernel)
+#                                                               tools/kernel_resources.sh regions bt_regions.hip   (regions_local_kernel, regions_seam_kernel, regions_flatten_kernel, regions_scan_kernel, regions_emit_kernel, regions_finish_kernel)
 R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/bevy_terrain_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I../../include -I. -S --cuda-device-only -o /tmp/bt_fused_gfx950.s "${2:-bt_fused.hip}" 2>/dev/null
